@@ -10,7 +10,9 @@ work "1e6 pts x 2048 hyps, 1/2/4/8 GPU"): rank r holds 1/N of the points and sco
 integer accumulators are summed by an RCCL all-reduce (bitwise the 1-GPU table), value = (points x hypotheses of the JOB) /
 time, "scaling": "strong".  --scaling strong / weak: the hypotheses split over the ranks (all-gather) / 2048 per rank.
 
-The JSON line carries, next to the headline:
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, ms_per_step, config,
+winner); --dump-outputs DIR writes what the last timed step computed (the hypothesis table and the winner) as float64 .npy
+files.  --full adds everything else to the line:
   roofline       HBM roofline of the dominant kernel: ALGORITHMIC bytes of SURVEY 8(d) (N d 8 + M p 8 + M 16 + N 8 for the
                  compound vector; no derived copies) / that kernel's HIP-event time measured live; PMC traffic from the
                  committed rocprofv3 passes; executed work from device counters (pgx_score_stats)
@@ -20,7 +22,7 @@ The JSON line carries, next to the headline:
                  -> select: end-to-end models/s), the dense unfiltered kernel with its true FP64 fraction, Sampson scoring at
                  C3 size, vanishing-point scoring at C5 size, one pgx_set_points
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 via
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]; for N > 1 via
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...
 (RANK / LOCAL_RANK / WORLD_SIZE from the env; torch itself is not imported: the data plane is RCCL inside libpgx).
 """
@@ -761,6 +763,26 @@ def compact_line(out):
     return c
 
 
+DUMP_MAX_BYTES = 64_000_000      # all files of --dump-outputs together
+
+
+def dump_outputs(path, res, best):
+    """What a caller of the timed path receives from its last step - the hypothesis table (counts, values, shared, scores) and
+    the winner select_best picked - as float64 .npy files under `path` (counts and the index are exact in float64).  A table
+    larger than DUMP_MAX_BYTES is written as a fixed sample of its rows, whose indices go to rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    table = {k: np.asarray(res[k], dtype=np.float64) for k in ("counts", "values", "shared", "scores")}
+    T = table["scores"].shape[0]
+    cap = (DUMP_MAX_BYTES - 4096) // (8 * (len(table) + 1))      # (+ rows.npy; 4 KB for the headers and winner.npy)
+    if T > cap:
+        rows = np.sort(np.random.default_rng(0).choice(T, cap, replace=False))
+        table = {k: v[rows] for k, v in table.items()}
+        table["rows"] = rows.astype(np.float64)
+    table["winner"] = np.array([best], dtype=np.float64)
+    for name, a in table.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 gt_pose0 = None
 
 
@@ -777,12 +799,19 @@ def main():
                          "scores all --hyps hypotheses against its 1/N slice of the points, the integer accumulators are summed by an "
                          "RCCL all-reduce (bitwise the 1-GPU table); strong: --hyps hypotheses in total, split over the GPUs, every "
                          "GPU holds all points (all-gather); weak: --hyps hypotheses per GPU, all points on every GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline and executed work (extra profiled launches), the "
+                         "secondary legs and the CPU baselines; prints the full record on a BENCH_DETAIL line before the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (counts, values, shared, scores, winner) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--cpu-labelling-bk-c5", action="store_true", help="also time Boykov-Kolmogorov on the C5 expansion (~110 s of CPU)")
     ap.add_argument("--stub", action="store_true", help="TEST HOOK (no GPU): take the context from the python file PGX_BENCH_STUB names; "
                                                         "without this flag the variable is ignored")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from pyprogressivex import _lib, datasets, parallel
     rank, world, local = parallel.rank_env()
@@ -830,7 +859,7 @@ def main():
     # a non-empty compound instance: the preference vector of the first accepted model (GT pose 0) - per point, so per slice
     ctx.preference(gt[0], T2, slot=0)
     ctx.compound_update([0])
-    comp = ctx.get_compound() if rank == 0 else None
+    comp = ctx.get_compound() if rank == 0 and args.full else None     # (the CPU baseline's input)
     ctx.score_upload(hyps)
     use_comm = world > 1 or os.environ.get("PGX_FORCE_COMM") == "1"   # PGX_FORCE_COMM: exercise RCCL with 1 rank
     if use_comm:
@@ -900,36 +929,23 @@ def main():
     elapsed = time.perf_counter() - t0
     if use_comm:
         elapsed = ctx.comm_allreduce_max(elapsed)
+    if rank == 0 and args.dump_outputs:         # before anything else launches on the context
+        dump_outputs(args.dump_outputs, res, best)
 
     if rank == 0:
         n, M = n_total, hyps.shape[0]
         total_hyps = M * world if args.scaling == "weak" else args.hyps
         pairs_per_step = n * total_hyps
         ms_per_step = 1e3 * elapsed / args.steps
-        alg_bytes, pairs = ctx.score_algorithmic_bytes()
-        kt = np.mean(np.array(kernel_ms), axis=0)
-        k_ms = float(kt[1]) if kt[1] > 0 else float(kt[0])      # the dominant kernel: group-major scoring (timed region)
-        ctx.score_profile(2)            # the per-kernel breakdown: events around every kernel, outside the timed region
-
-        def local_step():               # rank 0 alone from here on: no collective (the other ranks are at the final barrier)
-            ctx.score_launch(T2, has_compound=True)
-            ctx.score_fetch(exponent=2)
-            return ctx.score_kernel_times()
-        kt = np.mean(np.array([local_step() for _ in range(6)][1:]), axis=0)
-        launch_ms = float(kt.sum())
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
-        work = ctx.score_stats(T2, has_compound=True)
         default_workload = n == 1000000 and M == 2048
         out = {
             "metric": "residual_evals_per_sec",
             "value": pairs_per_step / (elapsed / args.steps),
             "unit": "residual-evals/s",
             "value_kind": "effective: (point, hypothesis) pairs COVERED per second - counts, masks and scores are those of evaluating "
-                          "every pair, but a group bound and an f32 filter decide most pairs without the FP64 residual (see executed)",
+                          "every pair, but a group bound and an f32 filter decide most pairs without the FP64 residual (--full: see executed)",
             "models_per_sec": total_hyps / (elapsed / args.steps),
             "co_headline": "models_per_sec (every hypothesis fully scored against all points): the figure that does not depend on how a pair is decided",
-            "executed_pairs_per_sec": (work["surviving_group_steps"] * 64 + work["exact_evaluations"]) * world / (elapsed / args.steps),
-            "executed_pairs_note": "f32 filter evaluations + exact FP64 evaluations actually run per second (rank 0's batch x ranks)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_extra_steps_by_time": extra_warmup,
             "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": "weak" if args.scaling == "weak" else "strong", "scaling_mode": args.scaling, "vs_baseline": None,
@@ -944,48 +960,64 @@ def main():
                                     if by_points else "rccl all-gather of (count,value,shared), overlapped with the next batch's scoring (two in flight)"),
                        "device": info["name"], "cu_count": info["cu_count"]},
             "winner": {"index": best, "inliers": int(res["counts"][best]) if best >= 0 else 0},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": PMC_TRAFFIC_DEFAULT if default_workload else None,
-                         "traffic_raw": PMC_TRAFFIC_RAW if default_workload else None,
-                         "traffic_source": f"NOT measured in this run: constant from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, "
-                                           f"{PMC['source']} (taken at commit {PMC.get('commit', '5d18ef3')}); traffic = 2 x FETCH + WRITE - the group "
-                                           f"kernel's WRITE ({PMC.get('atomic_write_kib', 0.0):.0f} KiB: L2 atomics tallied at 32 B each, no HBM bytes), "
-                                           "factors calibrated on known-bytes kernels in the same access patterns (profiles/round5_fetch_calibration.txt); "
-                                           "traffic_raw = 2 x FETCH + WRITE as rounds 1-4 quoted it",
-                         "kernel": "pgx::score_group_kernel<PnP>", "kernel_ms": k_ms,
-                         "kernel_ms_samples": len(kernel_ms),
-                         "kernel_ms_how": f"HIP events around the kernel on every {EVENT_EVERY}th launch of the timed region, on the context's stream",
-                         "launch_kernels_ms": {"cull": float(kt[0]), "group_major": float(kt[1]), "finish": float(kt[2]),
-                                               "exact_queue": float(kt[3]), "sum": launch_ms,
-                                               "note": "breakdown from 5 extra steps with events around every kernel (an event costs "
-                                                       "~5 us on the stream); kernel_ms above is from the timed region"},
-                         # what actually bounds the kernel travels with `frac`: executed arithmetic per second of
-                         # the dominant kernel and the busy fractions of the two units its filter loop is co-bound by
-                         "compute": {"fp64_exact_tflops": work["exact_evaluations"] * FLOPS_PER_PAIR["pnp"] / (k_ms * 1e-3) / 1e12,
-                                     "f32_filter_tflops": work["surviving_group_steps"] * 64 * F32_FLOPS_PER_FILTER_TEST / (k_ms * 1e-3) / 1e12,
-                                     "valu_busy": PMC.get("valu_busy_frac") if default_workload else None,
-                                     "lds_busy": PMC.get("lds_busy_frac") if default_workload else None,
-                                     "fp64_vector_peak_tflops_no_fma": 39.3,
-                                     "source": f"work counters of an untimed launch (pgx_score_stats) over the timed kernel duration; busy fractions from the "
-                                               f"SQ_ACTIVE_INST_VALU / SQ_ACTIVE_INST_LDS passes of {PMC['source']}"},
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "algorithmic_bytes_formula": "N d 8 + M p 8 + M 16 + N 8 (compound), SURVEY 8(d); no derived copies",
-                         "note": "arithmetic/latency bound by construction (~0.02 algorithmic B/pair): the fraction is small "
-                                 "whatever the kernel does; see `executed` for the work actually done"},
-            "executed": {"pairs": work["pairs"], "group_pairs": work["group_pairs"],
-                         "surviving_group_steps": work["surviving_group_steps"],
-                         "f32_filter_evaluations": work["surviving_group_steps"] * 64,
-                         "exact_fp64_evaluations": work["exact_evaluations"], "inlier_pairs": work["inlier_pairs"],
-                         "exact_fp64_tflops": work["exact_evaluations"] * FLOPS_PER_PAIR["pnp"] / (k_ms * 1e-3) / 1e12,
-                         "valu_busy_frac": PMC.get("valu_busy_frac") if default_workload else None,
-                         "valu_busy_source": f"SQ_ACTIVE_INST_VALU pass, {PMC['source']}",
-                         "source": "device counters of an untimed launch of the same kernels (pgx_score_stats)",
-                         "effective_fp64_tflops_if_every_pair_were_exact": pairs * FLOPS_PER_PAIR["pnp"] / (k_ms * 1e-3) / 1e12,
-                         "note": "'effective' is NOT a utilisation: a bound test culls (hypothesis, 64-point group) pairs, an f32 "
-                                 "filter the rest; only exact_fp64_evaluations run the reference's FP64 residual"},
         }
-        if world == 1 and not args.no_legs and default_workload:
+        if args.full:           # roofline and executed work: extra profiled launches and an untimed one, outside the timed region
+            alg_bytes, pairs = ctx.score_algorithmic_bytes()
+            kt = np.mean(np.array(kernel_ms), axis=0)
+            k_ms = float(kt[1]) if kt[1] > 0 else float(kt[0])      # the dominant kernel: group-major scoring (timed region)
+            ctx.score_profile(2)            # the per-kernel breakdown: events around every kernel, outside the timed region
+
+            def local_step():               # rank 0 alone from here on: no collective (the other ranks are at the final barrier)
+                ctx.score_launch(T2, has_compound=True)
+                ctx.score_fetch(exponent=2)
+                return ctx.score_kernel_times()
+            kt = np.mean(np.array([local_step() for _ in range(6)][1:]), axis=0)
+            launch_ms = float(kt.sum())
+            achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+            work = ctx.score_stats(T2, has_compound=True)
+            out["executed_pairs_per_sec"] = (work["surviving_group_steps"] * 64 + work["exact_evaluations"]) * world / (elapsed / args.steps)
+            out["executed_pairs_note"] = "f32 filter evaluations + exact FP64 evaluations actually run per second (rank 0's batch x ranks)"
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": PMC_TRAFFIC_DEFAULT if default_workload else None,
+                               "traffic_raw": PMC_TRAFFIC_RAW if default_workload else None,
+                               "traffic_source": f"NOT measured in this run: constant from the committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, "
+                                                 f"{PMC['source']} (taken at commit {PMC.get('commit', '5d18ef3')}); traffic = 2 x FETCH + WRITE - the group "
+                                                 f"kernel's WRITE ({PMC.get('atomic_write_kib', 0.0):.0f} KiB: L2 atomics tallied at 32 B each, no HBM bytes), "
+                                                 "factors calibrated on known-bytes kernels in the same access patterns (profiles/round5_fetch_calibration.txt); "
+                                                 "traffic_raw = 2 x FETCH + WRITE as rounds 1-4 quoted it",
+                               "kernel": "pgx::score_group_kernel<PnP>", "kernel_ms": k_ms,
+                               "kernel_ms_samples": len(kernel_ms),
+                               "kernel_ms_how": f"HIP events around the kernel on every {EVENT_EVERY}th launch of the timed region, on the context's stream",
+                               "launch_kernels_ms": {"cull": float(kt[0]), "group_major": float(kt[1]), "finish": float(kt[2]),
+                                                     "exact_queue": float(kt[3]), "sum": launch_ms,
+                                                     "note": "breakdown from 5 extra steps with events around every kernel (an event costs "
+                                                             "~5 us on the stream); kernel_ms above is from the timed region"},
+                               # what actually bounds the kernel travels with `frac`: executed arithmetic per second of
+                               # the dominant kernel and the busy fractions of the two units its filter loop is co-bound by
+                               "compute": {"fp64_exact_tflops": work["exact_evaluations"] * FLOPS_PER_PAIR["pnp"] / (k_ms * 1e-3) / 1e12,
+                                           "f32_filter_tflops": work["surviving_group_steps"] * 64 * F32_FLOPS_PER_FILTER_TEST / (k_ms * 1e-3) / 1e12,
+                                           "valu_busy": PMC.get("valu_busy_frac") if default_workload else None,
+                                           "lds_busy": PMC.get("lds_busy_frac") if default_workload else None,
+                                           "fp64_vector_peak_tflops_no_fma": 39.3,
+                                           "source": f"work counters of an untimed launch (pgx_score_stats) over the timed kernel duration; busy fractions from the "
+                                                     f"SQ_ACTIVE_INST_VALU / SQ_ACTIVE_INST_LDS passes of {PMC['source']}"},
+                               "algorithmic_bytes_per_launch": alg_bytes,
+                               "algorithmic_bytes_formula": "N d 8 + M p 8 + M 16 + N 8 (compound), SURVEY 8(d); no derived copies",
+                               "note": "arithmetic/latency bound by construction (~0.02 algorithmic B/pair): the fraction is small "
+                                       "whatever the kernel does; see `executed` for the work actually done"}
+            out["executed"] = {"pairs": work["pairs"], "group_pairs": work["group_pairs"],
+                               "surviving_group_steps": work["surviving_group_steps"],
+                               "f32_filter_evaluations": work["surviving_group_steps"] * 64,
+                               "exact_fp64_evaluations": work["exact_evaluations"], "inlier_pairs": work["inlier_pairs"],
+                               "exact_fp64_tflops": work["exact_evaluations"] * FLOPS_PER_PAIR["pnp"] / (k_ms * 1e-3) / 1e12,
+                               "valu_busy_frac": PMC.get("valu_busy_frac") if default_workload else None,
+                               "valu_busy_source": f"SQ_ACTIVE_INST_VALU pass, {PMC['source']}",
+                               "source": "device counters of an untimed launch of the same kernels (pgx_score_stats)",
+                               "effective_fp64_tflops_if_every_pair_were_exact": pairs * FLOPS_PER_PAIR["pnp"] / (k_ms * 1e-3) / 1e12,
+                               "note": "'effective' is NOT a utilisation: a bound test culls (hypothesis, 64-point group) pairs, an f32 "
+                                       "filter the rest; only exact_fp64_evaluations run the reference's FP64 residual"}
+        if world == 1 and args.full and not args.no_legs and default_workload:
             out["legs"] = secondary_legs(_lib, datasets, parallel, ctx, pts, hyps, gt_labels, T2, args.steps, args.warmup)
             out["legs"].update(labelling_legs(_lib, datasets, np.column_stack([x1, x2]), pts, gt[:10], thr))
             try:
@@ -1003,7 +1035,7 @@ def main():
                 out["legs"]["strong_points_projection"] = strong_points_legs(_lib, ctx, parallel, pts, hyps, gt[0], T2, args.steps, args.warmup)
             except Exception as e:
                 out["legs"]["strong_points_projection"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(pts, hyps, T2, comp)
             out["cpu_baseline"] = cb
             out["speedup_vs_cpu_port"] = out["models_per_sec"] / cb["models_per_sec"]
@@ -1021,8 +1053,11 @@ def main():
                             rec["gpu_over_cpu"] = rec["seconds"] / (g["expansion_ms"] * 1e-3)
                 except Exception as e:
                     cb["labelling"] = {"error": str(e)}
-        line = json.dumps(compact_line(out))
-        detail = json.dumps(out)
+        if args.full:
+            line = json.dumps(compact_line(out))
+            detail = json.dumps(out)
+        else:
+            line, detail = json.dumps(out), None
     else:
         line = detail = None
     if use_comm:
@@ -1037,6 +1072,9 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
+        if detail is None:              # a plain run: the headline line alone
+            print(line, flush=True)
+            return
         # The driver keeps an 8 KB tail of stdout and parses the LAST line: that line is the compact record (contract keys, config,
         # roofline, cpu_baseline, roofline_labelling, api wall times; < 8 000 bytes, asserted by tests/test_bench_contract.py).  The
         # full record (every leg, notes, projections) goes to an EARLIER line, prefixed so that it is not mistaken for the line,

@@ -5,6 +5,8 @@ import json
 import os
 import re
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -139,3 +141,27 @@ def test_bench_py_keeps_the_driver_flags_and_defaults():
     for flag in ("--gpus", "--steps", "--warmup"):
         assert f'"{flag}"' in src
     assert re.search(r'"--gpus", type=int, default=1', src)
+
+
+def test_dump_outputs_stays_under_its_size_cap(tmp_path):
+    """--dump-outputs writes the whole table when it fits and a fixed sample of its rows (indices in rows.npy) when it does not;
+    either way the files together stay under bench.DUMP_MAX_BYTES"""
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    T = 20000
+    res = {"counts": rng.integers(0, 1000, T), "values": rng.random(T), "shared": rng.random(T), "scores": rng.random(T)}
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), res, 7)
+    assert np.array_equal(np.load(whole / "counts.npy"), res["counts"]) and not (whole / "rows.npy").exists()
+    bench.DUMP_MAX_BYTES = 100_000
+    runs = []
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), res, 7)
+        runs.append({p.stem: np.load(p) for p in (tmp_path / name).glob("*.npy")})
+        assert sum(p.stat().st_size for p in (tmp_path / name).glob("*.npy")) <= bench.DUMP_MAX_BYTES
+    a, b = runs
+    rows = a["rows"].astype(np.int64)
+    assert 0 < len(rows) < T and np.all(np.diff(rows) > 0) and np.array_equal(a["rows"], b["rows"])      # fixed, sorted, distinct
+    for k in ("counts", "values", "shared", "scores"):
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], np.asarray(res[k], np.float64)[rows])
+    assert a["winner"][0] == 7
