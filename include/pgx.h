@@ -39,7 +39,8 @@ enum pgx_model_type {
     PGX_FUNDAMENTAL = 2,      /* point (x1,y1,x2,y2);    model F 3x3 row-major, Sampson       findTwoViewMotions   */
     PGX_PNP = 3,              /* point (u,v,X,Y,Z);      model [R|t] 3x4 row-major            find6DPoses          */
     PGX_VANISHING_POINT = 4,  /* point (xs,ys,xe,ye);    model (v0,v1,v2)                     findVanishingPoints  */
-    PGX_HOMOGRAPHY_SYM = 5    /* point (x1,y1,x2,y2);    model [H | H^-1], symmetric transfer error               */
+    PGX_HOMOGRAPHY_SYM = 5,   /* point (x1,y1,x2,y2);    model [H | H^-1], symmetric transfer error               */
+    PGX_PLANE3D = 6           /* point (x,y,z);          model (a,b,c,d), (a,b,c) unit normal findPlanes           */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -84,7 +85,7 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * indices; hypothesis s is generated straight into the resident hypothesis buffer (as after pgx_score_upload, in the
  * caller's order), so pgx_score_launch can follow without a model upload; models_out (may be NULL) copies them out.
  * Built: the 2-segment vanishing point solver (solver_vanishing_point_two_lines.h:147-185) and the 2-point line solver
- * [U-4] (samples[S][2], S x 3 models), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
+ * [U-4] (samples[S][2], S x 3 models), the 3-point plane solver (samples[S][3], S x 4, findPlanes), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
  * FOUR slots per sample: 4S x 12 [R|t], DefaultPnPEstimator progressivex_python.cpp:119, absent upstream); a degenerate sample

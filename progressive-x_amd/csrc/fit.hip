@@ -53,6 +53,7 @@ struct Acc {
 
 // row generators: Q = row length, emit(pt, prm, acc, w, bad)
 struct GenAffine2 { static constexpr int Q = 3, D = 2; };
+struct GenAffine3 { static constexpr int Q = 4, D = 3; };
 struct GenAffine4 { static constexpr int Q = 5, D = 4; };
 struct GenAffine5 { static constexpr int Q = 6, D = 5; };
 struct GenDltH { static constexpr int Q = 9, D = 4; };
@@ -67,6 +68,12 @@ template <>
 __device__ __forceinline__ void emit<GenAffine2>(const double* pt, const FitParams&, Acc<3>& acc, double w, int&)
 {
     const double a[3] = {1.0, pt[0], pt[1]};
+    acc.add(a, w);
+}
+template <>
+__device__ __forceinline__ void emit<GenAffine3>(const double* pt, const FitParams&, Acc<4>& acc, double w, int&)
+{
+    const double a[4] = {1.0, pt[0], pt[1], pt[2]};
     acc.add(a, w);
 }
 template <>
@@ -534,7 +541,7 @@ static int gram_row_length(pgx_ctx* ctx, const char* who, int kind, int nparams,
 {
     const int D = ctx->D;
     switch (kind) {
-    case PGX_GRAM_AFFINE: *q = D + 1; if (D != 2 && D != 4 && D != 5) return fail(ctx, PGX_ERR_INVALID, "%s: affine rows need 2-, 4- or 5-D points", who); break;
+    case PGX_GRAM_AFFINE: *q = D + 1; if (D < 2 || D > 5) return fail(ctx, PGX_ERR_INVALID, "%s: affine rows need 2-, 3-, 4- or 5-D points", who); break;
     case PGX_GRAM_DLT_H: case PGX_GRAM_EPI_F: *q = 9; if (D != 4 || nparams != 6) return fail(ctx, PGX_ERR_INVALID, "%s: needs 4-D correspondences and 6 normalisation parameters", who); break;
     case PGX_GRAM_VP: *q = 3; if (D != 4) return fail(ctx, PGX_ERR_INVALID, "%s: needs 4-D segments", who); break;
     case PGX_GRAM_PNP_GN: *q = 7; if (D != 5 || nparams != 12) return fail(ctx, PGX_ERR_INVALID, "%s: needs 5-D 2D-3D rows and a 3x4 pose", who); break;
@@ -578,6 +585,7 @@ int gram_batch_launch(pgx_ctx* ctx, int kind, const double* params, int nparams,
     switch (kind) {
     case PGX_GRAM_AFFINE:
         if (D == 2) launch_batch<GenAffine2>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
+        else if (D == 3) launch_batch<GenAffine3>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
         else if (D == 4) launch_batch<GenAffine4>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
         else launch_batch<GenAffine5>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
         break;
@@ -639,6 +647,7 @@ int gram_labels_launch(pgx_ctx* ctx, int kind, const double* params, int nparams
     switch (kind) {
     case PGX_GRAM_AFFINE:
         if (D == 2) launch_labels<GenAffine2>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
+        else if (D == 3) launch_labels<GenAffine3>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
         else if (D == 4) launch_labels<GenAffine4>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
         else launch_labels<GenAffine5>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
         break;
@@ -673,7 +682,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
     int q = 0;
     const int D = ctx->D;
     switch (kind) {
-    case PGX_GRAM_AFFINE: q = D + 1; if (D != 2 && D != 4 && D != 5) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: affine rows need 2-, 4- or 5-D points"); break;
+    case PGX_GRAM_AFFINE: q = D + 1; if (D < 2 || D > 5) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: affine rows need 2-, 3-, 4- or 5-D points"); break;
     case PGX_GRAM_DLT_H: case PGX_GRAM_EPI_F: q = 9; if (D != 4 || nparams != 6) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 4-D correspondences and 6 normalisation parameters"); break;
     case PGX_GRAM_VP: q = 3; if (D != 4) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 4-D segments"); break;
     case PGX_GRAM_PNP_GN: q = 7; if (D != 5 || nparams != 12) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 5-D 2D-3D rows and a 3x4 pose"); break;
@@ -727,6 +736,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
     switch (kind) {
     case PGX_GRAM_AFFINE:
         if (D == 2) launch<GenAffine2>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
+        else if (D == 3) launch<GenAffine3>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
         else if (D == 4) launch<GenAffine4>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
         else launch<GenAffine5>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
         break;

@@ -1,4 +1,4 @@
-// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types, gfx950 device code.
+// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and 3-D planes, gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -13,8 +13,8 @@
 namespace pgx {
 
 enum ModelType : int {
-    kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5,
-    kNumModelTypes = 6
+    kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
+    kNumModelTypes = 7
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -128,10 +128,26 @@ template <> struct Residual<kVanishingPoint> {
     }
 };
 
+// 3-D planes (findPlanes; no reference counterpart - the line construction one dimension up): model (a,b,c,d) with (a,b,c)
+// a unit normal, r = |((a x + b y) + c z) + d|, summed left to right.  This operation order is the contract of every plane
+// check (tests restate it in numpy).
+template <> struct Residual<kPlane3D> {
+    static constexpr int D = 3, P = 4;
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        return fabs(((m[0] * p[0] + m[1] * p[1]) + m[2] * p[2]) + m[3]);
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double r = plain(p, m);
+        return r * r;
+    }
+};
+
 // Host-side dims table (same numbers as the functors above).
 inline int model_dims(int mt, int* d, int* p) {
-    static const int D[kNumModelTypes] = {2, 4, 4, 5, 4, 4};
-    static const int P[kNumModelTypes] = {3, 9, 9, 12, 3, 18};
+    static const int D[kNumModelTypes] = {2, 4, 4, 5, 4, 4, 3};
+    static const int P[kNumModelTypes] = {3, 9, 9, 12, 3, 18, 4};
     if (mt < 0 || mt >= kNumModelTypes) return -1;
     if (d) *d = D[mt];
     if (p) *p = P[mt];

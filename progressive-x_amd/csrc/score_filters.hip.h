@@ -494,4 +494,58 @@ template <> struct Filter32<kLine2D> {
     }
 };
 
+// ---- 3-D planes: r = |((a x + b y) + c z) + d| (Residual<kPlane3D>), inlier iff r^2 < T2 -----------------------------------------
+// The line filter one dimension up.  n~ = fma(a~, x~, fma(b~, y~, fma(c~, z~, d~))) with every input rounded to f32 (the model
+// after the exact power-of-two scaling), u = 2^-24, eta = 2^-126, P = max(|x|, |y|, |z|, 1) rounded up.  Relative roundings each
+// term of n* = a x + b y + c z + d carries in the f32 chain:
+//   a x: a~, x~, the outer fma                    3        c z: c~, z~, all three fmas             5
+//   b y: b~, y~, the two outer fmas               4        d:   d~, all three fmas                 4
+// so |n~ - n*| <= 5 u (|a x| + |b y| + |c z| + |d|) + O(u^2); the exact path's own f64 chain (product, three sums: <= 4 * 2^-53
+// per term) and the O(u^2) terms fit in the extra 0.1 u.  Absolute (subnormal) errors, each < eta: the three coefficients a, b, c
+// times a coordinate (3 eta P), the three coordinates times a coefficient of magnitude < 1 (the normaliser: 3 eta), the three fma
+// results and d~ (4 eta) - at most 3 eta P + 7 eta <= 6 eta P + 4 eta for P >= 1.  Hence
+//   |n~ - n*| + |n_c - n*|  <=  E = 5.1 u ((|a| + |b| + |c|) P + |d|) + 6 eta P + 4 eta
+//   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  then |n_c| > T (1 + 2^-7) (m itself is rounded once) and fl(n_c^2) > T2.
+// The group test works on the 3-D ball (centre, radius R) of 64 Morton-consecutive points: for p in the ball
+// |n(p)| >= |n(centre)| - ||(a, b, c)|| R, the error term taken at the group's largest P (which bounds the stored centre too):
+//   reject the group  <=>  |n~(centre)| - ||(a, b, c)|| R - E(Pmax) > T''  (each factor inflated by 1.001).
+// Same switch-off as the line: an entry times the set's largest P beyond 1e36, a threshold outside the ordinary f32 range or a
+// model outside pow2_normaliser's band gives E = inf (never rejected); a NaN entry culls the hypothesis (all four enter every
+// residual).  On a planar scene a plane's inliers are a slab of width 2T, so the cull removes most (hypothesis, group) pairs.
+template <> struct Filter32<kPlane3D> {
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    struct Lane { float a, b, c, d, e1, e0, nrm, tpp, nanh; };
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m0, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        bool off;
+        const double sc = pow2_normaliser<4>(m0, &off);
+        const double m[4] = {m0[0] * sc, m0[1] * sc, m0[2] * sc, m0[3] * sc};
+        ln.a = (float)m[0]; ln.b = (float)m[1]; ln.c = (float)m[2]; ln.d = (float)m[3];
+        ln.nanh = (m0[0] == m0[0] && m0[1] == m0[1] && m0[2] == m0[2] && m0[3] == m0[3]) ? 0.0f : 1.0f;
+        const double Ts = sqrt(T2) * sc;
+        const bool big = !(fabs(m[0]) * pscale <= 1e36) || !(fabs(m[1]) * pscale <= 1e36) || !(fabs(m[2]) * pscale <= 1e36) ||
+                         !(fabs(m[3]) <= 1e36) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
+        const double u = 5.9604644775390625e-8, eta = 1.1754943508222875e-38;
+        ln.e1 = f32_up(5.1 * u * (fabs(m[0]) + fabs(m[1]) + fabs(m[2])) + 6.0 * eta);
+        ln.e0 = big ? __builtin_inff() : f32_up(5.1 * u * fabs(m[3]) + 4.0 * eta);
+        ln.nrm = f32_up(sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) * 1.001);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        return ln;
+    }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        const float n = __builtin_fmaf(ln.a, p[0], __builtin_fmaf(ln.b, p[1], __builtin_fmaf(ln.c, p[2], ln.d)));
+        const float m = fabsf(n) - __builtin_fmaf(ln.e1, p[5], ln.e0);
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (cx, cy, cz, R, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;
+        const float n = __builtin_fmaf(ln.a, g[0], __builtin_fmaf(ln.b, g[1], __builtin_fmaf(ln.c, g[2], ln.d)));
+        const float m = fabsf(n) - __builtin_fmaf(ln.e1, g[4], ln.e0) - ln.nrm * g[3] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
 }  // namespace pgx

@@ -434,7 +434,7 @@ __global__ __launch_bounds__(SPAN) void sp_vp_bounds_kernel(const double* __rest
 
 // ---- fundamental matrices: f32 rows (x_a, y_a, x_b, y_b, 0, P, P^2, 0) and group rows of the 4-D boxes ---------------------
 // (score.hip Filter32<kFundamental>: P = max(|coordinates|, 1) rounded up)
-__global__ __launch_bounds__(kSpBlock) void sp_fund_rows_kernel(const double* __restrict__ pts, int64_t n, int d /* 4, or 2 for lines */,
+__global__ __launch_bounds__(kSpBlock) void sp_fund_rows_kernel(const double* __restrict__ pts, int64_t n, int d /* 4, 2 for lines, 3 for planes */,
                                                                 float* __restrict__ p32, double* __restrict__ pmax)
 {
     const int64_t i = (int64_t)blockIdx.x * kSpBlock + threadIdx.x;
@@ -513,19 +513,20 @@ __global__ __launch_bounds__(SPAN) void sp_fund_bounds_kernel(const double* __re
     }
 }
 
-// 2-D lines: group rows (cx, cy, R, Pmax, 0 ...) - score.hip Filter32<kLine2D>
-template <int SPAN>
+// 2-D lines and 3-D planes: group rows (centre[DIM], R, Pmax, 0 ...) - score.hip Filter32<kLine2D> (DIM = 2), Filter32<kPlane3D>
+// (DIM = 3): the box centre in f64 -> f32, the radius of the ball about the STORED centre, inflated
+template <int SPAN, int DIM>
 __global__ __launch_bounds__(SPAN) void sp_line_bounds_kernel(const double* __restrict__ sp, int64_t n, float* __restrict__ rows)
 {
-    __shared__ double s_wlo[SPAN / 64][2], s_whi[SPAN / 64][2];
-    __shared__ float s_c[2];
+    __shared__ double s_wlo[SPAN / 64][DIM], s_whi[SPAN / 64][DIM];
+    __shared__ float s_c[DIM];
     __shared__ unsigned long long s_red[2];   // R^2, P
     const int64_t j = (int64_t)blockIdx.x * SPAN + threadIdx.x;
     const bool valid = j < n;
     if (threadIdx.x < 2) s_red[threadIdx.x] = 0ull;
-    double r[2] = {0, 0};
-    if (valid) { r[0] = sp[j * 2]; r[1] = sp[j * 2 + 1]; }
-    for (int k = 0; k < 2; ++k) {
+    double r[DIM];
+    for (int k = 0; k < DIM; ++k) r[k] = valid ? sp[j * DIM + k] : 0.0;
+    for (int k = 0; k < DIM; ++k) {
         double lo = valid ? r[k] : 1.7976931348623157e308, hi = valid ? r[k] : -1.7976931348623157e308;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -536,7 +537,7 @@ __global__ __launch_bounds__(SPAN) void sp_line_bounds_kernel(const double* __re
         if ((threadIdx.x & 63) == 0) { s_wlo[threadIdx.x >> 6][k] = lo; s_whi[threadIdx.x >> 6][k] = hi; }
     }
     __syncthreads();
-    if (threadIdx.x < 2) {
+    if (threadIdx.x < DIM) {
         double lo = s_wlo[0][threadIdx.x], hi = s_whi[0][threadIdx.x];
         for (int w = 1; w < SPAN / 64; ++w) {
             if (s_wlo[w][threadIdx.x] < lo) lo = s_wlo[w][threadIdx.x];
@@ -546,20 +547,22 @@ __global__ __launch_bounds__(SPAN) void sp_line_bounds_kernel(const double* __re
     }
     __syncthreads();
     if (valid) {
-        const double dx = r[0] - (double)s_c[0], dy = r[1] - (double)s_c[1];
-        double P = 1.0;
-        if (fabs(r[0]) > P) P = fabs(r[0]);
-        if (fabs(r[1]) > P) P = fabs(r[1]);
-        atomicMax(&s_red[0], (unsigned long long)__double_as_longlong(dx * dx + dy * dy));
+        double R2 = 0.0, P = 1.0;
+        for (int k = 0; k < DIM; ++k) {
+            const double df = r[k] - (double)s_c[k];
+            R2 = k == 0 ? df * df : R2 + df * df;
+            if (fabs(r[k]) > P) P = fabs(r[k]);
+        }
+        atomicMax(&s_red[0], (unsigned long long)__double_as_longlong(R2));
         atomicMax(&s_red[1], (unsigned long long)__double_as_longlong(P));
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         float* row = rows + (int64_t)blockIdx.x * kGroupRow;
-        row[0] = s_c[0]; row[1] = s_c[1];
-        row[2] = (float)(sqrt(__longlong_as_double((long long)s_red[0])) * kGroupInflate + 1e-30);
-        row[3] = (float)(__longlong_as_double((long long)s_red[1]) * 1.000002);   // >= |stored centre| too
-        for (int k = 4; k < kGroupRow; ++k) row[k] = 0.0f;
+        for (int k = 0; k < DIM; ++k) row[k] = s_c[k];
+        row[DIM] = (float)(sqrt(__longlong_as_double((long long)s_red[0])) * kGroupInflate + 1e-30);
+        row[DIM + 1] = (float)(__longlong_as_double((long long)s_red[1]) * 1.000002);   // >= |stored centre| too
+        for (int k = DIM + 2; k < kGroupRow; ++k) row[k] = 0.0f;
     }
 }
 
@@ -637,7 +640,7 @@ int set_points_device(pgx_ctx* ctx, int model_type, const double* points, int64_
         ctx->point_sort = 1;
         return PGX_OK;
     }
-    const bool line = model_type == kLine2D;
+    const bool line = model_type == kLine2D || model_type == kPlane3D;   // ball bounds about the box centre (d = 2 or 3)
     const bool fund = model_type == kFundamental || line;   // model types whose f32 rows / boxes are built from ALL coordinates
     if (!((obs0 >= 0 || fund) && ctx->group_filter && ctx->filter_enabled == 1 && std::isfinite(ctx->umax)) || (flags & 1u)) return PGX_OK;
     if (fund) {   // f32 rows of the Sampson / line filter (the prep kernel left them zero) + the scales
@@ -755,10 +758,15 @@ int set_points_device(pgx_ctx* ctx, int model_type, const double* points, int64_
                        ctx->p32_g.as<float>());
     PGX_HIP(ctx, hipGetLastError());
     const int ib0 = model_type == kPnP ? 2 : 0, ib1 = model_type == kPnP ? 4 : 1, ob0 = model_type == kPnP ? 0 : 2;
-    if (line) {
-        hipLaunchKernelGGL((sp_line_bounds_kernel<64>), dim3((unsigned)groups), dim3(64), 0, ctx->stream, ctx->pts_s.as<double>(), n,
+    if (line && d == 2) {
+        hipLaunchKernelGGL((sp_line_bounds_kernel<64, 2>), dim3((unsigned)groups), dim3(64), 0, ctx->stream, ctx->pts_s.as<double>(), n,
                            ctx->gbounds.as<float>());
-        hipLaunchKernelGGL((sp_line_bounds_kernel<64 * kSuper>), dim3((unsigned)supers), dim3(64 * kSuper), 0, ctx->stream,
+        hipLaunchKernelGGL((sp_line_bounds_kernel<64 * kSuper, 2>), dim3((unsigned)supers), dim3(64 * kSuper), 0, ctx->stream,
+                           ctx->pts_s.as<double>(), n, ctx->gbounds.as<float>() + groups * kGroupRow);
+    } else if (line) {
+        hipLaunchKernelGGL((sp_line_bounds_kernel<64, 3>), dim3((unsigned)groups), dim3(64), 0, ctx->stream, ctx->pts_s.as<double>(), n,
+                           ctx->gbounds.as<float>());
+        hipLaunchKernelGGL((sp_line_bounds_kernel<64 * kSuper, 3>), dim3((unsigned)supers), dim3(64 * kSuper), 0, ctx->stream,
                            ctx->pts_s.as<double>(), n, ctx->gbounds.as<float>() + groups * kGroupRow);
     } else if (fund) {
         hipLaunchKernelGGL((sp_fund_bounds_kernel<64>), dim3((unsigned)groups), dim3(64), 0, ctx->stream, ctx->pts_s.as<double>(), n,

@@ -18,6 +18,9 @@
 //   absolute pose from 3 points (P3P)   DefaultPnPEstimator's minimal solver (progressivex_python.cpp:119), absent upstream:
 //                                       Grunert's quartic, positive real roots by bisection between the critical points,
 //                                       pose from the orthonormal frames of the two congruent triangles; four slots
+//   3-D plane through three points      findPlanes' minimal solver (no reference counterpart): n = (p1 - p0) x (p2 - p0) in
+//                                       cross3's component order, ln = sqrt(n . n), (a, b, c) = n / ln,
+//                                       d = -((a x0 + b y0) + c z0); collinear or coincident points (ln == 0) give NaN
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
 // inlier; the caller drops it (the reference's solvers return "no model").
@@ -79,6 +82,37 @@ __global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __rest
     models[(int64_t)s * 3] = m[0];
     models[(int64_t)s * 3 + 1] = m[1];
     models[(int64_t)s * 3 + 2] = m[2];
+}
+
+// 3-point plane: samples[S][3] -> S x 4 models (a, b, c, d).  Operation order (the contract; PlaneEstimator.minimal restates it):
+//   u = p1 - p0, v = p2 - p0 (componentwise), n = cross3(u, v), ln = sqrt((n0 n0 + n1 n1) + n2 n2),
+//   a = n0 / ln, b = n1 / ln, c = n2 / ln, d = -((a x0 + b y0) + c z0).
+// An index outside 0 .. n-1, or ln == 0 (coincident or collinear points; also false on NaN) gives a NaN model.
+__global__ __launch_bounds__(kSolveBlock) void solve_plane_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
+                                                                  int S, double* __restrict__ models, int* __restrict__ perm, int Mpad)
+{
+    const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
+    if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
+    if (s >= S) return;
+    const int i0 = samples[3 * s], i1 = samples[3 * s + 1], i2 = samples[3 * s + 2];
+    double m[4];
+    const double nan = __builtin_nan("");
+    m[0] = m[1] = m[2] = m[3] = nan;
+    if (i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < n && i1 < n && i2 < n) {
+        const double* p0 = pts + (int64_t)i0 * 3;
+        const double* p1 = pts + (int64_t)i1 * 3;
+        const double* p2 = pts + (int64_t)i2 * 3;
+        double nv[3];
+        cross3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2], p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2], nv);
+        const double ln = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
+        if (ln > 0.0) {
+            m[0] = nv[0] / ln;
+            m[1] = nv[1] / ln;
+            m[2] = nv[2] / ln;
+            m[3] = -((m[0] * p0[0] + m[1] * p0[1]) + m[2] * p0[2]);
+        }
+    }
+    for (int k = 0; k < 4; ++k) models[(int64_t)s * 4 + k] = m[k];
 }
 
 // ---- P3P -------------------------------------------------------------------------------------------------------------
@@ -519,8 +553,23 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
         ctx->M = S; ctx->last_acc = nullptr;
         return PGX_OK;
     }
+    if (ctx->model_type == kPlane3D) {
+        ctx->Mpad = ((S + 255) / 256) * 256;
+        PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 4 * sizeof(double)));
+        PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
+        if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 3 * sizeof(int32_t)));
+        hipLaunchKernelGGL(solve_plane_kernel, dim3((unsigned)((ctx->Mpad + kSolveBlock - 1) / kSolveBlock)), dim3(kSolveBlock), 0, ctx->stream,
+                           ctx->pts.as<double>(), ctx->n, ctx->scratch.as<int>(), S, ctx->models.as<double>(), ctx->perm.as<int>(), ctx->Mpad);
+        PGX_HIP(ctx, hipGetLastError());
+        if (models_out) {
+            PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)S * 4 * sizeof(double)));
+            PGX_TRY(sync_deliver(ctx));
+        }
+        ctx->M = S; ctx->last_acc = nullptr;
+        return PGX_OK;
+    }
     if (ctx->model_type != kLine2D && ctx->model_type != kVanishingPoint)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 4-point homography, 7-point fundamental matrix, P3P)", ctx->model_type);
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point homography, 7-point fundamental matrix, P3P)", ctx->model_type);
     ctx->Mpad = ((S + 255) / 256) * 256;
     PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 3 * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
@@ -555,7 +604,7 @@ int solve_minimal_sampled_launch(pgx_ctx* ctx, int sampler, uint64_t key, uint32
     int m = 0;
     switch (ctx->model_type) {
     case kLine2D: case kVanishingPoint: m = 2; break;
-    case kPnP: m = 3; break;
+    case kPnP: case kPlane3D: m = 3; break;
     case kHomography: m = 4; break;
     case kFundamental: m = 7; break;
     default: return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: no device solver for model type %d", ctx->model_type);

@@ -1,10 +1,11 @@
 """pyprogressivex — drop-in replacement of the reference's pybind11 module
 (/root/reference/src/pyprogressivex/src/bindings.cpp:394-494) on top of libpgx.so (HIP, gfx950).
 
-The five entry points keep the reference's names, argument order, defaults, return layout and error messages.
+The five entry points keep the reference's names, argument order, defaults, return layout and error messages;
+findPlanes (3-D point clouds) is the same pipeline on a model type the reference does not have.
 """
-from ._api import (find6DPoses, findFundamentalMatrices, findHomographies, findLines, findTwoViewMotions,
+from ._api import (find6DPoses, findFundamentalMatrices, findHomographies, findLines, findPlanes, findTwoViewMotions,
                    findVanishingPoints)
 
 __all__ = ["find6DPoses", "findHomographies", "findTwoViewMotions", "findFundamentalMatrices", "findLines",
-           "findVanishingPoints"]
+           "findVanishingPoints", "findPlanes"]

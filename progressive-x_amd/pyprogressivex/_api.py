@@ -1,4 +1,4 @@
-"""The five entry points of the reference's pybind11 module, same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes, the same pipeline on 3-D point clouds), same names / argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -297,6 +297,46 @@ def findLines(points, weights, w, h, threshold=2.0, conf=0.5, spatial_coherence_
                              scoring_exponent=scoring_exponent, do_logging=False, seed=seed,
                              max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
     return _stack(est, models, 3), labels
+
+
+def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
+               neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
+               minimum_point_number=10, maximum_model_number=-1, sampler_id=2, scoring_exponent=2,
+               do_logging=False, *, seed=None, max_outer_iterations=10, neighborhood="flann_like",
+               local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+    """Multi-plane fitting of a 3-D point cloud (no reference counterpart: the findLines pipeline one dimension up).
+    points [n, 3]; returns (planes[K, 4] float64 (a, b, c, d) with (a, b, c) a unit normal, labels[n] int32) in findLines'
+    labelling convention.  threshold (point-to-plane distance) and neighborhood_ball_radius are in the cloud's own units: the
+    defaults (5 cm, 50 cm) suit a metre-scale scene such as a depth-sensor or LiDAR frame.  `weights` [n], when given, weight
+    the least-squares refits.  Sampler ids: 0 uniform, 1 PROSAC (points ordered by quality), 2 NAPSAC on the neighbourhood graph
+    (the default), 3 Progressive NAPSAC on a grid over the bounding box (1 and 3 take the points as ordered by quality: their
+    first samples come from the first points); any other id prints to stderr and returns zero models, as the other entry
+    points do.  Large clouds: the compound score value - shared^scoring_exponent squares the support a candidate shares with
+    the accepted planes, whose slabs cross every patch, so with the default 2 that penalty grows with n^2 against a value that
+    grows with n and later planes lose to tilted partial ones (six-plane scenes at 10^5 points: scoring_exponent=1 recovers all
+    six, 2 three to five - DESIGN.md 4.5); minimum_point_number has to exceed the outliers a slab of width 3 x threshold
+    holds, or spurious planes through the outliers are accepted."""
+    points = _as_f64(points)
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 3:
+        raise ValueError("points should be an array with dims [n,3], n>=3")
+    n = points.shape[0]
+    w = None if weights is None else _weights(weights, n)
+    if do_logging and sampler_id == 1:
+        print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
+    est = _estimators.PlaneEstimator()
+    lo = points.min(axis=0)
+    ext = points.max(axis=0) - lo
+    ext = np.where(np.isfinite(ext) & (ext > 0), ext, 1.0)
+    grid_pts = np.ascontiguousarray(points - lo)            # P-NAPSAC's grid starts at the bounding box's corner
+    models, labels, _ = _run(est, points, points, neighborhood_ball_radius,
+                             _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
+                                              est.sample_size),
+                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                             scoring_exponent=scoring_exponent, do_logging=bool(do_logging), weights=w, seed=seed,
+                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+    return _stack(est, models, 4), labels
 
 
 def find6DPoses(x1y1, x2y2z2, K, threshold=4.0, conf=0.90, spatial_coherence_weight=0.1,

@@ -219,6 +219,73 @@ class LineEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 3-D plane (findPlanes; no reference counterpart): the line estimator one dimension up
+# ---------------------------------------------------------------------------------------------------------------------
+class PlaneEstimator(Estimator):
+    model_type = _lib.PLANE3D
+    sample_size = 3
+    nonminimal_sample_size = 3
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
+    cols = 4
+
+    def minimal(self, pts, samples):
+        """samples [S, 3] -> unit-normal planes (a, b, c, d), bitwise csrc/solve.hip's solve_plane_kernel: n = u x v in cross3's
+        component order, ln = sqrt((n0 n0 + n1 n1) + n2 n2), (a, b, c) = n / ln, d = -((a x0 + b y0) + c z0).  Collinear or
+        coincident samples (ln == 0) give no model."""
+        p0, p1, p2 = pts[samples[:, 0]], pts[samples[:, 1]], pts[samples[:, 2]]
+        u, v = p1 - p0, p2 - p0
+        n0 = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
+        n1 = -(u[:, 0] * v[:, 2] - u[:, 2] * v[:, 0])
+        n2 = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
+        ln = np.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+        ok = ln > 0
+        ln = np.where(ok, ln, 1.0)
+        a, b, c = n0 / ln, n1 / ln, n2 / ln
+        d = -((a * p0[:, 0] + b * p0[:, 1]) + c * p0[:, 2])
+        models = np.column_stack([a, b, c, d])
+        return models[ok], np.nonzero(ok)[0]
+
+    def _normal(self, scatter):
+        """smallest eigenvectors of the 3x3 scatter matrices [B, 3, 3] (all finite) -> [B, 3]"""
+        if self.refit_solver == "jacobi":
+            return self._smallest(scatter)
+        return np.linalg.eigh(scatter)[1][:, :, 0]
+
+    def _fit(self, init):
+        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,x,y,z][1,x,y,z]^T
+        W = G[0, 0]
+        if cnt < 3 or not W > 0:
+            return []
+        mean = G[0, 1:] / W
+        scatter = G[1:, 1:] - W * np.outer(mean, mean)                          # weighted scatter about the mean
+        if not np.isfinite(scatter).all():
+            return []
+        nrm = self._normal(scatter[None])[0]
+        return [np.array([nrm[0], nrm[1], nrm[2], -nrm @ mean])]
+
+    def _fit_many(self, gram, B, inits):
+        """`_fit` for B items at once: one Gram launch, stacked 3x3 eigen-solves (bitwise the single-call models)."""
+        out = [[] for _ in range(B)]
+        G, cnt, _ = gram(_lib.GRAM_AFFINE, None, True, 1, np.arange(B))
+        W = G[:, 0, 0]
+        idx = np.nonzero((np.asarray(cnt) >= 3) & (W > 0))[0]
+        if idx.size == 0:
+            return out
+        Wk = W[idx]
+        mean = G[idx, 0, 1:] / Wk[:, None]
+        scatter = G[idx][:, 1:, 1:] - Wk[:, None, None] * (mean[:, :, None] * mean[:, None, :])
+        ok = np.isfinite(scatter).all(axis=(1, 2))
+        if not ok.any():
+            return out
+        nrms = self._normal(scatter[ok])
+        for k, b in enumerate(idx[ok]):
+            nrm = nrms[k]
+            m = mean[ok][k]
+            out[b] = [np.array([nrm[0], nrm[1], nrm[2], -nrm @ m])]
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # vanishing point: solver_vanishing_point_two_lines.h (in-tree, exact restatement)
 # ---------------------------------------------------------------------------------------------------------------------
 class VanishingPointEstimator(Estimator):

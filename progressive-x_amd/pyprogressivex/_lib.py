@@ -16,9 +16,9 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PGX_LIBPGX") or os.path.join(_HERE, "libpgx.so")   # PGX_LIBPGX: A/B of kernel builds
 
-LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM = range(6)
-POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4}
-PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18}
+LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM, PLANE3D = range(7)
+POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4, 6: 3}
+PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18, 6: 4}
 FIXED_ONE = float(1 << 32)
 UNIQUE_ID_BYTES = 128
 
@@ -479,11 +479,11 @@ class Context:
         return off, idx[:arcs], mult[:arcs]
 
     def solve_minimal(self, samples, fetch=True):
-        """pgx_solve_minimal: hypotheses of the 2-point line / 2-segment vanishing point solvers, generated from the
+        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, ...), generated from the
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)
-        want = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3}.get(self.model_type, 2)
+        want = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3}.get(self.model_type, 2)
         if smp.ndim != 2 or smp.shape[1] != want:
             raise ValueError(f"samples must be [S,{want}]")
         rows = smp.shape[0] * {FUNDAMENTAL: 3, PNP: 4}.get(self.model_type, 1)   # root slots per 7-point / P3P sample
@@ -497,7 +497,7 @@ class Context:
         """pgx_solve_minimal_sampled: S minimal samples drawn on the device by the in-repo generator (_rng.py gives the same rows:
         sampler "uniform", "napsac" on the resident neighbourhood graph, or "prosac" with the table of sampler_prosac_set) and solved into the resident hypothesis buffer.
         Returns (models or None, samples or None)."""
-        m = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3}.get(self.model_type, 2)
+        m = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3}.get(self.model_type, 2)
         rows = int(S) * {FUNDAMENTAL: 3, PNP: 4}.get(self.model_type, 1)
         out = np.empty((rows, PARAM_DIM[self.model_type]), dtype=np.float64) if fetch else None
         smp = np.empty((int(S), m), dtype=np.int32) if fetch_samples else None

@@ -59,6 +59,30 @@ def make_lines(n_per_line=500, n_lines=3, n_outliers=500, sigma=0.5, size=1000.0
     return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(models)
 
 
+def make_planes(n_per_plane=8000, n_planes=6, n_outliers=48000, sigma=0.01, size=10.0, patch=4.0, seed=0):
+    """findPlanes' workload: K planes with uniformly random unit normals through a patch centre drawn in the middle of the box
+    [0, size]^3; the inliers of plane k lie on a square patch (side `patch`, random in-plane orientation) around the centre with
+    Gaussian noise of `sigma` along the normal; the outliers are uniform in the box.  Returns (points [n, 3], labels [n]
+    (k + 1 = plane k, 0 = outlier), gt_planes [K, 4] = (a, b, c, d) with (a, b, c) a unit normal)."""
+    rng = np.random.default_rng(seed)
+    pts, labels, models = [], [], []
+    for k in range(n_planes):
+        nrm = rng.normal(size=3)
+        nrm /= np.linalg.norm(nrm)
+        centre = rng.uniform(0.3 * size, 0.7 * size, 3)
+        e1 = np.cross(nrm, rng.normal(size=3))
+        e1 /= np.linalg.norm(e1)
+        e2 = np.cross(nrm, e1)
+        st = rng.uniform(-0.5 * patch, 0.5 * patch, (n_per_plane, 2))
+        p = centre + st[:, :1] * e1 + st[:, 1:] * e2 + rng.normal(0, sigma, n_per_plane)[:, None] * nrm
+        pts.append(p)
+        labels.append(np.full(n_per_plane, k + 1))
+        models.append(np.array([nrm[0], nrm[1], nrm[2], -nrm @ centre]))
+    pts.append(rng.uniform(0, size, (n_outliers, 3)))
+    labels.append(np.zeros(n_outliers, dtype=int))
+    return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(models)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # C2  multi-homography
 # ---------------------------------------------------------------------------------------------------------------------
@@ -273,4 +297,4 @@ def misclassification_models(preferences, annotation, K_annot):
 
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
-                   vanishing_point=_lib.VANISHING_POINT)
+                   vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D)
