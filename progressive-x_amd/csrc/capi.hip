@@ -884,6 +884,16 @@ int pgx_set_weights(pgx_ctx* ctx, const double* weights, int64_t len)
     return PGX_OK;
 }
 
+int pgx_set_radius_range(pgx_ctx* ctx, double rmin, double rmax)
+{
+    CTX_GUARD(ctx);
+    if (!(rmin >= 0.0) || !(rmax >= rmin))   // also NaN
+        return fail(ctx, PGX_ERR_INVALID, "pgx_set_radius_range: need 0 <= rmin <= rmax (got %g, %g)", rmin, rmax);
+    ctx->rmin = rmin;
+    ctx->rmax = rmax;
+    return PGX_OK;
+}
+
 int pgx_gram(pgx_ctx* ctx, int kind, const double* params, int nparams, int sel, const int32_t* index, int64_t m, int label,
              int use_weights, int weight_power, double* out, int64_t* count, int64_t* bad)
 {

@@ -60,6 +60,7 @@ struct GenDltH { static constexpr int Q = 9, D = 4; };
 struct GenEpiF { static constexpr int Q = 9, D = 4; };
 struct GenVp { static constexpr int Q = 3, D = 4; };
 struct GenPnpGn { static constexpr int Q = 7, D = 5; };
+struct GenSphere { static constexpr int Q = 5, D = 3; };
 
 template <class G>
 __device__ __forceinline__ void emit(const double* pt, const FitParams& prm, Acc<G::Q>& acc, double w, int& bad);
@@ -134,6 +135,15 @@ __device__ __forceinline__ void emit<GenPnpGn>(const double* pt, const FitParams
     const double jv[7] = {a * (-rz) + c * ry, c * (-rx), a * rx, 0.0, a, c, dv};
     acc.add(ju, w);
     acc.add(jv, w);
+}
+
+// prm = (ox, oy, oz, s): the algebraic sphere row (1, u, v, w, (u u + v v) + w w) of (u, v, w) = (p - o) / s
+template <>
+__device__ __forceinline__ void emit<GenSphere>(const double* pt, const FitParams& prm, Acc<5>& acc, double w, int&)
+{
+    const double u = (pt[0] - prm.v[0]) / prm.v[3], v = (pt[1] - prm.v[1]) / prm.v[3], z = (pt[2] - prm.v[2]) / prm.v[3];
+    const double a[5] = {1.0, u, v, z, (u * u + v * v) + z * z};
+    acc.add(a, w);
 }
 
 template <class G>
@@ -545,6 +555,7 @@ static int gram_row_length(pgx_ctx* ctx, const char* who, int kind, int nparams,
     case PGX_GRAM_DLT_H: case PGX_GRAM_EPI_F: *q = 9; if (D != 4 || nparams != 6) return fail(ctx, PGX_ERR_INVALID, "%s: needs 4-D correspondences and 6 normalisation parameters", who); break;
     case PGX_GRAM_VP: *q = 3; if (D != 4) return fail(ctx, PGX_ERR_INVALID, "%s: needs 4-D segments", who); break;
     case PGX_GRAM_PNP_GN: *q = 7; if (D != 5 || nparams != 12) return fail(ctx, PGX_ERR_INVALID, "%s: needs 5-D 2D-3D rows and a 3x4 pose", who); break;
+    case PGX_GRAM_SPHERE: *q = 5; if (D != 3 || nparams != 4) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 4 parameters (ox, oy, oz, s)", who); break;
     default: return fail(ctx, PGX_ERR_INVALID, "%s: unknown row kind %d", who, kind);
     }
     return PGX_OK;
@@ -592,6 +603,7 @@ int gram_batch_launch(pgx_ctx* ctx, int kind, const double* params, int nparams,
     case PGX_GRAM_DLT_H: launch_batch<GenDltH>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
     case PGX_GRAM_EPI_F: launch_batch<GenEpiF>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
     case PGX_GRAM_VP: launch_batch<GenVp>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
+    case PGX_GRAM_SPHERE: launch_batch<GenSphere>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
     default: launch_batch<GenPnpGn>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
     }
     PGX_HIP(ctx, hipGetLastError());
@@ -654,6 +666,7 @@ int gram_labels_launch(pgx_ctx* ctx, int kind, const double* params, int nparams
     case PGX_GRAM_DLT_H: launch_labels<GenDltH>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
     case PGX_GRAM_EPI_F: launch_labels<GenEpiF>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
     case PGX_GRAM_VP: launch_labels<GenVp>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
+    case PGX_GRAM_SPHERE: launch_labels<GenSphere>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
     default: launch_labels<GenPnpGn>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
     }
     PGX_HIP(ctx, hipGetLastError());
@@ -686,6 +699,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
     case PGX_GRAM_DLT_H: case PGX_GRAM_EPI_F: q = 9; if (D != 4 || nparams != 6) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 4-D correspondences and 6 normalisation parameters"); break;
     case PGX_GRAM_VP: q = 3; if (D != 4) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 4-D segments"); break;
     case PGX_GRAM_PNP_GN: q = 7; if (D != 5 || nparams != 12) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 5-D 2D-3D rows and a 3x4 pose"); break;
+    case PGX_GRAM_SPHERE: q = 5; if (D != 3 || nparams != 4) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 3-D points and 4 parameters (ox, oy, oz, s)"); break;
     default: return fail(ctx, PGX_ERR_INVALID, "pgx_gram: unknown row kind %d", kind);
     }
     const int nv = q * (q + 1) / 2;
@@ -743,6 +757,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
     case PGX_GRAM_DLT_H: launch<GenDltH>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
     case PGX_GRAM_EPI_F: launch<GenEpiF>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
     case PGX_GRAM_VP: launch<GenVp>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
+    case PGX_GRAM_SPHERE: launch<GenSphere>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
     default: launch<GenPnpGn>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
     }
     PGX_HIP(ctx, hipGetLastError());

@@ -44,6 +44,7 @@ struct pgx_ctx {
     pgx::DevBuf pts32;       // N x 8 f32: coordinates + filter scale (FP32 pre-filter)
     double umax = 0.0;       // max |observed image coordinate| over all points
     double fscale = 0.0;     // max(1, max |coordinate|) over all points: isotropic pre-scaling of the minimal solvers
+    double rmin = 0.0, rmax = __builtin_inf();   // pgx_set_radius_range: the sphere solver's accepted radii (context state)
     int filter_enabled = 1;  // PGX_NO_FILTER: 1 = no rejection filter, 2 = FP64 filter only (A/B, debugging)
     int last_score_filtered = 0;
     int last_score_path = 0;       // 1 = chunked kernel (every pair visited), 2 = cull + group-major

@@ -137,6 +137,7 @@ int preference_launch(pgx_ctx* ctx, const double* model, double T2, double* d_pr
     case kVanishingPoint: r = preference_dispatch<kVanishingPoint>(ctx, mdl, T2, d_pref, blocks); break;
     case kHomographySym: r = preference_dispatch<kHomographySym>(ctx, mdl, T2, d_pref, blocks); break;
     case kPlane3D: r = preference_dispatch<kPlane3D>(ctx, mdl, T2, d_pref, blocks); break;
+    case kSphere3D: r = preference_dispatch<kSphere3D>(ctx, mdl, T2, d_pref, blocks); break;
     default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
     }
     PGX_TRY(r);
@@ -228,6 +229,7 @@ int unary_launch(pgx_ctx* ctx, int K, double threshold, double lambda)
     case kVanishingPoint: hipLaunchKernelGGL((unary_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
     case kHomographySym: hipLaunchKernelGGL((unary_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
     case kPlane3D: hipLaunchKernelGGL((unary_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
+    case kSphere3D: hipLaunchKernelGGL((unary_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
     default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
     }
     PGX_HIP(ctx, hipGetLastError());
@@ -361,6 +363,7 @@ int gc_labeling_launch(pgx_ctx* ctx, const double* model, double T2, double lamb
     case kVanishingPoint: hipLaunchKernelGGL((gc_energy_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
     case kHomographySym: hipLaunchKernelGGL((gc_energy_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
     case kPlane3D: hipLaunchKernelGGL((gc_energy_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
+    case kSphere3D: hipLaunchKernelGGL((gc_energy_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
     default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
     }
     PGX_HIP(ctx, hipGetLastError());
@@ -541,6 +544,7 @@ int residual_sums_launch(pgx_ctx* ctx, const double* models, int K, double* sums
     case kVanishingPoint: hipLaunchKernelGGL((residual_sums_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
     case kHomographySym: hipLaunchKernelGGL((residual_sums_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
     case kPlane3D: hipLaunchKernelGGL((residual_sums_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
+    case kSphere3D: hipLaunchKernelGGL((residual_sums_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
     default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
     }
     PGX_HIP(ctx, hipGetLastError());
@@ -572,6 +576,7 @@ int residual_sum_launch(pgx_ctx* ctx, const double* model, int label, double* su
     case kVanishingPoint: hipLaunchKernelGGL((residual_sum_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
     case kHomographySym: hipLaunchKernelGGL((residual_sum_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
     case kPlane3D: hipLaunchKernelGGL((residual_sum_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
+    case kSphere3D: hipLaunchKernelGGL((residual_sum_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
     default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
     }
     PGX_HIP(ctx, hipGetLastError());

@@ -1,4 +1,4 @@
-// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and 3-D planes, gfx950 device code.
+// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types, 3-D planes and spheres, gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -14,7 +14,7 @@ namespace pgx {
 
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
-    kNumModelTypes = 7
+    kSphere3D = 8, kNumModelTypes = 9   // 7 is not assigned (pgx_model_dims(7) is an error)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -144,11 +144,28 @@ template <> struct Residual<kPlane3D> {
     }
 };
 
-// Host-side dims table (same numbers as the functors above).
+// 3-D spheres (findSpheres; no reference counterpart): model (cx, cy, cz, r), dx = x - cx, dy = y - cy, dz = z - cz,
+// r = |sqrt((dx dx + dy dy) + dz dz) - cr|, summed left to right, plain IEEE sqrt (no intrinsic, no contraction).  This
+// operation order is the contract of every sphere check (tests restate it in numpy).
+template <> struct Residual<kSphere3D> {
+    static constexpr int D = 3, P = 4;
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        const double dx = p[0] - m[0], dy = p[1] - m[1], dz = p[2] - m[2];
+        return fabs(sqrt((dx * dx + dy * dy) + dz * dz) - m[3]);
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double r = plain(p, m);
+        return r * r;
+    }
+};
+
+// Host-side dims table (same numbers as the functors above; 0 = no such model type).
 inline int model_dims(int mt, int* d, int* p) {
-    static const int D[kNumModelTypes] = {2, 4, 4, 5, 4, 4, 3};
-    static const int P[kNumModelTypes] = {3, 9, 9, 12, 3, 18, 4};
-    if (mt < 0 || mt >= kNumModelTypes) return -1;
+    static const int D[kNumModelTypes] = {2, 4, 4, 5, 4, 4, 3, 0, 3};
+    static const int P[kNumModelTypes] = {3, 9, 9, 12, 3, 18, 4, 0, 4};
+    if (mt < 0 || mt >= kNumModelTypes || D[mt] == 0) return -1;
     if (d) *d = D[mt];
     if (p) *p = P[mt];
     return 0;

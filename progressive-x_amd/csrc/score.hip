@@ -692,9 +692,9 @@ static int score_dispatch(pgx_ctx* ctx, double T2, int has_compound, int want_ma
         filt32 = ctx->filter_enabled == 1 && T > 0.0 && std::isfinite(T) && T2 < 1e30;
     if constexpr (MT == kHomography || MT == kHomographySym)   // explicit per-pair error terms, no global guard (Filter32<kHomography>)
         filt32 = ctx->filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24;
-    if constexpr (MT == kLine2D || MT == kPlane3D) {   // per-pair error term, no global guard; T'' must be an ordinary f32
+    if constexpr (MT == kLine2D || MT == kPlane3D || MT == kSphere3D) {   // per-pair error term, no global guard; T'' must be an ordinary f32
         filt32 = ctx->filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24 && std::isfinite(ctx->fscale);
-        guard32 = ctx->fscale;             // Filter32<kLine2D / kPlane3D>::prep: overflow guard (fscale >= 1)
+        guard32 = ctx->fscale;             // Filter32<kLine2D / kPlane3D / kSphere3D>::prep: overflow guard (fscale >= 1)
     }
     if constexpr (MT == kFundamental) {    // likewise; the bounds on T keep T2 * D~^2 (D~ >= 1e-12) inside the f32 normal range
         filt32 = ctx->filter_enabled == 1 && T2 > 1e-12 && T2 < 1e12 && std::isfinite(ctx->fscale);
@@ -1055,6 +1055,7 @@ static int score_launch_typed(pgx_ctx* ctx, double T2, int has_compound, int wan
     case kVanishingPoint: return score_dispatch<kVanishingPoint>(ctx, T2, has_compound, want_masks);
     case kHomographySym: return score_dispatch<kHomographySym>(ctx, T2, has_compound, want_masks);
     case kPlane3D: return score_dispatch<kPlane3D>(ctx, T2, has_compound, want_masks);
+    case kSphere3D: return score_dispatch<kSphere3D>(ctx, T2, has_compound, want_masks);
     default: return fail(ctx, PGX_ERR_INVALID, "pgx_score: bad model type %d", ctx->model_type);
     }
 }

@@ -548,4 +548,69 @@ template <> struct Filter32<kPlane3D> {
     }
 };
 
+// ---- 3-D spheres: r = |sqrt((dx dx + dy dy) + dz dz) - cr| (Residual<kSphere3D>), inlier iff r^2 < T2 -------------------------------
+// Not homogeneous in the model (the centre is a point, the radius a length): no power-of-two scaling, the f32 copies are the model's
+// entries rounded once.  Per point, in f32: d~ = p~ - c~, q~ = fma(dx, dx, fma(dy, dy, dz dz)), s~ = sqrtf(q~), n~ = s~ - r~.  With
+// u = 2^-24, eta = 2^-126, s* = |p - c| (exact), P = max(|x|, |y|, |z|, 1) rounded up, |.| the Euclidean norm:
+//   inputs     |p~ - p| <= u |p| <= sqrt(3) u P,  |c~ - c| <= u |c|,  |r~ - cr| <= u |cr|
+//   d~         one rounding per component: |d~ - (p~ - c~)| <= u |p~ - c~| <= u s* + O(u^2)
+//   q~         three non-negative terms, at most three roundings each: q~ = |d~|^2 (1 + t), |t| <= 3 u + O(u^2) -> sqrt: 1.5 u
+//   sqrtf      gfx950 lowers sqrtf (no fast-math) to v_sqrt_f32 plus a correction step and a denormal scaling; the budget takes
+//              only v_sqrt_f32's documented 1 ulp = 2 u (correct rounding would be u)
+//   exact path d, q, sqrt and the final subtraction in f64: <= 3.5 * 2^-53 s* + 2^-53 |s_c - cr|  (~0.25 u s*, and the 2^-53 term
+//              is part of the T'' margin below)
+// so |(s~ - r~) - (s_c - cr)| <= sqrt(3) u P + u (|c| + |cr|) + (1 + 1.5 + 2 + 0.25) u s* + O(u^2).  Underflow: the squares and
+// sums below 2^-126 carry absolute errors <= eta each (even with denormals flushed), which move sqrt by <= sqrt(4 eta) < 2.2e-19.
+// The budget rounds every coefficient up by more than 10 % (which also pays for evaluating E itself in f32, and for the rounding of
+// n~, u |s~ - r~| <= u s~ + u |cr|):
+//   E = e1 P + e0 + e2 s~,   e1 = 2 u,   e0 = 2 u (|c| + |cr|) + 1e-18,   e2 = 8 u     (s~ for s*: the difference is O(u))
+//   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  m is rounded once and monotonically, so |s_c - cr| > T (1 + 2^-7), and the
+//   computed r_c^2 = fl(fl(|s_c - cr|)^2) > T2.
+// Group test on the 3-D ball (stored centre g, radius rho, Pmax) of 64 Morton-consecutive points (sp_line_bounds_kernel<SPAN, 3>):
+// every member's distance to the centre lies in [s_g - rho, s_g + rho] with s_g = |g - c| (g is an f32 value, no input rounding),
+// so its residual is at least the distance from r to that interval, |s_g - cr| - rho, less the errors above with P = Pmax and
+// s* <= s_g + rho:
+//   reject the group  <=>  |s~_g - r~| - E(Pmax, s~_g + rho) - 1.001 rho > 1.001 T''.
+// One rule for points outside the shell, inside it and for r < 0 (then every residual is s + |r|).  A NaN entry culls the hypothesis
+// (all four enter every residual).  A set with coordinates beyond 1e17, a centre or radius beyond 1e17 (q~ must stay below the f32
+// overflow) or a threshold outside the ordinary f32 range gives E = inf: never rejected, the exact path decides (r = inf included:
+// inf - inf is NaN, and a NaN comparison is false).  Scenes far from the origin lose the filter's precision (e1 P grows with the
+// offset, not with the scene): correct, only slower.
+template <> struct Filter32<kSphere3D> {
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    struct Lane { float cx, cy, cz, r, e1, e0, e2, tpp, nanh; };
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        ln.cx = (float)m[0]; ln.cy = (float)m[1]; ln.cz = (float)m[2]; ln.r = (float)m[3];
+        ln.nanh = (m[0] == m[0] && m[1] == m[1] && m[2] == m[2] && m[3] == m[3]) ? 0.0f : 1.0f;
+        const double Ts = sqrt(T2);
+        const double cn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
+        const bool big = !(pscale <= 1e17) || !(cn <= 1e17) || !(fabs(m[3]) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30);
+        const double u = 5.9604644775390625e-8;
+        ln.e1 = f32_up(2.0 * u);
+        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * (cn + fabs(m[3])) + 1e-18);
+        ln.e2 = f32_up(8.0 * u);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        return ln;
+    }
+    static __device__ __forceinline__ float dist(const float* p, const Lane& ln) {
+        const float dx = p[0] - ln.cx, dy = p[1] - ln.cy, dz = p[2] - ln.cz;
+        return sqrtf(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz)));
+    }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        const float s = dist(p, ln);
+        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, p[5], ln.e0) + ln.e2 * s);
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (cx, cy, cz, rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;
+        const float s = dist(g, ln);
+        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, g[4], ln.e0) + ln.e2 * (s + g[3])) - g[3] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
 }  // namespace pgx

@@ -21,6 +21,10 @@
 //   3-D plane through three points      findPlanes' minimal solver (no reference counterpart): n = (p1 - p0) x (p2 - p0) in
 //                                       cross3's component order, ln = sqrt(n . n), (a, b, c) = n / ln,
 //                                       d = -((a x0 + b y0) + c z0); collinear or coincident points (ln == 0) give NaN
+//   3-D sphere through four points      findSpheres' minimal solver (no reference counterpart): the centre offset e from p0
+//                                       solves a_i . e = |a_i|^2 / 2 (a_i = p_i - p0) by Cramer's rule on cross products;
+//                                       coplanar points (det == 0), non-finite values and radii outside the context's
+//                                       pgx_set_radius_range give NaN
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
 // inlier; the caller drops it (the reference's solvers return "no model").
@@ -110,6 +114,52 @@ __global__ __launch_bounds__(kSolveBlock) void solve_plane_kernel(const double* 
             m[1] = nv[1] / ln;
             m[2] = nv[2] / ln;
             m[3] = -((m[0] * p0[0] + m[1] * p0[1]) + m[2] * p0[2]);
+        }
+    }
+    for (int k = 0; k < 4; ++k) models[(int64_t)s * 4 + k] = m[k];
+}
+
+// 4-point sphere: samples[S][4] -> S x 4 models (cx, cy, cz, r).  Operation order (the contract; SphereEstimator.minimal restates it):
+//   a_i = p_i - p0 (componentwise, i = 1..3), h_i = 0.5 ((a_i0 a_i0 + a_i1 a_i1) + a_i2 a_i2),
+//   n1 = cross3(a2, a3), n2 = cross3(a3, a1), n3 = cross3(a1, a2), det = (a1_0 n1_0 + a1_1 n1_1) + a1_2 n1_2,
+//   e_k = ((h1 n1_k + h2 n2_k) + h3 n3_k) / det, r = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2), c = p0 + e.
+// An index outside 0 .. n-1, det == 0 (coplanar or coincident points), a non-finite centre or radius, or r outside [rmin, rmax]
+// gives a NaN model.
+__global__ __launch_bounds__(kSolveBlock) void solve_sphere_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
+                                                                   int S, double rmin, double rmax, double* __restrict__ models,
+                                                                   int* __restrict__ perm, int Mpad)
+{
+    const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
+    if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
+    if (s >= S) return;
+    int ix[4];
+    bool inb = true;
+    for (int k = 0; k < 4; ++k) {
+        ix[k] = samples[4 * s + k];
+        inb = inb && ix[k] >= 0 && ix[k] < n;
+    }
+    double m[4];
+    const double nan = __builtin_nan("");
+    m[0] = m[1] = m[2] = m[3] = nan;
+    if (inb) {
+        const double* p0 = pts + (int64_t)ix[0] * 3;
+        double a[3][3], h[3];
+        for (int i = 0; i < 3; ++i) {
+            const double* pi = pts + (int64_t)ix[i + 1] * 3;
+            for (int k = 0; k < 3; ++k) a[i][k] = pi[k] - p0[k];
+            h[i] = 0.5 * ((a[i][0] * a[i][0] + a[i][1] * a[i][1]) + a[i][2] * a[i][2]);
+        }
+        double n1[3], n2[3], n3[3];
+        cross3(a[1][0], a[1][1], a[1][2], a[2][0], a[2][1], a[2][2], n1);
+        cross3(a[2][0], a[2][1], a[2][2], a[0][0], a[0][1], a[0][2], n2);
+        cross3(a[0][0], a[0][1], a[0][2], a[1][0], a[1][1], a[1][2], n3);
+        const double det = (a[0][0] * n1[0] + a[0][1] * n1[1]) + a[0][2] * n1[2];
+        double e[3];
+        for (int k = 0; k < 3; ++k) e[k] = ((h[0] * n1[k] + h[1] * n2[k]) + h[2] * n3[k]) / det;
+        const double r = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+        const double c[3] = {p0[0] + e[0], p0[1] + e[1], p0[2] + e[2]};
+        if (det != 0.0 && isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(r) && r >= rmin && r <= rmax) {
+            m[0] = c[0]; m[1] = c[1]; m[2] = c[2]; m[3] = r;
         }
     }
     for (int k = 0; k < 4; ++k) models[(int64_t)s * 4 + k] = m[k];
@@ -568,8 +618,24 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
         ctx->M = S; ctx->last_acc = nullptr;
         return PGX_OK;
     }
+    if (ctx->model_type == kSphere3D) {
+        ctx->Mpad = ((S + 255) / 256) * 256;
+        PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 4 * sizeof(double)));
+        PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
+        if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 4 * sizeof(int32_t)));
+        hipLaunchKernelGGL(solve_sphere_kernel, dim3((unsigned)((ctx->Mpad + kSolveBlock - 1) / kSolveBlock)), dim3(kSolveBlock), 0, ctx->stream,
+                           ctx->pts.as<double>(), ctx->n, ctx->scratch.as<int>(), S, ctx->rmin, ctx->rmax, ctx->models.as<double>(),
+                           ctx->perm.as<int>(), ctx->Mpad);
+        PGX_HIP(ctx, hipGetLastError());
+        if (models_out) {
+            PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)S * 4 * sizeof(double)));
+            PGX_TRY(sync_deliver(ctx));
+        }
+        ctx->M = S; ctx->last_acc = nullptr;
+        return PGX_OK;
+    }
     if (ctx->model_type != kLine2D && ctx->model_type != kVanishingPoint)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point homography, 7-point fundamental matrix, P3P)", ctx->model_type);
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 4-point homography, 7-point fundamental matrix, P3P)", ctx->model_type);
     ctx->Mpad = ((S + 255) / 256) * 256;
     PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 3 * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
@@ -605,7 +671,7 @@ int solve_minimal_sampled_launch(pgx_ctx* ctx, int sampler, uint64_t key, uint32
     switch (ctx->model_type) {
     case kLine2D: case kVanishingPoint: m = 2; break;
     case kPnP: case kPlane3D: m = 3; break;
-    case kHomography: m = 4; break;
+    case kHomography: case kSphere3D: m = 4; break;
     case kFundamental: m = 7; break;
     default: return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: no device solver for model type %d", ctx->model_type);
     }

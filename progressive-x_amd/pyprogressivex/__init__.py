@@ -2,10 +2,10 @@
 (/root/reference/src/pyprogressivex/src/bindings.cpp:394-494) on top of libpgx.so (HIP, gfx950).
 
 The five entry points keep the reference's names, argument order, defaults, return layout and error messages;
-findPlanes (3-D point clouds) is the same pipeline on a model type the reference does not have.
+findPlanes and findSpheres (3-D point clouds) are the same pipeline on model types the reference does not have.
 """
-from ._api import (find6DPoses, findFundamentalMatrices, findHomographies, findLines, findPlanes, findTwoViewMotions,
-                   findVanishingPoints)
+from ._api import (find6DPoses, findFundamentalMatrices, findHomographies, findLines, findPlanes, findSpheres,
+                   findTwoViewMotions, findVanishingPoints)
 
 __all__ = ["find6DPoses", "findHomographies", "findTwoViewMotions", "findFundamentalMatrices", "findLines",
-           "findVanishingPoints", "findPlanes"]
+           "findVanishingPoints", "findPlanes", "findSpheres"]

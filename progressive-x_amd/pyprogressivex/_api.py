@@ -1,4 +1,4 @@
-"""The five entry points of the reference's pybind11 module (and findPlanes, the same pipeline on 3-D point clouds), same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres, the same pipeline on 3-D point clouds), same names / argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -77,7 +77,10 @@ def _unknown_sampler(sampler_id):
 def _run(estimator, pts, graph_points, radius, sampler_factory, *, threshold, conf, spatial_coherence_weight,
          maximum_tanimoto_similarity, max_iters, minimum_point_number, maximum_model_number, scoring_exponent=2,
          do_logging=False, weights=None, seed=None, max_outer_iterations=10, neighborhood="flann_like",
-         local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+         local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack",
+         setup=None):
+    """setup(ctx), when given, runs on the context before anything else touches it (per-call context state such as findSpheres'
+    radius range)."""
     n = pts.shape[0]
     if sampler_rng not in ("numpy", "philox"):
         raise ValueError("sampler_rng should be 'numpy' or 'philox'")
@@ -89,6 +92,8 @@ def _run(estimator, pts, graph_points, radius, sampler_factory, *, threshold, co
         _unknown_sampler(sampler_factory.sampler_id)
         return [], np.zeros(n, dtype=np.int32), None
     ctx = _context()
+    if setup is not None:
+        setup(ctx)
     # multi-GPU, OPT-IN (distributed=True or PGX_MULTI_GPU=1, one process per GPU, WORLD_SIZE > 1): the proposal batches are
     # sharded over the ranks and the score triples all-gathered over RCCL (parallel.py); everything else runs replicated, so
     # every rank returns the same result.  Every rank must make this call with the same data (checked) and draw the same
@@ -100,7 +105,8 @@ def _run(estimator, pts, graph_points, radius, sampler_factory, *, threshold, co
             type(estimator).__name__, float(radius), getattr(sampler_factory, "sampler_id", None), float(threshold), float(conf),
             float(spatial_coherence_weight), float(maximum_tanimoto_similarity), int(max_iters), int(minimum_point_number),
             int(maximum_model_number), int(scoring_exponent), seed, int(max_outer_iterations), str(neighborhood),
-            str(local_optimization), str(labeling_l0), str(sampler_rng), getattr(estimator, "validity", None), str(pearl_abs), str(refit_solver)))
+            str(local_optimization), str(labeling_l0), str(sampler_rng), getattr(estimator, "validity", None), str(pearl_abs), str(refit_solver))
+            + ((tuple(float(v) for v in estimator.radius_range),) if hasattr(estimator, "radius_range") else ()))
         if seed is None:
             seed = parallel.shared_seed()
     rng = np.random.default_rng(seed)
@@ -299,6 +305,19 @@ def findLines(points, weights, w, h, threshold=2.0, conf=0.5, spatial_coherence_
     return _stack(est, models, 3), labels
 
 
+def _point_cloud(points, weights, n_min):
+    """the input checks of the 3-D point-cloud calls: points [n, 3] with n >= n_min, weights [n] or None; and Progressive NAPSAC's
+    grid, which starts at the bounding box's corner and spans its extents.  Returns (points, weights, grid points, extents)."""
+    points = _as_f64(points)
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < n_min:
+        raise ValueError(f"points should be an array with dims [n,3], n>={n_min}")
+    w = None if weights is None else _weights(weights, points.shape[0])
+    lo = points.min(axis=0)
+    ext = points.max(axis=0) - lo
+    ext = np.where(np.isfinite(ext) & (ext > 0), ext, 1.0)
+    return points, w, np.ascontiguousarray(points - lo), ext
+
+
 def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
                neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
                minimum_point_number=10, maximum_model_number=-1, sampler_id=2, scoring_exponent=2,
@@ -316,18 +335,10 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
     grows with n and later planes lose to tilted partial ones (six-plane scenes at 10^5 points: scoring_exponent=1 recovers all
     six, 2 three to five - DESIGN.md 4.5); minimum_point_number has to exceed the outliers a slab of width 3 x threshold
     holds, or spurious planes through the outliers are accepted."""
-    points = _as_f64(points)
-    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 3:
-        raise ValueError("points should be an array with dims [n,3], n>=3")
-    n = points.shape[0]
-    w = None if weights is None else _weights(weights, n)
+    points, w, grid_pts, ext = _point_cloud(points, weights, 3)
     if do_logging and sampler_id == 1:
         print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
     est = _estimators.PlaneEstimator()
-    lo = points.min(axis=0)
-    ext = points.max(axis=0) - lo
-    ext = np.where(np.isfinite(ext) & (ext > 0), ext, 1.0)
-    grid_pts = np.ascontiguousarray(points - lo)            # P-NAPSAC's grid starts at the bounding box's corner
     models, labels, _ = _run(est, points, points, neighborhood_ball_radius,
                              _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
                                               est.sample_size),
@@ -336,6 +347,46 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
                              minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
                              scoring_exponent=scoring_exponent, do_logging=bool(do_logging), weights=w, seed=seed,
                              max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+    return _stack(est, models, 4), labels
+
+
+def findSpheres(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
+                neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
+                minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
+                do_logging=False, *, radius_range=None, seed=None, max_outer_iterations=10, neighborhood="flann_like",
+                local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+    """Multi-sphere fitting of a 3-D point cloud (no reference counterpart: findPlanes' pipeline with a 4-point sphere solver and an
+    algebraic refit).  points [n, 3]; returns (spheres[K, 4] float64 (cx, cy, cz, r), labels[n] int32) in findPlanes' labelling
+    convention.  threshold bounds the distance from the sphere's surface, abs(|p - c| - r), in the cloud's units.  radius_range=(rmin, rmax)
+    (keyword-only; default: any radius) drops hypotheses and refits whose radius lies outside it.  Sampler ids as findPlanes', but
+    the default is 3, Progressive NAPSAC on a grid over the bounding box: NAPSAC (2) draws the seed's nearest neighbours, which at
+    scan densities lie a few point spacings apart, where the curvature across four points is below the noise and the minimal sphere
+    is close to random; the grid's cells span caps with usable curvature.  Samplers 3 and 1 take the points as ordered by quality (every
+proposal starts from the first points): shuffle a cloud that comes in scan order.  Like findPlanes, minimum_point_number has to exceed the
+    outliers a shell of width 3 x threshold holds."""
+    points, w, grid_pts, ext = _point_cloud(points, weights, 4)
+    if radius_range is None:
+        rmin, rmax = 0.0, np.inf
+    else:
+        try:
+            rmin, rmax = (float(v) for v in radius_range)
+        except (TypeError, ValueError):
+            raise ValueError("radius_range should be a pair (rmin, rmax)") from None
+        if not (rmin >= 0.0 and rmax >= rmin):
+            raise ValueError("radius_range should satisfy 0 <= rmin <= rmax (no NaN)")
+    if do_logging and sampler_id == 1:
+        print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
+    est = _estimators.SphereEstimator()
+    est.radius_range = (rmin, rmax)
+    models, labels, _ = _run(est, points, points, neighborhood_ball_radius,
+                             _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
+                                              est.sample_size),
+                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                             scoring_exponent=scoring_exponent, do_logging=bool(do_logging), weights=w, seed=seed,
+                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver,
+                             setup=lambda ctx: ctx.set_radius_range(rmin, rmax))
     return _stack(est, models, 4), labels
 
 

@@ -286,6 +286,75 @@ class PlaneEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 3-D sphere (findSpheres; no reference counterpart): 4-point minimal solver, algebraic refit on normalised coordinates
+# ---------------------------------------------------------------------------------------------------------------------
+def _cross3(a, b):
+    """csrc/solve.hip cross3's component order on [S, 3] arrays"""
+    return (a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], -(a[:, 0] * b[:, 2] - a[:, 2] * b[:, 0]), a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0])
+
+
+class SphereEstimator(Estimator):
+    model_type = _lib.SPHERE3D
+    sample_size = 4
+    nonminimal_sample_size = 4
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
+    cols = 4
+    radius_range = (0.0, np.inf)   # the radii a model may have (findSpheres sets it; the device solver reads pgx_set_radius_range)
+
+    def _in_range(self, r):
+        return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
+
+    def minimal(self, pts, samples):
+        """samples [S, 4] -> spheres (cx, cy, cz, r), bitwise csrc/solve.hip's solve_sphere_kernel: a_i = p_i - p0,
+        h_i = 0.5 ((a_i0 a_i0 + a_i1 a_i1) + a_i2 a_i2), n1 = a2 x a3, n2 = a3 x a1, n3 = a1 x a2 in cross3's component order,
+        det = (a1_0 n1_0 + a1_1 n1_1) + a1_2 n1_2, e_k = ((h1 n1_k + h2 n2_k) + h3 n3_k) / det, r = sqrt((e0 e0 + e1 e1) + e2 e2),
+        c = p0 + e.  Coplanar or coincident samples (det == 0), non-finite values and radii outside radius_range give no model."""
+        p0 = pts[samples[:, 0]]
+        a = [pts[samples[:, i]] - p0 for i in (1, 2, 3)]
+        h = [0.5 * ((ai[:, 0] * ai[:, 0] + ai[:, 1] * ai[:, 1]) + ai[:, 2] * ai[:, 2]) for ai in a]
+        n1, n2, n3 = _cross3(a[1], a[2]), _cross3(a[2], a[0]), _cross3(a[0], a[1])
+        det = (a[0][:, 0] * n1[0] + a[0][:, 1] * n1[1]) + a[0][:, 2] * n1[2]
+        with np.errstate(all="ignore"):
+            e = [((h[0] * n1[k] + h[1] * n2[k]) + h[2] * n3[k]) / det for k in range(3)]
+            r = np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
+            models = np.column_stack([p0[:, 0] + e[0], p0[:, 1] + e[1], p0[:, 2] + e[2], r])
+            ok = (det != 0) & np.isfinite(models).all(axis=1) & self._in_range(r)
+        return models[ok], np.nonzero(ok)[0]
+
+    def _fit(self, init):
+        """Algebraic sphere fit in two Gram passes: the weighted mean o and the RMS distance s from it (GRAM_AFFINE), then the
+        smallest eigenvector theta of the Gram matrix of the rows (1, u, v, w, |(u, v, w)|^2), (u, v, w) = (p - o) / s
+        (GRAM_SPHERE): theta0 + theta1..3 . q + theta4 |q|^2 = 0 is the sphere |q + b|^2 = |b|^2 - theta0 / theta4 with
+        b = theta1..3 / (2 theta4), so c = o - s b and r = s sqrt(|b|^2 - theta0 / theta4).  The normalisation keeps the 5x5
+        matrix well conditioned for scenes far from the origin.  `init` is not used."""
+        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,x,y,z][1,x,y,z]^T
+        W = G[0, 0]
+        if cnt < 4 or not W > 0:
+            return []
+        o = G[0, 1:] / W
+        scatter = G[1:, 1:] - W * np.outer(o, o)
+        s = np.sqrt(np.trace(scatter) / W)
+        if not (np.isfinite(o).all() and s > 0 and np.isfinite(s)):
+            return []
+        G, _, _ = yield (_lib.GRAM_SPHERE, np.array([o[0], o[1], o[2], s]), True, 1)
+        if not np.isfinite(G).all():
+            return []
+        th = self._smallest(G[None])[0]
+        A = th[4]
+        if A == 0:
+            return []
+        b = th[1:4] / (2.0 * A)
+        rad = b @ b - th[0] / A
+        if not rad > 0:
+            return []
+        r = s * np.sqrt(rad)
+        c = o - s * b
+        if not (np.isfinite(c).all() and np.isfinite(r) and self._in_range(r)):
+            return []
+        return [np.array([c[0], c[1], c[2], r])]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # vanishing point: solver_vanishing_point_two_lines.h (in-tree, exact restatement)
 # ---------------------------------------------------------------------------------------------------------------------
 class VanishingPointEstimator(Estimator):

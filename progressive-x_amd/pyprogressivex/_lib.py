@@ -17,8 +17,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PGX_LIBPGX") or os.path.join(_HERE, "libpgx.so")   # PGX_LIBPGX: A/B of kernel builds
 
 LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM, PLANE3D = range(7)
-POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4, 6: 3}
-PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18, 6: 4}
+SPHERE3D = 8                   # (7 is not assigned: include/pgx.h)
+POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4, 6: 3, 8: 3}
+PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18, 6: 4, 8: 4}
 FIXED_ONE = float(1 << 32)
 UNIQUE_ID_BYTES = 128
 
@@ -29,7 +30,7 @@ ABI_SYMBOLS = [
     "pgx_set_points", "pgx_set_compound", "pgx_get_compound",
     "pgx_score", "pgx_score_upload", "pgx_score_launch", "pgx_score_fetch", "pgx_score_algorithmic_bytes", "pgx_score_stats", "pgx_score_profile", "pgx_score_kernel_times", "pgx_score_debug_fetch", "pgx_score_debug_geometry",
     "pgx_preference", "pgx_get_preference", "pgx_compound_update",
-    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal",
+    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range",
     "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch",
     "pgx_bucket", "pgx_residual_sum", "pgx_gc_labeling", "pgx_gc_inliers", "pgx_epipolar_support", "pgx_gram_batch", "pgx_gram_labels", "pgx_residual_sums", "pgx_pnp_refine_batch",
     "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_barrier", "pgx_comm_allreduce_max_f64",
@@ -40,8 +41,8 @@ ABI_SYMBOLS = [
 
 
 GRAPH_KNN_IN_BALL, GRAPH_BALL, GRAPH_KNN = 0, 1, 2
-GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN = 0, 1, 2, 3, 4
-GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7}   # GRAM_AFFINE: point dimension + 1
+GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE = 0, 1, 2, 3, 4, 5
+GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5}   # GRAM_AFFINE: point dimension + 1
 
 
 _TRIU = {}
@@ -269,6 +270,10 @@ class Context:
         self._ck(self._lib.pgx_set_weights(self._h, _ptr(w, C.c_double), C.c_int64(w.shape[0])), "pgx_set_weights")
         self._w_obj = weights
 
+    def set_radius_range(self, rmin=0.0, rmax=float("inf")):
+        """pgx_set_radius_range: the radii the 4-point sphere solver accepts (context state; [0, inf] at creation)"""
+        self._ck(self._lib.pgx_set_radius_range(self._h, C.c_double(float(rmin)), C.c_double(float(rmax))), "pgx_set_radius_range")
+
     def _use_weights(self, weights):
         """1 when `weights` (the same array object as last time, or a new one that is uploaded now) is to be used.  The
         arrays are treated as immutable: a caller that edits its weights in place calls set_weights again."""
@@ -479,11 +484,11 @@ class Context:
         return off, idx[:arcs], mult[:arcs]
 
     def solve_minimal(self, samples, fetch=True):
-        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, ...), generated from the
+        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, ...), generated from the
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)
-        want = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3}.get(self.model_type, 2)
+        want = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3, SPHERE3D: 4}.get(self.model_type, 2)
         if smp.ndim != 2 or smp.shape[1] != want:
             raise ValueError(f"samples must be [S,{want}]")
         rows = smp.shape[0] * {FUNDAMENTAL: 3, PNP: 4}.get(self.model_type, 1)   # root slots per 7-point / P3P sample
@@ -497,7 +502,7 @@ class Context:
         """pgx_solve_minimal_sampled: S minimal samples drawn on the device by the in-repo generator (_rng.py gives the same rows:
         sampler "uniform", "napsac" on the resident neighbourhood graph, or "prosac" with the table of sampler_prosac_set) and solved into the resident hypothesis buffer.
         Returns (models or None, samples or None)."""
-        m = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3}.get(self.model_type, 2)
+        m = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3, SPHERE3D: 4}.get(self.model_type, 2)
         rows = int(S) * {FUNDAMENTAL: 3, PNP: 4}.get(self.model_type, 1)
         out = np.empty((rows, PARAM_DIM[self.model_type]), dtype=np.float64) if fetch else None
         smp = np.empty((int(S), m), dtype=np.int32) if fetch_samples else None

@@ -83,6 +83,44 @@ def make_planes(n_per_plane=8000, n_planes=6, n_outliers=48000, sigma=0.01, size
     return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(models)
 
 
+def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.5), coverage=1.0, seed=0):
+    """findSpheres' workload: K non-overlapping spheres with radii uniform in `radius` and centres inside the box [0, size]^3 (each
+    sphere lies wholly inside it); the inliers of sphere k are uniform on its surface - or, with coverage < 1, on the cap of that
+    fraction of the surface facing a random direction (what one depth scan sees of a ball) - with Gaussian noise of `sigma` along
+    the radius; the outliers are uniform in the box.  Returns (points [n, 3], labels [n] (k + 1 = sphere k, 0 = outlier),
+    gt_spheres [K, 4] = (cx, cy, cz, r))."""
+    rng = np.random.default_rng(seed)
+    if not 0.0 < coverage <= 1.0:
+        raise ValueError("coverage should lie in (0, 1]")
+    spheres = []
+    for _ in range(100000):
+        if len(spheres) == n_spheres:
+            break
+        r = rng.uniform(radius[0], radius[1])
+        c = rng.uniform(r, size - r, 3)
+        if all(np.linalg.norm(c - g[:3]) > r + g[3] for g in spheres):
+            spheres.append(np.array([c[0], c[1], c[2], r]))
+    if len(spheres) < n_spheres:
+        raise ValueError("cannot place that many non-overlapping spheres in the box")
+    pts, labels = [], []
+    for k, g in enumerate(spheres):
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        # uniform on the cap {d : d . axis >= 1 - 2 coverage} (area fraction = coverage): the height d . axis is uniform
+        t = rng.uniform(1.0 - 2.0 * coverage, 1.0, n_per_sphere)
+        phi = rng.uniform(0.0, 2.0 * np.pi, n_per_sphere)
+        e1 = np.cross(axis, rng.normal(size=3))
+        e1 /= np.linalg.norm(e1)
+        e2 = np.cross(axis, e1)
+        rho = np.sqrt(np.maximum(0.0, 1.0 - t * t))
+        d = t[:, None] * axis + (rho * np.cos(phi))[:, None] * e1 + (rho * np.sin(phi))[:, None] * e2
+        pts.append(g[:3] + d * (g[3] + rng.normal(0, sigma, n_per_sphere))[:, None])
+        labels.append(np.full(n_per_sphere, k + 1))
+    pts.append(rng.uniform(0, size, (n_outliers, 3)))
+    labels.append(np.zeros(n_outliers, dtype=int))
+    return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(spheres).reshape(-1, 4)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # C2  multi-homography
 # ---------------------------------------------------------------------------------------------------------------------
@@ -297,4 +335,4 @@ def misclassification_models(preferences, annotation, K_annot):
 
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
-                   vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D)
+                   vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D)
