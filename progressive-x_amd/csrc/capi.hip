@@ -267,8 +267,9 @@ int pgx_device_info(pgx_ctx* ctx, char* name, int name_len, int* cu_count, int64
 /* ---- resident data ---------------------------------------------------------------------------------------- */
 // The host version of the preprocessing (round 1; PGX_SETPOINTS_HOST=1 keeps it for A/B and as the cross-check of
 // setpoints.hip: both produce the same sorted order and the same group rows).
-static int set_points_host(pgx_ctx* ctx, int model_type, const double* points, int64_t n, int d)
+static int set_points_host(pgx_ctx* ctx, const ModelInfo& mi, const double* points, int64_t n)
 {
+    const int d = mi.D;
     PGX_TRY(ensure(ctx, ctx->pts, (size_t)n * d * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->comp, (size_t)n * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->pmax, (size_t)n * sizeof(double)));
@@ -277,9 +278,7 @@ static int set_points_host(pgx_ctx* ctx, int model_type, const double* points, i
     std::vector<double> pmax((size_t)n, 1.0);
     std::vector<float> p32((size_t)n * 8, 0.0f);
     double umax = 0.0;
-    int obs0 = -1, obs1 = -1, in0 = 0, in1 = -1;
-    if (model_type == kPnP) { obs0 = 0; obs1 = 1; in0 = 2; in1 = 4; }
-    else if (model_type == kHomography || model_type == kHomographySym) { obs0 = 2; obs1 = 3; in0 = 0; in1 = 3; }
+    const int obs0 = mi.obs0, obs1 = mi.obs0 + 1, in0 = mi.in0, in1 = mi.in1;
     if (obs0 >= 0)
         for (int64_t i = 0; i < n; ++i) {
             const double* r = points + i * d;
@@ -308,18 +307,18 @@ static int set_points_host(pgx_ctx* ctx, int model_type, const double* points, i
     ctx->point_sort = 0;
     ctx->comp_dirty = 1;
     if (obs0 >= 0 && ctx->group_filter && ctx->filter_enabled == 1 && std::isfinite(umax))
-        PGX_TRY(score_sort_points(ctx, points, p32.data(), pmax.data()));
+        PGX_TRY(score_sort_points(ctx, mi, points, p32.data(), pmax.data()));
     return PGX_OK;
 }
 
 int pgx_set_points(pgx_ctx* ctx, int model_type, const double* points, int64_t n)
 {
     CTX_GUARD(ctx);
-    int d = 0, p = 0;
-    if (model_dims(model_type, &d, &p) != 0) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: bad model type %d", model_type);
+    ModelInfo mi;
+    if (!model_info(model_type, &mi)) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: bad model type %d", model_type);
     if (!points || n <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: empty input");
     if (n >= ((int64_t)1 << 31)) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: n must be < 2^31");
-    ctx->model_type = model_type; ctx->D = d; ctx->P = p; ctx->n = n;
+    ctx->model_type = model_type; ctx->D = mi.D; ctx->P = mi.P; ctx->n = n;
     ctx->points_version += 1;
     ctx->labels_all_zero = 0;
     ctx->M = 0; ctx->last_acc = nullptr; ctx->dq_n = 0; ctx->L = 0; ctx->labels_n = 0;
@@ -327,7 +326,7 @@ int pgx_set_points(pgx_ctx* ctx, int model_type, const double* points, int64_t n
     ctx->score_global_n = 0;   // the fixed-point scale of a sharded job belongs to that job's point set
     if (ctx->memo.snaps.p) { (void)hipStreamSynchronize(ctx->stream); release(ctx->memo.snaps); ctx->memo.cap = 0; ctx->memo.valid = 0; ctx->memo.n = 0; }   // first-cycle snapshots of the old point set
     // upload + every derived copy on the device (setpoints.hip): filter scales, f32 rows, Morton order, group bounds
-    const int rc = !ctx->setpoints_host ? set_points_device(ctx, model_type, points, n) : set_points_host(ctx, model_type, points, n, d);
+    const int rc = !ctx->setpoints_host ? set_points_device(ctx, mi, points, n) : set_points_host(ctx, mi, points, n);
     if (rc != PGX_OK) {   // half-built copies (an allocation failed midway): no resident problem, every later call fails cleanly
         ctx->n = 0; ctx->model_type = -1; ctx->D = 0; ctx->P = 0; ctx->point_sort = 0; ctx->mirror_valid = 0;
         return rc;

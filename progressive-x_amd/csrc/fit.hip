@@ -561,6 +561,25 @@ static int gram_row_length(pgx_ctx* ctx, const char* who, int kind, int nparams,
     return PGX_OK;
 }
 
+// the row generator of a kind that gram_row_length accepted: calls f(Gen{})
+template <class F>
+static void with_gram_generator(int kind, int D, F&& f)
+{
+    switch (kind) {
+    case PGX_GRAM_AFFINE:
+        if (D == 2) f(GenAffine2{});
+        else if (D == 3) f(GenAffine3{});
+        else if (D == 4) f(GenAffine4{});
+        else f(GenAffine5{});
+        break;
+    case PGX_GRAM_DLT_H: f(GenDltH{}); break;
+    case PGX_GRAM_EPI_F: f(GenEpiF{}); break;
+    case PGX_GRAM_VP: f(GenVp{}); break;
+    case PGX_GRAM_SPHERE: f(GenSphere{}); break;
+    default: f(GenPnpGn{}); break;
+    }
+}
+
 int gram_batch_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, const int32_t* index, int B, int m,
                       const double* wsel, int wpow, double* out, int32_t* bad)
 {
@@ -592,20 +611,7 @@ int gram_batch_launch(pgx_ctx* ctx, int kind, const double* params, int nparams,
     if (tot > 0) PGX_HIP(ctx, hipMemcpyAsync(d_idx, index, (size_t)tot * 4, hipMemcpyHostToDevice, ctx->stream));
     if (w_bytes) PGX_HIP(ctx, hipMemcpyAsync(d_w, wsel, w_bytes, hipMemcpyHostToDevice, ctx->stream));
     const double* ww = wsel ? d_w : nullptr;
-    const int D = ctx->D;
-    switch (kind) {
-    case PGX_GRAM_AFFINE:
-        if (D == 2) launch_batch<GenAffine2>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
-        else if (D == 3) launch_batch<GenAffine3>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
-        else if (D == 4) launch_batch<GenAffine4>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
-        else launch_batch<GenAffine5>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad);
-        break;
-    case PGX_GRAM_DLT_H: launch_batch<GenDltH>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
-    case PGX_GRAM_EPI_F: launch_batch<GenEpiF>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
-    case PGX_GRAM_VP: launch_batch<GenVp>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
-    case PGX_GRAM_SPHERE: launch_batch<GenSphere>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
-    default: launch_batch<GenPnpGn>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); break;
-    }
+    with_gram_generator(kind, ctx->D, [&](auto gen) { launch_batch<decltype(gen)>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); });
     PGX_HIP(ctx, hipGetLastError());
     PGX_TRY(d2h(ctx, out, d_out, out_bytes));
     if (bad) PGX_TRY(d2h(ctx, bad, d_bad, bad_bytes));
@@ -655,20 +661,7 @@ int gram_labels_launch(pgx_ctx* ctx, int kind, const double* params, int nparams
     for (int k = 0; k < K; ++k)
         for (int j = 0; j < nparams; ++j) hp[cnt_bytes / 8 + (size_t)k * 12 + j] = params[(size_t)k * nparams + j];
     PGX_HIP(ctx, hipMemcpyAsync(d_cnt, hp.data(), cnt_bytes + prm_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int D = ctx->D;
-    switch (kind) {
-    case PGX_GRAM_AFFINE:
-        if (D == 2) launch_labels<GenAffine2>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
-        else if (D == 3) launch_labels<GenAffine3>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
-        else if (D == 4) launch_labels<GenAffine4>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
-        else launch_labels<GenAffine5>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt);
-        break;
-    case PGX_GRAM_DLT_H: launch_labels<GenDltH>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
-    case PGX_GRAM_EPI_F: launch_labels<GenEpiF>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
-    case PGX_GRAM_VP: launch_labels<GenVp>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
-    case PGX_GRAM_SPHERE: launch_labels<GenSphere>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
-    default: launch_labels<GenPnpGn>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); break;
-    }
+    with_gram_generator(kind, ctx->D, [&](auto gen) { launch_labels<decltype(gen)>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); });
     PGX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(gram_final_labels_kernel, dim3((unsigned)K), dim3(1024), 0, ctx->stream, d_part, blocks, nv, d_out);
     PGX_HIP(ctx, hipGetLastError());
@@ -693,15 +686,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
     if (nparams < 0 || nparams > 12 || (nparams > 0 && !params)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: bad parameter block");
     if (!out) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: out is NULL");
     int q = 0;
-    const int D = ctx->D;
-    switch (kind) {
-    case PGX_GRAM_AFFINE: q = D + 1; if (D < 2 || D > 5) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: affine rows need 2-, 3-, 4- or 5-D points"); break;
-    case PGX_GRAM_DLT_H: case PGX_GRAM_EPI_F: q = 9; if (D != 4 || nparams != 6) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 4-D correspondences and 6 normalisation parameters"); break;
-    case PGX_GRAM_VP: q = 3; if (D != 4) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 4-D segments"); break;
-    case PGX_GRAM_PNP_GN: q = 7; if (D != 5 || nparams != 12) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 5-D 2D-3D rows and a 3x4 pose"); break;
-    case PGX_GRAM_SPHERE: q = 5; if (D != 3 || nparams != 4) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: needs 3-D points and 4 parameters (ox, oy, oz, s)"); break;
-    default: return fail(ctx, PGX_ERR_INVALID, "pgx_gram: unknown row kind %d", kind);
-    }
+    PGX_TRY(gram_row_length(ctx, "pgx_gram", kind, nparams, &q));
     const int nv = q * (q + 1) / 2;
     int64_t work = 0;
     if (sel == PGX_SEL_INDEX) {
@@ -747,19 +732,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
         if (idx_bytes) PGX_HIP(ctx, hipMemcpyAsync(d_idx, index, idx_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     const int* ix = sel == PGX_SEL_INDEX ? d_idx : nullptr;
-    switch (kind) {
-    case PGX_GRAM_AFFINE:
-        if (D == 2) launch<GenAffine2>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
-        else if (D == 3) launch<GenAffine3>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
-        else if (D == 4) launch<GenAffine4>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
-        else launch<GenAffine5>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt);
-        break;
-    case PGX_GRAM_DLT_H: launch<GenDltH>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
-    case PGX_GRAM_EPI_F: launch<GenEpiF>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
-    case PGX_GRAM_VP: launch<GenVp>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
-    case PGX_GRAM_SPHERE: launch<GenSphere>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
-    default: launch<GenPnpGn>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); break;
-    }
+    with_gram_generator(kind, ctx->D, [&](auto gen) { launch<decltype(gen)>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); });
     PGX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(gram_final_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_part, blocks, nv, d_out);
     PGX_HIP(ctx, hipGetLastError());

@@ -246,7 +246,7 @@ constexpr int kGroupRow = 12;  // floats per group: c[3], rho, ub, vb, ru, rv, s
 constexpr int kSuper = 8;      // groups per super-group (512 points): first level of the cull kernel
 
 // launchers implemented in the .hip translation units
-int set_points_device(pgx_ctx* ctx, int model_type, const double* points, int64_t n);  // setpoints.hip: upload + all preprocessing
+int set_points_device(pgx_ctx* ctx, const ModelInfo& mi, const double* points, int64_t n);  // setpoints.hip: upload + all preprocessing
 int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks);
 int score_inliers_launch(pgx_ctx* ctx, int row, int32_t* index, int64_t* count);   // pointwise.hip
 // point-sharded exchange (comm.hip): the last launch's integer accumulators, replicas summed, in the caller's hypothesis order
@@ -254,7 +254,7 @@ int score_inliers_launch(pgx_ctx* ctx, int row, int32_t* index, int64_t* count);
 int score_acc_export(pgx_ctx* ctx, unsigned long long* out, hipStream_t stream);
 int score_acc_import(pgx_ctx* ctx, const unsigned long long* in, int M, int Mpad, double qscale, long long* counts, double* values,
                      double* shared, hipStream_t stream);
-int score_sort_points(pgx_ctx* ctx, const double* points, const float* p32, const double* pmax);  // builds the sorted copies
+int score_sort_points(pgx_ctx* ctx, const ModelInfo& mi, const double* points, const float* p32, const double* pmax);  // builds the sorted copies
 int preference_launch(pgx_ctx* ctx, const double* model, double T2, double* d_pref, double out3[3]);
 int compound_launch(pgx_ctx* ctx, const int32_t* slots, int K);
 int unary_launch(pgx_ctx* ctx, int K, double threshold, double lambda);

@@ -110,16 +110,6 @@ __global__ __launch_bounds__(kPwBlock) void preference_kernel(const double* __re
     }
 }
 
-template <int MT>
-static int preference_dispatch(pgx_ctx* ctx, const ModelArg& mdl, double T2, double* d_pref, int blocks)
-{
-    hipLaunchKernelGGL((preference_kernel<MT>), dim3((unsigned)blocks), dim3(kPwBlock), 0, ctx->stream,
-                       ctx->pts.as<double>(), ctx->n, mdl, T2, ctx->comp.as<double>(), d_pref,
-                       ctx->red_partials.as<double>());
-    PGX_HIP(ctx, hipGetLastError());
-    return PGX_OK;
-}
-
 int preference_launch(pgx_ctx* ctx, const double* model, double T2, double* d_pref, double out3[3])
 {
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_preference: points not set");
@@ -128,19 +118,12 @@ int preference_launch(pgx_ctx* ctx, const double* model, double T2, double* d_pr
     const int blocks = (int)((ctx->n + kPwBlock - 1) / kPwBlock);
     PGX_TRY(ensure(ctx, ctx->red_partials, (size_t)blocks * 3 * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->red_out, 8 * sizeof(double)));
-    int r;
-    switch (ctx->model_type) {
-    case kLine2D: r = preference_dispatch<kLine2D>(ctx, mdl, T2, d_pref, blocks); break;
-    case kHomography: r = preference_dispatch<kHomography>(ctx, mdl, T2, d_pref, blocks); break;
-    case kFundamental: r = preference_dispatch<kFundamental>(ctx, mdl, T2, d_pref, blocks); break;
-    case kPnP: r = preference_dispatch<kPnP>(ctx, mdl, T2, d_pref, blocks); break;
-    case kVanishingPoint: r = preference_dispatch<kVanishingPoint>(ctx, mdl, T2, d_pref, blocks); break;
-    case kHomographySym: r = preference_dispatch<kHomographySym>(ctx, mdl, T2, d_pref, blocks); break;
-    case kPlane3D: r = preference_dispatch<kPlane3D>(ctx, mdl, T2, d_pref, blocks); break;
-    case kSphere3D: r = preference_dispatch<kSphere3D>(ctx, mdl, T2, d_pref, blocks); break;
-    default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
-    }
-    PGX_TRY(r);
+    if (!with_model_type(ctx->model_type, [&](auto mt) {
+            hipLaunchKernelGGL((preference_kernel<decltype(mt)::value>), dim3((unsigned)blocks), dim3(kPwBlock), 0, ctx->stream,
+                               ctx->pts.as<double>(), ctx->n, mdl, T2, ctx->comp.as<double>(), d_pref, ctx->red_partials.as<double>());
+        }))
+        return fail(ctx, PGX_ERR_INVALID, "bad model type");
+    PGX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL((final_sum_kernel<3>), dim3(1), dim3(kPwBlock), 0, ctx->stream,
                        ctx->red_partials.as<double>(), blocks, ctx->red_out.as<double>());
     PGX_HIP(ctx, hipGetLastError());
@@ -221,17 +204,8 @@ int unary_launch(pgx_ctx* ctx, int K, double threshold, double lambda)
     const double* pts = ctx->pts.as<double>();
     const double* mdl = ctx->kmodels.as<double>();
     long long* dq = ctx->dq.as<long long>();
-    switch (ctx->model_type) {
-    case kLine2D: hipLaunchKernelGGL((unary_kernel<kLine2D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    case kHomography: hipLaunchKernelGGL((unary_kernel<kHomography>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    case kFundamental: hipLaunchKernelGGL((unary_kernel<kFundamental>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    case kPnP: hipLaunchKernelGGL((unary_kernel<kPnP>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    case kVanishingPoint: hipLaunchKernelGGL((unary_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    case kHomographySym: hipLaunchKernelGGL((unary_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    case kPlane3D: hipLaunchKernelGGL((unary_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    case kSphere3D: hipLaunchKernelGGL((unary_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); break;
-    default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
-    }
+    if (!with_model_type(ctx->model_type, [&](auto mt) { hipLaunchKernelGGL((unary_kernel<decltype(mt)::value>), g, b, 0, ctx->stream, pts, ctx->n, mdl, K, T2, oml, dq); }))
+        return fail(ctx, PGX_ERR_INVALID, "bad model type");
     PGX_HIP(ctx, hipGetLastError());
     return PGX_OK;
 }
@@ -355,17 +329,8 @@ int gc_labeling_launch(pgx_ctx* ctx, const double* model, double T2, double lamb
     const int blocks = (int)((n + kPwBlock - 1) / kPwBlock);
     dim3 g((unsigned)blocks), b(kPwBlock);
     const double* pts = ctx->pts.as<double>();
-    switch (ctx->model_type) {
-    case kLine2D: hipLaunchKernelGGL((gc_energy_kernel<kLine2D>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    case kHomography: hipLaunchKernelGGL((gc_energy_kernel<kHomography>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    case kFundamental: hipLaunchKernelGGL((gc_energy_kernel<kFundamental>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    case kPnP: hipLaunchKernelGGL((gc_energy_kernel<kPnP>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    case kVanishingPoint: hipLaunchKernelGGL((gc_energy_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    case kHomographySym: hipLaunchKernelGGL((gc_energy_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    case kPlane3D: hipLaunchKernelGGL((gc_energy_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    case kSphere3D: hipLaunchKernelGGL((gc_energy_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); break;
-    default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
-    }
+    if (!with_model_type(ctx->model_type, [&](auto mt) { hipLaunchKernelGGL((gc_energy_kernel<decltype(mt)::value>), g, b, 0, ctx->stream, pts, n, mdl, T2, e); }))
+        return fail(ctx, PGX_ERR_INVALID, "bad model type");
     PGX_HIP(ctx, hipGetLastError());
     const long long lambda_q = quantize_lambda(lambda);
     // Orientation.  As stated above every site starts "inlier" and alpha = "outlier": then every site beyond the threshold
@@ -536,17 +501,8 @@ int residual_sums_launch(pgx_ctx* ctx, const double* models, int K, double* sums
     const double* mdl = ctx->kmodels.as<double>();
     const int* lab = ctx->labels.as<int>();
     double* part = ctx->red_partials.as<double>();
-    switch (ctx->model_type) {
-    case kLine2D: hipLaunchKernelGGL((residual_sums_kernel<kLine2D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    case kHomography: hipLaunchKernelGGL((residual_sums_kernel<kHomography>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    case kFundamental: hipLaunchKernelGGL((residual_sums_kernel<kFundamental>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    case kPnP: hipLaunchKernelGGL((residual_sums_kernel<kPnP>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    case kVanishingPoint: hipLaunchKernelGGL((residual_sums_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    case kHomographySym: hipLaunchKernelGGL((residual_sums_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    case kPlane3D: hipLaunchKernelGGL((residual_sums_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    case kSphere3D: hipLaunchKernelGGL((residual_sums_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); break;
-    default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
-    }
+    if (!with_model_type(ctx->model_type, [&](auto mt) { hipLaunchKernelGGL((residual_sums_kernel<decltype(mt)::value>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); }))
+        return fail(ctx, PGX_ERR_INVALID, "bad model type");
     PGX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(final_sums_kernel, dim3((unsigned)K), dim3(kPwBlock), 0, ctx->stream, part, blocks, ctx->red_out.as<double>());
     PGX_HIP(ctx, hipGetLastError());
@@ -568,17 +524,8 @@ int residual_sum_launch(pgx_ctx* ctx, const double* model, int label, double* su
     const double* pts = ctx->pts.as<double>();
     const int* lab = ctx->labels.as<int>();
     double* part = ctx->red_partials.as<double>();
-    switch (ctx->model_type) {
-    case kLine2D: hipLaunchKernelGGL((residual_sum_kernel<kLine2D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    case kHomography: hipLaunchKernelGGL((residual_sum_kernel<kHomography>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    case kFundamental: hipLaunchKernelGGL((residual_sum_kernel<kFundamental>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    case kPnP: hipLaunchKernelGGL((residual_sum_kernel<kPnP>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    case kVanishingPoint: hipLaunchKernelGGL((residual_sum_kernel<kVanishingPoint>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    case kHomographySym: hipLaunchKernelGGL((residual_sum_kernel<kHomographySym>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    case kPlane3D: hipLaunchKernelGGL((residual_sum_kernel<kPlane3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    case kSphere3D: hipLaunchKernelGGL((residual_sum_kernel<kSphere3D>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); break;
-    default: return fail(ctx, PGX_ERR_INVALID, "bad model type");
-    }
+    if (!with_model_type(ctx->model_type, [&](auto mt) { hipLaunchKernelGGL((residual_sum_kernel<decltype(mt)::value>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); }))
+        return fail(ctx, PGX_ERR_INVALID, "bad model type");
     PGX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL((final_sum_kernel<1>), dim3(1), dim3(kPwBlock), 0, ctx->stream, part, blocks,
                        ctx->red_out.as<double>());

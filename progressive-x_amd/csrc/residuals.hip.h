@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace pgx {
 
 enum ModelType : int {
@@ -21,11 +23,29 @@ enum ModelType : int {
 __device__ __forceinline__ double cv_max(double a, double b) { return a < b ? b : a; }
 __device__ __forceinline__ double cv_min(double a, double b) { return a > b ? b : a; }
 
+// What the group bound of the sorted points is made of (setpoints.hip builds the rows, score.hip's cull kernel tests them).
+enum GroupBound : int {
+    kBoundBox,        // box of the observed pair + box and ball of the coordinates the projective map multiplies
+    kBoundBoxAll,     // box of all coordinates (Sampson)
+    kBoundBall,       // ball of all coordinates about the box centre (D = 2 or 3)
+    kBoundVanishing   // rows of the normalised segment features
+};
+
+// Residual<MT> is the one description of a model type: every per-type fact the library needs is a member here, and
+// with_model_type() below is the one list of types.  Besides the two residual functions:
+//   D, P            doubles per point row / per model
+//   sample, slots   minimal sample size and hypothesis slots per sample of the device solver (solve.hip); 0 = no solver
+//   bound           the kind of group bound
+//   obs0            first of the two observed image coordinates (-1: none; then no scales either)
+//   in0 .. in1      coordinates whose magnitude, at least 1, scales the point filter (in1 < in0: none)
+//   in0 .. box1     coordinates the projective map multiplies (the box / ball part of a kBoundBox row)
 template <int MT> struct Residual;
 
+struct NoProjectiveMap { static constexpr int obs0 = -1, in0 = 0, in1 = -1, box1 = -1; };
+
 // Default2DLineEstimator (progressivex_python.cpp:489) [U-4]: model (a,b,c), r = |a x + b y + c|.
-template <> struct Residual<kLine2D> {
-    static constexpr int D = 2, P = 3;
+template <> struct Residual<kLine2D> : NoProjectiveMap {
+    static constexpr int D = 2, P = 3, sample = 2, slots = 1, bound = kBoundBall;
     template <class PT, class MD>
     static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
         return fabs(m[0] * p[0] + m[1] * p[1] + m[2]);
@@ -40,7 +60,8 @@ template <> struct Residual<kLine2D> {
 // DefaultHomographyEstimator (progressivex_python.cpp:252) [U-1]: one-way forward transfer error,
 // H row-major 3x3 (progressivex_python.cpp:292-300).
 template <> struct Residual<kHomography> {
-    static constexpr int D = 4, P = 9;
+    static constexpr int D = 4, P = 9, sample = 4, slots = 1, bound = kBoundBox;
+    static constexpr int obs0 = 2, in0 = 0, in1 = 3, box1 = 1;   // the scale runs over all four coordinates (Filter32<kHomography>)
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& h) {
         const double t1 = h[0] * p[0] + h[1] * p[1] + h[2];
@@ -56,7 +77,8 @@ template <> struct Residual<kHomography> {
 
 // Symmetric transfer error (north-star wording): model = [H | H^-1].
 template <> struct Residual<kHomographySym> {
-    static constexpr int D = 4, P = 18;
+    static constexpr int D = 4, P = 18, sample = 0, slots = 0, bound = kBoundBox;
+    static constexpr int obs0 = 2, in0 = 0, in1 = 3, box1 = 1;   // the forward part
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& h) {
         const double t1 = h[0] * p[0] + h[1] * p[1] + h[2];
@@ -77,8 +99,8 @@ template <> struct Residual<kHomographySym> {
 
 // DefaultFundamentalMatrixEstimator (progressivex_python.cpp:616) [U-2]: squared Sampson distance,
 // F row-major (progressivex_python.cpp:654-662).
-template <> struct Residual<kFundamental> {
-    static constexpr int D = 4, P = 9;
+template <> struct Residual<kFundamental> : NoProjectiveMap {
+    static constexpr int D = 4, P = 9, sample = 7, slots = 3, bound = kBoundBoxAll;
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& f) {
         const double rxc = f[0] * p[2] + f[3] * p[3] + f[6];
@@ -96,7 +118,8 @@ template <> struct Residual<kFundamental> {
 // DefaultPnPEstimator (progressivex_python.cpp:119) [U-3]: squared reprojection error in normalised image
 // coordinates; P=[R|t] row-major 3x4 (progressivex_python.cpp:156-167); row (u,v,X,Y,Z) (:88-92).
 template <> struct Residual<kPnP> {
-    static constexpr int D = 5, P = 12;
+    static constexpr int D = 5, P = 12, sample = 3, slots = 4, bound = kBoundBox;
+    static constexpr int obs0 = 0, in0 = 2, in1 = 4, box1 = 4;
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
         const double px = m[0] * p[2] + m[1] * p[3] + m[2] * p[4] + m[3];
@@ -111,8 +134,8 @@ template <> struct Residual<kPnP> {
 };
 
 // VanishingPointEstimator::residual, vanishing_point_estimator.h:166-189 (squared at :134-140), in-tree.
-template <> struct Residual<kVanishingPoint> {
-    static constexpr int D = 4, P = 3;
+template <> struct Residual<kVanishingPoint> : NoProjectiveMap {
+    static constexpr int D = 4, P = 3, sample = 2, slots = 1, bound = kBoundVanishing;
     template <class PT, class MD>
     static __device__ __forceinline__ double plain(const PT& p, const MD& v) {
         const double mx = (p[0] + p[2]) / 2.0, my = (p[1] + p[3]) / 2.0;
@@ -131,8 +154,8 @@ template <> struct Residual<kVanishingPoint> {
 // 3-D planes (findPlanes; no reference counterpart - the line construction one dimension up): model (a,b,c,d) with (a,b,c)
 // a unit normal, r = |((a x + b y) + c z) + d|, summed left to right.  This operation order is the contract of every plane
 // check (tests restate it in numpy).
-template <> struct Residual<kPlane3D> {
-    static constexpr int D = 3, P = 4;
+template <> struct Residual<kPlane3D> : NoProjectiveMap {
+    static constexpr int D = 3, P = 4, sample = 3, slots = 1, bound = kBoundBall;
     template <class PT, class MD>
     static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
         return fabs(((m[0] * p[0] + m[1] * p[1]) + m[2] * p[2]) + m[3]);
@@ -147,8 +170,8 @@ template <> struct Residual<kPlane3D> {
 // 3-D spheres (findSpheres; no reference counterpart): model (cx, cy, cz, r), dx = x - cx, dy = y - cy, dz = z - cz,
 // r = |sqrt((dx dx + dy dy) + dz dz) - cr|, summed left to right, plain IEEE sqrt (no intrinsic, no contraction).  This
 // operation order is the contract of every sphere check (tests restate it in numpy).
-template <> struct Residual<kSphere3D> {
-    static constexpr int D = 3, P = 4;
+template <> struct Residual<kSphere3D> : NoProjectiveMap {
+    static constexpr int D = 3, P = 4, sample = 4, slots = 1, bound = kBoundBall;
     template <class PT, class MD>
     static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
         const double dx = p[0] - m[0], dy = p[1] - m[1], dz = p[2] - m[2];
@@ -161,13 +184,36 @@ template <> struct Residual<kSphere3D> {
     }
 };
 
-// Host-side dims table (same numbers as the functors above; 0 = no such model type).
+// The one list of model types: calls f(std::integral_constant<int, MT>{}) for the runtime type mt; false if mt is not a type.
+template <class F> inline bool with_model_type(int mt, F&& f) {
+    switch (mt) {
+    case kLine2D: f(std::integral_constant<int, kLine2D>{}); return true;
+    case kHomography: f(std::integral_constant<int, kHomography>{}); return true;
+    case kFundamental: f(std::integral_constant<int, kFundamental>{}); return true;
+    case kPnP: f(std::integral_constant<int, kPnP>{}); return true;
+    case kVanishingPoint: f(std::integral_constant<int, kVanishingPoint>{}); return true;
+    case kHomographySym: f(std::integral_constant<int, kHomographySym>{}); return true;
+    case kPlane3D: f(std::integral_constant<int, kPlane3D>{}); return true;
+    case kSphere3D: f(std::integral_constant<int, kSphere3D>{}); return true;
+    default: return false;
+    }
+}
+
+// The constants of Residual<mt> for host code that holds the type as a number.
+struct ModelInfo { int D, P, sample, slots, bound, obs0, in0, in1, box1; };
+
+inline bool model_info(int mt, ModelInfo* out) {
+    return with_model_type(mt, [&](auto t) {
+        using R = Residual<decltype(t)::value>;
+        *out = {R::D, R::P, R::sample, R::slots, R::bound, R::obs0, R::in0, R::in1, R::box1};
+    });
+}
+
 inline int model_dims(int mt, int* d, int* p) {
-    static const int D[kNumModelTypes] = {2, 4, 4, 5, 4, 4, 3, 0, 3};
-    static const int P[kNumModelTypes] = {3, 9, 9, 12, 3, 18, 4, 0, 4};
-    if (mt < 0 || mt >= kNumModelTypes || D[mt] == 0) return -1;
-    if (d) *d = D[mt];
-    if (p) *p = P[mt];
+    ModelInfo mi;
+    if (!model_info(mt, &mi)) return -1;
+    if (d) *d = mi.D;
+    if (p) *p = mi.P;
     return 0;
 }
 

@@ -310,14 +310,14 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
         for (int q = 0; q < R::D; ++q) pt[q] = pts_g[((int64_t)g * R::D + q) * 64 + lane];
 #pragma unroll
         for (int q = 0; q < 8; ++q) p32[q] = 0.0f;
-        if constexpr (RowFromPoint<MT>::in1 >= RowFromPoint<MT>::in0) {
+        if constexpr (R::in1 >= R::in0) {
             // the generic f32 row (sp_prep_kernel) recomputed from the f64 row just loaded - the same operations, the same bits -
             // instead of a second 24-byte row per point from memory (24 MB of 89 fetched per launch at 10^6 points)
 #pragma unroll
             for (int q = 0; q < R::D; ++q) p32[q] = (float)pt[q];
             double pm = 1.0;
 #pragma unroll
-            for (int q = RowFromPoint<MT>::in0; q <= RowFromPoint<MT>::in1; ++q) { const double a = fabs(pt[q]); if (!(a <= pm)) pm = a; }
+            for (int q = R::in0; q <= R::in1; ++q) { const double a = fabs(pt[q]); if (!(a <= pm)) pm = a; }
             p32[5] = (float)(pm * 1.000001);
         } else {
 #pragma unroll
@@ -688,15 +688,15 @@ static int score_dispatch(pgx_ctx* ctx, double T2, int has_compound, int want_ma
         guard32 = 5.5 * 5.9604644775390625e-8 * (1.0 + ctx->umax + T) * 1024.0 / T;
         filt32 = std::isfinite(guard32) && guard32 < 1e30;
     }
-    if constexpr (MT == kVanishingPoint)   // its own trust test per pair, no global guard (Filter32<kVanishingPoint>)
+    if constexpr (Residual<MT>::bound == kBoundVanishing)   // its own trust test per pair, no global guard (Filter32<kVanishingPoint>)
         filt32 = ctx->filter_enabled == 1 && T > 0.0 && std::isfinite(T) && T2 < 1e30;
-    if constexpr (MT == kHomography || MT == kHomographySym)   // explicit per-pair error terms, no global guard (Filter32<kHomography>)
+    if constexpr (std::is_base_of_v<Filter32<kHomography>, Filter32<MT>>)   // explicit per-pair error terms, no global guard (Filter32<kHomography>)
         filt32 = ctx->filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24;
-    if constexpr (MT == kLine2D || MT == kPlane3D || MT == kSphere3D) {   // per-pair error term, no global guard; T'' must be an ordinary f32
+    if constexpr (Residual<MT>::bound == kBoundBall) {   // per-pair error term, no global guard; T'' must be an ordinary f32
         filt32 = ctx->filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24 && std::isfinite(ctx->fscale);
         guard32 = ctx->fscale;             // Filter32<kLine2D / kPlane3D / kSphere3D>::prep: overflow guard (fscale >= 1)
     }
-    if constexpr (MT == kFundamental) {    // likewise; the bounds on T keep T2 * D~^2 (D~ >= 1e-12) inside the f32 normal range
+    if constexpr (Residual<MT>::bound == kBoundBoxAll) {    // likewise; the bounds on T keep T2 * D~^2 (D~ >= 1e-12) inside the f32 normal range
         filt32 = ctx->filter_enabled == 1 && T2 > 1e-12 && T2 < 1e12 && std::isfinite(ctx->fscale);
         guard32 = ctx->fscale * ctx->fscale;   // Filter32<kFundamental>::prep: overflow guard of the f32 terms (fscale >= 1)
     }
@@ -859,7 +859,7 @@ __global__ __launch_bounds__(256) void mask_unpermute_kernel(const unsigned long
 }
 
 // Host: Morton order of all coordinates, sorted copies, per-group bounds (rows of kGroupRow floats, see above).
-int score_sort_points(pgx_ctx* ctx, const double* points, const float* p32, const double* pmax)
+int score_sort_points(pgx_ctx* ctx, const ModelInfo& mi, const double* points, const float* p32, const double* pmax)
 {
     const int64_t n = ctx->n;
     const int d = ctx->D;
@@ -911,10 +911,8 @@ int score_sort_points(pgx_ctx* ctx, const double* points, const float* p32, cons
         for (int k = 0; k < 8; ++k) sp32[(size_t)j * 8 + k] = p32[i * 8 + k];
         spm[(size_t)j] = pmax[i];
     }
-    // which coordinates the projective map multiplies / which are observed (as in pgx_set_points)
-    int in0, in1, ob0;
-    if (ctx->model_type == kPnP) { in0 = 2; in1 = 4; ob0 = 0; }
-    else { in0 = 0; in1 = 1; ob0 = 2; }
+    // which coordinates the projective map multiplies / which are observed (a kBoundBox model type: pgx_set_points)
+    const int in0 = mi.in0, in1 = mi.box1, ob0 = mi.obs0;
     auto bounds = [&](int64_t a, int64_t b, float* row) {  // bounds of the sorted points [a, b)
         // centre = box centre of the f32 rows (the values the kernel's per-point filter sees are not needed here: the
         // bound is about the exact f64 points; extents are inflated below)
@@ -1047,17 +1045,10 @@ int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks)
 
 static int score_launch_typed(pgx_ctx* ctx, double T2, int has_compound, int want_masks)
 {
-    switch (ctx->model_type) {
-    case kLine2D: return score_dispatch<kLine2D>(ctx, T2, has_compound, want_masks);
-    case kHomography: return score_dispatch<kHomography>(ctx, T2, has_compound, want_masks);
-    case kFundamental: return score_dispatch<kFundamental>(ctx, T2, has_compound, want_masks);
-    case kPnP: return score_dispatch<kPnP>(ctx, T2, has_compound, want_masks);
-    case kVanishingPoint: return score_dispatch<kVanishingPoint>(ctx, T2, has_compound, want_masks);
-    case kHomographySym: return score_dispatch<kHomographySym>(ctx, T2, has_compound, want_masks);
-    case kPlane3D: return score_dispatch<kPlane3D>(ctx, T2, has_compound, want_masks);
-    case kSphere3D: return score_dispatch<kSphere3D>(ctx, T2, has_compound, want_masks);
-    default: return fail(ctx, PGX_ERR_INVALID, "pgx_score: bad model type %d", ctx->model_type);
-    }
+    int rc = PGX_OK;
+    if (!with_model_type(ctx->model_type, [&](auto mt) { rc = score_dispatch<decltype(mt)::value>(ctx, T2, has_compound, want_masks); }))
+        return fail(ctx, PGX_ERR_INVALID, "pgx_score: bad model type %d", ctx->model_type);
+    return rc;
 }
 
 }  // namespace pgx

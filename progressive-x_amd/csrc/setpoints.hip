@@ -568,12 +568,10 @@ __global__ __launch_bounds__(SPAN) void sp_line_bounds_kernel(const double* __re
 
 }  // namespace
 
-int set_points_device(pgx_ctx* ctx, int model_type, const double* points, int64_t n)
+int set_points_device(pgx_ctx* ctx, const ModelInfo& mi, const double* points, int64_t n)
 {
-    const int d = ctx->D;
-    int obs0 = -1, in0 = 0, in1 = -1;
-    if (model_type == kPnP) { obs0 = 0; in0 = 2; in1 = 4; }
-    else if (model_type == kHomography || model_type == kHomographySym) { obs0 = 2; in0 = 0; in1 = 3; }  // scale over all four coordinates (Filter32<kHomography>); Sym: the forward part
+    const int d = mi.D, model_type = ctx->model_type;
+    const int obs0 = mi.obs0, in0 = mi.in0, in1 = mi.in1;
     PGX_TRY(ensure(ctx, ctx->pts, (size_t)n * d * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->comp, (size_t)n * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->pmax, (size_t)n * sizeof(double)));
@@ -598,7 +596,7 @@ int set_points_device(pgx_ctx* ctx, int model_type, const double* points, int64_
     ctx->fscale = fs > 1.0 ? fs : 1.0;   // NaN coordinates leave it at what the finite ones give; the solvers then produce NaN models
     ctx->point_sort = 0;
     ctx->comp_dirty = 1;
-    if (model_type == kVanishingPoint && ctx->group_filter && ctx->filter_enabled == 1 && !(flags & 1u) && n >= 1) {
+    if (mi.bound == kBoundVanishing && ctx->group_filter && ctx->filter_enabled == 1 && !(flags & 1u) && n >= 1) {
         // ---- segments: f32 feature rows, Hough order of the segments' lines (sp_vp_rows_kernel), group rows of the normalised features
         const double xa = std::fmin(key_f64(st[0]), key_f64(st[2])), xb = std::fmax(key_f64(st[5]), key_f64(st[7]));
         const double ya = std::fmin(key_f64(st[1]), key_f64(st[3])), yb = std::fmax(key_f64(st[6]), key_f64(st[8]));
@@ -640,8 +638,8 @@ int set_points_device(pgx_ctx* ctx, int model_type, const double* points, int64_
         ctx->point_sort = 1;
         return PGX_OK;
     }
-    const bool line = model_type == kLine2D || model_type == kPlane3D || model_type == kSphere3D;   // ball bounds about the box centre (d = 2 or 3)
-    const bool fund = model_type == kFundamental || line;   // model types whose f32 rows / boxes are built from ALL coordinates
+    const bool line = mi.bound == kBoundBall;            // ball bounds about the box centre (d = 2 or 3)
+    const bool fund = mi.bound == kBoundBoxAll || line;   // model types whose f32 rows / boxes are built from ALL coordinates
     if (!((obs0 >= 0 || fund) && ctx->group_filter && ctx->filter_enabled == 1 && std::isfinite(ctx->umax)) || (flags & 1u)) return PGX_OK;
     if (fund) {   // f32 rows of the Sampson / line filter (the prep kernel left them zero) + the scales
         hipLaunchKernelGGL(sp_fund_rows_kernel, dim3(blocks), dim3(kSpBlock), 0, ctx->stream, ctx->pts.as<double>(), n, d, ctx->pts32.as<float>(),
@@ -757,7 +755,7 @@ int set_points_device(pgx_ctx* ctx, int model_type, const double* points, int64_
                        ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->pmax_s.as<double>(), ctx->pts_g.as<double>(),
                        ctx->p32_g.as<float>());
     PGX_HIP(ctx, hipGetLastError());
-    const int ib0 = model_type == kPnP ? 2 : 0, ib1 = model_type == kPnP ? 4 : 1, ob0 = model_type == kPnP ? 0 : 2;
+    const int ib0 = mi.in0, ib1 = mi.box1, ob0 = mi.obs0;
     if (line && d == 2) {
         hipLaunchKernelGGL((sp_line_bounds_kernel<64, 2>), dim3((unsigned)groups), dim3(64), 0, ctx->stream, ctx->pts_s.as<double>(), n,
                            ctx->gbounds.as<float>());

@@ -551,108 +551,39 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
 {
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: points not set");
     if ((!samples && !resident) || S <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: empty sample batch");
-    if (ctx->model_type == kFundamental) {
-        // three model slots per sample; isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1
-        // for this model type, so it is recomputed here from the caller-visible data: umax is not kept either)
-        if (!(ctx->fscale >= 1.0)) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: coordinate scale not available");
-        const int Mtot = 3 * S;
-        ctx->Mpad = ((Mtot + 255) / 256) * 256;
-        PGX_TRY(ensure(ctx, ctx->models, (size_t)Mtot * 9 * sizeof(double)));
-        PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
-        if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 7 * sizeof(int32_t)));
-        const unsigned blocks = (unsigned)((S + 63) / 64);
-        hipLaunchKernelGGL(solve_f7_kernel, dim3(blocks), dim3(64), 0, ctx->stream, ctx->pts.as<double>(), ctx->n,
-                           ctx->scratch.as<int>(), S, ctx->fscale, ctx->models.as<double>(), ctx->perm.as<int>(), ctx->Mpad);
-        PGX_HIP(ctx, hipGetLastError());
-        if (models_out) {
-            PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)Mtot * 9 * sizeof(double)));
-            PGX_TRY(sync_deliver(ctx));
-        }
-        ctx->M = Mtot; ctx->last_acc = nullptr;
-        return PGX_OK;
-    }
-    if (ctx->model_type == kPnP) {
-        const int Mtot = 4 * S;  // four solution slots per sample
-        ctx->Mpad = ((Mtot + 255) / 256) * 256;
-        PGX_TRY(ensure(ctx, ctx->models, (size_t)Mtot * 12 * sizeof(double)));
-        PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
-        if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 3 * sizeof(int32_t)));
-        hipLaunchKernelGGL(solve_p3p_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, ctx->stream, ctx->pts.as<double>(), ctx->n,
-                           ctx->scratch.as<int>(), S, ctx->models.as<double>(), ctx->perm.as<int>(), ctx->Mpad);
-        PGX_HIP(ctx, hipGetLastError());
-        if (models_out) {
-            PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)Mtot * 12 * sizeof(double)));
-            PGX_TRY(sync_deliver(ctx));
-        }
-        ctx->M = Mtot; ctx->last_acc = nullptr;
-        return PGX_OK;
-    }
-    if (ctx->model_type == kHomography) {
-        if (!(ctx->fscale >= 1.0)) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: coordinate scale not available");
-        ctx->Mpad = ((S + 255) / 256) * 256;
-        PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 9 * sizeof(double)));
-        PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
-        if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 4 * sizeof(int32_t)));
-        hipLaunchKernelGGL(solve_h4_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, ctx->stream, ctx->pts.as<double>(), ctx->n,
-                           ctx->scratch.as<int>(), S, ctx->fscale, ctx->models.as<double>(), ctx->perm.as<int>(), ctx->Mpad);
-        PGX_HIP(ctx, hipGetLastError());
-        if (models_out) {
-            PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)S * 9 * sizeof(double)));
-            PGX_TRY(sync_deliver(ctx));
-        }
-        ctx->M = S; ctx->last_acc = nullptr;
-        return PGX_OK;
-    }
-    if (ctx->model_type == kPlane3D) {
-        ctx->Mpad = ((S + 255) / 256) * 256;
-        PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 4 * sizeof(double)));
-        PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
-        if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 3 * sizeof(int32_t)));
-        hipLaunchKernelGGL(solve_plane_kernel, dim3((unsigned)((ctx->Mpad + kSolveBlock - 1) / kSolveBlock)), dim3(kSolveBlock), 0, ctx->stream,
-                           ctx->pts.as<double>(), ctx->n, ctx->scratch.as<int>(), S, ctx->models.as<double>(), ctx->perm.as<int>(), ctx->Mpad);
-        PGX_HIP(ctx, hipGetLastError());
-        if (models_out) {
-            PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)S * 4 * sizeof(double)));
-            PGX_TRY(sync_deliver(ctx));
-        }
-        ctx->M = S; ctx->last_acc = nullptr;
-        return PGX_OK;
-    }
-    if (ctx->model_type == kSphere3D) {
-        ctx->Mpad = ((S + 255) / 256) * 256;
-        PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 4 * sizeof(double)));
-        PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
-        if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 4 * sizeof(int32_t)));
-        hipLaunchKernelGGL(solve_sphere_kernel, dim3((unsigned)((ctx->Mpad + kSolveBlock - 1) / kSolveBlock)), dim3(kSolveBlock), 0, ctx->stream,
-                           ctx->pts.as<double>(), ctx->n, ctx->scratch.as<int>(), S, ctx->rmin, ctx->rmax, ctx->models.as<double>(),
-                           ctx->perm.as<int>(), ctx->Mpad);
-        PGX_HIP(ctx, hipGetLastError());
-        if (models_out) {
-            PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)S * 4 * sizeof(double)));
-            PGX_TRY(sync_deliver(ctx));
-        }
-        ctx->M = S; ctx->last_acc = nullptr;
-        return PGX_OK;
-    }
-    if (ctx->model_type != kLine2D && ctx->model_type != kVanishingPoint)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 4-point homography, 7-point fundamental matrix, P3P)", ctx->model_type);
-    ctx->Mpad = ((S + 255) / 256) * 256;
-    PGX_TRY(ensure(ctx, ctx->models, (size_t)S * 3 * sizeof(double)));
+    const int mt = ctx->model_type;
+    ModelInfo mi;
+    if (!model_info(mt, &mi) || mi.slots == 0)
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+    // isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1 for these model types, so the solvers take
+    // fscale, which pgx_set_points computes from the caller-visible data: umax is not kept either)
+    const bool scaled = mt == kFundamental || mt == kHomography;
+    if (scaled && !(ctx->fscale >= 1.0)) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: coordinate scale not available");
+    const int Mtot = mi.slots * S;
+    ctx->Mpad = ((Mtot + 255) / 256) * 256;
+    PGX_TRY(ensure(ctx, ctx->models, (size_t)Mtot * mi.P * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
-    if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * 2 * sizeof(int32_t)));
-    const unsigned blocks = (unsigned)((ctx->Mpad + kSolveBlock - 1) / kSolveBlock);
-    if (ctx->model_type == kLine2D)
-        hipLaunchKernelGGL((solve_kernel<kLine2D>), dim3(blocks), dim3(kSolveBlock), 0, ctx->stream, ctx->pts.as<double>(), ctx->n,
-                           ctx->scratch.as<int>(), S, ctx->models.as<double>(), ctx->perm.as<int>(), ctx->Mpad);
-    else
-        hipLaunchKernelGGL((solve_kernel<kVanishingPoint>), dim3(blocks), dim3(kSolveBlock), 0, ctx->stream, ctx->pts.as<double>(), ctx->n,
-                           ctx->scratch.as<int>(), S, ctx->models.as<double>(), ctx->perm.as<int>(), ctx->Mpad);
+    if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * mi.sample * sizeof(int32_t)));
+    const double* pts = ctx->pts.as<double>();
+    const int* smp = ctx->scratch.as<int>();
+    double* models = ctx->models.as<double>();
+    int* perm = ctx->perm.as<int>();
+    const dim3 gs((unsigned)((S + 63) / 64)), bs(64);                                            // one lane per sample
+    const dim3 gm((unsigned)((ctx->Mpad + kSolveBlock - 1) / kSolveBlock)), bm(kSolveBlock);      // one lane per padded model
+    if (mt == kFundamental) hipLaunchKernelGGL(solve_f7_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, ctx->Mpad);
+    else if (mt == kHomography) hipLaunchKernelGGL(solve_h4_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, ctx->Mpad);
+    else if (mt == kPnP) hipLaunchKernelGGL(solve_p3p_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
+    else if (mt == kPlane3D) hipLaunchKernelGGL(solve_plane_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
+    else if (mt == kSphere3D) hipLaunchKernelGGL(solve_sphere_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, ctx->Mpad);
+    else if (mt == kLine2D) hipLaunchKernelGGL((solve_kernel<kLine2D>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
+    else if (mt == kVanishingPoint) hipLaunchKernelGGL((solve_kernel<kVanishingPoint>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
+    else return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal (internal): model type %d declares a solver that has no launch line", mt);
     PGX_HIP(ctx, hipGetLastError());
     if (models_out) {
-        PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)S * 3 * sizeof(double)));
+        PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)Mtot * mi.P * sizeof(double)));
         PGX_TRY(sync_deliver(ctx));
     }
-    ctx->M = S; ctx->last_acc = nullptr;
+    ctx->M = Mtot; ctx->last_acc = nullptr;
     return PGX_OK;
 }
 
@@ -667,14 +598,9 @@ int solve_minimal_sampled_launch(pgx_ctx* ctx, int sampler, uint64_t key, uint32
     if (sampler == 1 && (ctx->gn != ctx->n || ctx->gE <= 0)) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: NAPSAC needs the neighbourhood graph of the resident points (pgx_graph_build / pgx_set_graph)");
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: points not set");
     if (S <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: empty sample batch");
-    int m = 0;
-    switch (ctx->model_type) {
-    case kLine2D: case kVanishingPoint: m = 2; break;
-    case kPnP: case kPlane3D: m = 3; break;
-    case kHomography: case kSphere3D: m = 4; break;
-    case kFundamental: m = 7; break;
-    default: return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: no device solver for model type %d", ctx->model_type);
-    }
+    ModelInfo mi;
+    if (!model_info(ctx->model_type, &mi) || mi.slots == 0) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: no device solver for model type %d", ctx->model_type);
+    const int m = mi.sample;
     if (ctx->n < m) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: %lld points, the minimal sample needs %d", (long long)ctx->n, m);
     PGX_TRY(ensure(ctx, ctx->scratch, (size_t)S * m * sizeof(int32_t)));
     if (sampler == 0)

@@ -18,8 +18,12 @@ LIB_PATH = os.environ.get("PGX_LIBPGX") or os.path.join(_HERE, "libpgx.so")   # 
 
 LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM, PLANE3D = range(7)
 SPHERE3D = 8                   # (7 is not assigned: include/pgx.h)
-POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4, 6: 3, 8: 3}
-PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18, 6: 4, 8: 4}
+# per model type: (doubles per point, doubles per model, minimal sample size, hypotheses per sample of the device solver);
+# sample size 0 = no device solver (pgx_solve_minimal fails).  The numbers of csrc/residuals.hip.h; tests/test_abi.py compares.
+MODEL_TABLE = {LINE2D: (2, 3, 2, 1), HOMOGRAPHY: (4, 9, 4, 1), FUNDAMENTAL: (4, 9, 7, 3), PNP: (5, 12, 3, 4),
+               VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1)}
+POINT_DIM = {t: row[0] for t, row in MODEL_TABLE.items()}
+PARAM_DIM = {t: row[1] for t, row in MODEL_TABLE.items()}
 FIXED_ONE = float(1 << 32)
 UNIQUE_ID_BYTES = 128
 
@@ -488,11 +492,11 @@ class Context:
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)
-        want = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3, SPHERE3D: 4}.get(self.model_type, 2)
-        if smp.ndim != 2 or smp.shape[1] != want:
+        _, nparam, want, slots = MODEL_TABLE.get(self.model_type, (0, 0, 0, 0))   # (points not set: the C call says so)
+        if smp.ndim != 2 or (want and smp.shape[1] != want):   # (want = 0, no device solver: likewise)
             raise ValueError(f"samples must be [S,{want}]")
-        rows = smp.shape[0] * {FUNDAMENTAL: 3, PNP: 4}.get(self.model_type, 1)   # root slots per 7-point / P3P sample
-        out = np.empty((rows, PARAM_DIM[self.model_type]), dtype=np.float64) if fetch else None
+        rows = smp.shape[0] * slots
+        out = np.empty((rows, nparam), dtype=np.float64) if fetch else None
         self._ck(self._lib.pgx_solve_minimal(self._h, _ptr(smp, C.c_int32), C.c_int(smp.shape[0]), _ptr(out, C.c_double)),
                  "pgx_solve_minimal")
         self.M = rows
@@ -502,9 +506,9 @@ class Context:
         """pgx_solve_minimal_sampled: S minimal samples drawn on the device by the in-repo generator (_rng.py gives the same rows:
         sampler "uniform", "napsac" on the resident neighbourhood graph, or "prosac" with the table of sampler_prosac_set) and solved into the resident hypothesis buffer.
         Returns (models or None, samples or None)."""
-        m = {FUNDAMENTAL: 7, HOMOGRAPHY: 4, PNP: 3, PLANE3D: 3, SPHERE3D: 4}.get(self.model_type, 2)
-        rows = int(S) * {FUNDAMENTAL: 3, PNP: 4}.get(self.model_type, 1)
-        out = np.empty((rows, PARAM_DIM[self.model_type]), dtype=np.float64) if fetch else None
+        _, nparam, m, slots = MODEL_TABLE.get(self.model_type, (0, 0, 0, 0))
+        rows = int(S) * slots
+        out = np.empty((rows, nparam), dtype=np.float64) if fetch else None
         smp = np.empty((int(S), m), dtype=np.int32) if fetch_samples else None
         self._ck(self._lib.pgx_solve_minimal_sampled(self._h, C.c_int({"uniform": 0, "napsac": 1, "prosac": 2}[sampler]), C.c_uint64(int(key) & 0xFFFFFFFFFFFFFFFF),
                                                      C.c_uint32(int(batch) & 0xFFFFFFFF), C.c_int(int(S)), _ptr(smp, C.c_int32), _ptr(out, C.c_double)),

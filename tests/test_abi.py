@@ -29,11 +29,20 @@ def test_library_loads_and_exports_the_whole_abi():
 def test_model_dims_table():
     from pyprogressivex import _lib
     lib = _lib.load()
-    for mt in range(6):
+    for mt in _lib.MODEL_TABLE:
         d, p = ctypes.c_int(), ctypes.c_int()
         assert lib.pgx_model_dims(mt, ctypes.byref(d), ctypes.byref(p)) == 0
         assert (d.value, p.value) == (_lib.POINT_DIM[mt], _lib.PARAM_DIM[mt])
     assert lib.pgx_model_dims(9, None, None) != 0
+    # the estimator classes state the device solvers' sample size and slots themselves: the same numbers as the table
+    from pyprogressivex import _estimators
+    seen = set()
+    for cls in vars(_estimators).values():
+        if isinstance(cls, type) and issubclass(cls, _estimators.Estimator) and cls.model_type is not None:
+            sample, slots = _lib.MODEL_TABLE[cls.model_type][2:]
+            assert ((cls.sample_size, cls.device_slots) if cls.device_minimal else (0, 0)) == (sample, slots), cls.__name__
+            seen.add(cls.model_type)
+    assert seen == set(_lib.MODEL_TABLE)
 
 
 def test_product_fails_loudly_without_a_gpu():
