@@ -21,9 +21,10 @@
 
 int pgxo_model_dims(int model_type, int *point_dim, int *param_dim)
 {
-    static const int pd[6] = {2, 4, 4, 5, 4, 4};
-    static const int md[6] = {3, 9, 9, 12, 3, 18};
-    if (model_type < 0 || model_type > 5) return -1;
+    /* type 7 is not assigned (include/pgx.h): -1 marks it, as pgx_model_dims fails for it */
+    static const int pd[PGXO_MODEL_TYPES] = {2, 4, 4, 5, 4, 4, 3, -1, 3};
+    static const int md[PGXO_MODEL_TYPES] = {3, 9, 9, 12, 3, 18, 4, -1, 4};
+    if (model_type < 0 || model_type >= PGXO_MODEL_TYPES || pd[model_type] < 0) return -1;
     if (point_dim) *point_dim = pd[model_type];
     if (param_dim) *param_dim = md[model_type];
     return 0;
@@ -114,6 +115,25 @@ static double vp_residual(const double *p, const double *d)
     return fabs(lx * xs + ly * ys + lz) / sqrt(lx * lx + ly * ly);
 }
 
+/* 3-D plane (findPlanes; no reference counterpart): model (a,b,c,d), (a,b,c) a unit normal.  Point-to-plane distance
+ * r = |((a x + b y) + c z) + d|, the products summed left to right (the contract stated in include/pgx.h's type table and
+ * DESIGN.md 4.5). */
+static double plane_residual(const double *p, const double *m)
+{
+    const double s = (m[0] * p[0] + m[1] * p[1]) + m[2] * p[2];
+    return fabs(s + m[3]);
+}
+
+/* 3-D sphere (findSpheres; no reference counterpart): model (cx,cy,cz,cr).  Distance from the surface
+ * r = |sqrt((dx dx + dy dy) + dz dz) - cr| with d = p - c, IEEE sqrt, summed left to right.  A negative cr is
+ * not special: the formula is evaluated as it stands. */
+static double sphere_residual(const double *p, const double *m)
+{
+    const double dx = p[0] - m[0], dy = p[1] - m[1], dz = p[2] - m[2];
+    const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+    return fabs(dist - m[3]);
+}
+
 /* U-14: the F estimator's symmetric-epipolar support (restated from the literature; see include/pgx.h pgx_epipolar_support).
  * out[0] = Sampson inliers (fundamental_sq < T2, strict as the scorer), out[1] = those with r^2 (1/|F x1|^2 + 1/|F^T x2|^2) < S2. */
 void pgxo_epipolar_support(const double *pts, int64_t n, const double *f, double T2, double S2, int64_t *out)
@@ -149,17 +169,22 @@ double pgxo_squared_residual(int model_type, const double *pt, const double *mod
     case PGXO_VANISHING_POINT: /* vanishing_point_estimator.h:134-140 */
         r = vp_residual(pt, model); return r * r;
     case PGXO_HOMOGRAPHY_SYM: return homography_sym_sq(pt, model);
+    case PGXO_PLANE3D: r = plane_residual(pt, model); return r * r;
+    case PGXO_SPHERE3D: r = sphere_residual(pt, model); return r * r;
     default: return NAN;
     }
 }
 
 /* Unsquared residual used by PEARL::parameterEstimation (PEARL.h:371,390).  For the estimators whose
- * source is absent it is restated as sqrt(squaredResidual) [UPSTREAM-MEMORY]. */
+ * source is absent it is restated as sqrt(squaredResidual) [UPSTREAM-MEMORY].  The types whose squared residual is DEFINED as
+ * r * r (line, vanishing point, plane, sphere) return r itself: sqrt(r * r) differs from r in the last bit for some r. */
 double pgxo_residual(int model_type, const double *pt, const double *model)
 {
     switch (model_type) {
     case PGXO_LINE2D: return line_residual(pt, model);
     case PGXO_VANISHING_POINT: return vp_residual(pt, model);
+    case PGXO_PLANE3D: return plane_residual(pt, model);
+    case PGXO_SPHERE3D: return sphere_residual(pt, model);
     default: return sqrt(pgxo_squared_residual(model_type, pt, model));
     }
 }
@@ -1084,8 +1109,73 @@ static void solve_h4(const double *pts, int64_t n, const int32_t *smp, double sc
     for (int k = 0; k < 9; ++k) out[k] = h[k];
 }
 
+/* 3-point plane (include/pgx.h pgx_solve_minimal; PlaneEstimator.minimal's docstring): u = p1 - p0, v = p2 - p0, n = u x v in
+ * cross3's component order, ln = sqrt((n0 n0 + n1 n1) + n2 n2), (a, b, c) = n / ln, d = -((a x0 + b y0) + c z0).  ln == 0
+ * (collinear or coincident points) and NaN (ln > 0 is false) leave the NaN row. */
+static void solve_plane3(const double *pts, int64_t n, const int32_t *smp, double *out)
+{
+    out[0] = out[1] = out[2] = out[3] = NAN;
+    for (int k = 0; k < 3; ++k) if (smp[k] < 0 || smp[k] >= n) return;
+    const double *p0 = pts + (size_t)smp[0] * 3, *p1 = pts + (size_t)smp[1] * 3, *p2 = pts + (size_t)smp[2] * 3;
+    double nv[3];
+    cross3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2], p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2], nv);
+    const double ln = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
+    if (!(ln > 0.0)) return;
+    const double a = nv[0] / ln, b = nv[1] / ln, c = nv[2] / ln;
+    out[0] = a; out[1] = b; out[2] = c;
+    out[3] = -((a * p0[0] + b * p0[1]) + c * p0[2]);
+}
+
+/* 4-point sphere (include/pgx.h pgx_solve_minimal / pgx_set_radius_range; SphereEstimator.minimal's docstring): a_i = p_i - p0,
+ * h_i = 0.5 ((a_i0 a_i0 + a_i1 a_i1) + a_i2 a_i2); the centre offset e solves a_i . e = h_i by Cramer's rule on cross products:
+ * n1 = a2 x a3, n2 = a3 x a1, n3 = a1 x a2, det = (a1_0 n1_0 + a1_1 n1_1) + a1_2 n1_2, e_k = ((h1 n1_k + h2 n2_k) + h3 n3_k) / det,
+ * r = sqrt((e0 e0 + e1 e1) + e2 e2), c = p0 + e.  det == 0 (coplanar / coincident), a non-finite centre or radius and a radius
+ * outside the INCLUSIVE range [rmin, rmax] leave the NaN row. */
+static void solve_sphere4(const double *pts, int64_t n, const int32_t *smp, double rmin, double rmax, double *out)
+{
+    out[0] = out[1] = out[2] = out[3] = NAN;
+    for (int k = 0; k < 4; ++k) if (smp[k] < 0 || smp[k] >= n) return;
+    const double *p0 = pts + (size_t)smp[0] * 3;
+    double a[3][3], h[3], n1[3], n2[3], n3[3], e[3], c[3];
+    for (int i = 0; i < 3; ++i) {
+        const double *pi = pts + (size_t)smp[i + 1] * 3;
+        for (int k = 0; k < 3; ++k) a[i][k] = pi[k] - p0[k];
+        h[i] = 0.5 * ((a[i][0] * a[i][0] + a[i][1] * a[i][1]) + a[i][2] * a[i][2]);
+    }
+    cross3(a[1][0], a[1][1], a[1][2], a[2][0], a[2][1], a[2][2], n1);
+    cross3(a[2][0], a[2][1], a[2][2], a[0][0], a[0][1], a[0][2], n2);
+    cross3(a[0][0], a[0][1], a[0][2], a[1][0], a[1][1], a[1][2], n3);
+    const double det = (a[0][0] * n1[0] + a[0][1] * n1[1]) + a[0][2] * n1[2];
+    if (!(det != 0.0)) return;                 /* also NaN */
+    for (int k = 0; k < 3; ++k) {
+        e[k] = ((h[0] * n1[k] + h[1] * n2[k]) + h[2] * n3[k]) / det;
+        c[k] = p0[k] + e[k];
+    }
+    const double r = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    if (!(isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(r))) return;
+    if (!(r >= rmin && r <= rmax)) return;
+    out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = r;
+}
+
 int pgxo_solve_minimal(int model_type, const double *pts, int64_t n, const int32_t *samples, int S, double *models_out)
 {
+    return pgxo_solve_minimal_range(model_type, pts, n, samples, S, 0.0, INFINITY, models_out);
+}
+
+/* pgxo_solve_minimal with the radius range the sphere solver accepts (pgx_set_radius_range is context state on the device; the
+ * oracle has no context, so the caller passes it; the other solvers ignore it).  -2: an invalid range (NaN, rmin < 0, rmax < rmin). */
+int pgxo_solve_minimal_range(int model_type, const double *pts, int64_t n, const int32_t *samples, int S, double rmin, double rmax,
+                             double *models_out)
+{
+    if (!(rmin >= 0.0 && rmax >= rmin)) return -2;
+    if (model_type == PGXO_PLANE3D) {
+        for (int s = 0; s < S; ++s) solve_plane3(pts, n, samples + (size_t)s * 3, models_out + (size_t)s * 4);
+        return 0;
+    }
+    if (model_type == PGXO_SPHERE3D) {
+        for (int s = 0; s < S; ++s) solve_sphere4(pts, n, samples + (size_t)s * 4, rmin, rmax, models_out + (size_t)s * 4);
+        return 0;
+    }
     if (model_type == PGXO_PNP) {
         for (int s = 0; s < S; ++s) solve_p3p(pts, n, samples + (size_t)s * 3, models_out + (size_t)s * 48);
         return 0;

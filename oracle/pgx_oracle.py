@@ -14,8 +14,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("PGX_ORACLE_SO") or os.path.join(_HERE, "libpgx_oracle.so")   # (scripts/sanitize.sh points it at the ASAN/UBSAN build)
 
 LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM = range(6)
-POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4}
-PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18}
+PLANE3D, SPHERE3D = 6, 8            # 7 is not assigned (include/pgx.h)
+POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4, PLANE3D: 3, SPHERE3D: 3}
+PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18, PLANE3D: 4, SPHERE3D: 4}
+SAMPLE_SIZE = {0: 2, 1: 4, 2: 7, 3: 3, 4: 2, PLANE3D: 3, SPHERE3D: 4}      # the types with a minimal solver here
 FIXED_ONE = 1 << 32
 
 
@@ -338,15 +340,28 @@ def residual_sum(model_type, pts, model, labels, label):
                                    _p(model, C.c_double), _p(labels, C.c_int32), C.c_int(label))
 
 
-def solve_minimal(model_type, pts, samples):
-    """[S,3] models of the 2-point line / 2-segment vanishing point solvers, [3S,9] (three slots per sample) of the
-    7-point fundamental matrix solver; NaN rows = no model"""
+def model_dims(model_type):
+    """pgxo_model_dims: (point_dim, param_dim), or None for a number that is not a model type"""
+    d, p = C.c_int(), C.c_int()
+    if lib().pgxo_model_dims(C.c_int(int(model_type)), C.byref(d), C.byref(p)) != 0:
+        return None
+    return d.value, p.value
+
+
+def solve_minimal(model_type, pts, samples, radius_range=(0.0, np.inf)):
+    """[S,3] models of the 2-point line / 2-segment vanishing point solvers, [S,4] of the 3-point plane / 4-point sphere solvers,
+    [3S,9] (three slots per sample) of the 7-point fundamental matrix solver; NaN rows = no model.  radius_range: the inclusive
+    (rmin, rmax) the sphere solver accepts (the device's pgx_set_radius_range), ignored by the other solvers"""
     pts = _f64(pts); samples = _i32(samples)
-    shape = {FUNDAMENTAL: (samples.shape[0] * 3, 9), HOMOGRAPHY: (samples.shape[0], 9),
-             PNP: (samples.shape[0] * 4, 12)}.get(model_type, (samples.shape[0], 3))
+    shape = {FUNDAMENTAL: (samples.shape[0] * 3, 9), HOMOGRAPHY: (samples.shape[0], 9), PNP: (samples.shape[0] * 4, 12),
+             PLANE3D: (samples.shape[0], 4), SPHERE3D: (samples.shape[0], 4)}.get(model_type, (samples.shape[0], 3))
     out = np.empty(shape, dtype=np.float64)
-    r = lib().pgxo_solve_minimal(C.c_int(model_type), _p(pts, C.c_double), C.c_int64(pts.shape[0]), _p(samples, C.c_int32),
-                                 C.c_int(samples.shape[0]), _p(out, C.c_double))
+    fn = lib().pgxo_solve_minimal_range
+    fn.restype = C.c_int
+    r = fn(C.c_int(model_type), _p(pts, C.c_double), C.c_int64(pts.shape[0]), _p(samples, C.c_int32), C.c_int(samples.shape[0]),
+           C.c_double(float(radius_range[0])), C.c_double(float(radius_range[1])), _p(out, C.c_double))
+    if r == -2:
+        raise ValueError("solve_minimal: radius range should satisfy 0 <= rmin <= rmax (no NaN)")
     if r != 0:
         raise ValueError("solve_minimal: model type without a device solver")
     return out
@@ -378,11 +393,14 @@ def graph_lists(points, k, radius=None, rows=None):
     if k <= 0:
         return out
     r2 = np.inf if radius is None else float(radius) * float(radius)
+    # Non-finite coordinates: a squared distance that is NaN (inf - inf, anything with NaN) or +inf is no distance.  Such a pair is
+    # never listed, with or without a radius, so a point with a NaN or Inf coordinate has no neighbours and is nobody's neighbour.
     if n <= 4000:   # brute force: the whole distance matrix, ranking by a stable sort (ties -> lower index)
-        S = (pts[rows, 0][:, None] - pts[None, :, 0]) * (pts[rows, 0][:, None] - pts[None, :, 0])
-        for j in range(1, pts.shape[1]):
-            df = pts[rows, j][:, None] - pts[None, :, j]
-            S = S + df * df
+        with np.errstate(invalid="ignore", over="ignore"):
+            S = (pts[rows, 0][:, None] - pts[None, :, 0]) * (pts[rows, 0][:, None] - pts[None, :, 0])
+            for j in range(1, pts.shape[1]):
+                df = pts[rows, j][:, None] - pts[None, :, j]
+                S = S + df * df
         S[np.arange(len(rows)), rows] = np.inf
         S[~(S <= r2)] = np.inf
         order = np.argsort(S, axis=1, kind="stable")[:, :k]
@@ -390,25 +408,59 @@ def graph_lists(points, k, radius=None, rows=None):
         out[:] = np.where(ok, order, -1)
         return out
     from scipy.spatial import cKDTree
-    tree = cKDTree(pts)
-    kk = min(n, k + 17)
-    if radius is None:
-        _, cands = tree.query(pts[rows], k=kk)
-    else:
-        _, cands = tree.query(pts[rows], k=kk, distance_upper_bound=float(radius) * (1.0 + 1e-9))
+    # the tree holds the tame rows only: it refuses NaN / Inf and overflows on coordinates like 1e200.  Finite rows beyond 1e150 are
+    # few in any test; they are candidates of every row and rank their own lists against every finite row, by the exact arithmetic
+    tame, wild = _tame_and_wild(pts)
+    both = np.concatenate([tame, wild])
+    tree = cKDTree(pts[tame])
+    kk = min(len(tame), k + 17)
+    is_tame = np.zeros(n, dtype=bool)
+    is_tame[tame] = True
+    qrows = np.nonzero(is_tame[rows])[0]
+    cands = np.full((len(rows), max(kk, 1)), len(tame), dtype=np.int64)
+    if kk > 0 and len(qrows) > 0:
+        if radius is None:
+            _, c = tree.query(pts[rows[qrows]], k=kk)
+        else:
+            _, c = tree.query(pts[rows[qrows]], k=kk, distance_upper_bound=float(radius) * (1.0 + 1e-9))
+        cands[qrows] = np.asarray(c).reshape(len(qrows), -1)
+    tame_ext = np.concatenate([tame, [n]])                       # the tree's "no neighbour" index maps to n
+    is_wild = np.zeros(n, dtype=bool)
+    is_wild[wild] = True
     for r, i in enumerate(rows):
-        cand = np.asarray(cands[r])
-        cand = cand[(cand < n) & (cand != i)]
-        s = _sqdist_rows(pts[i], pts[cand])
-        keep = s <= r2
+        if is_wild[i]:
+            cand, exhaustive = both[both != i], True
+        elif is_tame[i]:
+            cand = tame_ext[np.asarray(cands[r])]
+            cand, exhaustive = cand[(cand < n) & (cand != i)], False
+        else:
+            continue                                             # a NaN / Inf row: no neighbours
+        with np.errstate(over="ignore"):
+            s = _sqdist_rows(pts[i], pts[cand])
+        keep = (s <= r2) & (s < np.inf)
         cand, s = cand[keep], s[keep]
-        full = np.lexsort((cand, s))
-        order = full[:k]
-        if len(order) == k and len(cand) >= kk - 1:
+        if not exhaustive and len(cand) >= k and len(cand) >= kk - 1:
             # all candidates tied with the k-th must be inside the margin for the ranking to be decided here
-            assert s[full[-1]] > s[order[-1]], "tie margin exhausted: raise the candidate margin"
+            full = np.lexsort((cand, s))
+            assert s[full[-1]] > s[full[k - 1]], "tie margin exhausted: raise the candidate margin"
+        if not exhaustive and len(wild):
+            with np.errstate(over="ignore"):
+                sw = _sqdist_rows(pts[i], pts[wild])
+            kw = (sw <= r2) & (sw < np.inf)
+            cand, s = np.concatenate([cand, wild[kw]]), np.concatenate([s, sw[kw]])
+        order = np.lexsort((cand, s))[:k]
         out[r, :len(order)] = cand[order]
     return out
+
+
+def _tame_and_wild(pts):
+    """(rows a kd-tree can hold: finite, every |coordinate| <= 1e150; the other finite rows) as ascending index arrays"""
+    finite = np.isfinite(pts).all(axis=1)
+    with np.errstate(invalid="ignore"):
+        big = finite & (np.abs(pts).max(axis=1) > 1e150)
+    wild = np.nonzero(big)[0]
+    assert len(wild) <= 512, "too many huge rows for the exhaustive side of the oracle's graph builder"
+    return np.nonzero(finite & ~big)[0], wild
 
 
 def graph_from_lists(lists):
@@ -437,20 +489,29 @@ def graph_ball(points, radius):
     n = pts.shape[0]
     r2 = float(radius) * float(radius)
     if n <= 4000:
-        S = (pts[:, 0][:, None] - pts[None, :, 0]) * (pts[:, 0][:, None] - pts[None, :, 0])
-        for j in range(1, pts.shape[1]):
-            df = pts[:, j][:, None] - pts[None, :, j]
-            S = S + df * df
-        a, b = np.nonzero((S <= r2) & ~np.eye(n, dtype=bool))
+        with np.errstate(invalid="ignore", over="ignore"):      # NaN / overflowed distances are outside every ball
+            S = (pts[:, 0][:, None] - pts[None, :, 0]) * (pts[:, 0][:, None] - pts[None, :, 0])
+            for j in range(1, pts.shape[1]):
+                df = pts[:, j][:, None] - pts[None, :, j]
+                S = S + df * df
+        a, b = np.nonzero((S <= r2) & (S < np.inf) & ~np.eye(n, dtype=bool))
     else:
         from scipy.spatial import cKDTree
-        pairs = cKDTree(pts).query_pairs(r=float(radius) * (1.0 + 1e-9), output_type="ndarray")
+        tame, wild = _tame_and_wild(pts)      # the tree holds the tame rows; NaN / Inf rows have no neighbours, huge rows pair exhaustively
+        pairs = tame[cKDTree(pts[tame]).query_pairs(r=float(radius) * (1.0 + 1e-9), output_type="ndarray")]
         i, j = pairs[:, 0], pairs[:, 1]
-        s = (pts[i, 0] - pts[j, 0]) * (pts[i, 0] - pts[j, 0])
-        for c in range(1, pts.shape[1]):
-            df = pts[i, c] - pts[j, c]
-            s = s + df * df
-        keep = s <= r2
+        if len(wild):
+            others = np.concatenate([tame, wild])
+            wi, wj = np.repeat(wild, len(others)), np.tile(others, len(wild))
+            once = (wi < wj) | np.isin(wj, tame)             # a pair of huge rows once, a huge and a tame row once
+            once &= wi != wj
+            i, j = np.concatenate([i, wi[once]]), np.concatenate([j, wj[once]])
+        with np.errstate(over="ignore"):
+            s = (pts[i, 0] - pts[j, 0]) * (pts[i, 0] - pts[j, 0])
+            for c in range(1, pts.shape[1]):
+                df = pts[i, c] - pts[j, c]
+                s = s + df * df
+        keep = (s <= r2) & (s < np.inf)
         a = np.concatenate([i[keep], j[keep]])
         b = np.concatenate([j[keep], i[keep]])
     o = np.lexsort((b, a))
@@ -474,7 +535,7 @@ def graph_build(points, kind, radius=0.0, k=5):
 # the other estimators' solvers are absent from the snapshot (graph-cut-ransac submodule) and restated from the
 # literature: normalised DLT / 8-point rows, Gauss-Newton rows of the reprojection error at [R|t].
 # ---------------------------------------------------------------------------------------------------------------------
-GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN = 0, 1, 2, 3, 4
+GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE = 0, 1, 2, 3, 4, 5
 
 
 def gram_rows(kind, p, params=None):
@@ -510,6 +571,12 @@ def gram_rows(kind, p, params=None):
         ju = np.column_stack([b * ry, a * rz - b * rx, -a * ry, a, z, b, du])
         jv = np.column_stack([-a * rz + c * ry, -c * rx, a * rx, z, a, c, dv])
         return [ju, jv], bad
+    if kind == GRAM_SPHERE:
+        # include/pgx.h PGX_GRAM_SPHERE: (1, u, v, w, (u u + v v) + w w), (u, v, w) = (p - o) / s, params = (ox, oy, oz, s): the rows
+        # of the algebraic sphere fit on coordinates centred at o and scaled by s (3-D points)
+        ox, oy, oz, sc = [float(v) for v in params]
+        u, v, w = (p[:, 0] - ox) / sc, (p[:, 1] - oy) / sc, (p[:, 2] - oz) / sc
+        return [np.column_stack([one, u, v, w, (u * u + v * v) + w * w])], bad
     raise ValueError(kind)
 
 

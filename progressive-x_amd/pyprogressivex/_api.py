@@ -307,13 +307,19 @@ def findLines(points, weights, w, h, threshold=2.0, conf=0.5, spatial_coherence_
 
 def _point_cloud(points, weights, n_min):
     """the input checks of the 3-D point-cloud calls: points [n, 3] with n >= n_min, weights [n] or None; and Progressive NAPSAC's
-    grid, which starts at the bounding box's corner and spans its extents.  Returns (points, weights, grid points, extents)."""
+    grid, which starts at the corner of the bounding box of the finite coordinates and spans its extents.  Returns (points, weights, grid points, extents)."""
     points = _as_f64(points)
     if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < n_min:
         raise ValueError(f"points should be an array with dims [n,3], n>={n_min}")
     w = None if weights is None else _weights(weights, points.shape[0])
-    lo = points.min(axis=0)
-    ext = points.max(axis=0) - lo
+    finite = np.isfinite(points)
+    if finite.all():
+        lo = points.min(axis=0)
+        ext = points.max(axis=0) - lo
+    else:   # the box of the finite values: one NaN or Inf row must not flatten the grid for all the others
+        lo = np.where(finite, points, np.inf).min(axis=0)
+        ext = np.where(finite, points, -np.inf).max(axis=0) - lo
+        lo = np.where(np.isfinite(lo), lo, 0.0)
     ext = np.where(np.isfinite(ext) & (ext > 0), ext, 1.0)
     return points, w, np.ascontiguousarray(points - lo), ext
 

@@ -277,7 +277,10 @@ class ProgressiveNapsacSampler(UniformSampler):
         sizes = np.asarray(sizes, dtype=np.float64).reshape(-1)[:pts.shape[1]]
         self.cells = []          # per layer: (cell id per point, members per cell in index order)
         for div in layers:
-            cell = np.clip(np.floor(pts / (sizes / div)), 0, div - 1).astype(np.int64)
+            c = np.floor(pts / (sizes / div))
+            # clip to 0 .. div - 1 by comparisons, as csrc/sampler_host.hip does: a NaN coordinate lands in cell 0 (np.clip would hand
+            # NaN to the integer cast, whose result is platform-defined)
+            cell = np.where(c > 0.0, np.where(c > div - 1, float(div - 1), c), 0.0).astype(np.int64)
             cid = np.zeros(n, dtype=np.int64)
             for d in range(cell.shape[1]):
                 cid = cid * div + cell[:, d]

@@ -119,13 +119,16 @@ PNAPSAC_LAYERS = (16, 8, 4, 2)     # gcransac::sampler::ProgressiveNapsacSampler
 
 def pnapsac_cells(pts, sizes, layers=PNAPSAC_LAYERS):
     """Per grid layer: (cell id per point, {cell id: member indices in ascending = quality order}).  Cell coordinate of a point in
-    dimension d = clip(floor(x_d / (size_d / div)), 0, div - 1), id = the coordinates as digits in base div."""
+    dimension d = clip(floor(x_d / (size_d / div)), 0, div - 1) with NaN -> 0, id = the coordinates as digits in base div."""
     pts = np.asarray(pts, dtype=np.float64)[:, :4]
     n, dims = pts.shape
     sizes = np.asarray(sizes, dtype=np.float64).reshape(-1)[:dims]
     out = []
     for div in layers:
-        cell = np.clip(np.floor(pts / (sizes / div)), 0, div - 1).astype(np.int64)
+        c = np.floor(pts / (sizes / div))
+        # clip to 0 .. div - 1 by comparisons, as csrc/sampler_host.hip does: a NaN coordinate lands in cell 0 (np.clip would hand
+        # NaN to the integer cast, whose result is platform-defined)
+        cell = np.where(c > 0.0, np.where(c > div - 1, float(div - 1), c), 0.0).astype(np.int64)
         cid = np.zeros(n, dtype=np.int64)
         for d in range(dims):
             cid = cid * div + cell[:, d]

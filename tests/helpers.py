@@ -4,6 +4,10 @@ import numpy as np
 from pyprogressivex import datasets
 
 MODEL_CASES = {"line": 0, "homography": 1, "fundamental": 2, "pnp": 3, "vanishing_point": 4, "homography_sym": 5}
+# The 3-D point-cloud types live in a table of their own: tests index per-name dictionaries with MODEL_CASES and the soaks pick the
+# type by trial % len(MODEL_CASES), so growing that table would silently change what the committed seeds test.
+MODEL_CASES_3D = {"plane": 6, "sphere": 8}
+ALL_MODEL_CASES = {**MODEL_CASES, **MODEL_CASES_3D}
 
 
 def _fit_n(rng, arr, n):
@@ -18,7 +22,7 @@ def make_case(name, n, M, seed=0):
     """(model_type, points[n,d], models[M,p], threshold): a few ground-truth structures with inliers, outliers, and
     hypotheses that are ground truth, perturbed ground truth or random (so counts span 0 .. many)."""
     rng = np.random.default_rng(seed)
-    mt = MODEL_CASES[name]
+    mt = ALL_MODEL_CASES[name]
     per = max(2, n // 5)
     if name == "line":
         pts, _, gt = datasets.make_lines(n_per_line=per, n_lines=3, n_outliers=per, seed=seed)
@@ -38,6 +42,12 @@ def make_case(name, n, M, seed=0):
     elif name == "vanishing_point":
         pts, _, gt = datasets.make_vanishing_points(n_inliers=3 * per, n_vps=3, n_outliers=per, seed=seed)
         thr = 1.5
+    elif name == "plane":
+        pts, _, gt = datasets.make_planes(n_per_plane=per, n_planes=3, n_outliers=per, seed=seed)
+        thr = 0.05
+    elif name == "sphere":
+        pts, _, gt = datasets.make_spheres(n_per_sphere=per, n_spheres=3, n_outliers=per, seed=seed)
+        thr = 0.05
     else:
         raise KeyError(name)
     pts = _fit_n(rng, pts, n)
@@ -116,3 +126,59 @@ def fixed_point_accumulators(O, mt, pts, models, T2, comp=None, n_total=None):
         if comp is not None:
             shared_q[m] = int(np.rint(np.minimum(np.asarray(comp)[inl], sc) * q).astype(np.int64).sum())
     return dict(counts=counts, values_q=values_q, shared_q=shared_q)
+
+
+# ---- 3-D point-cloud scenes shared by the CPU and GPU files of findPlanes / findSpheres ------------------------------------------
+def scene_3d(kind, per=800, structures=3, outliers=800, seed=0):
+    """(points [n, 3] in random order, labels, ground truth [K, 4]) of datasets.make_planes / make_spheres.  Shuffled: PROSAC and
+    Progressive NAPSAC read the order as quality, and the generators emit structure by structure."""
+    mk = datasets.make_planes if kind == "plane" else datasets.make_spheres
+    pts, gt, models = mk(per, structures, outliers, seed=seed)
+    order = np.random.default_rng(seed + 100).permutation(len(pts))
+    return np.ascontiguousarray(pts[order]), gt[order], models
+
+
+def match_3d(kind, found, truth):
+    """for every ground-truth structure the distance to the nearest found model: planes max(|n x n'| sign-free normal difference,
+    |d - d'|), spheres max(|c - c'|, |r - r'|)"""
+    out = []
+    for g in truth:
+        best = np.inf
+        for m in found:
+            if kind == "plane":
+                s = 1.0 if float(m[:3] @ g[:3]) >= 0 else -1.0
+                best = min(best, float(np.abs(s * m - g).max()))
+            else:
+                best = min(best, float(np.abs(m - g).max()))
+        out.append(best)
+    return np.array(out)
+
+
+def edge_clouds_3d(kind):
+    """name -> (points, zero_models): the degenerate and hostile clouds every findPlanes / findSpheres path has to get through.
+    zero_models: no structure of this kind can be generated from the cloud, so no model may come back.  The degenerate clouds have
+    dyadic coordinates of a few bits, so that every difference and product of the minimal solvers is exact and the degeneracy is
+    exact too (ln == 0, det == 0: NaN rows); with rounded coordinates a plane through a line, or a huge sphere hugging a plane, is a
+    legitimate model.  Non-finite values sit in the third column: pgx_graph_build refuses them in the first two ("refused_*")."""
+    rng = np.random.default_rng(17)
+    m = 3 if kind == "plane" else 4
+    t = rng.integers(-24, 25, 60) / 8.0
+    uv = rng.integers(-32, 33, (120, 2)) / 16.0
+    base, _, _ = scene_3d(kind, per=150, structures=2, outliers=100, seed=4)
+    nan_row, inf_row, refused_nan, refused_inf = base.copy(), base.copy(), base.copy(), base.copy()
+    nan_row[5, 2] = np.nan
+    inf_row[7, 2] = np.inf
+    refused_nan[5, 0] = np.nan
+    refused_inf[7, 1] = -np.inf
+    return {
+        "n_equals_sample_size": (rng.uniform(0.0, 10.0, (m, 3)), False),
+        "coincident": (np.tile(np.array([[1.5, -2.0, 3.25]]), (60, 1)), True),
+        "collinear": (np.array([1.0, 2.0, 3.0]) + t[:, None] * np.array([0.5, 0.0, 0.75]), True),
+        "coplanar": (np.column_stack([uv[:, 0], uv[:, 1], 0.25 * uv[:, 0] - 0.5 * uv[:, 1] + 1.0]), kind == "sphere"),
+        "outliers_only": (rng.uniform(0.0, 10.0, (300, 3)), False),
+        "offset_1e6": (base + np.array([1e6, -1e6, 5e5]), False),
+        "nan_row": (nan_row, False),
+        "inf_row": (inf_row, False),
+        "refused_nan": (refused_nan, False),
+        "refused_inf": (refused_inf, False),
+    }

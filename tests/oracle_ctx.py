@@ -21,6 +21,7 @@ class OracleContext:
         self.labels = None
         self.Dq = None
         self._stats = dict(mincuts=0, sweeps=0, global_relabels=0, bfs_levels=0, relabelled_sites=0)
+        self.radius_range = (0.0, float("inf"))     # include/pgx.h pgx_set_radius_range: context state, [0, +inf] at creation
 
     def close(self):
         pass
@@ -75,8 +76,16 @@ class OracleContext:
     def set_graph(self, off, idx, mult):
         self.graph = (np.asarray(off, np.int32), np.asarray(idx, np.int32), np.asarray(mult, np.int32))
 
+    def set_radius_range(self, rmin=0.0, rmax=float("inf")):
+        """pgx_set_radius_range: context state that only the sphere solver reads and that set_points leaves alone; NaN, rmin < 0 or
+        rmax < rmin are refused (the device returns PGX_ERR_INVALID, which _lib raises as RuntimeError), rmax = +inf is allowed"""
+        rmin, rmax = float(rmin), float(rmax)
+        if not (rmin >= 0.0 and rmax >= rmin):
+            raise RuntimeError("pgx_set_radius_range: needs 0 <= rmin <= rmax (no NaN)")
+        self.radius_range = (rmin, rmax)
+
     def solve_minimal(self, samples, fetch=True):
-        self.models = O.solve_minimal(self.model_type, self.pts, samples)
+        self.models = O.solve_minimal(self.model_type, self.pts, samples, radius_range=self.radius_range)
         self.M = len(self.models)
         return self.models.copy() if fetch else None
 
@@ -117,6 +126,11 @@ class OracleContext:
         return vec, val
 
     def graph_build(self, points, kind, radius=0.0, k=5, fetch=True):
+        # pgx_graph_build lays its grid over the first two coordinates and refuses a point set in which one of them is not finite
+        # (PGX_ERR_INVALID, which _lib raises as PgxError, a RuntimeError); non-finite values in the other columns are distances
+        first = np.asarray(points, dtype=np.float64)[:, :2]
+        if not np.isfinite(first).all():
+            raise RuntimeError(f"pgx_graph_build: non-finite coordinate in row {int(np.nonzero(~np.isfinite(first).all(axis=1))[0][0])}")
         self.graph = O.graph_build(points, kind, radius=radius, k=k)
         return self.graph if fetch else len(self.graph[1])
 

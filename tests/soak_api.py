@@ -96,7 +96,7 @@ class _WithoutShortcuts:
     """the GPU context without its device-only shortcuts (pgx_score_inliers: the inlier list compacted on the device, where the
     oracle-backed context unpacks the mask row - the same set, tests/test_gpu_parity.py): both sides then make the SAME sequence of
     context calls and classify() can compare them call by call"""
-    HIDDEN = ("score_inliers", "solve_minimal_sampled")
+    HIDDEN = ("score_inliers", "solve_minimal_sampled", "sampler_prosac_set")   # (the last only ever precedes solve_minimal_sampled)
 
     def __init__(self, inner):
         self._i = inner
@@ -164,8 +164,35 @@ def classify(fn, args, kw, gpu, _aligned=False):
     return "fp-order", "every call agreed to 1e-9; the returned arrays differ beyond the soak's 1e-7"
 
 
-def soak(seed, trials, verbose=True, only=None):
+def problem_3d(rng, name, s, K, per, nout, kw):
+    """a findPlanes / findSpheres call on a random small cloud (shared with tests/soak_replay.py): (fn, args, kw).  The cloud is
+    shuffled (samplers 1 and 3 read the order as quality), a third of them lie far from the origin, half of the calls carry
+    weights, half of the sphere calls a radius range; thresholds and ball radii are in the generators' units (box 10, noise 0.01)."""
+    mk = datasets.make_planes if name == "plane" else datasets.make_spheres
+    pts, gt, _ = mk(per, K, nout, seed=s)
+    pts = np.ascontiguousarray(pts[rng.permutation(len(pts))])
+    if rng.random() < 0.34:
+        t = rng.normal(size=3)
+        pts = pts + t * (10.0 ** rng.uniform(0, 6) / np.linalg.norm(t))
+    kw = dict(kw)
+    kw.update(threshold=float(rng.choice([0.03, 0.05, 0.1])), sampler_id=int(rng.choice([0, 1, 2, 2, 3, 3])),
+              minimum_point_number=int(rng.choice([10, 30])), neighborhood_ball_radius=float(rng.choice([0.3, 0.8, 2.0])),
+              scoring_exponent=int(rng.choice([1, 2])))
+    if rng.random() < 0.5:
+        kw["weights"] = rng.random(len(pts)) + 0.25
+    if name == "sphere" and rng.random() < 0.5:
+        kw["radius_range"] = (float(rng.choice([0.0, 0.2, 0.6])), float(rng.choice([1.0, 2.0, np.inf])))
+    return (px.findPlanes if name == "plane" else px.findSpheres), (pts,), kw
+
+
+LAST = {}      # statistics of the last soak() call
+
+
+def soak(seed, trials, verbose=True, only=None, types=None):
+    """types: names of 3-D point-cloud types ("plane", "sphere") to draw instead of the five image-space calls (default: those
+    five, trial % 5 - the stream every committed seed was run with)"""
     rng = np.random.default_rng(seed)
+    per_type = {}
     bad = 0
     chaos = 0
     found = 0
@@ -187,7 +214,11 @@ def soak(seed, trials, verbose=True, only=None):
         K = int(rng.integers(1, 5))
         per = int(rng.choice([40, 150, 400, 1500]))
         nout = int(rng.choice([0, 50, 400]))
-        if which == 0:
+        if types is not None:
+            name3d = list(types)[trial % len(types)]
+            which = 5 if name3d == "plane" else 6
+            fn, args, kw = problem_3d(rng, name3d, s, K, per, nout, kw)
+        elif which == 0:
             pts, gt, _ = datasets.make_lines(n_per_line=per, n_lines=K, n_outliers=nout, seed=s)
             fn, args = px.findLines, (pts, np.array(0), 1000, 1000)
             kw.update(threshold=float(rng.choice([1.0, 2.0, 4.0])), sampler_id=int(rng.choice([0, 0, 1, 1, 2, 2, 2, 3])),
@@ -217,6 +248,7 @@ def soak(seed, trials, verbose=True, only=None):
                       neighborhood_ball_radius=float(rng.choice([20.0, 60.0])))
         if only is not None and not (only[0] <= trial <= only[1]):
             continue
+        per_type[fn.__name__] = per_type.get(fn.__name__, 0) + 1
         try:
             with contextlib.redirect_stdout(io.StringIO()), contextlib.redirect_stderr(io.StringIO()):
                 _api._ctx = gpu
@@ -235,16 +267,18 @@ def soak(seed, trials, verbose=True, only=None):
             A, B = M.reshape(-1, rows * M.shape[1]), Mr.reshape(-1, rows * M.shape[1])
             tol = 1e-7 * np.abs(B).max(axis=1, keepdims=True) + 1e-9
             same = np.all(np.abs(A - B) <= tol, axis=1)
-            if which != 4:
+            if which not in (4, 6):           # (a pose and a sphere have one sign)
                 same |= np.all(np.abs(A + B) <= tol, axis=1)
             ok = bool(same.all())
         if not ok:
             kind, why = classify(fn, args, kw, gpu)
             bad += kind == "bug"
             chaos += kind != "bug"
-            print("MISMATCH" if kind == "bug" else "fp-order divergence", "trial", trial, "-", why, "|", fn.__name__, "data seed", s, "K", K, "per", per, "nout", nout, kw, "models", M.shape, Mr.shape,
+            print("MISMATCH" if kind == "bug" else "fp-order divergence", "trial", trial, "-", why, "|", fn.__name__, "data seed", s, "K", K, "per", per, "nout", nout, {k: v for k, v in kw.items() if k != "weights"}, "models", M.shape, Mr.shape,
                   "labels differing", int((lab != labr).sum()) if lab.shape == labr.shape else "shape",
                   "max model diff", float(np.abs(M - Mr).max()) if M.shape == Mr.shape and M.size else None, flush=True)
+    LAST.clear()
+    LAST.update(calls=trials, mismatches=bad, fp_order=chaos, model_rows=found, per_type=per_type)
     if verbose:
         print(f"api soak done: seed {seed}, {trials} calls, {bad} mismatches, {chaos} fp-order divergences, {found} model rows returned, {time.time() - t0:.0f} s")
     return bad

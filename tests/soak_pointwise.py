@@ -10,7 +10,8 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [HERE, os.path.join(HERE, "..", "progressive-x_amd"), os.path.join(HERE, "..", "oracle"), os.path.join(HERE, "..")]
 import numpy as np
-from helpers import MODEL_CASES, make_case
+from helpers import MODEL_CASES, MODEL_CASES_3D, make_case
+from soak_scoring import offset_scene
 from pyprogressivex import _lib
 import pgx_oracle as O
 
@@ -37,11 +38,18 @@ def same(a, b):
     return a.shape == b.shape and bool(np.all((a == b) | (np.isnan(a) & np.isnan(b))))
 
 
-def soak(seed, trials, verbose=True):
+LAST = {}      # statistics of the last soak() call
+
+
+def soak(seed, trials, verbose=True, types=None):
+    """types: the model types to draw, by name (default: the six of MODEL_CASES - the stream every committed seed was run with); the
+    3-D types also get whole scenes moved far from the origin and, for spheres, a radius range on the solver"""
     rng = np.random.default_rng(seed)
     ctx = _lib.Context(0)
     bad = 0
     checked = 0
+    names = list(MODEL_CASES) if types is None else list(types)
+    per_type = {}
     t0 = time.time()
 
     def report(what, *info):
@@ -50,7 +58,8 @@ def soak(seed, trials, verbose=True):
         print("MISMATCH", what, *info, flush=True)
 
     for trial in range(trials):
-        name = list(MODEL_CASES)[trial % len(MODEL_CASES)]
+        name = names[trial % len(names)]
+        per_type[name] = per_type.get(name, 0) + 1
         n = int(rng.choice([1, 2, 63, 64, 65, 500, 3000, 4097, 20011]))
         M = int(rng.choice([1, 3, 9]))
         mt, pts, models, thr = make_case(name, n, M, seed=int(rng.integers(1 << 30)))
@@ -63,6 +72,8 @@ def soak(seed, trials, verbose=True):
             pts *= 10.0 ** rng.uniform(-30, 30)          # the whole data set at an absurd scale
         elif mode == 3 and rng.random() < 0.3:
             pts[rng.integers(0, n, 3)] = rng.choice([np.nan, np.inf, -np.inf, 1e200, 1e-200])
+        if name in MODEL_CASES_3D and rng.random() < 0.34:
+            pts, models = offset_scene(rng, name, pts, models)
         T2 = 2.25 * thr * thr * 10.0 ** (rng.uniform(-3, 3) if rng.random() < 0.8 else rng.uniform(-14, 14))
         tag = (name, n, M, mode, trial)
         ctx.set_points(mt, pts)
@@ -98,12 +109,19 @@ def soak(seed, trials, verbose=True):
                     report("residual_sum", tag, a, b, "model", model[:4])
             # minimal solvers
             if name != "homography_sym":
-                m = {"fundamental": 7, "homography": 4, "pnp": 3}.get(name, 2)
+                m = O.SAMPLE_SIZE[mt]
                 S = 300
                 samples = rng.integers(0, n, (S, m)).astype(np.int32)
                 samples[:10, 1] = samples[:10, 0]
+                rr = (0.0, np.inf)
+                if name == "sphere" and rng.random() < 0.5:          # pgx_set_radius_range: context state, reset below
+                    lo = float(10.0 ** rng.uniform(-2, 1))
+                    rr = (lo, float(lo * 10.0 ** rng.uniform(0, 2))) if rng.random() < 0.8 else (lo, np.inf)
+                    ctx.set_radius_range(*rr)
                 got = ctx.solve_minimal(samples)
-                ref = O.solve_minimal(mt, pts, samples)
+                ref = O.solve_minimal(mt, pts, samples, radius_range=rr)
+                if rr != (0.0, np.inf):
+                    ctx.set_radius_range()
                 checked += ref.size
                 if not same(got, ref):
                     w = np.nonzero(~((got == ref) | (np.isnan(got) & np.isnan(ref))).all(axis=1))[0]
@@ -137,6 +155,8 @@ def soak(seed, trials, verbose=True):
                     if not (np.array_equal(ctx.get_labels(), rl) and ge == re):
                         report("greedy", tag, h)
     ctx.close()
+    LAST.clear()
+    LAST.update(cases=trials, mismatches=bad, values_compared=int(checked), per_type=per_type)
     if verbose:
         print(f"pointwise soak done: seed {seed}, {trials} cases, {bad} mismatches, {checked} values compared, {time.time() - t0:.0f} s")
     return bad

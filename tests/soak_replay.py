@@ -20,7 +20,7 @@ import progx_proposal as Q
 import replay_helpers as H
 
 
-def problem(rng, trial):
+def problem(rng, trial, types=None):
     which = trial % 5
     s = int(rng.integers(1 << 30))
     kw = dict(conf=float(rng.choice([0.5, 0.9, 0.99])), seed=int(rng.integers(1000)),
@@ -37,7 +37,11 @@ def problem(rng, trial):
     K = int(rng.integers(1, 5))
     per = int(rng.choice([40, 150, 400, 1000]))
     nout = int(rng.choice([0, 50, 400]))
-    if which == 0:
+    if types is not None:
+        import soak_api
+        fn, args, kw = soak_api.problem_3d(rng, list(types)[trial % len(types)], s, K, per, nout, kw)
+        rows = 1
+    elif which == 0:
         pts, gt, _ = datasets.make_lines(n_per_line=per, n_lines=K, n_outliers=nout, seed=s)
         fn, args, rows = px.findLines, (pts, np.array(0), 1000, 1000), 1
         kw.update(threshold=float(rng.choice([1.0, 2.0, 4.0])), sampler_id=int(rng.choice([0, 0, 1, 2, 2, 3])),
@@ -66,18 +70,25 @@ def problem(rng, trial):
     return fn, args, kw, rows, s
 
 
-def soak(seed, trials, verbose=True, tie=1e-12):
+LAST = {}      # statistics of the last soak() call
+
+
+def soak(seed, trials, verbose=True, tie=1e-12, types=None):
+    """types: names of 3-D point-cloud types ("plane", "sphere") to draw instead of the five image-space calls (default: those
+    five - the stream every committed seed was run with)"""
     rng = np.random.default_rng(seed)
     bad = ties = events = pearl = walks = walk_events = 0
+    per_type = {}
     t0 = time.time()
     for trial in range(trials):
-        fn, args, kw, rows, s = problem(rng, trial)
+        fn, args, kw, rows, s = problem(rng, trial, types)
+        per_type[fn.__name__] = per_type.get(fn.__name__, 0) + 1
         try:
             with contextlib.redirect_stdout(io.StringIO()), contextlib.redirect_stderr(io.StringIO()):
                 out, rec, rep = H.run_and_replay(fn, *args, refit_tie_rtol=tie, **kw)
         except R.ReplayError as e:
             bad += 1
-            print("MISMATCH trial", trial, fn.__name__, "data seed", s, kw, "-", e, flush=True)
+            print("MISMATCH trial", trial, fn.__name__, "data seed", s, {k: v for k, v in kw.items() if k != "weights"}, "-", e, flush=True)
             continue
         if rep is None:           # unknown sampler id: zero models, no run (progressivex_python.cpp:240-245)
             continue
@@ -98,6 +109,8 @@ def soak(seed, trials, verbose=True, tie=1e-12):
             if wd is not None:
                 bad += 1
                 print("MISMATCH trial", trial, fn.__name__, "data seed", s, kw, "- proposal", k, wd, flush=True)
+    LAST.clear()
+    LAST.update(calls=trials, mismatches=bad, events=events, pearl_iterations=pearl, ties=ties, proposals=walks, per_type=per_type)
     if verbose:
         print(f"replay soak done: seed {seed}, {trials} calls, {events} decision events ({pearl} PEARL iterations), {ties} summation-order ties "
               f"followed; {walks} proposals ({walk_events} proposal-loop decisions) against the proposal replay; {bad} mismatches, {time.time() - t0:.0f} s")

@@ -1,5 +1,5 @@
 """Scoring soak (tests/test_gpu_fuzz.py runs a bounded slice of it; run it by hand for longer): the cull + f32 filter + exact path against the CPU oracle on randomly generated
-cases of all six model types - random sizes, hypotheses a hair from ground truth, garbage hypotheses at several scales,
+cases of the six image-space model types (default) or of the 3-D point-cloud types (types=) - random sizes, hypotheses a hair from ground truth, garbage hypotheses at several scales,
 thresholds exactly on residuals.  usage: python tests/soak_scoring.py <seed> <trials>"""
 import os
 import sys
@@ -8,13 +8,33 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [HERE, os.path.join(HERE, "..", "progressive-x_amd"), os.path.join(HERE, "..", "oracle"), os.path.join(HERE, "..")]
 import numpy as np
-from helpers import MODEL_CASES, make_case
+from helpers import MODEL_CASES, MODEL_CASES_3D, make_case
 from pyprogressivex import _lib
 import pgx_oracle as O
 
 
-def soak(seed, trials, verbose=True, verify=True):
-    """verify: the context is created with PGX_VERIFY=1 and every batch is also re-decided pair by pair on the device
+LAST = {}      # statistics of the last soak() call: cases, mismatches, contradictions, verified pairs, cases per type
+
+
+def offset_scene(rng, name, pts, models):
+    """3-D types only: the whole scene - points and every hypothesis with them - moved by a vector of length 10^U(0, 8).  A plane
+    (n, d) becomes (n, d - n . t), a sphere (c, r) becomes (c + t, r): the residuals are the same numbers mathematically, the
+    filters' error budgets and the group balls are not."""
+    t = rng.normal(size=3)
+    t *= 10.0 ** rng.uniform(0, 8) / np.linalg.norm(t)
+    models = models.copy()
+    if name == "plane":
+        models[:, 3] = models[:, 3] - models[:, :3] @ t
+    else:
+        models[:, :3] = models[:, :3] + t
+    return pts + t, models
+
+
+def soak(seed, trials, verbose=True, verify=True, types=None):
+    """types: the model types to draw, by name (default: the six of MODEL_CASES, trial % 6 - the stream every committed seed was
+    run with).  For the 3-D types "rescaled by 10^+-160" reads per type: a plane's four numbers scale together; a sphere's centre and
+    radius scale together (the sphere blown up about the origin), and a third of the cases move the whole scene far from the origin.
+    verify: the context is created with PGX_VERIFY=1 and every batch is also re-decided pair by pair on the device
     (pgx_score_stats[5]): a pair the group bound or the f32 filter discarded although the exact residual calls it an inlier is a
     contradiction - a hole in a filter proof - whether or not it happens to change a count."""
     rng = np.random.default_rng(seed)
@@ -31,9 +51,12 @@ def soak(seed, trials, verbose=True, verify=True):
     bad = 0
     contradictions = 0
     checked_pairs = 0
+    names = list(MODEL_CASES) if types is None else list(types)
+    per_type = {}
     t0 = time.time()
     for trial in range(trials):
-        name = list(MODEL_CASES)[trial % len(MODEL_CASES)]
+        name = names[trial % len(names)]
+        per_type[name] = per_type.get(name, 0) + 1
         n = int(rng.choice([1, 63, 64, 65, 500, 4097, 20011, 60000]))
         M = int(rng.choice([1, 3, 64, 65, 257, 700]))
         mt, pts, models, thr = make_case(name, n, M, seed=int(rng.integers(1 << 30)))
@@ -53,6 +76,9 @@ def soak(seed, trials, verbose=True, verify=True):
         if n >= 500 and trial % 3 == 0:
             pts[rng.integers(0, n, 20)] *= 10.0 ** rng.uniform(-6, 8)
             pts[10:30] = pts[10]
+        if name in MODEL_CASES_3D and rng.random() < 0.34:
+            pts, models = offset_scene(rng, name, pts, models)
+            gt = models[0].copy()
         sq0 = O.squared_residuals(mt, pts, gt)
         fin = np.sort(sq0[np.isfinite(sq0) & (sq0 > 0)])
         T2s = [2.25 * thr * thr * 10.0 ** (rng.uniform(-3, 3) if rng.random() < 0.8 else rng.uniform(-14, 14))]
@@ -90,6 +116,8 @@ def soak(seed, trials, verbose=True, verify=True):
                     print("   dense path counts", dd["counts"][w[:4]], "values", dd["values"][vw[:4]]); d.close()
                     del os.environ["PGX_NO_GROUP"]
     ctx.close()
+    LAST.clear()
+    LAST.update(cases=trials, mismatches=bad, contradictions=contradictions, verified_pairs=int(checked_pairs), per_type=per_type)
     if verbose:
         print(f"soak done: seed {seed}, {trials} cases, {bad} mismatches, {contradictions} contradictions in {checked_pairs:.3g} verified pairs, "
               f"{time.time() - t0:.0f} s")

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import pyprogressivex as px
+from helpers import edge_clouds_3d, match_3d, scene_3d
 from oracle_ctx import OracleContext
 from pyprogressivex import _api, datasets
 
@@ -90,6 +91,36 @@ def test_vanishing_points_identical_to_cpu_restatement(monkeypatch):
                                  spatial_coherence_weight=0.05, neighborhood_ball_radius=15.0)
     assert np.array_equal(lab, labr) and np.allclose(V, Vr, rtol=1e-8, atol=1e-10)
     assert V.shape[0] >= 4
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+@pytest.mark.parametrize("sampler_id", [0, 2, 3])
+@pytest.mark.parametrize("kind", ["plane", "sphere"])
+def test_planes_and_spheres_identical_to_cpu_restatement(monkeypatch, kind, sampler_id, weighted):
+    """findPlanes / findSpheres on the GPU return the labels (bit for bit) and the models (1e-8) of the same call on the
+    oracle-backed context - whose plane / sphere rows are checked against exact arithmetic (tests/test_oracle.py) and whose
+    decisions against the replays (tests/test_api3d_cpu.py) - for the uniform sampler, NAPSAC and Progressive NAPSAC, with and
+    without refit weights; the structures the sampler can find are the generator's"""
+    fn = px.findPlanes if kind == "plane" else px.findSpheres
+    pts, gt, truth = scene_3d(kind)
+    w = np.random.default_rng(3).random(len(pts)) + 0.25 if weighted else None
+    (M, lab), (Mr, labr) = _both(monkeypatch, fn, pts, weights=w, seed=1, sampler_id=sampler_id, minimum_point_number=100)
+    assert M.shape == Mr.shape and np.array_equal(lab, labr) and np.allclose(M, Mr, rtol=1e-8, atol=1e-10)
+    found = int((match_3d(kind, M, truth) <= 0.05).sum())
+    assert found == 3 or (kind == "sphere" and sampler_id == 0 and found >= 1)     # (uniform samples rarely put four points on one sphere: DESIGN.md 4.6)
+
+
+def test_spheres_with_radius_range_coherence_and_philox_identical_to_cpu_restatement(monkeypatch):
+    pts, gt, truth = scene_3d("sphere")
+    for kw in (dict(radius_range=(0.2, 1.0)), dict(spatial_coherence_weight=0.1), dict(sampler_rng="philox"), dict(scoring_exponent=1, sampler_id=2)):
+        (M, lab), (Mr, labr) = _both(monkeypatch, px.findSpheres, pts, seed=2, minimum_point_number=100, **kw)
+        assert M.shape == Mr.shape and M.shape[0] >= 1 and np.array_equal(lab, labr) and np.allclose(M, Mr, rtol=1e-8, atol=1e-10), kw
+        if "radius_range" in kw:
+            assert (M[:, 3] >= 0.2).all() and (M[:, 3] <= 1.0).all()
+    pts, gt, truth = scene_3d("plane")
+    for kw in (dict(spatial_coherence_weight=0.1), dict(sampler_rng="philox", sampler_id=0), dict(scoring_exponent=1, sampler_id=1), dict(neighborhood="radius", neighborhood_ball_radius=0.3, spatial_coherence_weight=0.05)):
+        (M, lab), (Mr, labr) = _both(monkeypatch, px.findPlanes, pts, seed=2, minimum_point_number=100, **kw)
+        assert M.shape == Mr.shape == (3, 4) and np.array_equal(lab, labr) and np.allclose(M, Mr, rtol=1e-8, atol=1e-10), kw
 
 
 # ---- the reference's own recorded results (the only reference-held evidence): every bundled scene with EXACTLY the
@@ -233,6 +264,13 @@ def _edge_cases():
     cases.append(("poses_planar_object", px.find6DPoses, (x1, flat, K), dict(seed=1, minimum_point_number=10)))
     cases.append(("poses_all_outliers", px.find6DPoses, (rng.random((300, 2)) * 700, rng.random((300, 3)) * 100, K),
                   dict(seed=1, minimum_point_number=30, max_iters=100)))
+    for kind, fn in (("plane", px.findPlanes), ("sphere", px.findSpheres)):          # the 3-D point-cloud calls (helpers.edge_clouds_3d)
+        clouds = edge_clouds_3d(kind)
+        # (a scene 1e6 from the origin for spheres only: the plane refit's un-centred sums amplify the last bit of the Gram pass by
+        # ~|o|^2 there, so the two contexts' models part at 1e-4 - tests/test_oracle.py pins that law, DESIGN.md 4.5 states it)
+        for name in ("n_equals_sample_size", "coincident", "collinear", "coplanar", "outliers_only", "nan_row", "inf_row") + (("offset_1e6",) if kind == "sphere" else ()):
+            for sampler_id in (0, 3):
+                cases.append((f"{kind}s_{name}_sampler{sampler_id}", fn, (clouds[name][0],), dict(sampler_id=sampler_id, seed=1, minimum_point_number=20)))
     return cases
 
 
@@ -243,12 +281,19 @@ def test_edge_inputs_identical_to_cpu_restatement(monkeypatch, case, capsys):
     assert M.shape == Mr.shape and lab.shape == (len(args[0]),) and lab.dtype == np.int32
     assert np.array_equal(lab, labr)
     if M.size:
-        rows = {px.findLines: 1, px.findVanishingPoints: 1}.get(fn, 3)
+        rows = {px.findLines: 1, px.findVanishingPoints: 1, px.findPlanes: 1, px.findSpheres: 1}.get(fn, 3)
         A, B = M.reshape(-1, rows * M.shape[1]), Mr.reshape(-1, rows * M.shape[1])
         tol = 1e-7 * np.abs(B).max(axis=1, keepdims=True) + 1e-9
         same = np.all(np.abs(A - B) <= tol, axis=1)
-        if fn is not px.find6DPoses:
+        if fn not in (px.find6DPoses, px.findSpheres):
             same |= np.all(np.abs(A + B) <= tol, axis=1)       # homogeneous models: either sign
         assert same.all(), (name, M, Mr)
-    K = M.shape[0] // {px.findLines: 1, px.findVanishingPoints: 1}.get(fn, 3)
+    K = M.shape[0] // {px.findLines: 1, px.findVanishingPoints: 1, px.findPlanes: 1, px.findSpheres: 1}.get(fn, 3)
     assert lab.min() >= 0 and lab.max() <= max(K, 1)            # K = outlier label (0 / 1 with a single model; all 0 with none)
+    if fn in (px.findPlanes, px.findSpheres):
+        kind = "plane" if fn is px.findPlanes else "sphere"
+        cloud = name[len(kind) + 2:name.rindex("_sampler")]
+        if edge_clouds_3d(kind)[cloud][1] or cloud == "n_equals_sample_size":
+            assert K == 0, name                                 # an exactly degenerate cloud holds no structure of this kind
+        bad = np.nonzero(~np.isfinite(args[0]).all(axis=1))[0]
+        assert (lab[bad] == K).all() or K == 0                  # a row with a NaN / an Inf is never an inlier

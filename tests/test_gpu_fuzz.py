@@ -112,3 +112,52 @@ def test_replay_soak_slice():
     (tests/soak_replay.py; the long campaigns are in profiles/)"""
     import soak_replay
     assert soak_replay.soak(2024, 60, verbose=False) == 0
+
+
+# ---- the same soaks on the 3-D point-cloud types (planes, type 6; spheres, type 8): new seeds, the `types=` stream -----------------------
+TYPES_3D = ("plane", "sphere")
+
+
+@pytest.mark.parametrize("seed", [111, 112, 113])
+def test_scoring_soak_slice_3d(oracle, seed):
+    """60 cases per seed (30 per type) of tests/soak_scoring.py on planes and spheres: hypotheses a hair from the truth, garbage,
+    rescaled by up to 10^+-160 (a sphere's centre and radius together), entries of wildly different magnitude, a third of the
+    scenes moved up to 1e8 from the origin, outliers blown up inside a group, thresholds on a residual and one ulp either side -
+    counts, masks and values against the oracle, and under PGX_VERIFY=1 no inlier pair that the ball bound or the f32 filter threw
+    away (the contradiction count of pgx_score_stats must be 0 over all verified pairs)"""
+    import soak_scoring
+    assert soak_scoring.soak(seed, 60, verbose=False, types=TYPES_3D) == 0
+    st = soak_scoring.LAST
+    print(f"3-D scoring soak seed {seed}: {st['per_type']}, {st['verified_pairs']:.3g} verified pairs, {st['contradictions']} contradictions")
+    assert st["contradictions"] == 0 and st["verified_pairs"] > 0 and st["per_type"] == {"plane": 30, "sphere": 30}
+
+
+@pytest.mark.parametrize("seed", [211, 212])
+def test_pointwise_soak_slice_3d(oracle, seed):
+    """150 cases per seed (75 per type) of tests/soak_pointwise.py on planes and spheres: preference vectors, compound maximum,
+    unary table, residual sums, the 3-point / 4-point solvers (spheres: half of the cases under a radius range), neighbourhood
+    graph, the inlier/outlier cut and the greedy labelling - bit-exact against the oracle on wild hypotheses and point sets"""
+    import soak_pointwise
+    assert soak_pointwise.soak(seed, 150, verbose=False, types=TYPES_3D) == 0
+    print(f"3-D pointwise soak seed {seed}: {soak_pointwise.LAST}")
+    assert soak_pointwise.LAST["per_type"] == {"plane": 75, "sphere": 75}
+
+
+@pytest.mark.parametrize("seed", [311, 312])
+def test_api_soak_slice_3d(oracle, seed):
+    """30 calls per seed (15 per type) of tests/soak_api.py: findPlanes / findSpheres with random arguments (samplers 0 to 3, both
+    exponents, weights, radius ranges, neighbourhoods, local optimisation, scenes far from the origin) on the GPU and through the
+    same host code over the CPU oracle; classified as in test_api_soak_slice"""
+    import soak_api
+    assert soak_api.soak(seed, 30, verbose=False, types=TYPES_3D) == 0
+    print(f"3-D api soak seed {seed}: {soak_api.LAST}")
+    assert soak_api.LAST["per_type"] == {"findPlanes": 15, "findSpheres": 15}
+
+
+def test_replay_soak_slice_3d():
+    """40 random findPlanes / findSpheres calls through libpgx, every decision against the independent replay and every proposal
+    walk against the proposal replay (tests/soak_replay.py, types=)"""
+    import soak_replay
+    assert soak_replay.soak(2025, 40, verbose=False, types=TYPES_3D) == 0
+    print(f"3-D replay soak: {soak_replay.LAST}")
+    assert soak_replay.LAST["per_type"] == {"findPlanes": 20, "findSpheres": 20}

@@ -8,7 +8,7 @@ compound max) are required to be bit-identical: the kernels use the oracle's ope
 import numpy as np
 import pytest
 
-from helpers import (MODEL_CASES, csr_from_pairs, make_case, random_sym_graph, realistic_labeling_problem)
+from helpers import (ALL_MODEL_CASES, MODEL_CASES, MODEL_CASES_3D, csr_from_pairs, make_case, random_sym_graph, realistic_labeling_problem)
 from pyprogressivex import _lib, datasets
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +25,7 @@ def _rel(a, b):
 # ----------------------------------------------------------------------------------------------------------------------
 # a2 / a3 / a4 : preference vector (bit-exact), Tanimoto terms, compound max
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 20011])
 def test_preference_bit_exact(gpu_ctx, oracle, name, n):
     mt, pts, models, thr = make_case(name, n, 3, seed=n)
@@ -64,7 +64,7 @@ def test_preference_huge_threshold_exercises_every_lane(gpu_ctx, oracle):
 # ----------------------------------------------------------------------------------------------------------------------
 # a1 : batched scoring
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 @pytest.mark.parametrize("n,M", [(1, 1), (64, 3), (65, 257), (4097, 64), (20000, 300)])
 def test_score_matches_oracle(gpu_ctx, oracle, name, n, M):
     mt, pts, models, thr = make_case(name, n, M, seed=n + M)
@@ -104,6 +104,121 @@ def test_score_threshold_boundary_is_strict(gpu_ctx, oracle):
     thr = 4.0 / 3.0
     Dq = gpu_ctx.pearl_unary(model, thr, 0.25, want_table=True)
     assert np.array_equal(Dq, oracle.unary_q(mt, pts, model, thr, 0.25))
+
+
+@pytest.mark.parametrize("name", ["plane", "sphere"])
+def test_score_threshold_boundary_is_strict_3d(gpu_ctx, oracle, name):
+    """the same boundary for the 3-D types: the plane z = 0 / the sphere of radius 3 about the origin, points exactly 2 off it on
+    both sides (inside and outside the shell), a hair nearer, a hair farther and on it: r^2 == T2 = 4 is no inlier for the scorer
+    (strict <) and is within the threshold for PEARL's data term; then the threshold one ulp either side of a residual of a
+    realistic cloud, on the group path (n = 20011) as well"""
+    mt = ALL_MODEL_CASES[name]
+    if name == "plane":
+        pts = np.array([[7.0, 5.0, 2.0], [-1.0, 1.0, -2.0], [3.0, 0.0, 1.999999], [0.0, 0.0, 0.0], [1.0, 3.0, 2.0000001], [4.0, 4.0, -1.5]])
+        model = np.array([[0.0, 0.0, 1.0, 0.0]])
+    else:
+        pts = np.array([[5.0, 0.0, 0.0], [0.0, -1.0, 0.0], [0.0, 0.0, 4.999999], [0.0, 3.0, 0.0], [0.0, 0.0, 0.9999999], [0.0, 1.5, 0.0]])
+        model = np.array([[0.0, 0.0, 0.0, 3.0]])
+    gpu_ctx.set_points(mt, pts)
+    got = gpu_ctx.score(model, 4.0, want_masks=True)
+    ref = oracle.score(mt, pts, model, 4.0, want_masks=True)
+    assert got["counts"][0] == ref["counts"][0] == 3 and int(got["masks"][0, 0]) == 0b101100
+    thr = 4.0 / 3.0
+    Dq = gpu_ctx.pearl_unary(model, thr, 0.25, want_table=True)
+    assert np.array_equal(Dq, oracle.unary_q(mt, pts, model, thr, 0.25))
+    assert Dq[0, 0] == Dq[1, 0] == oracle.quantize(0.75) and Dq[4, 0] == oracle.quantize(1.5)     # at the threshold: priced, beyond it: 2 (1 - lambda)
+    for n in (500, 20011):
+        mt, pts, models, thr = make_case(name, n, 40, seed=n)
+        gpu_ctx.set_points(mt, pts)
+        sq = np.sort(oracle.squared_residuals(mt, pts, models[0]))
+        for mid in sq[[3, n // 10, n // 5, n // 2]]:
+            for T2 in (float(mid), float(np.nextafter(mid, np.inf)), float(np.nextafter(mid, 0.0))):
+                got = gpu_ctx.score(models, T2, want_masks=True)
+                ref = oracle.score(mt, pts, models, T2, want_masks=True)
+                assert np.array_equal(got["counts"], ref["counts"]) and np.array_equal(got["masks"], ref["masks"]), (name, n, T2)
+        c = oracle.score(mt, pts, models[:1], float(sq[n // 5]))["counts"][0]             # (the cloud holds duplicated rows: ties)
+        assert c == int((sq < sq[n // 5]).sum()) <= n // 5
+        assert oracle.score(mt, pts, models[:1], float(np.nextafter(sq[n // 5], np.inf)))["counts"][0] == int((sq <= sq[n // 5]).sum()) > c
+
+
+@pytest.mark.parametrize("name", ["plane", "sphere"])
+def test_3d_filters_adversarial(oracle, name, monkeypatch):
+    """The f32 filter and the ball bound of the 3-D types (score_filters.hip.h Filter32<kPlane3D> / <kSphere3D>) must never change
+    a result: hypotheses at relative distance 1e-13 .. 1e-3 from the truth, thresholds exactly on residuals, scenes moved 1e3 .. 1e8
+    from the origin (the budget's |d| and |c| terms), outliers blown up by 1e8 inside a group, spheres with r = 0, r < 0, a centre
+    far outside the cloud and a radius that swallows it, whole-scene scales 1e-6 and 1e6, NaN / Inf rows.  Counts and masks equal
+    the oracle's, and with PGX_VERIFY=1 the device's own pair-by-pair recount finds no inlier that a bound or the filter discarded."""
+    from pyprogressivex import parallel
+    monkeypatch.setenv("PGX_VERIFY", "1")
+    ctx = _lib.Context(0)
+    try:
+        rng = np.random.default_rng(31)
+        pairs = 0
+        for variant in ("plain", "offset_1e3", "offset_1e6", "offset_1e8", "scaled_up", "scaled_down", "blown_outliers", "non_finite"):
+            mt, pts, models, thr = make_case(name, 20011, 96, seed=17)
+            pts, models = pts.copy(), models.copy()
+            gt = models[0].copy()
+            for k in range(8, 48):
+                models[k] = gt * (1.0 + rng.normal(0, 10.0 ** rng.uniform(-13, -3), gt.shape))
+            if name == "sphere":
+                models[48] = [gt[0], gt[1], gt[2], 0.0]
+                models[49] = [gt[0], gt[1], gt[2], -gt[3]]
+                models[50] = [gt[0] + 1e4, gt[1], gt[2], 1e4 + gt[3]]          # the cloud's side of a huge sphere: nearly a plane
+                models[51] = [5.0, 5.0, 5.0, 40.0]                              # swallows the box: every point deep inside
+                models[52] = [5.0, 5.0, 5.0, 1e-300]
+            else:
+                models[48] = [gt[0], gt[1], gt[2], gt[3] + 1e3]                 # a parallel plane far away
+                models[49] = gt * 1e-8                                         # not a unit normal
+                models[50] = gt * 1e8
+                models[51] = [0.0, 0.0, 0.0, 0.01]                              # no normal at all: r = |d| for every point
+            scale = 1.0
+            if variant.startswith("offset"):
+                t = rng.normal(size=3)
+                t *= float(variant[7:]) / np.linalg.norm(t)
+                models2 = models.copy()
+                if name == "plane":
+                    models2[:, 3] = models[:, 3] - models[:, :3] @ t
+                else:
+                    models2[:, :3] = models[:, :3] + t
+                pts, models = pts + t, models2
+            elif variant.startswith("scaled"):
+                scale = 1e6 if variant == "scaled_up" else 1e-6
+                pts = pts * scale
+                if name == "plane":
+                    models[:, 3] *= scale
+                else:
+                    models *= scale
+            elif variant == "blown_outliers":
+                pts[rng.integers(0, len(pts), 40)] *= 1e8
+                pts[100:130] = pts[100]
+            elif variant == "non_finite":
+                pts[rng.integers(0, len(pts), 6), rng.integers(0, 3, 6)] = [np.nan, np.inf, -np.inf, 1e200, -1e200, 1e-200]
+            ctx.set_points(mt, pts)
+            comp = rng.random(len(pts)) * (rng.random(len(pts)) < 0.5)
+            ctx.set_compound(comp)
+            with np.errstate(all="ignore"):
+                sq0 = oracle.squared_residuals(mt, pts, models[0])
+            fin = np.sort(sq0[np.isfinite(sq0) & (sq0 > 0)])
+            base = 2.25 * (thr * scale) ** 2
+            for T2 in (base, base * 1e-4, base * 1e4, float(fin[len(fin) // 3]), float(np.nextafter(fin[len(fin) // 3], np.inf)), float(fin[5])):
+                ref = oracle.score(mt, pts, models, T2, compound=comp, has_compound=True, exponent=2, want_masks=True)
+                got = ctx.score(models, T2, has_compound=True, exponent=2, want_masks=True)
+                assert np.array_equal(got["counts"], ref["counts"]), (name, variant, T2, np.nonzero(got["counts"] != ref["counts"])[0][:5])
+                assert np.array_equal(got["masks"], ref["masks"]), (name, variant, T2)
+                # sums: REL, plus what the number format takes - the group-major path adds every inlier's term rounded to a multiple
+                # of 2^-q (q = 47 at this n: half a unit per inlier), which shows where a threshold one ulp above a residual leaves
+                # a hypothesis a single inlier with a preference of 1e-16
+                unit = ref["counts"] / parallel.fixed_point_scale(len(pts))
+                for k in ("values", "shared"):
+                    assert np.all(np.abs(got[k] - ref[k]) <= REL * np.abs(ref[k]) + unit), (name, variant, T2, k)
+                st = ctx.score_stats(T2, has_compound=True)
+                assert st["contradictions"] <= 0, (name, variant, T2, st)
+                pairs += st["pairs"] if st["contradictions"] == 0 else 0
+            if variant in ("plain", "offset_1e3"):        # the scene is still the scene: the ground truth keeps its inliers
+                assert oracle.score(mt, pts, models[:1], base)["counts"][0] > 2000
+        assert pairs > 10 * 20011 * 96                    # the verifying recount did run on most of the batches
+    finally:
+        ctx.close()
 
 
 @pytest.mark.parametrize("name", ["pnp", "homography"])
@@ -518,7 +633,7 @@ def test_score_is_reproducible_and_batch_invariant(gpu_ctx):
 # ----------------------------------------------------------------------------------------------------------------------
 # a6 : unary table
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 def test_unary_table_bit_exact(gpu_ctx, oracle, name):
     mt, pts, models, thr = make_case(name, 3001, 7, seed=21)
     gpu_ctx.set_points(mt, pts)
@@ -545,7 +660,7 @@ def test_bucket_matches_oracle(gpu_ctx, oracle, n, L):
     assert none is None and np.array_equal(sizes, rc)
 
 
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 def test_residual_sum(gpu_ctx, oracle, name):
     mt, pts, models, thr = make_case(name, 5003, 2, seed=31)
     labels = np.random.default_rng(1).integers(0, 3, 5003).astype(np.int32)
@@ -555,6 +670,25 @@ def test_residual_sum(gpu_ctx, oracle, name):
         got = gpu_ctx.residual_sum(model, k)
         ref = oracle.residual_sum(mt, pts, model, labels, k)
         assert abs(got - ref) <= REL * max(abs(ref), 1e-300), name
+
+
+@pytest.mark.parametrize("name", ["plane", "sphere"])
+def test_residual_sum_at_the_ends_of_the_range_3d(gpu_ctx, oracle, name):
+    """PEARL's refit sums add the plain residual r, not sqrt(r * r).  In range the two are the same double; they part where r * r
+    under- or overflows (r = 1e-170: r * r = 0; r = 1e200: r * r = inf).  Device and oracle both return r + r there - an oracle left on
+    its sqrt(squared) fallback, or a kernel summing roots of squares, returns 0 or inf."""
+    mt = ALL_MODEL_CASES[name]
+    for r in (1e-170, 1e200):
+        if name == "plane":      # the plane z = 0, two points r above it
+            pts, model = np.array([[0.0, 0.0, r], [1.0, 2.0, r], [3.0, 3.0, 1.0]]), np.array([0.0, 0.0, 1.0, 0.0])
+        else:                    # two points at the centre of a sphere of radius r
+            pts, model = np.array([[1.0, 2.0, 3.0], [1.0, 2.0, 3.0], [9.0, 9.0, 9.0]]), np.array([1.0, 2.0, 3.0, r])
+        labels = np.array([0, 0, 1], np.int32)
+        gpu_ctx.set_points(mt, pts)
+        gpu_ctx.set_labels(labels)
+        got, ref = gpu_ctx.residual_sum(model, 0), oracle.residual_sum(mt, pts, model, labels, 0)
+        assert got == ref == r + r, (name, r, got, ref)
+        assert gpu_ctx.residual_sums(np.stack([model, model]))[0] == r + r
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1000,6 +1134,24 @@ def test_graph_ball_matches_oracle(gpu_ctx, oracle, style, n, d):
             assert all(np.array_equal(a, b) for a, b in zip(got, ref))
 
 
+@pytest.mark.parametrize("n,d", [(300, 3), (300, 5), (5000, 3), (5000, 4)])
+def test_graph_build_with_non_finite_tail_coordinates_matches_oracle(gpu_ctx, oracle, n, d):
+    """NaN / +Inf / -Inf / 1e200 outside the two grid coordinates (pgx_graph_build refuses them inside: test_graph_build_error_paths):
+    a distance that is NaN or infinite is no distance, so such a point has no neighbours and is nobody's neighbour - the device's
+    lists equal the oracle's for every graph kind, on the oracle's brute-force path (n = 300) and its kd-tree path (n = 5000)"""
+    rng = np.random.default_rng(n + d)
+    pts = rng.random((n, d)) * (6.0 if n == 300 else 18.0)
+    bad = rng.choice(n, 12, replace=False)
+    pts[bad, rng.integers(2, d, 12)] = np.tile([np.nan, np.inf, -np.inf, 1e200], 3)
+    lone = bad[np.arange(12) % 4 != 3]           # (two rows at 1e200 in the same column ARE neighbours: a finite distance)
+    for kind, radius, k in ((_lib.GRAPH_KNN_IN_BALL, 1.0, 5), (_lib.GRAPH_KNN_IN_BALL, 1e4, 8), (_lib.GRAPH_KNN, 0.0, 6), (_lib.GRAPH_BALL, 1.0, 5)):
+        ref = oracle.graph_build(pts, kind, radius=radius, k=k)
+        got = gpu_ctx.graph_build(pts, kind, radius=radius, k=k)
+        for what, a, b in zip(("off", "idx", "mult"), got, ref):
+            assert np.array_equal(a, b), f"n={n} d={d} kind={kind} r={radius}: {what} differs"
+        assert (np.diff(ref[0])[lone] == 0).all() and not np.isin(ref[1], lone).any() and len(ref[1]) > 0
+
+
 def test_graph_build_feeds_the_expansion(gpu_ctx, oracle):
     # the resident graph of pgx_graph_build is the one the moves run on: same labels as with pgx_set_graph(oracle CSR)
     rng = np.random.default_rng(5)
@@ -1087,32 +1239,65 @@ def test_graph_build_error_paths(gpu_ctx):
 # ----------------------------------------------------------------------------------------------------------------------
 # SURVEY 8f rank 1 (first slice): minimal solvers on the GPU — bit-exact models, then scored where they are
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["line", "vanishing_point", "homography", "fundamental", "pnp"])
+@pytest.mark.parametrize("name", ["line", "vanishing_point", "homography", "fundamental", "pnp", "plane", "sphere"])
 def test_solve_minimal_matches_oracle_and_scores_in_place(gpu_ctx, oracle, name):
     mt, pts, models, thr = make_case(name, 5000, 4, seed=9)
     rng = np.random.default_rng(4)
-    m = {"fundamental": 7, "homography": 4, "pnp": 3}.get(name, 2)
+    m = {"fundamental": 7, "homography": 4, "pnp": 3, "plane": 3, "sphere": 4}.get(name, 2)
     slots = {"fundamental": 3, "pnp": 4}.get(name, 1)
     samples = rng.integers(0, 5000, (3000, m)).astype(np.int32)
     if name in ("fundamental", "pnp"):                      # some all-inlier samples of one structure as well
         for s in range(100, 400):
             samples[s] = rng.choice(np.nonzero(np.arange(5000) % 5 == s % 3)[0], m, replace=False)
+    if name in MODEL_CASES_3D:                              # samples from the inliers of the three ground-truth structures
+        inl = [np.flatnonzero(oracle.squared_residuals(mt, pts, models[k]) < thr * thr) for k in range(3)]
+        for s in range(100, 400):
+            samples[s] = rng.choice(inl[s % 3], m, replace=False)
     samples[:40, 1] = samples[:40, 0]                      # degenerate: the same point / segment twice
     gpu_ctx.set_points(mt, pts)
     got = gpu_ctx.solve_minimal(samples)
     ref = oracle.solve_minimal(mt, pts, samples)
-    assert got.shape == ref.shape == (3000 * slots, {"fundamental": 9, "homography": 9, "pnp": 12}.get(name, 3))
-    assert np.array_equal(np.isnan(got), np.isnan(ref)) and np.isnan(got[:40 * slots]).all()
+    assert got.shape == ref.shape == (3000 * slots, {"fundamental": 9, "homography": 9, "pnp": 12, "plane": 4, "sphere": 4}.get(name, 3))
+    assert np.array_equal(np.isnan(got), np.isnan(ref))
+    if name == "sphere":     # a repeated point: det cancels to 0 only up to rounding; where it does not, the numerators cancel exactly
+        assert (np.isnan(got[:40, 3]) | (got[:40, 3] == 0.0)).all()          # (n2 = 0, n3 = -n1, h3 = h1): the sphere of radius 0 at p0
+    else:
+        assert np.isnan(got[:40 * slots]).all()
     ok = ~np.isnan(ref[:, 0])
     assert np.array_equal(got[ok], ref[ok]), "generated hypotheses must be bit-identical to the oracle's"
     T2 = 9.0 / 4.0 * thr * thr
     gpu_ctx.score_launch(T2)                              # scores the resident, device-generated batch
     a = gpu_ctx.score_fetch()
     b = oracle.score(mt, pts, np.where(np.isnan(ref), np.nan, ref), T2)
-    assert np.array_equal(a["counts"], b["counts"]) and a["counts"][:40 * slots].max() == 0
+    assert np.array_equal(a["counts"], b["counts"]) and a["counts"][:40 * slots][np.isnan(ref[:40 * slots, 0])].max(initial=0) == 0
     assert _rel(a["values"], b["values"]) < REL
     up = gpu_ctx.score(ref[ok], T2)                       # the same models through the upload path
     assert np.array_equal(up["counts"], a["counts"][ok])
+    if name in MODEL_CASES_3D:
+        assert a["counts"][100:400].max() > 500           # the all-inlier samples found their structure
+    if name == "sphere":
+        # pgx_set_radius_range (context state): inclusive at both ends - the upper end IS a radius of the batch - and the rows it
+        # removes are NaN on both sides; the kept rows are the unrestricted rows bit for bit; invalid ranges are refused
+        radii = np.sort(ref[ok, 3])
+        rmin, rmax = float(radii[len(radii) // 4]), float(radii[3 * len(radii) // 4])
+        try:
+            for rr in ((rmin, rmax), (rmin, np.inf), (0.0, rmax), (rmax, rmax)):
+                gpu_ctx.set_radius_range(*rr)
+                ranged = gpu_ctx.solve_minimal(samples)
+                ref_r = oracle.solve_minimal(mt, pts, samples, radius_range=rr)
+                assert np.array_equal(ranged, ref_r, equal_nan=True), rr
+                keep = ~np.isnan(ranged[:, 0])
+                assert np.array_equal(keep, ok & (ref[:, 3] >= rr[0]) & (ref[:, 3] <= rr[1])) and np.array_equal(ranged[keep], ref[keep])
+                assert 0 < keep.sum() < ok.sum()
+                gpu_ctx.score_launch(T2)
+                assert np.array_equal(gpu_ctx.score_fetch()["counts"], oracle.score(mt, pts, ref_r, T2)["counts"])
+            for bad in ((-1.0, 1.0), (2.0, 1.0), (np.nan, 1.0), (0.0, np.nan)):
+                with pytest.raises(_lib.PgxError):
+                    gpu_ctx.set_radius_range(*bad)
+            assert np.array_equal(gpu_ctx.solve_minimal(samples), ref_r, equal_nan=True)      # a refused range leaves the state alone
+        finally:
+            gpu_ctx.set_radius_range()
+        assert np.array_equal(gpu_ctx.solve_minimal(samples), ref, equal_nan=True)
 
 
 def test_solve_minimal_error_paths(gpu_ctx):
@@ -1129,7 +1314,7 @@ def test_solve_minimal_error_paths(gpu_ctx):
 # ----------------------------------------------------------------------------------------------------------------------
 # a9: Gram pass of the non-minimal refits — floating-point sums, 1e-9 relative to the matrix scale
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 @pytest.mark.parametrize("n", [1, 257, 20011])
 def test_gram_matches_oracle(gpu_ctx, oracle, name, n):
     mt, pts, models, thr = make_case(name, n, 2, seed=n + 11)
@@ -1143,7 +1328,9 @@ def test_gram_matches_oracle(gpu_ctx, oracle, name, n):
              "homography": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_DLT_H, np.array([0.01, 300.0, 200.0, 0.012, 310.0, 190.0]))],
              "homography_sym": [(_lib.GRAM_DLT_H, np.array([0.01, 300.0, 200.0, 0.012, 310.0, 190.0]))],
              "fundamental": [(_lib.GRAM_EPI_F, np.array([0.01, 300.0, 200.0, 0.012, 310.0, 190.0]))],
-             "pnp": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_PNP_GN, models[0][:12])]}[name]
+             "pnp": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_PNP_GN, models[0][:12])],
+             "plane": [(_lib.GRAM_AFFINE, None)],
+             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, np.array([5.1, 4.9, 5.3, 2.5]))]}[name]
     index = rng.permutation(n)[: max(1, n // 2)]
     for kind, prm in kinds:
         for sel, ref_index in ((("index", index), index), (("label", 1), np.nonzero(labels == 1)[0])):
@@ -1161,7 +1348,7 @@ def test_gram_matches_oracle(gpu_ctx, oracle, name, n):
     assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 @pytest.mark.parametrize("B,m", [(1, 1), (3, 14), (50, 49), (7, 64), (5, 200)])
 def test_gram_batch_matches_oracle(gpu_ctx, oracle, name, B, m):
     """pgx_gram_batch (one wave per selection, per-selection parameter blocks) against the oracle's per-selection Gram."""
@@ -1176,7 +1363,9 @@ def test_gram_batch_matches_oracle(gpu_ctx, oracle, name, B, m):
              "homography": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_DLT_H, norm)],
              "homography_sym": [(_lib.GRAM_DLT_H, norm)],
              "fundamental": [(_lib.GRAM_EPI_F, norm)],
-             "pnp": [(_lib.GRAM_PNP_GN, lambda: models[0][:12] + 1e-3 * rng.random(12))]}[name]
+             "pnp": [(_lib.GRAM_PNP_GN, lambda: models[0][:12] + 1e-3 * rng.random(12))],
+             "plane": [(_lib.GRAM_AFFINE, None)],
+             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, lambda: np.array([5.1, 4.9, 5.3, 2.5]) * (1.0 + 0.1 * rng.random(4)))]}[name]
     index = np.array([rng.choice(n, m, replace=False) for _ in range(B)])
     for kind, make in kinds:
         prm = None if make is None else np.array([make() for _ in range(B)])
@@ -1197,9 +1386,10 @@ def test_batched_refits_equal_single_refits(gpu_ctx):
     selection (same algebra; only the reduction tree of the Gram pass differs: 1e-9)."""
     from pyprogressivex import _estimators
     rng = np.random.default_rng(4)
-    for name in ("line", "vanishing_point", "homography", "homography_sym", "fundamental", "pnp"):
+    table = dict(_estimators.ESTIMATORS, plane=_estimators.PlaneEstimator, sphere=_estimators.SphereEstimator)
+    for name in ("line", "vanishing_point", "homography", "homography_sym", "fundamental", "pnp", "plane", "sphere"):
         mt, pts, models, thr = make_case(name, 4000, 1, seed=9)
-        est = _estimators.ESTIMATORS[name]()
+        est = table[name]()
         gpu_ctx.set_points(mt, pts)
         m = 7 * est.sample_size
         one = gpu_ctx.score(models[:1], 2.25 * thr * thr, want_masks=True)
@@ -1212,7 +1402,7 @@ def test_batched_refits_equal_single_refits(gpu_ctx):
             single = est.nonminimal(gpu_ctx, ("index", picks[b]), None, init=init)
             assert len(single) == len(batch[b]) == 1
             a, c = np.asarray(single[0]), np.asarray(batch[b][0])
-            if np.dot(a, c) < 0 and name in ("line", "vanishing_point", "fundamental"):
+            if np.dot(a, c) < 0 and name in ("line", "vanishing_point", "fundamental", "plane"):
                 c = -c                                             # eigenvector sign
             assert np.abs(a - c).max() <= 1e-6 * max(1.0, np.abs(a).max()), name
 
@@ -1284,7 +1474,7 @@ def test_device_pose_refits_reproduce_the_host_iteration(gpu_ctx):
         gpu_ctx.pnp_refine_batch(models[:1], np.full((1, 5), len(pts), np.int32))
 
 
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 def test_label_batched_gram_and_residual_sums_are_bitwise_the_single_label_calls(gpu_ctx, name):
     # pgx_gram_labels / pgx_residual_sums: all instances of a PEARL iteration in one launch, same trees as the single calls
     n, K = 30011, 5
@@ -1303,7 +1493,9 @@ def test_label_batched_gram_and_residual_sums_are_bitwise_the_single_label_calls
              "homography": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_DLT_H, np.array([norm * (1 + 0.1 * k) for k in range(K)]))],
              "homography_sym": [(_lib.GRAM_DLT_H, np.array([norm * (1 + 0.1 * k) for k in range(K)]))],
              "fundamental": [(_lib.GRAM_EPI_F, np.array([norm * (1 + 0.1 * k) for k in range(K)]))],
-             "pnp": [(_lib.GRAM_PNP_GN, models[:, :12])]}[name]
+             "pnp": [(_lib.GRAM_PNP_GN, models[:, :12])],
+             "plane": [(_lib.GRAM_AFFINE, None)],
+             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, np.array([np.array([5.1, 4.9, 5.3, 2.5]) * (1 + 0.1 * k) for k in range(K)]))]}[name]
     for kind, prm in kinds:
         for w, wpow in ((None, 2), (weights, 1), (weights, 2)):
             G, cnt, bad = gpu_ctx.gram_labels(kind, K, params=prm, weights=w, wpow=wpow)
@@ -1377,7 +1569,7 @@ def test_asymmetric_graph_is_rejected(gpu_ctx):
 # GC-RANSAC's inlier/outlier graph cut (pgx_gc_labeling) — flags bit-exact against the oracle, which
 # builds upstream's add_term1/add_term2 graph while the device solves the re-parameterised Potts form
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 @pytest.mark.parametrize("n,lam", [(2, 0.5), (65, 0.1), (3000, 0.3), (20011, 0.14), (20011, 0.9)])
 def test_gc_labeling_matches_oracle(gpu_ctx, oracle, name, n, lam):
     mt, pts, models, thr = make_case(name, n, 6, seed=n)
@@ -1564,7 +1756,7 @@ def test_inlier_indices_at_the_one_launch_compaction_limits(gpu_ctx, oracle, n):
         assert np.array_equal(gpu_ctx.gc_inliers(m, T2, 0.2), np.flatnonzero(oracle.gc_labeling(mt, pts, m, T2, 0.2, graph)))
 
 
-@pytest.mark.parametrize("name", ["pnp", "homography", "line"])
+@pytest.mark.parametrize("name", ["pnp", "homography", "line", "plane", "sphere"])
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 5000, 100003])
 def test_score_inliers_are_the_mask_row(gpu_ctx, oracle, name, n):
     """pgx_score_inliers: the inlier vector of getScore (scoring_function_with_compound_model.h:88) as ascending indices,
@@ -1656,7 +1848,7 @@ def test_point_sharded_accumulators_are_exact(gpu_ctx, oracle):
     point-sharded job all-reduce is bitwise the single-GPU table."""
     from helpers import fixed_point_accumulators
     from pyprogressivex import parallel
-    for name in ("pnp", "fundamental", "vanishing_point"):
+    for name in ("pnp", "fundamental", "vanishing_point", "plane", "sphere"):
         mt, pts, models, thr = make_case(name, 20011, 96, seed=9)
         T2 = 2.25 * thr * thr
         n = pts.shape[0]
@@ -1921,6 +2113,49 @@ def test_set_points_device_equals_host_preprocessing(name, n, monkeypatch, oracl
         assert np.array_equal(got["0"]["score"][k], got["1"]["score"][k]), k
     ref = oracle.score(mt, pts, models, T2, want_masks=True)
     assert np.array_equal(got["0"]["score"]["counts"], ref["counts"]) and np.array_equal(got["0"]["score"]["masks"], ref["masks"])
+
+
+@pytest.mark.parametrize("name,n", [("plane", 1), ("plane", 63), ("plane", 64), ("plane", 65), ("plane", 5000), ("plane", 100003),
+                                    ("sphere", 513), ("sphere", 20011)])
+def test_set_points_device_preprocessing_of_3d_points(name, n, monkeypatch, oracle):
+    """Point dimension 3.  The host preprocessing of round 1 (PGX_SETPOINTS_HOST=1) has no sorted path for the types without a
+    projective map: it scores every pair.  That makes it the independent side here: the device preprocessing (Morton order of all
+    three coordinates, 64-point balls, f32 rows) must return the host path's counts, values and masks bit for bit - and both the
+    oracle's - with exact duplicates and a far point in the cloud; the order it derived is a permutation of the points, the sorted
+    f64 copy holds exactly the caller's rows in that order, and every group ball contains its 64 points."""
+    mt, pts, models, thr = make_case(name, n, 70, seed=n)
+    if n > 1000:
+        pts[7] = pts[3]
+        pts[11, 0] = pts[:, 0].max() * 3.0
+    T2 = 2.25 * thr * thr
+    got, order, rows64 = {}, None, None
+    for mode in ("0", "1"):
+        monkeypatch.setenv("PGX_SETPOINTS_HOST", mode)
+        ctx = _lib.Context(0)
+        try:
+            ctx.set_points(mt, pts)
+            got[mode] = ctx.score(models, T2, want_masks=True)
+            got[mode + "path"] = ctx.score_stats(T2)["path"]
+            if mode == "0" and got["0path"] == "cull + group-major":
+                order, rows64 = ctx.score_debug_fetch("order"), ctx.score_debug_fetch("rows64")
+        finally:
+            ctx.close()
+    monkeypatch.delenv("PGX_SETPOINTS_HOST")
+    ref = oracle.score(mt, pts, models, T2, want_masks=True)
+    for k in ("counts", "masks"):
+        assert np.array_equal(got["0"][k], got["1"][k]) and np.array_equal(got["0"][k], ref[k]), k
+    assert _rel(got["0"]["values"], ref["values"]) <= REL and _rel(got["1"]["values"], ref["values"]) <= REL
+    assert got["1path"] == "every pair"                  # the host preprocessing has no sorted path for these types
+    if n >= 5000:
+        assert got["0path"] == "cull + group-major"      # the device preprocessing has
+    if order is not None:
+        assert np.array_equal(np.sort(order), np.arange(n))
+        full = n // 64
+        blocked = pts[order[:full * 64]].reshape(full, 64, 3).transpose(0, 2, 1)
+        assert np.array_equal(rows64[:full], blocked)    # the group-blocked f64 copy: the caller's rows, bit for bit, in that order
+        tail = n - full * 64
+        if tail:
+            assert np.array_equal(rows64[full][:, :tail], pts[order[full * 64:]].T)
 
 
 @pytest.mark.parametrize("n", [129, 130, 4097, 5000, 100003])

@@ -1,5 +1,8 @@
-"""findPlanes on the MI355X: every layer of the 3-D plane type against a numpy restatement of its arithmetic (the oracle knows no
-planes), and against the oracle where the step is model-agnostic (the neighbourhood graph, alpha-expansion on a given table).
+"""findPlanes on the MI355X: every layer of the 3-D plane type against a numpy restatement of its arithmetic written next to the
+kernels, and against the oracle where the step is model-agnostic (the neighbourhood graph, alpha-expansion on a given table).  The CPU
+oracle has its own plane rows since (oracle/pgx_oracle.c, checked against exact arithmetic in tests/test_oracle.py): the per-type
+sweeps of tests/test_gpu_parity.py, the API / replay files and the soaks hold the device to those; this file stays as a second,
+numpy-side statement of the same contract.
 
 Residual<kPlane3D> (residuals.hip.h) is the contract: r = |((a x + b y) + c z) + d|, r^2 = r * r, inlier iff r^2 < T2."""
 import numpy as np

@@ -1,5 +1,8 @@
-"""findSpheres on the MI355X: every layer of the 3-D sphere type against a numpy restatement of its arithmetic (the oracle knows no
-spheres), and against the oracle where the step is model-agnostic (the neighbourhood graph, alpha-expansion on a given table).
+"""findSpheres on the MI355X: every layer of the 3-D sphere type against a numpy restatement of its arithmetic written next to the
+kernels, and against the oracle where the step is model-agnostic (the neighbourhood graph, alpha-expansion on a given table).  The CPU
+oracle has its own sphere rows since (oracle/pgx_oracle.c, checked against exact arithmetic in tests/test_oracle.py): the per-type
+sweeps of tests/test_gpu_parity.py, the API / replay files and the soaks hold the device to those; this file stays as a second,
+numpy-side statement of the same contract.
 
 Residual<kSphere3D> (residuals.hip.h) is the contract: dx = x - cx, dy = y - cy, dz = z - cz,
 r = |sqrt((dx dx + dy dy) + dz dz) - cr|, r^2 = r * r, inlier iff r^2 < T2."""

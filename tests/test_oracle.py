@@ -4,6 +4,7 @@ max-flow against scipy, expansion moves against brute force, and the committed g
 The reference ships no tests or golden vectors for this path (SURVEY.md §0.3) => parity is UNPINNED against upstream;
 these tests pin the oracle against the mathematics it restates and against regressions.
 """
+import decimal
 import itertools
 import os
 from fractions import Fraction as Fr
@@ -11,7 +12,7 @@ from fractions import Fraction as Fr
 import numpy as np
 import pytest
 
-from helpers import MODEL_CASES, make_case, random_sym_graph
+from helpers import ALL_MODEL_CASES, MODEL_CASES, MODEL_CASES_3D, make_case, random_sym_graph
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_v1.npz")
 
@@ -43,6 +44,17 @@ def test_residual_known_answers(oracle):
     # unsquared residual used by PEARL's refit test
     assert O.residual(O.LINE2D, [5.0, 9.0], [1.0, 0.0, -3.0]) == 2.0
     assert O.residual(O.HOMOGRAPHY, [1, 2, 4, 6], np.eye(3).reshape(-1)) == 5.0
+    # plane z = 3, i.e. (0, 0, 1, -3): a point 2 above it, one 2 below it, one on it
+    assert O.squared_residuals(O.PLANE3D, [[7.0, -1.0, 5.0], [0.0, 4.0, 1.0], [9.0, 9.0, 3.0]], [0.0, 0.0, 1.0, -3.0]).tolist() == [4.0, 4.0, 0.0]
+    assert O.residual(O.PLANE3D, [7.0, -1.0, 5.0], [0.0, 0.0, 1.0, -3.0]) == 2.0
+    # sphere of radius 3 about (1, 2, 3): 2 outside the shell, 2 inside it, on it, and its centre (|0 - 3| = 3)
+    sph = [1.0, 2.0, 3.0, 3.0]
+    assert O.squared_residuals(O.SPHERE3D, [[6.0, 2.0, 3.0], [1.0, 1.0, 3.0], [1.0, 2.0, 0.0], [1.0, 2.0, 3.0]], sph).tolist() == [4.0, 4.0, 0.0, 9.0]
+    assert O.residual(O.SPHERE3D, [6.0, 2.0, 3.0], sph) == 2.0 and O.residual(O.SPHERE3D, [1.0, 1.0, 3.0], sph) == 2.0
+    # r = 0 is the distance from the centre; r < 0 is evaluated as the formula stands: | |p - c| - r | = |p - c| + |r|
+    assert O.squared_residuals(O.SPHERE3D, [[4.0, 6.0, 3.0]], [1.0, 2.0, 3.0, 0.0]).tolist() == [25.0]
+    assert O.squared_residuals(O.SPHERE3D, [[4.0, 6.0, 3.0]], [1.0, 2.0, 3.0, -2.0]).tolist() == [49.0]
+    assert O.residual(O.SPHERE3D, [4.0, 6.0, 3.0], [1.0, 2.0, 3.0, -2.0]) == 7.0
 
 
 def _exact_sq(name, p, m):
@@ -79,10 +91,20 @@ def _exact_sq(name, p, m):
         mx, my = (xs + xe) / 2, (ys + ye) / 2
         lx, ly, lz = my * m[2] - m[1], -(mx * m[2] - m[0]), mx * m[1] - my * m[0]
         return (lx * xs + ly * ys + lz) ** 2 / (lx * lx + ly * ly)
+    if name == "plane":
+        return (m[0] * p[0] + m[1] * p[1] + m[2] * p[2] + m[3]) ** 2
+    if name == "sphere":
+        # (|p - c| - r)^2 = q + r^2 - 2 r sqrt(q), q = |p - c|^2 rational; the root to 80 significant digits
+        q = (p[0] - m[0]) ** 2 + (p[1] - m[1]) ** 2 + (p[2] - m[2]) ** 2
+        with decimal.localcontext() as c:
+            c.prec = 80
+            root = (decimal.Decimal(q.numerator) / decimal.Decimal(q.denominator)).sqrt()
+            rq = Fr(*root.as_integer_ratio())
+        return q + m[3] ** 2 - 2 * m[3] * rq
     raise KeyError(name)
 
 
-@pytest.mark.parametrize("name", list(MODEL_CASES))
+@pytest.mark.parametrize("name", list(ALL_MODEL_CASES))
 def test_residuals_against_exact_rational_arithmetic(oracle, name):
     """Independent check of every formula: evaluate the published definition in exact rational arithmetic."""
     mt, pts, models, thr = make_case(name, 40, 4, seed=1)
@@ -541,3 +563,293 @@ def test_jacobi_eigen_solver_against_lapack_and_by_hand(oracle):
     bad[1, 0, 2] = bad[1, 2, 0] = np.inf
     vec, val, sw = oracle.eigh_smallest(bad)
     assert np.array_equal(vec[2], [1.0, 0.0, 0.0]) and val[2] == 0.0
+
+
+# ---- the 3-D point-cloud types (planes, type 6; spheres, type 8): the oracle rows against exact arithmetic --------------------------
+GOLDEN_3D = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_3d_v1.npz")
+
+
+def test_model_dims_agree_with_the_product_table_for_every_type_number(oracle):
+    """pgxo_model_dims against pyprogressivex._lib.MODEL_TABLE (the numbers of csrc/residuals.hip.h) for 0 .. 9: the same types
+    exist on both sides (7 and 9 do not), with the same point and parameter dimensions and, where the oracle has a solver, the
+    same sample size"""
+    from pyprogressivex import _lib
+    for t in range(10):
+        dims = oracle.model_dims(t)
+        if t in _lib.MODEL_TABLE:
+            assert dims == _lib.MODEL_TABLE[t][:2] == (oracle.POINT_DIM[t], oracle.PARAM_DIM[t]), t
+            assert oracle.SAMPLE_SIZE.get(t, 0) == _lib.MODEL_TABLE[t][2], t
+        else:
+            assert dims is None and t not in oracle.POINT_DIM and t not in oracle.PARAM_DIM, t
+    assert oracle.model_dims(-1) is None and np.isnan(oracle.squared_residuals(7, np.zeros((0, 3)), np.zeros(4))).all()
+    assert (oracle.PLANE3D, oracle.SPHERE3D) == (_lib.PLANE3D, _lib.SPHERE3D) == (6, 8)
+    assert oracle.GRAM_SPHERE == _lib.GRAM_SPHERE and oracle.GRAM_AFFINE == _lib.GRAM_AFFINE
+
+
+@pytest.mark.parametrize("name", list(MODEL_CASES_3D))
+def test_plain_residual_of_the_3d_types_is_not_the_root_of_the_square(oracle, name):
+    """pgxo_residual (PEARL's refit sums) returns r itself for the types whose squared residual is defined as r * r, as the device's
+    Residual<>::plain does.  In binary floating point sqrt(fl(r * r)) == r as long as r * r neither overflows nor underflows, so the
+    two readings part only at the ends of the range: r = 1e-170 (r * r = 0) and r = 1e200 (r * r = inf).  Both are pinned here; in
+    range, r * r is the squared residual bit for bit and agrees with exact arithmetic."""
+    mt, pts, models, thr = make_case(name, 200, 3, seed=3)
+    for model in models:
+        sq = oracle.squared_residuals(mt, pts, model)
+        for i in range(pts.shape[0]):
+            r = oracle.residual(mt, pts[i], model)
+            assert r >= 0.0 and r * r == sq[i] and np.sqrt(sq[i]) == r
+            ex = float(_exact_sq(name, pts[i], model))
+            assert abs(r * r - ex) <= 1e-9 * max(abs(ex), 1e-30) + 1e-18 * max(1.0, abs(ex))
+    if name == "plane":      # the plane z = 0 and points 1e-170 / 1e200 above it
+        cases = [([0.0, 0.0, 1e-170], [0.0, 0.0, 1.0, 0.0], 1e-170), ([0.0, 0.0, 1e200], [0.0, 0.0, 1.0, 0.0], 1e200)]
+    else:                    # the centre of a sphere of radius 1e-170 / 1e200
+        cases = [([1.0, 2.0, 3.0], [1.0, 2.0, 3.0, 1e-170], 1e-170), ([1.0, 2.0, 3.0], [1.0, 2.0, 3.0, 1e200], 1e200)]
+    for p, m, r in cases:
+        sq = oracle.squared_residuals(mt, [p], m)[0]
+        assert oracle.residual(mt, p, m) == r and np.sqrt(sq) != r and sq in (0.0, np.inf)
+        assert oracle.residual_sum(mt, np.array([p, p]), m, np.zeros(2, np.int32), 0) == r + r
+    labels = np.arange(pts.shape[0], dtype=np.int32) % 3
+    seq = 0.0
+    for i in np.nonzero(labels == 1)[0]:
+        seq += oracle.residual(mt, pts[i], models[0])
+    assert oracle.residual_sum(mt, pts, models[0], labels, 1) == seq
+
+
+def _exact_circumsphere(P):
+    """centre (Fractions), squared radius (Fraction) and squared conditioning det^2 / (|a1|^2 |a2|^2 |a3|^2) of the sphere through
+    the four points P [4][3] of doubles, by Cramer's rule in exact rational arithmetic; None for coplanar points"""
+    P = [[Fr(float(v)) for v in row] for row in P]
+    a = [[P[i][k] - P[0][k] for k in range(3)] for i in (1, 2, 3)]
+    h = [sum(v * v for v in ai) / 2 for ai in a]
+
+    def det3(m):
+        return (m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0])
+                + m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]))
+    det = det3(a)
+    if det == 0:
+        return None
+    e = []
+    for k in range(3):
+        mk = [[h[i] if j == k else a[i][j] for j in range(3)] for i in range(3)]
+        e.append(det3(mk) / det)
+    cond2 = det * det / (sum(v * v for v in a[0]) * sum(v * v for v in a[1]) * sum(v * v for v in a[2]))
+    return [P[0][k] + e[k] for k in range(3)], sum(v * v for v in e), cond2
+
+
+def _sqrt_fraction(q, digits=60):
+    with decimal.localcontext() as c:
+        c.prec = digits
+        return Fr(*(decimal.Decimal(q.numerator) / decimal.Decimal(q.denominator)).sqrt().as_integer_ratio())
+
+
+def test_sphere_solver_against_exact_rational_arithmetic(oracle):
+    """The oracle's 4-point sphere solver against the circumsphere in exact arithmetic (the centre of four points with double
+    coordinates is a rational number; the radius is the root of one, taken to 60 digits): centre and radius within 1e-9 relative
+    on every sample whose conditioning |det(a1, a2, a3)| / (|a1| |a2| |a3|) is at least 1e-3; at most 5 % of the samples may fall
+    under that rule.  400 samples of a four-sphere scene, half from one sphere and half anywhere."""
+    from pyprogressivex import datasets
+    pts, gt, _ = datasets.make_spheres(500, 4, 500, seed=0)
+    rng = np.random.default_rng(0)
+    one = np.nonzero(gt == 1)[0]
+    smp = np.vstack([np.stack([rng.choice(one, 4, replace=False) for _ in range(200)]),
+                     np.stack([rng.choice(len(pts), 4, replace=False) for _ in range(200)])]).astype(np.int32)
+    got = oracle.solve_minimal(oracle.SPHERE3D, pts, smp)
+    skipped, worst_c, worst_r = 0, 0.0, 0.0
+    for s in range(len(smp)):
+        ex = _exact_circumsphere(pts[smp[s]])
+        if ex is None or ex[2] < Fr(1, 10 ** 6):
+            skipped += 1
+            continue
+        c, r2, _ = ex
+        r = _sqrt_fraction(r2)
+        assert np.isfinite(got[s]).all(), s
+        ec = max(abs(Fr(float(got[s, k])) - c[k]) for k in range(3)) / max(abs(v) for v in c)
+        er = abs(Fr(float(got[s, 3])) - r) / r
+        worst_c, worst_r = max(worst_c, float(ec)), max(worst_r, float(er))
+        assert ec <= Fr(1, 10 ** 9) and er <= Fr(1, 10 ** 9), (s, float(ec), float(er))
+    print(f"sphere solver: {skipped} of {len(smp)} samples under the conditioning rule, worst relative error centre {worst_c:.3g} radius {worst_r:.3g}")
+    assert skipped <= 0.05 * len(smp)
+    # every point of a sample lies on its sphere: the exact residual of the oracle's model is at rounding level
+    for s in range(0, 200, 20):
+        for i in smp[s]:
+            assert float(_exact_sq("sphere", pts[i], got[s])) <= (1e-9 * max(1.0, abs(got[s]).max())) ** 2
+
+
+def test_plane_solver_against_exact_rational_arithmetic(oracle):
+    """The oracle's 3-point plane solver: the exact (rational) residual of the three sample points under the returned model and
+    | |n|^2 - 1 | are bounded by 1e-9 x the coordinate scale (10)"""
+    from pyprogressivex import datasets
+    pts, gt, _ = datasets.make_planes(500, 4, 500, seed=0)
+    rng = np.random.default_rng(1)
+    one = np.nonzero(gt == 1)[0]
+    smp = np.vstack([np.stack([rng.choice(one, 3, replace=False) for _ in range(150)]),
+                     np.stack([rng.choice(len(pts), 3, replace=False) for _ in range(150)])]).astype(np.int32)
+    got = oracle.solve_minimal(oracle.PLANE3D, pts, smp)
+    scale = float(np.abs(pts).max())
+    assert 1.0 <= scale <= 10.0 + 1.0
+    worst_r, worst_n = 0.0, 0.0
+    for s in range(len(smp)):
+        assert np.isfinite(got[s]).all()
+        m = [Fr(float(v)) for v in got[s]]
+        for i in smp[s]:
+            p = [Fr(float(v)) for v in pts[i]]
+            worst_r = max(worst_r, abs(float(m[0] * p[0] + m[1] * p[1] + m[2] * p[2] + m[3])))
+        worst_n = max(worst_n, abs(float(m[0] * m[0] + m[1] * m[1] + m[2] * m[2] - 1)))
+    print(f"plane solver: worst exact residual of a sample point {worst_r:.3g}, worst | |n|^2 - 1 | {worst_n:.3g}")
+    assert worst_r <= 1e-9 * scale and worst_n <= 1e-9 * scale
+
+
+def test_3d_solvers_hand_checked_degenerate_and_radius_range(oracle):
+    O = oracle
+    pts = np.array([[1.0, 0, 0], [-1.0, 0, 0], [0, 1.0, 0], [0, 0, 1.0], [0, -1.0, 0], [2.0, 0, 0], [3.0, 0, 0], [0, 0, 0],
+                    [np.nan, 0, 0], [np.inf, 1, 1], [0, 0, 5.0]])
+    # the unit sphere about the origin through four of its points; the plane z = 0 through three of them
+    m = O.solve_minimal(O.SPHERE3D, pts, np.array([[0, 1, 2, 3]], np.int32))
+    assert m[0].tolist() == [0.0, 0.0, 0.0, 1.0]
+    m = O.solve_minimal(O.PLANE3D, pts, np.array([[0, 1, 2], [0, 2, 1]], np.int32))
+    assert np.abs(m[0]).tolist() == [0.0, 0.0, 1.0, 0.0] and np.abs(m[1]).tolist() == [0.0, 0.0, 1.0, 0.0] and m[0][2] == -m[1][2]
+    # plane: collinear, coincident, out-of-range index, NaN and Inf coordinates -> NaN rows
+    bad = O.solve_minimal(O.PLANE3D, pts, np.array([[0, 5, 6], [0, 0, 2], [0, 1, 11], [0, -1, 2], [0, 1, 8], [0, 1, 9]], np.int32))
+    assert np.isnan(bad).all()
+    # sphere: coplanar (four points of z = 0), coincident, out-of-range, NaN and Inf -> NaN rows
+    bad = O.solve_minimal(O.SPHERE3D, pts, np.array([[0, 1, 2, 4], [0, 0, 2, 3], [0, 1, 2, 11], [-1, 1, 2, 3], [0, 1, 2, 8], [0, 1, 2, 9]], np.int32))
+    assert np.isnan(bad).all()
+    # the radius range is inclusive at both ends: the sphere through (+-1, 0, 0), (0, 1, 0), (0, 0, 5) has r = 2.6 about (0, 0, 2.4)
+    smp = np.array([[0, 1, 2, 10], [0, 1, 2, 3]], np.int32)
+    free = O.solve_minimal(O.SPHERE3D, pts, smp)
+    assert np.allclose(free[0], [0.0, 0.0, 2.4, 2.6], rtol=1e-15, atol=1e-15) and free[1, 3] == 1.0
+    r = float(free[0, 3])
+    for rng_, keep in (((r, r), [True, False]), ((1.0, r), [True, True]), ((1.0, np.nextafter(r, 0.0)), [False, True]),
+                       ((np.nextafter(1.0, 2.0), np.inf), [True, False]), ((0.0, 1.0), [False, True]), ((0.0, np.inf), [True, True])):
+        out = O.solve_minimal(O.SPHERE3D, pts, smp, radius_range=rng_)
+        assert (~np.isnan(out[:, 0])).tolist() == keep, rng_
+        assert np.array_equal(out[keep], free[keep])
+    for bad_range in ((-1.0, 2.0), (2.0, 1.0), (np.nan, 1.0), (0.0, np.nan)):
+        with pytest.raises(ValueError):
+            O.solve_minimal(O.SPHERE3D, pts, smp, radius_range=bad_range)
+    # the plane solver does not read the range
+    assert np.array_equal(O.solve_minimal(O.PLANE3D, pts, smp[:, :3].copy(), radius_range=(5.0, 6.0)), O.solve_minimal(O.PLANE3D, pts, smp[:, :3].copy()))
+
+
+def test_3d_solvers_are_bitwise_the_host_estimators(oracle):
+    """two restatements of the operation order in include/pgx.h (C here, numpy in _estimators.py) return the same bits and the same
+    set of samples without a model, with and without a radius range"""
+    from pyprogressivex import _estimators, datasets
+    rng = np.random.default_rng(5)
+    pts, _, _ = datasets.make_planes(300, 3, 300, seed=2)
+    smp = rng.integers(0, len(pts), (600, 3)).astype(np.int32)
+    smp[:10, 2] = smp[:10, 0]
+    ref, src = _estimators.PlaneEstimator().minimal(pts, smp)
+    got = oracle.solve_minimal(oracle.PLANE3D, pts, smp)
+    assert np.isnan(got[:10]).all() and np.array_equal(np.nonzero(~np.isnan(got[:, 0]))[0], src) and np.array_equal(got[src], ref)
+    pts, _, _ = datasets.make_spheres(300, 3, 300, seed=2)
+    smp = rng.integers(0, len(pts), (600, 4)).astype(np.int32)
+    smp[:10, 3] = smp[:10, 1]
+    for rr in ((0.0, np.inf), (0.4, 2.0)):
+        est = _estimators.SphereEstimator()
+        est.radius_range = rr
+        ref, src = est.minimal(pts, smp)
+        got = oracle.solve_minimal(oracle.SPHERE3D, pts, smp, radius_range=rr)
+        # a repeated point makes det cancel to 0 only up to rounding: where it does not, the numerators cancel exactly (n2 = 0,
+        # n3 = -n1, h3 = h1), so the row is the sphere of radius 0 at p0 - which a range with rmin > 0 removes
+        assert (np.isnan(got[:10, 3]) | (got[:10, 3] == 0.0)).all() and (rr[0] == 0.0 or np.isnan(got[:10]).all())
+        assert np.array_equal(np.nonzero(~np.isnan(got[:, 0]))[0], src) and np.array_equal(got[src], ref)
+        assert 10 < len(src) < 590 or rr[1] == np.inf          # the range keeps some samples and removes others
+
+
+def test_gram_sphere_rows_hand_checked_and_affine_on_3d_points(oracle):
+    O = oracle
+    pts = np.array([[3.0, 2.0, 1.0], [1.0, 2.0, 5.0]])
+    # o = (1, 2, 1), s = 2: rows (1, 1, 0, 0, 1) and (1, 0, 0, 2, 4)
+    blocks, bad = O.gram_rows(O.GRAM_SPHERE, pts, [1.0, 2.0, 1.0, 2.0])
+    assert len(blocks) == 1 and not bad.any() and blocks[0].tolist() == [[1.0, 1.0, 0.0, 0.0, 1.0], [1.0, 0.0, 0.0, 2.0, 4.0]]
+    G, cnt, nbad = O.gram(O.GRAM_SPHERE, pts, [0, 1], params=[1.0, 2.0, 1.0, 2.0])
+    assert cnt == 2 and nbad == 0 and G.tolist() == [[2, 1, 0, 2, 5], [1, 1, 0, 0, 1], [0, 0, 0, 0, 0], [2, 0, 0, 4, 8], [5, 1, 0, 8, 17]]
+    G, cnt, nbad = O.gram(O.GRAM_SPHERE, pts, [0, 1], params=[1.0, 2.0, 1.0, 2.0], weights=np.array([2.0, 3.0]), wpow=1)
+    assert G[0].tolist() == [5.0, 2.0, 0.0, 6.0, 14.0]
+    # GRAM_AFFINE needs nothing for 3-column points: rows (1, x, y, z)
+    G, cnt, nbad = O.gram(O.GRAM_AFFINE, pts, [0, 1])
+    assert G.shape == (4, 4) and G[0].tolist() == [2.0, 4.0, 4.0, 6.0] and G[3, 3] == 26.0
+
+
+@pytest.mark.parametrize("offset", [0.0, 1e3, 1e6])
+def test_refits_on_the_oracle_rows_recover_noise_free_structures(oracle, offset):
+    """PlaneEstimator / SphereEstimator driven by the ORACLE's Gram rows recover a known plane / sphere from noise-free points, also
+    1e3 and 1e6 from the origin (the case DESIGN.md 4.6 gives for the normalised sphere rows).
+
+    Bounds, from the arithmetic and not from the results.  The inputs themselves are rounded to ulp(|o|), and both refits solve a
+    small eigenproblem whose condition number on these scenes is of the order 10^2, so neither can do better than ~10^2 ulp(|o|): the
+    floor is set to 10^3 ulp(max(1, |o|)).  The SPHERE rows are centred and scaled before they are squared, so that floor is its
+    whole bound (1.2e-7 at 1e6; measured 3e-12).  The PLANE refit forms its scatter as G - W mean mean^T from the UN-centred sums of
+    GRAM_AFFINE: the entries of both terms are ~|o|^2, each carries a few eps of relative rounding, so the scatter is known to
+    ~4 eps |o|^2 and the normal to that over the smallest in-plane variance (4^2 / 12 for this patch): 1.5e-3 at 1e6 (measured
+    3e-4 .. 5e-4 in the normal, 1.4e-3 in the residual of a patch corner), 1.5e-9 at 1e3, rounding level at the origin.  That
+    loss is a property of the plane refit, stated in DESIGN.md 4.5: a cloud in map coordinates should be shifted to its centroid."""
+    from oracle_ctx import OracleContext
+    from pyprogressivex import _estimators
+    rng = np.random.default_rng(2)
+    ctx = OracleContext()
+    o = np.array([offset, -offset, 0.5 * offset])
+    floor = 1e3 * np.spacing(max(1.0, offset))
+    # plane: unit normal n through c, a 4 x 4 patch
+    nrm = np.array([2.0, -1.0, 2.0]) / 3.0
+    e1 = np.array([1.0, 2.0, 0.0]) / np.sqrt(5.0)
+    e2 = np.cross(nrm, e1)
+    st = rng.uniform(-2.0, 2.0, (300, 2))
+    c = o + np.array([1.0, 2.0, 3.0])
+    pts = c + st[:, :1] * e1 + st[:, 1:] * e2
+    plane_bound = 4.0 * np.finfo(np.float64).eps * float(c @ c) / (16.0 / 12.0) + floor
+    ctx.set_points(oracle.PLANE3D, pts)
+    for w in (None, rng.random(300) + 0.5):
+        fit = _estimators.PlaneEstimator().nonminimal(ctx, ("index", np.arange(300)), w)
+        assert len(fit) == 1
+        m = fit[0] * np.sign(fit[0][:3] @ nrm)
+        err_n = np.abs(m[:3] - nrm).max()
+        err_r = np.sqrt(oracle.squared_residuals(oracle.PLANE3D, pts, fit[0])).max()
+        print(f"plane refit at offset {offset:g}: normal error {err_n:.3g}, worst residual {err_r:.3g} (bound {plane_bound:.3g})")
+        assert abs(m[:3] @ m[:3] - 1.0) <= 1e-12
+        assert err_n <= plane_bound and err_r <= 2.0 * np.sqrt(2.0) * plane_bound + floor     # a corner lies 2 sqrt(2) from the centre
+    # sphere: radius 1.5 about c, the cap z > 0.3 r and beyond
+    d = rng.normal(size=(400, 3))
+    d[:, 2] = np.abs(d[:, 2]) + 0.3
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    pts = c + 1.5 * d
+    ctx.set_points(oracle.SPHERE3D, pts)
+    for w in (None, rng.random(400) + 0.5):
+        fit = _estimators.SphereEstimator().nonminimal(ctx, ("index", np.arange(400)), w)
+        assert len(fit) == 1
+        err_c, err_r = np.abs(fit[0][:3] - c).max(), abs(fit[0][3] - 1.5)
+        print(f"sphere refit at offset {offset:g}: centre error {err_c:.3g}, radius error {err_r:.3g} (bound {floor:.3g})")
+        assert err_c <= floor and err_r <= floor
+    sel = np.arange(0, 400, 2)
+    ctx.set_labels((np.arange(400) % 2).astype(np.int32))
+    a = _estimators.SphereEstimator().nonminimal(ctx, ("label", 0), None)
+    b = _estimators.SphereEstimator().nonminimal(ctx, ("index", sel), None)
+    assert np.array_equal(a[0], b[0])
+
+
+def test_golden_3d_rows(oracle):
+    """the committed known answers of the plane / sphere rows (tests/golden/make_golden_3d.py): residuals, score table, preference,
+    unary table, solver outputs (with a radius range) bit for bit, Gram matrices to 1e-12"""
+    g = np.load(GOLDEN_3D)
+    for name, mt in MODEL_CASES_3D.items():
+        pts, models, thr, comp = g[f"{name}_pts"], g[f"{name}_models"], float(g[f"{name}_thr"][0]), g[f"{name}_comp"]
+        T2 = 2.25 * thr * thr
+        assert np.array_equal(oracle.squared_residuals(mt, pts, models[0]), g[f"{name}_sq0"])
+        assert np.array_equal(np.array([oracle.residual(mt, p, models[0]) for p in pts]), g[f"{name}_plain0"])
+        sc = oracle.score(mt, pts, models, T2, compound=comp, has_compound=True, exponent=2, want_masks=True)
+        for k in ("counts", "values", "shared", "scores", "masks"):
+            assert np.array_equal(sc[k], g[f"{name}_{k}"]), k
+        assert sc["counts"].max() > 30
+        assert np.array_equal(oracle.preference(mt, pts, models[0], T2), g[f"{name}_pref0"])
+        assert np.array_equal(oracle.unary_q(mt, pts, models[:3], thr, 0.1), g[f"{name}_unary_q"])
+        assert np.array_equal(oracle.solve_minimal(mt, pts, g[f"{name}_samples"]), g[f"{name}_solved"], equal_nan=True)
+        for kind in (oracle.GRAM_AFFINE,) + ((oracle.GRAM_SPHERE,) if name == "sphere" else ()):
+            prm = g["sphere_gram_params"] if kind == oracle.GRAM_SPHERE else None
+            G, cnt, bad = oracle.gram(kind, pts, g[f"{name}_idx"], params=prm, weights=g[f"{name}_w"], wpow=1)
+            ref = g[f"{name}_G{kind}"]
+            assert cnt == 120 and bad == 0 and np.abs(G - ref).max() <= 1e-12 * np.abs(ref).max()
+    rr = g["sphere_radius_range"]
+    out = oracle.solve_minimal(oracle.SPHERE3D, g["sphere_pts"], g["sphere_samples"], radius_range=(float(rr[0]), float(rr[1])))
+    assert np.array_equal(out, g["sphere_solved_ranged"], equal_nan=True)
+    assert np.isnan(out[:, 0]).sum() > np.isnan(g["sphere_solved"][:, 0]).sum()

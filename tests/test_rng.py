@@ -100,14 +100,26 @@ def test_prosac_samples_follow_the_subset_sizes(oracle):
 
 
 @pytest.mark.parametrize("n,m,count,variant", [(300, 7, 1000, "plain"), (187, 7, 10000, "plain"), (50, 4, 400, "duplicates"), (2000, 4, 3000, "outside"),
-                                               (8, 7, 50, "plain"), (40, 2, 100, "plain"), (3000, 7, 4000, "clustered")])
+                                               (8, 7, 50, "plain"), (40, 2, 100, "plain"), (3000, 7, 4000, "clustered"),
+                                               (400, 4, 1500, "nonfinite3d"), (900, 3, 2000, "nonfinite3d")])
 def test_progressive_napsac_native_draw_equals_the_numpy_restatement(oracle, n, m, count, variant):
     """Progressive NAPSAC on the in-repo generator: libpgx.so's host code (csrc/sampler_host.hip, pgx_pnapsac_*; no GPU involved)
     against _rng.pnapsac_samples and the oracle's C restatement (pgxo_sample_pnapsac) row for row; the grid cells are those of the numpy-stream sampler of _proposal.py; rows are m
-    distinct indices; a local row ends with (the last member of the centre's neighbourhood, the centre = the sample number)."""
+    distinct indices; a local row ends with (the last member of the centre's neighbourhood, the centre = the sample number).
+    "nonfinite3d": a 3-D cloud (findPlanes / findSpheres) in which every eighth row holds a NaN, +Inf or -Inf: the three
+    implementations state one rule (clip by comparisons: NaN and -Inf land in cell 0, +Inf in the last cell) and none of them may hand a
+    NaN to an integer cast - numpy's warning about that is an error here."""
+    import warnings
     rng = np.random.default_rng(n + m)
     sizes = [1024.0, 768.0, 1024.0, 768.0]
     pts = rng.random((n, 4)) * sizes
+    if variant == "nonfinite3d":
+        sizes = sizes[:3]
+        pts = np.ascontiguousarray(pts[:, :3])
+        bad = np.arange(3, n, 8)
+        pts[bad, bad % 3] = np.array([np.nan, np.inf, -np.inf, np.nan])[(bad // 8) % 4]
+        pts[bad[::5]] = np.nan                   # whole rows as well
+        assert len(bad) >= n // 8 - 1
     if variant == "duplicates":
         pts[:20] = pts[0]
     if variant == "outside":
@@ -115,8 +127,12 @@ def test_progressive_napsac_native_draw_equals_the_numpy_restatement(oracle, n, 
         pts[::7, 1] = -5.0
     if variant == "clustered":
         pts[:, :2] = pts[:, :2] * 0.05 + 300.0
-    ref = _proposal.ProgressiveNapsacSampler(n, rng, pts, sizes, m)
-    cells = _rng.pnapsac_cells(pts, sizes)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        ref = _proposal.ProgressiveNapsacSampler(n, rng, pts, sizes, m)
+        cells = _rng.pnapsac_cells(pts, sizes)
+    if variant == "nonfinite3d":                 # the rule itself, on the finest layer: a row of NaN is cell (0, 0, 0)
+        assert (cells[0][0][np.isnan(pts).all(axis=1)] == 0).all() and (cells[0][0] >= 0).all() and (cells[0][0] < 16 ** 3).all()
     for (c1, m1), (c2, m2) in zip(cells, ref.cells):
         assert np.array_equal(c1, c2) and set(m1) == set(m2) and all(np.array_equal(m1[k], m2[k]) for k in m2)
     tops = ref.prosac.subset_sizes(1, count, m)
