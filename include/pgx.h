@@ -143,7 +143,8 @@ int pgx_score_fetch(pgx_ctx *ctx, int exponent, int64_t *counts, double *values,
                     double *scores, uint64_t *masks);
 /* The inlier set of hypothesis `row` of the last launch that produced masks (pgx_score with masks / pgx_score_launch with
  * want_masks), as ascending point indices - the `inliers` vector getScore fills (scoring_function_with_compound_model.h:88) -
- * compacted on the device.  index: room for n entries. */
+ * compacted on the device.  index: room for n entries.  A later launch without masks, or pgx_set_points, ends that launch: the call is
+ * then refused (PGX_ERR_INVALID) - it never returns a row of an earlier launch. */
 int pgx_score_inliers(pgx_ctx *ctx, int row, int32_t *index, int64_t *count);
 /* what one pgx_score_launch reads+writes at minimum (points + models + compound + results), for rooflines */
 int pgx_score_algorithmic_bytes(pgx_ctx *ctx, int want_masks, int64_t *bytes, int64_t *pairs);

@@ -48,6 +48,8 @@ void release(DevBuf& b)
     b.cap = 0;
 }
 
+// (both sides of kStageMax, per entry point: tests/test_gpu_switches.py test_*_either_side_of_the_ring; its docstring says why no entry
+//  point can fill kStageRing, and test_graph_fetch_either_side_of_the_ring holds the three staged copies that come closest)
 constexpr size_t kStageRing = 256 << 10, kStageMax = 32 << 10;
 
 int d2h(pgx_ctx* ctx, void* dst, const void* src, size_t bytes)
@@ -434,11 +436,12 @@ int pgx_score_upload(pgx_ctx* ctx, const double* models, int M)
     std::vector<int> perm((size_t)M);
     for (int m = 0; m < M; ++m) perm[(size_t)m] = m;
     std::vector<uint64_t> keys;
+    // (M = 64 | 65, and Mpad at 255 .. 257, 511 .. 513, 2049: tests/test_gpu_switches.py test_score_batch_sizes_across_the_reorder_and_the_padding)
     const bool reorder = ctx->score_sort && M > 64 && locality_keys(ctx, models, M, keys);
     if (reorder) radix_perm(keys, perm);   // 33-bit keys (locality_keys)
     if (!reorder) ctx->h_perm.clear();     // identity
     else ctx->h_perm.assign(perm.begin(), perm.end());
-    ctx->Mpad = ((M + 255) / 256) * 256;
+    ctx->Mpad = ((M + 255) / 256) * 256;   // (the tail of the permutation below is zero-filled: same test)
     // The (reordered) batch and its permutation are assembled in a pinned staging buffer owned by the context: the caller's
     // array is consumed before the call returns, and the copies need no synchronisation - the host goes on to enqueue the
     // scoring kernels behind them.  An event guards the staging buffer against the next upload.
@@ -472,9 +475,7 @@ int pgx_score_upload(pgx_ctx* ctx, const double* models, int M)
 int pgx_solve_minimal(pgx_ctx* ctx, const int32_t* samples, int S, double* models_out)
 {
     CTX_GUARD(ctx);
-    ctx->h_perm.clear();   // device-generated batches stay in the caller's order
-    ctx->mirror_valid = 0; // (see pgx_score_upload: the mirror of an earlier launch goes with that launch's order)
-    return solve_minimal_launch(ctx, samples, S, models_out);
+    return solve_minimal_launch(ctx, samples, S, models_out);   // (ends the host permutation of an uploaded batch once it has accepted the call)
 }
 
 int pgx_solve_minimal_sampled(pgx_ctx* ctx, int sampler, uint64_t key, uint32_t batch, int S, int32_t* samples_out, double* models_out)
@@ -698,7 +699,8 @@ int pgx_score_stats(pgx_ctx* ctx, double T2, int has_compound, int64_t stats[8])
 /* ---- preference / compound -------------------------------------------------------------------------------- */
 static int slot_buffer(pgx_ctx* ctx, int slot, double** out)
 {
-    if (slot < 0 || slot > 4096) return fail(ctx, PGX_ERR_INVALID, "preference slot %d out of range", slot);
+    if (slot < 0 || slot > 4096)   // (4096 | 4097: tests/test_gpu_switches.py test_preference_slot_limit)
+        return fail(ctx, PGX_ERR_INVALID, "preference slot %d out of range", slot);
     if ((int)ctx->slots.size() <= slot) ctx->slots.resize((size_t)slot + 1);
     PGX_TRY(ensure(ctx, ctx->slots[slot], (size_t)ctx->n * sizeof(double)));
     *out = ctx->slots[slot].as<double>();

@@ -26,6 +26,11 @@ namespace pgx {
 namespace {
 
 constexpr int kFitBlock = 256;
+// pgx_gram: the longest index list that is uploaded in one command with the zeroed counters in front of it
+// (65 536 | 65 537 | 70 001: tests/test_gpu_switches.py test_gram_index_lists_either_side_of_the_fused_upload)
+constexpr int64_t kFusedIndexMax = 65536;
+// pgx_gram_labels: the most labels of one call (4096 | 4097: tests/test_gpu_switches.py test_gram_labels_up_to_the_label_limit)
+constexpr int kMaxGramLabels = 4096;
 
 struct FitParams {
     double v[12];
@@ -638,7 +643,7 @@ int gram_labels_launch(pgx_ctx* ctx, int kind, const double* params, int nparams
     if (ctx->labels_n != ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: labels not set");
     if (wpow != 1 && wpow != 2) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: weight power must be 1 or 2");
     if (nparams < 0 || nparams > 12 || (nparams > 0 && !params)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: bad parameter block");
-    if (!out || K <= 0 || K > 4096) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: bad argument");
+    if (!out || K <= 0 || K > kMaxGramLabels) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: bad argument");
     int q = 0;
     PGX_TRY(gram_row_length(ctx, "pgx_gram_labels", kind, nparams, &q));
     const int nv = q * (q + 1) / 2;
@@ -723,7 +728,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
     int* d_idx = (int*)(base + part_bytes + 64 * sizeof(double) + 64);
     // counters (64 bytes, zero) | index list are adjacent: a short list is uploaded together with the zeros (one command instead of two)
     std::vector<int32_t> up;   // (alive until the stream has been synchronised below)
-    if (idx_bytes && m <= 65536) {
+    if (idx_bytes && m <= kFusedIndexMax) {
         up.assign(16 + (size_t)m, 0);
         memcpy(up.data() + 16, index, idx_bytes);
         PGX_HIP(ctx, hipMemcpyAsync(d_cnt, up.data(), 64 + idx_bytes, hipMemcpyHostToDevice, ctx->stream));

@@ -33,7 +33,7 @@ namespace pgx {
 namespace {
 
 constexpr int kGBlock = 256;
-constexpr int kMaxCells = 1 << 22;
+constexpr int kMaxCells = 1 << 22;   // (a grid beyond it: tests/test_gpu_switches.py test_graph_grid_is_coarsened_beyond_the_cell_limit)
 constexpr int kTile = 256;
 
 struct GridSpec {

@@ -154,6 +154,7 @@ int compound_launch(pgx_ctx* ctx, const int32_t* slots, int K)
     const int blocks = (int)((ctx->n + kPwBlock - 1) / kPwBlock);
     // the kernel argument holds 32 pointers; max is associative and exact, so more models run as chunks of 32 that continue
     // from the compound vector written by the chunk before
+    // (K = 32 | 33 | 64 | 65: tests/test_gpu_switches.py test_compound_update_at_the_chunk_limits)
     for (int k0 = 0; k0 < K; k0 += 32) {
         const int kc = K - k0 < 32 ? K - k0 : 32;
         SlotArg a;
@@ -592,7 +593,7 @@ int epipolar_support_launch(pgx_ctx* ctx, const double* F, double T2, double S2,
 
 // ---- a9: bucket by label (PEARL.h:342-352) -----------------------------------------------------------------------
 // Labels >= L-1 fall into the last (outlier) bucket, as `label < instance_number` does at PEARL.h:348.
-constexpr int kMaxBucketLabels = 64;
+constexpr int kMaxBucketLabels = 64;   // (63 | 64 | 65: tests/test_gpu_switches.py test_bucket_at_the_label_limit)
 
 __global__ __launch_bounds__(kPwBlock) void bucket_count_kernel(const int* __restrict__ labels, int64_t n, int L,
                                                                 unsigned* __restrict__ block_counts /*[blocks][L]*/,

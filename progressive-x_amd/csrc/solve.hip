@@ -559,8 +559,15 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     // fscale, which pgx_set_points computes from the caller-visible data: umax is not kept either)
     const bool scaled = mt == kFundamental || mt == kHomography;
     if (scaled && !(ctx->fscale >= 1.0)) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: coordinate scale not available");
+    // Device-generated batches stay in the caller's order (the kernels below write the identity permutation), so the host copy of an
+    // uploaded batch's locality order and the mirror of its launch end HERE - for pgx_solve_minimal and pgx_solve_minimal_sampled
+    // alike, and only once the call is accepted: a refused call leaves the uploaded batch resident, and its order with it.  (The sampled
+    // entry point used to keep the stale order: the next mirrored fetch came back shuffled by it.  tests/test_gpu_switches.py
+    // test_device_generated_batches_come_back_in_sample_order_after_a_reordered_upload)
+    ctx->h_perm.clear();
+    ctx->mirror_valid = 0;
     const int Mtot = mi.slots * S;
-    ctx->Mpad = ((Mtot + 255) / 256) * 256;
+    ctx->Mpad = ((Mtot + 255) / 256) * 256;   // (255 .. 257 and the other edges of the rounding: test_score_batch_sizes_across_the_reorder_and_the_padding)
     PGX_TRY(ensure(ctx, ctx->models, (size_t)Mtot * mi.P * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
     if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * mi.sample * sizeof(int32_t)));
