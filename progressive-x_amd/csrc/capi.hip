@@ -143,14 +143,14 @@ int pgx_create(int device_id, pgx_ctx** out)
     if (const char* ns = std::getenv("PGX_NO_SORT")) ctx->score_sort = (ns[0] == '1') ? 0 : 1;
     if (const char* b = std::getenv("PGX_SP_KD")) { const int v = std::atoi(b); ctx->sp_kd = v < 0 ? 0 : (v > 2 ? 2 : v); }
     if (const char* b = std::getenv("PGX_SETPOINTS_HOST")) ctx->setpoints_host = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_GC_FLIP")) ctx->gc_flip = std::atoi(b) ? 1 : 0;
+    if (const char* b = std::getenv("PGX_GC_FLIP")) ctx->route.gc_flip = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_SCORE_MIRROR")) ctx->score_mirror = std::atoi(b) != 0;
     if (const char* b = std::getenv("PGX_SCORE_NO_CULL")) ctx->score_cull = std::atoi(b) ? 0 : 1;
     if (const char* b = std::getenv("PGX_NO_GROUP")) ctx->group_filter = std::atoi(b) ? 0 : 1;
     if (const char* b = std::getenv("PGX_VERIFY")) ctx->verify = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_MF_TILE")) ctx->mf_tile = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_MF_TILE_BATCH")) ctx->mf_tile_batch = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_MF_REGION")) ctx->mf_region = std::atoi(b) ? 1 : 0;
+    if (const char* b = std::getenv("PGX_MF_TILE")) ctx->route.mf_tile = std::atoi(b) ? 1 : 0;
+    if (const char* b = std::getenv("PGX_MF_TILE_BATCH")) ctx->route.mf_tile_batch = std::atoi(b) ? 1 : 0;
+    if (const char* b = std::getenv("PGX_MF_REGION")) ctx->route.mf_region = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_MEMO")) ctx->mf_memo = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_DONE_VERIFY")) ctx->mf_done_verify = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_XCD")) ctx->mf_xcd = std::atoi(b) ? 1 : 0;
@@ -159,7 +159,7 @@ int pgx_create(int device_id, pgx_ctx** out)
     if (const char* b = std::getenv("PGX_MF_XCD_MAXN")) ctx->mf_xcd_max_n = std::atoll(b);
     if (const char* b = std::getenv("PGX_MF_SWEEPS")) ctx->mf_sweeps = std::atoi(b);
     if (const char* b = std::getenv("PGX_TILE_MINI")) ctx->tile_mini = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_TILE_EXPANSION_MAX")) { const int v = std::atoi(b); ctx->tile_expansion_max = v < 0 ? 0 : v; }
+    if (const char* b = std::getenv("PGX_TILE_EXPANSION_MAX")) { const int v = std::atoi(b); ctx->route.tile_expansion_max = v < 0 ? 0 : v; }
     if (const char* b = std::getenv("PGX_TILE_MINI_SWEEPS")) { const int v = std::atoi(b); ctx->tile_mini_sweeps = v < 1 ? 1 : v; }
     if (const char* b = std::getenv("PGX_MF_DEBUG")) ctx->tile_debug = std::atoi(b);
     *out = ctx;
@@ -952,14 +952,15 @@ int pgx_energy(pgx_ctx* ctx, double lambda, double label_cost, int64_t* energy_q
 int pgx_expand_alpha(pgx_ctx* ctx, double lambda, double label_cost, int alpha, int64_t* changed)
 {
     CTX_GUARD(ctx);
-    int64_t lq, hq, ch = 0;
-    PGX_TRY(flow_params(ctx, lambda, label_cost, &lq, &hq));
+    MoveRequest rq;
+    PGX_TRY(flow_params(ctx, lambda, label_cost, &rq.lambda_q, &rq.h_q));
+    rq.alpha = alpha;
     for (int k = 0; k < 8; ++k) ctx->stats[k] = 0;
     ctx->labels_all_zero = 0;
     ctx->last_done.valid = 0;
     ctx->labels_version += 1;
-    PGX_TRY(expand_alpha_launch(ctx, lq, hq, alpha, &ch));
-    if (changed) *changed = ch;
+    PGX_TRY(expand_alpha_launch(ctx, rq));
+    if (changed) *changed = rq.changed;
     return PGX_OK;
 }
 
@@ -1040,6 +1041,10 @@ int pgx_expansion(pgx_ctx* ctx, double lambda, double label_cost, int max_cycles
         PGX_HIP(ctx, hipMemcpyAsync((char*)memo.snaps.p + (size_t)a * (size_t)n_sites * 4, ctx->labels.p, (size_t)n_sites * 4, hipMemcpyDeviceToDevice, ctx->stream));
         return PGX_OK;
     };
+    auto move = [&](int a) { MoveRequest rq; rq.lambda_q = lq; rq.h_q = hq; rq.alpha = a; return rq; };
+    // the cycle's moves enqueued back to back.  (The planner does not look at L: a table of more labels than a move takes opens a batch, and the
+    //  batch's first expand_alpha_launch refuses it with the message of an unbatched move - the batch's state is reset by the next region_batch_begin.)
+    const bool batched = plan_move(ctx->route, ctx->dq_n, ctx->max_degree, ctx->gn, MoveKind::Cycle, false).batched;
     auto memo_record = [&](int a, int64_t ch) {  // once move a's outcome is known (moves are recorded in order: valid stays a prefix)
         if (memo.valid == a) { memo.ident[(size_t)a] = ctx->unary_ident[(size_t)a]; memo.changed[(size_t)a] = ch; memo.valid = a + 1; }
     };
@@ -1066,9 +1071,8 @@ int pgx_expansion(pgx_ctx* ctx, double lambda, double label_cost, int max_cycles
             std::vector<int> ev((size_t)(ctx->L > 0 ? ctx->L : 1), 0);
             PGX_TRY(expand_cycle_l0(ctx, hq, ch.data(), ev.data()));
             for (int alpha = 0; alpha < ctx->L; ++alpha) changed_total += ch[(size_t)alpha];
-        } else if ((ctx->mf_tile && ctx->mf_tile_batch && ctx->dq_n <= ctx->tile_single_max && ctx->dq_n <= 8192 && ctx->L <= 64) ||
-                   (region_moves_apply(ctx) && !(ctx->mf_tile && ctx->dq_n <= ctx->tile_single_max && ctx->dq_n <= ctx->tile_expansion_max))) {
-            // (graphs of <= 8192 sites - the reference's own scenes: every move is ONE launch of the one-workgroup solver,
+        } else if (batched) {
+            // (graphs the one-workgroup solver takes whole - the reference's own scenes: every move is ONE launch of it,
             //  maxflow_tile.hip expand_alpha_tile; batched the same way, a read-back per move was two thirds of a move's time)
             // Region moves (maxflow_tile.hip): the moves of the cycle are enqueued back to back and resolved together - one
             // host round trip per batch instead of one per move.  A move that declines poisons the rest of its batch on the device
@@ -1083,14 +1087,12 @@ int pgx_expansion(pgx_ctx* ctx, double lambda, double label_cost, int max_cycles
                 int rc = PGX_OK;
                 for (int a = alpha; a < ctx->L && rc == PGX_OK; ++a) {
                     if (batch.empty() && noop_at[a] == version) { ctx->stats[7]++; alpha = a + 1; continue; }   // (known now: nothing is in flight)
-                    ctx->region_defer = 1;
-                    ctx->region_slot = (int)batch.size();
-                    ctx->region_skip_rel = noop_at[a] >= version0 ? (int)(noop_at[a] - version0) : -1;
-                    int64_t ch = 0;
-                    rc = expand_alpha_launch(ctx, lq, hq, a, &ch);
-                    ctx->region_defer = 0;
-                    if (rc == PGX_REGION_PENDING) { batch.push_back(a); rc = keep ? memo_snapshot(a) : PGX_OK; }
-                    else if (rc == PGX_OK) rc = fail(ctx, PGX_ERR_INVALID, "pgx_expansion: a batched move was not enqueued");
+                    MoveRequest rq = move(a);
+                    rq.batch_slot = (int)batch.size();
+                    rq.skip_rel = noop_at[a] >= version0 ? (int)(noop_at[a] - version0) : -1;
+                    rc = expand_alpha_launch(ctx, rq);
+                    if (rc == PGX_OK && rq.outcome != MoveOutcome::Pending) rc = fail(ctx, PGX_ERR_INVALID, "pgx_expansion (internal): a batched move was not enqueued");
+                    else if (rc == PGX_OK) { batch.push_back(a); rc = keep ? memo_snapshot(a) : PGX_OK; }
                 }
                 if (rc != PGX_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
                 if (batch.empty()) break;
@@ -1108,11 +1110,10 @@ int pgx_expansion(pgx_ctx* ctx, double lambda, double label_cost, int max_cycles
                         continue;
                     }
                     if (status == 1) {   // declined: the general path, then a new batch behind it
-                        const int region_on = ctx->mf_region;
-                        ctx->mf_region = 0;
-                        const int r1 = expand_alpha_launch(ctx, lq, hq, a, &ch);
-                        ctx->mf_region = region_on;
-                        PGX_TRY(r1);
+                        MoveRequest rq = move(a);
+                        rq.region_declined = true;
+                        PGX_TRY(expand_alpha_launch(ctx, rq));
+                        ch = rq.changed;
                         if (cycle == 1 && memo_on) PGX_TRY(memo_snapshot(a));   // (the snapshot taken behind the declined move holds the untouched labels)
                         next = a + 1;
                     }
@@ -1129,8 +1130,9 @@ int pgx_expansion(pgx_ctx* ctx, double lambda, double label_cost, int max_cycles
             // a move is a deterministic function of (labelling, alpha): one that relabelled nothing and has seen no
             // label change since would relabel nothing again — skipped (typically the tail of the verifying cycle)
             if (noop_at[alpha] == version) { ctx->stats[7]++; continue; }
-            int64_t ch = 0;
-            PGX_TRY(expand_alpha_launch(ctx, lq, hq, alpha, &ch));
+            MoveRequest rq = move(alpha);
+            PGX_TRY(expand_alpha_launch(ctx, rq));
+            const int64_t ch = rq.changed;
             if (keep) { PGX_TRY(memo_snapshot(alpha)); memo_record(alpha, ch); }
             changed_total += ch;
             if (ch > 0) { ++version; noop_at[alpha] = -1; }

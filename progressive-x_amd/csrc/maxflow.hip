@@ -41,6 +41,7 @@ struct MaxflowState {
 };
 
 constexpr int kMfMaxLabels = 64;
+static_assert(kMfMaxLabels == kRouteMaxLabels, "a move with more labels is refused before it is routed (check_resident_problem)");
 
 // What a workgroup reports when it retires - a minimum per label, a "something happened" flag - lands on a handful of
 // addresses, and same-address atomics serialise at ~20 ns each: 512 workgroups reporting the same hub height cost 10 us at
@@ -1109,17 +1110,26 @@ static int expand_alpha_l0(pgx_ctx* ctx, int64_t h_q, int alpha, int64_t* change
     return PGX_OK;
 }
 
-// One cycle over all labels at lambda = 0, enqueued back to back; one read-back at the end.  changed[alpha] = sites that
-// took alpha in move alpha, evaluated[alpha] = 0 when every site already carried alpha.
-int expand_cycle_l0(pgx_ctx* ctx, int64_t h_q, int64_t* changed, int* evaluated)
+static int check_resident_problem(pgx_ctx* ctx, int alpha_first, int alpha_last)   // a unary table, labels of its length and range, the moves' alphas inside it
 {
     const int64_t n = ctx->dq_n;
     const int L = ctx->L;
     if (n <= 0 || L <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: unary table not set");
     if (ctx->labels_n != n) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: labels not set (or wrong length)");
     if (ctx->labels_max >= L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: label %d out of range (the unary table has %d labels)", ctx->labels_max, L);
+    if (alpha_first < 0 || alpha_last >= L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: alpha %d out of range", alpha_first < 0 ? alpha_first : alpha_last);
     if (L > kMfMaxLabels) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: at most %d labels (got %d)", kMfMaxLabels, L);
-    if (L - 1 > ctx->labels_max) ctx->labels_max = L - 1;   // the cycle may write every label
+    if (alpha_last > ctx->labels_max) ctx->labels_max = alpha_last;   // the moves may write these labels: a later, smaller table must see it
+    return PGX_OK;
+}
+
+// One cycle over all labels at lambda = 0, enqueued back to back; one read-back at the end.  changed[alpha] = sites that
+// took alpha in move alpha, evaluated[alpha] = 0 when every site already carried alpha.
+int expand_cycle_l0(pgx_ctx* ctx, int64_t h_q, int64_t* changed, int* evaluated)
+{
+    PGX_TRY(check_resident_problem(ctx, 0, ctx->L - 1));   // (the cycle may write every label)
+    const int64_t n = ctx->dq_n;
+    const int L = ctx->L;
     if (!ctx->mf) {
         ctx->mf = new MaxflowState();
         PGX_HIP(ctx, hipHostMalloc((void**)&ctx->mf->h_flags, 64, hipHostMallocDefault));
@@ -1157,51 +1167,44 @@ int expand_cycle_l0(pgx_ctx* ctx, int64_t h_q, int64_t* changed, int* evaluated)
     return PGX_OK;
 }
 
-int expand_alpha_launch(pgx_ctx* ctx, int64_t lambda_q, int64_t h_q, int alpha, int64_t* changed)
+int expand_alpha_launch(pgx_ctx* ctx, MoveRequest& rq)
 {
-    const int64_t n = ctx->dq_n;
-    const int L = ctx->L;
-    if (n <= 0 || L <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: unary table not set");
-    if (ctx->labels_n != n) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: labels not set (or wrong length)");
-    if (ctx->labels_max >= L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: label %d out of range (the unary table has %d labels)", ctx->labels_max, L);
-    if (alpha < 0 || alpha >= L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: alpha %d out of range", alpha);
-    if (L > kMfMaxLabels) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: at most %d labels (got %d)", kMfMaxLabels, L);
-    if (alpha > ctx->labels_max) ctx->labels_max = alpha;   // the move may write alpha: a later, smaller table must see it
-    if (lambda_q <= 0) return expand_alpha_l0(ctx, h_q, alpha, changed);
-    return expand_alpha_on(ctx, n, L, ctx->dq.as<long long>(), ctx->labels.as<int>(), nullptr, lambda_q, h_q, alpha, changed);
+    PGX_TRY(check_resident_problem(ctx, rq.alpha, rq.alpha));
+    rq.n = ctx->dq_n; rq.L = ctx->L; rq.dq = ctx->dq.as<long long>(); rq.labels = ctx->labels.as<int>(); rq.wq = nullptr;
+    if (rq.lambda_q <= 0) return expand_alpha_l0(ctx, rq.h_q, rq.alpha, &rq.changed);
+    return run_move(ctx, rq);
 }
 
-// Region moves (maxflow_tile.hip expand_alpha_region) apply to the resident problem: a graph whose rows fit the compact arrays,
-// beyond the one-workgroup size (smaller graphs are solved whole), at most 64 labels.
-bool region_moves_apply(const pgx_ctx* ctx)
+static int try_tile(pgx_ctx* ctx, MoveRequest& rq)   // the whole-graph one-workgroup solver's turn; a move it hands back is counted (pgx_expansion_paths[5])
 {
-    return ctx->mf_region && ctx->max_degree >= 1 && ctx->max_degree <= 32 && ctx->L <= 64 && ctx->gn < ((int64_t)1 << 30);
+    PGX_TRY(expand_alpha_tile(ctx, rq));
+    if (rq.outcome == MoveOutcome::HandedBack) ctx->tile_fallbacks += 1;
+    return PGX_OK;
 }
 
-// One expansion move on caller-chosen tables: dq [L][n] label-major, labels [n], and optionally per-arc weights wq [E]
-// (used by the binary inlier/outlier cut of gclo.hip, whose pairwise weights depend on both end points).
-int expand_alpha_on(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* labels, const long long* wq,
-                    int64_t lambda_q, int64_t h_q, int alpha, int64_t* changed, bool source_reach)
+// One expansion move with lambda > 0 on the request's tables, by the solvers move_route.h lists for it, in that order.  The list is
+// walked in the order of what each solver needs: Tile nothing, Region and Level the view set up in between.
+int run_move(pgx_ctx* ctx, MoveRequest& rq)
 {
-    if (source_reach && h_q != 0) return fail(ctx, PGX_ERR_INVALID, "expansion move: the source-side variant takes no label cost");
-    const bool pair = true;
+    const int64_t n = rq.n;
+    const int L = rq.L, alpha = rq.alpha;
+    if (rq.source_reach && rq.h_q != 0) return fail(ctx, PGX_ERR_INVALID, "expansion move: the source-side variant takes no label cost");
     if (ctx->gn != n) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: lambda > 0 needs a graph over %lld sites", (long long)n);
-    // Expansion moves on graphs of tile_expansion_max (1 024) .. 8192 sites try the region path FIRST (measured at 5 000 sites, C2: 6.2 ms per
-    // expansion against 7.7 with every move on the whole-graph kernel, which works out of memory beyond the LDS-resident kernel's 1 024 sites;
-    // 2 000 sites: 1.99 against 2.03); a move the region path declines goes to the whole-graph kernel (the caller re-runs it with the region
-    // path off; unbatched: below).
-    const bool region_first = !source_reach && wq == nullptr && L <= 64 && n > ctx->tile_expansion_max && region_moves_apply(ctx);
-    if (ctx->mf_tile && !source_reach && n <= ctx->tile_single_max && n <= 8192 && L <= 64 && !region_first) {   // (the sizes expand_alpha_tile takes)
-        const int r = expand_alpha_tile(ctx, n, L, dq, labels, lambda_q, h_q, alpha, changed, wq);
-        if (r != PGX_TILE_FALLBACK) return r;
-        ctx->tile_fallbacks += 1;   // the one-workgroup solver ran and gave the move back
+    // (the solvers and the cut's orientation: whether a cycle is batched is pgx_expansion's question, and a cycle's move is routed like a single one)
+    const MoveRoute route = plan_move(ctx->route, n, ctx->max_degree, ctx->gn, rq.wq ? MoveKind::Cut : MoveKind::Single, rq.region_declined);
+    if (rq.source_reach != route.flip) return fail(ctx, PGX_ERR_INVALID, "expansion move (internal): the cut's orientation is not the planner's");
+    int next = 0;
+    if (route.order[next] == Solver::Tile) {
+        PGX_TRY(try_tile(ctx, rq));
+        if (rq.outcome != MoveOutcome::HandedBack) return PGX_OK;
+        ++next;
     }
     if (!ctx->mf) {
         ctx->mf = new MaxflowState();
         PGX_HIP(ctx, hipHostMalloc((void**)&ctx->mf->h_flags, 64, hipHostMallocDefault));
     }
     MaxflowState* st = ctx->mf;
-    const int64_t E = pair ? ctx->gE : 0;
+    const int64_t E = ctx->gE;
     PGX_TRY(ensure(ctx, st->cap, (size_t)(E > 0 ? E : 1) * sizeof(long long)));
     PGX_TRY(ensure(ctx, st->tot, (size_t)(E > 0 ? E : 1) * sizeof(long long)));
     PGX_TRY(ensure(ctx, st->ex, (size_t)n * sizeof(long long)));
@@ -1223,11 +1226,9 @@ int expand_alpha_on(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* la
     PGX_TRY(ensure(ctx, st->small, small_bytes));
     char* sp = (char*)st->small.p;
     MfView v;
-    v.n = n; v.L = L; v.alpha = alpha; v.lambda_q = lambda_q; v.h_q = h_q;
-    v.dq = dq;
-    v.labels = labels;
-    v.wq = wq;
-    v.off = pair ? ctx->goff.as<int>() : nullptr;
+    v.n = n; v.L = L; v.alpha = alpha; v.lambda_q = rq.lambda_q; v.h_q = rq.h_q;
+    v.dq = rq.dq; v.labels = rq.labels; v.wq = rq.wq;
+    v.off = ctx->goff.as<int>();
     v.idx = ctx->gidx.as<int>(); v.mult = ctx->gmult.as<int>(); v.rev = ctx->grev.as<int>();
     v.cap = st->cap.as<long long>(); v.tot = st->tot.as<long long>(); v.ex = st->ex.as<long long>(); v.rt = st->rt.as<long long>();
     v.d = st->d.as<int>(); v.f = st->f.as<long long>(); v.g = st->g.as<long long>();
@@ -1252,7 +1253,7 @@ int expand_alpha_on(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* la
     v.swept = nullptr;
     v.gate = 1;   // an unused alpha is handled by the stranded-excess test (maxflow_body.hip.h); the materialised hub stays in the bodies for the CPU emulation
 
-    HipBackend be{ctx, st, (unsigned)((n + kMfBlock - 1) / kMfBlock), pair, 1};
+    HipBackend be{ctx, st, (unsigned)((n + kMfBlock - 1) / kMfBlock), true, 1};
     if (!st->bar.p) {
         PGX_TRY(ensure(ctx, st->bar, 64));
         PGX_HIP(ctx, hipMemsetAsync(st->bar.p, 0, 64, ctx->stream));
@@ -1266,7 +1267,7 @@ int expand_alpha_on(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* la
     if (tune.list_div > 0) be.list_blocks = (unsigned)((n / tune.list_div + kMfBlock - 1) / kMfBlock + 1);
     tune.debug = ctx->tile_debug;
     tune.bfs_hint = st->bfs_hint;
-    tune.source_reach = source_reach ? 1 : 0;
+    tune.source_reach = rq.source_reach ? 1 : 0;
     {   // schedule knobs for A/B runs (any schedule gives the same cut; defaults = the measured ones in maxflow_driver.inl)
         static const int e_wave_max = std::getenv("PGX_MF_WAVE_MAX") ? std::atoi(std::getenv("PGX_MF_WAVE_MAX")) : -1;
         static const int e_wave_from = std::getenv("PGX_MF_WAVE_FROM") ? std::atoi(std::getenv("PGX_MF_WAVE_FROM")) : -1;
@@ -1285,17 +1286,19 @@ int expand_alpha_on(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* la
     }
     // A move with few OPEN sites (no t-link: excess or relay) is solved by one workgroup on their compacted sub-graph
     // (maxflow_tile.hip expand_alpha_region); it needs the t-links and arcs set up here first and leaves them intact when it declines.
-    if (!source_reach && wq == nullptr && pair && L <= 64 && region_moves_apply(ctx)) {   // (then expand_alpha_region runs its first kernel = the per-site initialisation)
-        const int rr = expand_alpha_region(ctx, v, changed);   // (its first kernel is init_sites + the label count fused with the search for open sites)
-        if (rr != PGX_TILE_FALLBACK) return rr;   // solved, enqueued (PGX_REGION_PENDING) or an error
-        if (region_first && ctx->mf_tile && n <= ctx->tile_single_max && n <= 8192) {   // declined, and the graph fits the whole-graph kernel
-            const int r = expand_alpha_tile(ctx, n, L, dq, labels, lambda_q, h_q, alpha, changed, wq);
-            if (r != PGX_TILE_FALLBACK) return r;
-            ctx->tile_fallbacks += 1;
+    if (route.order[next] == Solver::Region) {   // (its first kernel is init_sites + the label count fused with the search for open sites)
+        PGX_TRY(expand_alpha_region(ctx, rq, v));
+        if (rq.outcome != MoveOutcome::HandedBack) return PGX_OK;   // solved, or enqueued in the batch
+        ++next;
+        if (route.order[next] == Solver::Tile) {   // declined, and the graph fits the whole-graph kernel
+            PGX_TRY(try_tile(ctx, rq));
+            if (rq.outcome != MoveOutcome::HandedBack) return PGX_OK;
+            ++next;
         }
         tune.preinit = 1;   // the sites are initialised; the hub set-up (which does not touch them) is still to run
     }
-    const int r = mf_expand_alpha(be, v, tune, changed, ctx->stats);
+    rq.outcome = MoveOutcome::Done;   // (route.order[next] == Solver::Level: it solves every move or fails)
+    const int r = mf_expand_alpha(be, v, tune, &rq.changed, ctx->stats);
     if (be.err != hipSuccess) return fail(ctx, PGX_ERR_HIP, "expansion move failed: %s", hipGetErrorString(be.err));
     if (r != 0)
         return fail(ctx, PGX_ERR_NOCONVERGE, "push-relabel did not converge within %d global relabels (alpha=%d)",

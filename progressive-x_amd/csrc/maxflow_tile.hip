@@ -24,10 +24,9 @@
 // hub's excess through one aggregated reservation per hub; a member pushes back through its own counter f.
 // An unused alpha is handled by the stranded-excess test (maxflow_body.hip.h, "gate").  Anything else (materialised alpha
 // hub, per-arc weights, the source-side variant of the local optimisation's cut, a hub that only reaches t through
-// members without t-links) falls back to maxflow.hip: the function returns PGX_TILE_FALLBACK before touching the labels.
+// members without t-links) falls back to maxflow.hip: the move is handed back (MoveOutcome::HandedBack) before the labels are touched.
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -1469,12 +1468,16 @@ constexpr int kRegionSlots = 64;   // moves in flight per batch (one per label: 
 constexpr size_t kRegionBlock = (SmallLayout::bytes + sizeof(RegionInfo) + 255) / 256 * 256;   // a move's small block + region info
 constexpr size_t kRegionHostOff = SmallLayout::flags;   // the host mirror has the device layout: a slot's flags[8] | count, bad, cnt_alpha sit at this offset of its block
 
-// One expansion move on a graph that fits one workgroup (<= 8192 sites): one launch.  Returns PGX_OK (done, *changed set),
-// PGX_TILE_FALLBACK (not handled: the caller runs maxflow.hip; labels untouched) or an error.
-int expand_alpha_tile(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* labels, int64_t lambda_q, int64_t h_q, int alpha, int64_t* changed,
-                      const long long* wq)
+static_assert(kMaxL == kRouteMaxLabels, "the hub slots of the one-workgroup kernels: the planner routes no move with more labels here");
+
+// One expansion move on a graph that fits one workgroup (move_route.h kTileMaxSites): one launch.  rq.outcome: Done (rq.changed set),
+// HandedBack (the solver gave up: the caller runs the next one; labels untouched) or Pending (enqueued in rq.batch_slot).
+int expand_alpha_tile(pgx_ctx* ctx, MoveRequest& rq)
 {
-    if (n > ctx->tile_single_max || n > 8192 || L > kMaxL) { ctx->tile_pre_sync = nullptr; return PGX_TILE_FALLBACK; }
+    const int64_t n = rq.n;
+    const int alpha = rq.alpha;
+    if (n > kTileMaxSites || rq.L > kMaxL)   // (the planner's promise: the kernels' arrays end there)
+        return fail(ctx, PGX_ERR_INVALID, "one-workgroup move (internal): %lld sites, %d labels were routed here", (long long)n, rq.L);
     PGX_TRY(tile_graph_prepare(ctx));
     TileState* ts = ctx->tile;
     const int64_t E = ts->E;
@@ -1486,16 +1489,16 @@ int expand_alpha_tile(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* 
     PGX_TRY(ensure(ctx, ts->lab, (size_t)n * 4));
     PGX_TRY(ensure(ctx, ts->small, SmallLayout::bytes));
     if (!ts->h_small) PGX_HIP(ctx, hipHostMalloc(&ts->h_small, SmallLayout::bytes, hipHostMallocDefault));
-    // enqueued in a batch (pgx_expansion, ctx->region_defer): the move's small block is a slot of the batch - cleared by
+    // enqueued in a batch (pgx_expansion, rq.batch_slot): the move's small block is a slot of the batch - cleared by
     // region_batch_begin, read back by region_batch_fetch, interpreted by region_result - and nothing here waits for the device
-    const bool defer = ctx->region_defer != 0 && wq == nullptr;
-    if (defer && (ctx->region_slot < 0 || ctx->region_slot >= kRegionSlots || !ts->rg_small.p || !ts->rg_ctl.p))
-        return fail(ctx, PGX_ERR_INVALID, "batched move: slot %d not prepared", ctx->region_slot);
-    char* sp = defer ? (char*)ts->rg_small.p + (size_t)ctx->region_slot * kRegionBlock : (char*)ts->small.p;
-    if (defer) ts->slot_is_tile[ctx->region_slot] = true;
+    const bool defer = rq.batch_slot >= 0;
+    if (defer && (rq.batch_slot >= kRegionSlots || !ts->rg_small.p || !ts->rg_ctl.p))
+        return fail(ctx, PGX_ERR_INVALID, "batched move: slot %d not prepared", rq.batch_slot);
+    char* sp = defer ? (char*)ts->rg_small.p + (size_t)rq.batch_slot * kRegionBlock : (char*)ts->small.p;
+    if (defer) ts->slot_is_tile[rq.batch_slot] = true;
     TView v;
-    v.n = n; v.L = L; v.alpha = alpha; v.lambda_q = lambda_q; v.h_q = h_q;
-    v.dq = dq; v.labels = labels;
+    v.n = n; v.L = rq.L; v.alpha = alpha; v.lambda_q = rq.lambda_q; v.h_q = rq.h_q;
+    v.dq = rq.dq; v.labels = rq.labels;
     v.perm = ts->perm.as<int>();
     v.off = ts->off.as<int>(); v.idx = ts->idx.as<int>(); v.rev = ts->rev.as<int>(); v.mult = ts->mult.as<int>();
     v.cap = ts->cap.as<long long>(); v.ex = ts->ex.as<long long>();
@@ -1507,10 +1510,10 @@ int expand_alpha_tile(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* 
     v.flags = (int*)(sp + SmallLayout::flags);
     v.rg = nullptr;
     v.ctl = defer ? ts->rg_ctl.as<int>() : nullptr;
-    v.skip_rel = defer ? ctx->region_skip_rel : -1;
+    v.skip_rel = defer ? rq.skip_rel : -1;
     v.alpha_apply = alpha;
-    v.wq = wq; v.goff = wq ? ctx->goff.as<int>() : nullptr;
-    *changed = 0;
+    v.wq = rq.wq; v.goff = rq.wq ? ctx->goff.as<int>() : nullptr;
+    rq.changed = 0;
     v.dbg = nullptr;
     if (ctx->tile_debug) {
         PGX_TRY(ensure(ctx, ts->dbg, 16 * 8));
@@ -1528,16 +1531,13 @@ int expand_alpha_tile(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* 
     else hipLaunchKernelGGL((t_move_kernel<1024, 8, 16>), dim3(1), dim3(1024), 0, ctx->stream, v, sweeps, max_rounds);
     if (!(ctx->tile_mini && n <= kMiniSites && E <= kMiniArcs)) ctx->tile_launches[1] += 1;
     PGX_HIP(ctx, hipGetLastError());
-    if (defer) return PGX_REGION_PENDING;
+    if (defer) { rq.outcome = MoveOutcome::Pending; return PGX_OK; }
     char* hs = (char*)ts->h_small;
-    std::function<int()> hook;
-    hook.swap(ctx->tile_pre_sync);
-    ctx->tile_pre_sync_ran = false;
-    if (hook) PGX_TRY(hook());   // (the caller's work behind the move: shares the synchronisation below)
+    if (rq.pre_sync) PGX_TRY(rq.pre_sync(ctx, rq));   // (the caller's work behind the move: shares the synchronisation below)
     PGX_HIP(ctx, hipMemcpyAsync(hs, sp, SmallLayout::bytes, hipMemcpyDeviceToHost, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int* h_flags = (const int*)(hs + SmallLayout::flags);
-    ctx->tile_pre_sync_ran = (bool)hook && h_flags[5] == 0;
+    rq.pre_sync_ran = rq.pre_sync != nullptr && h_flags[5] == 0;
     if (ctx->tile_debug) {
         unsigned long long t[16];
         (void)hipMemcpy(t, ts->dbg.p, sizeof(t), hipMemcpyDeviceToHost);
@@ -1553,30 +1553,30 @@ int expand_alpha_tile(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* 
                          (double)ts->dbg_acc[13] / (double)ts->dbg_moves);
         }
     }
-    if (h_flags[5] != 0) return PGX_TILE_FALLBACK;
+    if (h_flags[5] != 0) { rq.outcome = MoveOutcome::HandedBack; return PGX_OK; }
     ctx->stats[0] += 1;
     ctx->paths[0] += 1;
     ctx->stats[2] += h_flags[4];
-    *changed = h_flags[1];
-    ctx->stats[4] += *changed;
+    rq.changed = h_flags[1];
+    ctx->stats[4] += rq.changed;
+    rq.outcome = MoveOutcome::Done;
     return PGX_OK;
 }
 
 // One expansion move through the region path.  `mv` = the move's view of maxflow.hip; nothing has run for it yet: the per-site
-// initialisation (t-links, arcs) and the label count are this function's first kernel, fused with the search for open sites.  PGX_OK: done, *changed set.  PGX_TILE_FALLBACK: declined - the labels are untouched and mv's state is
-// initialised and intact, the general path continues from it.  The caller checks the applicability conditions of the first
-// line (maxflow.hip): when they fail nothing has been initialised.
-
-int expand_alpha_region(pgx_ctx* ctx, const MfView& mv, int64_t* changed)
+// initialisation (t-links, arcs) and the label count are this function's first kernel, fused with the search for open sites.  rq.outcome: Done (rq.changed set),
+// Pending (enqueued in rq.batch_slot) or HandedBack: declined - the labels are untouched and mv's state is initialised and intact, the general path continues from it.
+int expand_alpha_region(pgx_ctx* ctx, MoveRequest& rq, const MfView& mv)
 {
     const int64_t n = mv.n;
     const int stride = ctx->max_degree;
-    if (stride < 1 || stride > 32 || mv.L > kMaxL || n >= ((int64_t)1 << 30)) return PGX_TILE_FALLBACK;
+    if (stride < 1 || stride > kRegionMaxDegree || mv.L > kMaxL || n >= kRegionMaxSites)   // (the planner's promise: the compact arc rows, 30-bit site numbers)
+        return fail(ctx, PGX_ERR_INVALID, "region move (internal): %lld sites of degree %d, %d labels were routed here", (long long)n, stride, mv.L);
     if (!ctx->tile) ctx->tile = new TileState();
     TileState* ts = ctx->tile;
-    const bool defer = ctx->region_defer != 0;
-    const int slot = defer ? ctx->region_slot : 0;
-    if (slot < 0 || slot >= kRegionSlots) return fail(ctx, PGX_ERR_INVALID, "region move: slot %d out of range", slot);
+    const bool defer = rq.batch_slot >= 0;
+    const int slot = defer ? rq.batch_slot : 0;
+    if (slot >= kRegionSlots) return fail(ctx, PGX_ERR_INVALID, "region move: slot %d out of range", slot);
     const size_t C = kRegionCap, A = C * (size_t)stride;
     PGX_TRY(ensure(ctx, ts->rg_slot, (size_t)n * 4));
     PGX_TRY(ensure(ctx, ts->rg_need, (size_t)n * 8));
@@ -1618,8 +1618,8 @@ int expand_alpha_region(pgx_ctx* ctx, const MfView& mv, int64_t* changed)
     RegionInfo* rg = (RegionInfo*)(sp + SmallLayout::bytes);
     v.rg = rg;
     v.ctl = defer ? ts->rg_ctl.as<int>() : nullptr;
-    v.skip_rel = defer ? ctx->region_skip_rel : -1;
-    *changed = 0;
+    v.skip_rel = defer ? rq.skip_rel : -1;
+    rq.changed = 0;
     // (a batch's slots are cleared together by region_batch_begin and read back together by region_batch_fetch: one fill and one
     //  copy command per batch instead of one each per move - 8 000 + 9 200 commands of ~3.5 us in a findVanishingPoints call at C5)
     if (!defer) PGX_HIP(ctx, hipMemsetAsync(sp, 0, SmallLayout::bytes + sizeof(RegionInfo), ctx->stream));
@@ -1637,13 +1637,14 @@ int expand_alpha_region(pgx_ctx* ctx, const MfView& mv, int64_t* changed)
     hipLaunchKernelGGL((t_move_kernel<1024, 8, 16>), dim3(1), dim3(1024), 0, ctx->stream, v, ctx->tile_sweeps, 4096);
     PGX_HIP(ctx, hipGetLastError());
     static_assert(SmallLayout::flags + 8 * 4 == SmallLayout::bytes, "the flags end the small block: flags | region info head is one copy");
-    if (defer) return PGX_REGION_PENDING;   // (region_batch_fetch copies the batch's slots)
+    if (defer) { rq.outcome = MoveOutcome::Pending; return PGX_OK; }   // (region_batch_fetch copies the batch's slots)
     char* hs = (char*)ts->h_rg + (size_t)slot * kRegionBlock + kRegionHostOff;
     PGX_HIP(ctx, hipMemcpyAsync(hs, sp + SmallLayout::flags, 8 * 4 + 16, hipMemcpyDeviceToHost, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     int status = 0;
-    PGX_TRY(region_result(ctx, 0, mv.alpha, &status, changed));
-    return status == 0 ? PGX_OK : PGX_TILE_FALLBACK;
+    PGX_TRY(region_result(ctx, 0, mv.alpha, &status, &rq.changed));
+    rq.outcome = status == 0 ? MoveOutcome::Done : MoveOutcome::HandedBack;
+    return PGX_OK;
 }
 
 // the batch's control words back to zero (enqueued: the moves that follow on the stream see them cleared)

@@ -4,11 +4,11 @@
 
 #include <cstdint>
 #include <cstdio>
-#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/pgx.h"
+#include "move_route.h"
 #include "residuals.hip.h"
 
 namespace pgx {
@@ -59,7 +59,6 @@ struct pgx_ctx {
     pgx::DevBuf pts_s, pts32_s, pmax_s, comp_s, pperm, gbounds, masks_s;
     pgx::DevBuf pts_g, p32_g;    // group-blocked SoA copies of the sorted rows: [group][coordinate][64] (group-major kernel)
     int setpoints_host = 0;      // PGX_SETPOINTS_HOST=1: round 1's host preprocessing in pgx_set_points (A/B, cross-check)
-    int gc_flip = 1;             // PGX_GC_FLIP=0: the inlier / outlier cut in its original orientation (pointwise.hip gc_labeling_launch)
     int score_dense_min = 32;    // steps with at least this many candidates of 64 are evaluated in place, not queued (PGX_SCORE_DENSE; 65 = never)
     int score_cull_segs = 256;   // segments of groups per hypothesis word in the cull kernel (PGX_SCORE_CULL_SEGS; 8192 waves at M = 2048)
     int score_nrep = 0;         // replicas of the integer accumulators (PGX_SCORE_NREP, multiple of 8); 0 = automatic: 8 when a group's waves share an XCD, else 1
@@ -147,32 +146,18 @@ struct pgx_ctx {
     int64_t graph_version = 0;   // bumped whenever the resident graph changes (graph_build_reverse)
     pgx::DevBuf gorder;          // sites in the Morton order of the coordinates the graph was built on (graph.hip); gorder_n == gn when valid
     int64_t gorder_n = 0;
-    int mf_tile_batch = 1;       // PGX_MF_TILE_BATCH=0: one host round trip per one-workgroup move (A/B)
-    int mf_tile = 1;             // PGX_MF_TILE=0: level-synchronous schedule of maxflow.hip for every move (A/B)
+    pgx::RouteSwitches route;    // PGX_MF_TILE, PGX_MF_TILE_BATCH, PGX_MF_REGION, PGX_GC_FLIP, PGX_TILE_EXPANSION_MAX: which solver takes a move (move_route.h)
     int tile_order = 1;          // sites of the tile path in the Morton order of the graph's coordinates (0: the caller's order)
-    int tile_single_max = 8192;  // graphs up to this many sites: the whole move in one launch of one workgroup
-    int tile_expansion_max = 1024;   // PGX_TILE_EXPANSION_MAX: expansion moves on larger graphs (up to tile_single_max) try the region path first (maxflow.hip expand_alpha_on);
-                                     // = the LDS-resident whole-graph kernel's limit: beyond it the region path with ITS LDS-resident solver is as fast or faster
-                                     // (2 000 sites 1.99 vs 2.03 ms per expansion, 5 000 sites 6.2 vs 7.7; unihouse, 2 084 points: 74 -> 67 ms per call)
     int mf_xcd = 1;              // PGX_MF_XCD=0: no persistent one-XCD rounds (maxflow_xcd.hip.h); read at pgx_create like the switches above
     int mf_xcd_search = 1;       // PGX_MF_XCD_SEARCH=0: no one-launch global relabels
     int mf_xcd_min_depth = 24;   // PGX_MF_XCD_MIN_DEPTH: a search runs as one launch when the previous search of its kind was deeper than this
     long long mf_xcd_max_n = 300000;   // PGX_MF_XCD_MAXN: graphs beyond this stay on level launches (measured: maxflow.hip)
     int mf_sweeps = 0;           // PGX_MF_SWEEPS: sweeps per round, list mode and all-sites alike (0 = the measured defaults; tests shorten the rounds)
-    int mf_region = 1;           // PGX_MF_REGION=0: no region moves (maxflow_tile.hip expand_alpha_region)
     int tile_sweeps = 24;        // push-relabel sweeps per discharge launch
-    // a caller of a single whole-graph move (the inlier / outlier cut) may leave work here that expand_alpha_tile enqueues BEHIND the move and
-    // BEFORE its one synchronisation (the compaction of the cut's flags and its copy back): one host round trip for both.  Consumed
-    // (cleared) by the move; tile_pre_sync_ran says it ran and the move was solved (not handed back)
-    std::function<int()> tile_pre_sync;
-    bool tile_pre_sync_ran = false;
     int tile_mini = 1;           // PGX_TILE_MINI=0: graphs of <= 1024 sites and <= 8192 arcs go through t_move_kernel too (A/B; default: the LDS-resident t_mini_kernel)
     int64_t tile_launches[2] = {0, 0};   // pgx_one_workgroup_launches: whole-graph moves enqueued on t_mini_kernel / on t_move_kernel
     int tile_mini_sweeps = 24;   // PGX_TILE_MINI_SWEEPS: sweeps between two exact searches of t_mini_kernel
     int64_t paths[6] = {0, 0, 0, 0, 0, 0};   // pgx_expansion_paths
-    int region_defer = 0;        // region moves are enqueued without a host round trip (pgx_expansion's batches): slot / skip rule below
-    int region_slot = 0;
-    int region_skip_rel = -1;
     int64_t tile_fallbacks = 0;  // moves the tile path handed back to maxflow.hip
     int tile_debug = 0;          // PGX_MF_DEBUG: one stderr line per global relabel
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -279,24 +264,38 @@ int gram_batch_launch(pgx_ctx* ctx, int kind, const double* params, int nparams,
                       const double* wsel, int wpow, double* out, int32_t* bad);
 int pnp_refine_batch_launch(pgx_ctx* ctx, const double* inits, const int32_t* index, int B, int m, const double* wsel, int wpow,
                             int iterations, double* out, int32_t* status);
-int expand_alpha_launch(pgx_ctx* ctx, int64_t lambda_q, int64_t h_q, int alpha, int64_t* changed);
+// One expansion move, as its caller states it and as the solvers report on it (maxflow.hip run_move walks the planner's list with it).
+enum class MoveOutcome { Done, HandedBack, Pending };   // solved (`changed` set) | not solved, labels untouched: the next solver | enqueued in the batch: region_result
+struct MoveRequest {
+    int64_t n = 0;                  // the tables: dq [L][n] label-major, labels [n], optionally per-arc weights wq [E] (the inlier / outlier cut)
+    int L = 0, alpha = 0;
+    const long long *dq = nullptr, *wq = nullptr;
+    int* labels = nullptr;
+    int64_t lambda_q = 0, h_q = 0;
+    bool source_reach = false;      // alpha goes to the sites the SOURCE reaches (the flipped cut; level-synchronous only)
+    int batch_slot = -1;            // >= 0: enqueued in this slot of pgx_expansion's batch, no host round trip ...
+    int skip_rel = -1;              // ... and skipped on the device if exactly this many moves of the batch before it relabelled something (-1: always runs)
+    bool region_declined = false;   // the batch gave this move back: from scratch, without the region path
+    // work enqueued BEHIND an unbatched whole-graph move and BEFORE its one synchronisation (the compaction of the cut's flags and its
+    // copy back: one host round trip for both); pre_sync_ran: it was enqueued and the solver did not give the move up
+    int (*pre_sync)(pgx_ctx*, const MoveRequest&) = nullptr;
+    bool pre_sync_ran = false;
+    int64_t changed = 0;            // results
+    MoveOutcome outcome = MoveOutcome::Done;
+};
+int expand_alpha_launch(pgx_ctx* ctx, MoveRequest& rq);   // a move on the resident problem: fills in the tables (the caller gives lambda_q, h_q, alpha, the batch fields)
 int expand_cycle_l0(pgx_ctx* ctx, int64_t h_q, int64_t* changed, int* evaluated);  // lambda = 0: all labels, one read-back
-int expand_alpha_on(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* labels, const long long* wq, int64_t lambda_q,
-                    int64_t h_q, int alpha, int64_t* changed, bool source_reach = false);
+int run_move(pgx_ctx* ctx, MoveRequest& rq);              // lambda > 0, any tables
 void maxflow_free(pgx_ctx* ctx);
 int maxflow_schedule_stats(pgx_ctx* ctx, int64_t out[8]);   // maxflow.hip
 int eigh_smallest_launch(pgx_ctx* ctx, const double* A, int q, int64_t B, double* vec, double* val);   // fit.hip
-constexpr int PGX_TILE_FALLBACK = 1000;   // expand_alpha_tile: not handled, run the level-synchronous path (labels untouched)
-int expand_alpha_tile(pgx_ctx* ctx, int64_t n, int L, const long long* dq, int* labels, int64_t lambda_q, int64_t h_q, int alpha,
-                      int64_t* changed, const long long* wq = nullptr);
+int expand_alpha_tile(pgx_ctx* ctx, MoveRequest& rq);   // maxflow_tile.hip: the whole graph in one workgroup, one launch
 void tile_free(pgx_ctx* ctx);
 struct MfView;
-constexpr int PGX_REGION_PENDING = 1001;  // expand_alpha_region with ctx->region_defer: enqueued, result by region_result after a synchronisation
 int region_batch_begin(pgx_ctx* ctx);
 int region_batch_fetch(pgx_ctx* ctx, int slots);   // the batch's results to the host mirror (one copy), before the synchronisation
 int region_result(pgx_ctx* ctx, int slot, int alpha, int* status, int64_t* changed);
-bool region_moves_apply(const pgx_ctx* ctx);   // maxflow.hip: pgx_expansion's moves on the resident problem go through expand_alpha_region
-int expand_alpha_region(pgx_ctx* ctx, const MfView& mv, int64_t* changed);   // maxflow_tile.hip: a move with few open sites, one workgroup
+int expand_alpha_region(pgx_ctx* ctx, MoveRequest& rq, const MfView& mv);   // maxflow_tile.hip: a move with few open sites, one workgroup
 void comm_free(pgx_ctx* ctx);
 
 }  // namespace pgx

@@ -339,25 +339,23 @@ int gc_labeling_launch(pgx_ctx* ctx, const double* model, double T2, double lamb
     // the terminals swapped - every site starts "outlier", alpha = "inlier", and alpha goes to the sites the SOURCE reaches
     // (maxflow.hip mf_k_src_*: the minimal source side, i.e. exactly "reaches t" of the original orientation, ties -> outlier) -
     // has the ~5 % near the model as its excess sites.  Same flags bit for bit (PGX_GC_FLIP=0 for A/B; GPU test).
-    // A graph the one-workgroup solver takes (<= 8192 sites: the reference's own scenes) is cut in the original orientation - one
+    // A graph the one-workgroup solver takes (move_route.h: the reference's own scenes) is cut in the original orientation - one
     // launch instead of the level-synchronous schedule's dozens (0.6 ms -> 0.1 ms per cut on a 187-point scene, a fifth of a
     // findTwoViewMotions call there); that solver applies alpha to the sites that cannot reach t, i.e. the same flags.
-    const bool flip = ctx->gc_flip != 0 && !(ctx->mf_tile && n <= ctx->tile_single_max && n <= 8192);
+    const bool flip = plan_move(ctx->route, n, ctx->max_degree, ctx->gn, MoveKind::Cut, false).flip;
     hipLaunchKernelGGL(gc_terms_kernel, g, b, 0, ctx->stream, e, n, ctx->goff.as<int>(), ctx->gidx.as<int>(), lambda, lambda_q, dq,
                        wq, labels, flip ? 0 : 1);
     PGX_HIP(ctx, hipGetLastError());
-    int64_t changed = 0;
     // a small scene's cut is one one-workgroup launch: the compaction of its flags and the copy back ride behind it, before the one
     // synchronisation of the move (two round trips before)
     const bool small = want_index && !flip && n <= kCompactSmall;
-    if (small) ctx->tile_pre_sync = [ctx, labels, n]() { return compact_small_enqueue<false>(ctx, nullptr, labels, n); };
-    ctx->tile_pre_sync_ran = false;
-    const int rc = expand_alpha_on(ctx, n, 2, dq, labels, wq, lambda_q, 0, flip ? 1 : 0, &changed, flip);
-    ctx->tile_pre_sync = nullptr;
-    const bool have_small = ctx->tile_pre_sync_ran;
-    ctx->tile_pre_sync_ran = false;
-    PGX_TRY(rc);
-    const int64_t inliers = flip ? changed : n - changed;
+    MoveRequest rq;
+    rq.n = n; rq.L = 2; rq.dq = dq; rq.labels = labels; rq.wq = wq;
+    rq.lambda_q = lambda_q; rq.alpha = flip ? 1 : 0; rq.source_reach = flip;
+    if (small) rq.pre_sync = [](pgx_ctx* c, const MoveRequest& m) { return compact_small_enqueue<false>(c, nullptr, m.labels, m.n); };
+    PGX_TRY(run_move(ctx, rq));
+    const bool have_small = rq.pre_sync_ran;
+    const int64_t inliers = flip ? rq.changed : n - rq.changed;
     if (have_small) {
         const int* hs = (const int*)ctx->h_res;
         if (hs[0] != (int)inliers) return fail(ctx, PGX_ERR_INVALID, "pgx_gc_inliers (internal): %d indices for %lld inliers", hs[0], (long long)inliers);

@@ -26,3 +26,7 @@ mkdir -p build/san
     -std=c++17 -I/opt/rocm/include progressive-x_amd/csrc/sampler_host.hip -x c++ tests/emu/pnapsac_driver.cpp -o build/san/pnapsac_san \
     -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/pnapsac_san
+# csrc/move_route.h (which min-cut solver takes an expansion move: host code of libpgx.so, no HIP in it) under tests/emu/move_route_driver.cpp
+g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 \
+    -o build/san/move_route_san tests/emu/move_route_driver.cpp
+ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/move_route_san

@@ -14,6 +14,7 @@
 
 #include "../../progressive-x_amd/csrc/maxflow_driver.inl"
 #include "../../progressive-x_amd/csrc/maxflow_l0.hip.h"
+#include "../../progressive-x_amd/csrc/move_route.h"
 
 using namespace pgx;
 
@@ -354,4 +355,17 @@ extern "C" int emu_expand_alpha(int64_t n, int L, const int64_t* Dq_point_major,
     st[7] = (int64_t)be.xcd_searches * 1000000 + be.xcd_round_launches;   // (what of the above ran the one-launch way)
     if (stats) for (int k = 0; k < 8; ++k) stats[k] = st[k];
     return r;
+}
+
+// The planner of csrc/move_route.h as libpgx.so compiles it (tests/test_move_route.py): out = order[3] | flip | batched
+extern "C" void emu_plan_move(int mf_tile, int mf_tile_batch, int mf_region, int gc_flip, int tile_expansion_max, int64_t n,
+                              int max_degree, int64_t gn, int kind, int region_declined, int32_t out[5])
+{
+    pgx::RouteSwitches sw;
+    sw.mf_tile = mf_tile; sw.mf_tile_batch = mf_tile_batch; sw.mf_region = mf_region; sw.gc_flip = gc_flip;
+    sw.tile_expansion_max = tile_expansion_max;
+    const pgx::MoveRoute r = pgx::plan_move(sw, n, max_degree, gn, (pgx::MoveKind)kind, region_declined != 0);
+    for (int k = 0; k < 3; ++k) out[k] = (int32_t)r.order[k];
+    out[3] = r.flip ? 1 : 0;
+    out[4] = r.batched ? 1 : 0;
 }
