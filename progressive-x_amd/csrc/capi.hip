@@ -151,8 +151,8 @@ int pgx_create(int device_id, pgx_ctx** out)
     if (const char* b = std::getenv("PGX_MF_TILE")) ctx->route.mf_tile = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_TILE_BATCH")) ctx->route.mf_tile_batch = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_REGION")) ctx->route.mf_region = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_MF_MEMO")) ctx->mf_memo = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_MF_DONE_VERIFY")) ctx->mf_done_verify = std::atoi(b) ? 1 : 0;
+    if (const char* b = std::getenv("PGX_MF_MEMO")) ctx->expansion.mf_memo = std::atoi(b) ? 1 : 0;
+    if (const char* b = std::getenv("PGX_MF_DONE_VERIFY")) ctx->expansion.mf_done_verify = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_XCD")) ctx->mf_xcd = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_XCD_SEARCH")) ctx->mf_xcd_search = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_XCD_MIN_DEPTH")) ctx->mf_xcd_min_depth = std::atoi(b);
@@ -180,7 +180,7 @@ void pgx_destroy(pgx_ctx* ctx)
                       &ctx->red_partials, &ctx->red_out, &ctx->dq, &ctx->kmodels, &ctx->labels, &ctx->goff,
                       &ctx->gidx, &ctx->gmult, &ctx->grev, &ctx->scratch, &ctx->fit_scratch, &ctx->pts_s, &ctx->pts32_s,
                       &ctx->pmax_s, &ctx->comp_s, &ctx->pperm, &ctx->gbounds, &ctx->masks_s, &ctx->cull_lists, &ctx->cull_counts, &ctx->gc, &ctx->gc_sel,
-                      &ctx->weights, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo.snaps, &ctx->prosac_tops};
+                      &ctx->weights, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops};
     for (DevBuf* b : bufs) release(*b);
     for (DevBuf& b : ctx->slots) release(b);
     if (ctx->h_res) (void)hipHostFree(ctx->h_res);
@@ -321,12 +321,10 @@ int pgx_set_points(pgx_ctx* ctx, int model_type, const double* points, int64_t n
     if (!points || n <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: empty input");
     if (n >= ((int64_t)1 << 31)) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: n must be < 2^31");
     ctx->model_type = model_type; ctx->D = mi.D; ctx->P = mi.P; ctx->n = n;
-    ctx->points_version += 1;
-    ctx->labels_all_zero = 0;
     ctx->M = 0; ctx->last_acc = nullptr; ctx->dq_n = 0; ctx->L = 0; ctx->labels_n = 0;
     ctx->weights_n = 0;  // weights belong to a point set
     ctx->score_global_n = 0;   // the fixed-point scale of a sharded job belongs to that job's point set
-    if (ctx->memo.snaps.p) { (void)hipStreamSynchronize(ctx->stream); release(ctx->memo.snaps); ctx->memo.cap = 0; ctx->memo.valid = 0; ctx->memo.n = 0; }   // first-cycle snapshots of the old point set
+    expansion_points_changed(ctx);
     // upload + every derived copy on the device (setpoints.hip): filter scales, f32 rows, Morton order, group bounds
     const int rc = !ctx->setpoints_host ? set_points_device(ctx, mi, points, n) : set_points_host(ctx, mi, points, n);
     if (rc != PGX_OK) {   // half-built copies (an allocation failed midway): no resident problem, every later call fails cleanly
@@ -761,12 +759,13 @@ int pgx_pearl_unary(pgx_ctx* ctx, const double* models, int K, double threshold,
         PGX_HIP(ctx, hipMemcpyAsync(ctx->kmodels.p, models, (size_t)K * ctx->P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PGX_TRY(unary_launch(ctx, K, threshold, lambda));
     {   // what each column was computed from, byte for byte (the first-cycle memo of pgx_expansion compares these)
-        ctx->unary_ident.assign((size_t)L, std::string());
+        std::vector<std::string> ident((size_t)L);
         char head[64];
-        const int hl = std::snprintf(head, sizeof head, "%d|%lld|%a|%a|", ctx->model_type, (long long)ctx->points_version, threshold, lambda);
+        const int hl = std::snprintf(head, sizeof head, "%d|%lld|%a|%a|", ctx->model_type, (long long)ctx->expansion.points_version, threshold, lambda);
         for (int l = 0; l < K; ++l)
-            ctx->unary_ident[(size_t)l] = std::string(head, (size_t)hl) + std::string((const char*)(models + (size_t)l * ctx->P), (size_t)ctx->P * sizeof(double));
-        ctx->unary_ident[(size_t)K] = std::string(head, (size_t)hl) + "outlier";
+            ident[(size_t)l] = std::string(head, (size_t)hl) + std::string((const char*)(models + (size_t)l * ctx->P), (size_t)ctx->P * sizeof(double));
+        ident[(size_t)K] = std::string(head, (size_t)hl) + "outlier";
+        ctx->expansion.unary_resident(std::move(ident));
     }
     ctx->L = L;
     ctx->dq_n = ctx->n;
@@ -798,7 +797,7 @@ int pgx_set_unary_q(pgx_ctx* ctx, const int64_t* Dq, int64_t n, int L)
             if (v > mx) mx = v;
         }
     ctx->dq_max = mx;
-    ctx->unary_ident.clear();   // an injected table has no identity: no first-cycle memo, no identical-call shortcut
+    ctx->expansion.unary_injected();
     PGX_TRY(ensure(ctx, ctx->dq, tmp.size() * sizeof(int64_t)));
     PGX_HIP(ctx, hipMemcpyAsync(ctx->dq.p, tmp.data(), tmp.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -814,10 +813,7 @@ int pgx_set_labels(pgx_ctx* ctx, const int32_t* labels, int64_t n)
     int32_t lo = labels[0], hi = labels[0];
     for (int64_t i = 1; i < n; ++i) { lo = labels[i] < lo ? labels[i] : lo; hi = labels[i] > hi ? labels[i] : hi; }
     if (lo < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_set_labels: negative label %d", (int)lo);
-    ctx->labels_max = hi;
-    ctx->labels_all_zero = hi == 0 ? 1 : 0;
-    ctx->last_done.valid = 0;   // (the labels are the caller's now)
-    ctx->labels_version += 1;
+    ctx->expansion.labels_uploaded(hi);
     PGX_TRY(ensure(ctx, ctx->labels, (size_t)n * sizeof(int32_t)));
     PGX_HIP(ctx, hipMemcpyAsync(ctx->labels.p, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -956,201 +952,22 @@ int pgx_expand_alpha(pgx_ctx* ctx, double lambda, double label_cost, int alpha, 
     PGX_TRY(flow_params(ctx, lambda, label_cost, &rq.lambda_q, &rq.h_q));
     rq.alpha = alpha;
     for (int k = 0; k < 8; ++k) ctx->stats[k] = 0;
-    ctx->labels_all_zero = 0;
-    ctx->last_done.valid = 0;
-    ctx->labels_version += 1;
+    ctx->expansion.labels_written();
     PGX_TRY(expand_alpha_launch(ctx, rq));
     if (changed) *changed = rq.changed;
     return PGX_OK;
 }
 
-// GCO-v3 "standard cycles" loop [U-5] as PEARL drives it (PEARL.h:550-551): cycle over the labels in index order until
-// a whole cycle leaves the energy unchanged, at most max_cycles cycles.
-static thread_local bool done_verify_running = false;   // (PGX_MF_DONE_VERIFY: the nested call must run the real cycle)
-
 int pgx_expansion(pgx_ctx* ctx, double lambda, double label_cost, int max_cycles, int64_t* energy_q, double* energy,
                   int* cycles)
 {
     CTX_GUARD(ctx);
-    int64_t lq, hq;
+    int64_t lq, hq, e = 0;
     PGX_TRY(flow_params(ctx, lambda, label_cost, &lq, &hq));
-    for (int k = 0; k < 8; ++k) ctx->stats[k] = 0;
-    // ---- identical call (pgx_internal.h ExpansionDone): the labels are those the last expansion left at a fixed point, and columns,
-    // weights and graph are what it was computed from => one verifying cycle of no-ops and the same energy, without running it
-    pgx_ctx::ExpansionDone& last = ctx->last_done;
-    const bool ident_known = ctx->L > 0 && (int)ctx->unary_ident.size() == ctx->L && ctx->labels_n == ctx->dq_n;
-    if (ctx->mf_memo && last.valid && ident_known && max_cycles >= 1 && last.lq == lq && last.hq == hq && last.n == ctx->dq_n &&
-        (lq <= 0 || last.graph_version == ctx->graph_version) && last.ident == ctx->unary_ident &&
-        last.labels_version == ctx->labels_version && !done_verify_running) {
-        if (ctx->labels_max >= ctx->L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: label %d out of range (the unary table has %d labels)", ctx->labels_max, ctx->L);
-        ctx->memo_hits += ctx->L;
-        ctx->stats[7] += ctx->L;   // "moves skipped because the labelling had not changed since that label's last move, which relabelled nothing"
-        if (ctx->mf_done_verify) {   // debug mode: run the cycle the shortcut stands for and insist on what it promises
-            int64_t eq2 = 0;
-            int cyc2 = 0;
-            const int64_t want_e = last.energy_q;
-            done_verify_running = true;
-            const int rc = pgx_expansion(ctx, lambda, label_cost, max_cycles, &eq2, nullptr, &cyc2);
-            done_verify_running = false;
-            if (rc != PGX_OK) return rc;
-            if (eq2 != want_e || cyc2 != 1 || ctx->stats[4] != 0)
-                return fail(ctx, PGX_ERR_INVALID, "pgx_expansion (PGX_MF_DONE_VERIFY): the identical-call shortcut would have answered energy %lld, 1 cycle, 0 changes; "
-                                                  "the real cycle gave energy %lld, %d cycle(s), %lld change(s)", (long long)want_e, (long long)eq2, cyc2, (long long)ctx->stats[4]);
-        }
-        if (energy_q) *energy_q = last.energy_q;
-        if (energy) *energy = (double)last.energy_q / 4294967296.0;
-        if (cycles) *cycles = 1;
-        return PGX_OK;
-    }
-    last.valid = 0;
-    ctx->labels_version += 1;   // (the moves below write the labels)
-    int64_t new_e = 0;
-    PGX_TRY(energy_launch(ctx, lq, hq, &new_e));
-    int64_t old_e = new_e + 1;
     int done = 0;
-    int64_t last_cycle_changed = -1;
-    int64_t version = 0;
-    std::vector<int64_t> noop_at((size_t)(ctx->L > 0 ? ctx->L : 1), -1);
-    // ---- first-cycle memo (pgx_internal.h ExpansionMemo): usable when this expansion starts from the all-zero labelling on columns
-    // of known identity; `keep` = first-cycle moves recorded by this call, `memo_p` = leading moves restored instead of solved
-    pgx_ctx::ExpansionMemo& memo = ctx->memo;
-    const int64_t n_sites = ctx->dq_n;
-    const bool memo_on = ctx->mf_memo && lq > 0 && ctx->labels_all_zero && ctx->L > 1 && (int)ctx->unary_ident.size() == ctx->L &&
-                         ctx->labels_n == n_sites && (size_t)ctx->L * (size_t)n_sites * 4 <= ((size_t)2 << 30);
-    ctx->labels_all_zero = 0;
-    int memo_p = 0;
-    if (memo_on) {
-        if (memo.n != n_sites || memo.lq != lq || memo.hq != hq || memo.graph_version != ctx->graph_version) memo.valid = 0;
-        while (memo_p < memo.valid && memo_p < ctx->L && memo.ident[(size_t)memo_p] == ctx->unary_ident[(size_t)memo_p]) ++memo_p;
-        if (memo.cap < ctx->L || memo.n != n_sites) {   // room for this call's snapshots (the kept prefix moves along)
-            pgx::DevBuf grown;
-            PGX_TRY(ensure(ctx, grown, (size_t)ctx->L * (size_t)n_sites * 4));
-            if (memo_p > 0)
-                PGX_HIP(ctx, hipMemcpyAsync(grown.p, memo.snaps.p, (size_t)memo_p * (size_t)n_sites * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            release(memo.snaps);
-            memo.snaps = grown;
-            memo.cap = ctx->L;
-        }
-        memo.ident.resize((size_t)ctx->L);
-        memo.changed.resize((size_t)ctx->L, 0);
-        memo.valid = memo_p;
-        memo.n = n_sites; memo.lq = lq; memo.hq = hq; memo.graph_version = ctx->graph_version;
-    }
-    auto memo_snapshot = [&](int a) -> int {     // enqueued right behind move a of the first cycle: the labels it left
-        PGX_HIP(ctx, hipMemcpyAsync((char*)memo.snaps.p + (size_t)a * (size_t)n_sites * 4, ctx->labels.p, (size_t)n_sites * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        return PGX_OK;
-    };
-    auto move = [&](int a) { MoveRequest rq; rq.lambda_q = lq; rq.h_q = hq; rq.alpha = a; return rq; };
-    // the cycle's moves enqueued back to back.  (The planner does not look at L: a table of more labels than a move takes opens a batch, and the
-    //  batch's first expand_alpha_launch refuses it with the message of an unbatched move - the batch's state is reset by the next region_batch_begin.)
-    const bool batched = plan_move(ctx->route, ctx->dq_n, ctx->max_degree, ctx->gn, MoveKind::Cycle, false).batched;
-    auto memo_record = [&](int a, int64_t ch) {  // once move a's outcome is known (moves are recorded in order: valid stays a prefix)
-        if (memo.valid == a) { memo.ident[(size_t)a] = ctx->unary_ident[(size_t)a]; memo.changed[(size_t)a] = ch; memo.valid = a + 1; }
-    };
-    for (int cycle = 1; cycle <= max_cycles; ++cycle) {
-        if (new_e == old_e) break;
-        old_e = new_e;
-        int64_t changed_total = 0;
-        int alpha0 = 0;
-        const bool keep = memo_on && cycle == 1;
-        if (keep && memo_p > 0) {   // the leading moves as they went last time: their label changes, the skip rule's bookkeeping, the labels
-            for (int a = 0; a < memo_p; ++a) {
-                const int64_t ch = memo.changed[(size_t)a];
-                changed_total += ch;
-                if (ch > 0) { ++version; noop_at[(size_t)a] = -1; }
-                else noop_at[(size_t)a] = version;
-            }
-            PGX_HIP(ctx, hipMemcpyAsync(ctx->labels.p, (char*)memo.snaps.p + (size_t)(memo_p - 1) * (size_t)n_sites * 4, (size_t)n_sites * 4,
-                                        hipMemcpyDeviceToDevice, ctx->stream));
-            ctx->memo_hits += memo_p;
-            alpha0 = memo_p;
-        }
-        if (lq <= 0) {  // no pairwise term: closed-form moves, the whole cycle enqueued at once (one host round trip)
-            std::vector<int64_t> ch((size_t)(ctx->L > 0 ? ctx->L : 1), 0);
-            std::vector<int> ev((size_t)(ctx->L > 0 ? ctx->L : 1), 0);
-            PGX_TRY(expand_cycle_l0(ctx, hq, ch.data(), ev.data()));
-            for (int alpha = 0; alpha < ctx->L; ++alpha) changed_total += ch[(size_t)alpha];
-        } else if (batched) {
-            // (graphs the one-workgroup solver takes whole - the reference's own scenes: every move is ONE launch of it,
-            //  maxflow_tile.hip expand_alpha_tile; batched the same way, a read-back per move was two thirds of a move's time)
-            // Region moves (maxflow_tile.hip): the moves of the cycle are enqueued back to back and resolved together - one
-            // host round trip per batch instead of one per move.  A move that declines poisons the rest of its batch on the device
-            // (they return untouched); it is solved by the general path and the cycle resumes behind it.  The skip rule below is
-            // applied on the device for moves behind others of the same batch (their outcome is not known when they are enqueued).
-            int alpha = alpha0;
-            std::vector<int> batch;
-            while (alpha < ctx->L) {
-                batch.clear();
-                PGX_TRY(region_batch_begin(ctx));
-                const int64_t version0 = version;
-                int rc = PGX_OK;
-                for (int a = alpha; a < ctx->L && rc == PGX_OK; ++a) {
-                    if (batch.empty() && noop_at[a] == version) { ctx->stats[7]++; alpha = a + 1; continue; }   // (known now: nothing is in flight)
-                    MoveRequest rq = move(a);
-                    rq.batch_slot = (int)batch.size();
-                    rq.skip_rel = noop_at[a] >= version0 ? (int)(noop_at[a] - version0) : -1;
-                    rc = expand_alpha_launch(ctx, rq);
-                    if (rc == PGX_OK && rq.outcome != MoveOutcome::Pending) rc = fail(ctx, PGX_ERR_INVALID, "pgx_expansion (internal): a batched move was not enqueued");
-                    else if (rc == PGX_OK) { batch.push_back(a); rc = keep ? memo_snapshot(a) : PGX_OK; }
-                }
-                if (rc != PGX_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-                if (batch.empty()) break;
-                PGX_TRY(region_batch_fetch(ctx, (int)batch.size()));
-                PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                int next = ctx->L;
-                for (size_t k = 0; k < batch.size(); ++k) {
-                    const int a = batch[k];
-                    int status = 0;
-                    int64_t ch = 0;
-                    PGX_TRY(region_result(ctx, (int)k, a, &status, &ch));
-                    if (status == 2) {   // the device applied the skip rule
-                        if (noop_at[a] != version) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: move %d of a batch did not run", a);
-                        ctx->stats[7]++;
-                        continue;
-                    }
-                    if (status == 1) {   // declined: the general path, then a new batch behind it
-                        MoveRequest rq = move(a);
-                        rq.region_declined = true;
-                        PGX_TRY(expand_alpha_launch(ctx, rq));
-                        ch = rq.changed;
-                        if (cycle == 1 && memo_on) PGX_TRY(memo_snapshot(a));   // (the snapshot taken behind the declined move holds the untouched labels)
-                        next = a + 1;
-                    }
-                    if (cycle == 1 && memo_on) memo_record(a, ch);
-                    changed_total += ch;
-                    if (ch > 0) { ++version; noop_at[a] = -1; }
-                    else noop_at[a] = version;
-                    if (status == 1) break;
-                }
-                alpha = next;
-            }
-        } else
-        for (int alpha = alpha0; alpha < ctx->L; ++alpha) {
-            // a move is a deterministic function of (labelling, alpha): one that relabelled nothing and has seen no
-            // label change since would relabel nothing again — skipped (typically the tail of the verifying cycle)
-            if (noop_at[alpha] == version) { ctx->stats[7]++; continue; }
-            MoveRequest rq = move(alpha);
-            PGX_TRY(expand_alpha_launch(ctx, rq));
-            const int64_t ch = rq.changed;
-            if (keep) { PGX_TRY(memo_snapshot(alpha)); memo_record(alpha, ch); }
-            changed_total += ch;
-            if (ch > 0) { ++version; noop_at[alpha] = -1; }
-            else noop_at[alpha] = version;
-        }
-        // a cycle that relabels nothing leaves the energy unchanged by construction: skip the recomputation
-        if (changed_total > 0) PGX_TRY(energy_launch(ctx, lq, hq, &new_e));
-        done = cycle;
-        last_cycle_changed = changed_total;
-    }
-    if (ident_known && done >= 1 && last_cycle_changed == 0) {   // a fixed point of the whole cycle (a final cycle that moved ties at equal energy is not)
-        last.valid = 1;
-        last.ident = ctx->unary_ident;
-        last.lq = lq; last.hq = hq; last.n = ctx->dq_n; last.graph_version = ctx->graph_version; last.energy_q = new_e;
-        last.labels_version = ctx->labels_version;
-    }
-    if (energy_q) *energy_q = new_e;
-    if (energy) *energy = (double)new_e / 4294967296.0;
+    PGX_TRY(expansion_launch(ctx, lq, hq, max_cycles, true, &e, &done));
+    if (energy_q) *energy_q = e;
+    if (energy) *energy = (double)e / 4294967296.0;
     if (cycles) *cycles = done;
     return PGX_OK;
 }
@@ -1179,7 +996,7 @@ int pgx_expansion_paths(pgx_ctx* ctx, int64_t paths[6])
 {
     if (!ctx || !paths) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion_paths: NULL argument");
     for (int k = 0; k < 6; ++k) paths[k] = ctx->paths[k];
-    paths[1] = ctx->memo_hits;
+    paths[1] = ctx->expansion.memo_hits;
     paths[5] = ctx->tile_fallbacks;
     return PGX_OK;
 }

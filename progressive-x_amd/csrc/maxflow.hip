@@ -1116,10 +1116,10 @@ static int check_resident_problem(pgx_ctx* ctx, int alpha_first, int alpha_last)
     const int L = ctx->L;
     if (n <= 0 || L <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: unary table not set");
     if (ctx->labels_n != n) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: labels not set (or wrong length)");
-    if (ctx->labels_max >= L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: label %d out of range (the unary table has %d labels)", ctx->labels_max, L);
+    if (ctx->expansion.labels_max >= L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: label %d out of range (the unary table has %d labels)", ctx->expansion.labels_max, L);
     if (alpha_first < 0 || alpha_last >= L) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: alpha %d out of range", alpha_first < 0 ? alpha_first : alpha_last);
     if (L > kMfMaxLabels) return fail(ctx, PGX_ERR_INVALID, "pgx_expansion: at most %d labels (got %d)", kMfMaxLabels, L);
-    if (alpha_last > ctx->labels_max) ctx->labels_max = alpha_last;   // the moves may write these labels: a later, smaller table must see it
+    if (alpha_last > ctx->expansion.labels_max) ctx->expansion.labels_max = alpha_last;   // the moves may write these labels: a later, smaller table must see it
     return PGX_OK;
 }
 

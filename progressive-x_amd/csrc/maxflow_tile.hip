@@ -68,7 +68,7 @@ struct RegionInfo {
 // words in device memory keep that exact:  ctl[0] "poison" - a move declined (the general path has to solve it): every later move
 // of the batch returns at once, untouched, and is enqueued again after the host has solved the declined one;  ctl[1] - the moves
 // of the batch that relabelled sites so far: a move that relabelled nothing last time and has seen no relabelling since would
-// relabel nothing again (it is a function of the labelling and alpha) and returns at once (the host's skip rule, capi.hip).
+// relabel nothing again (it is a function of the labelling and alpha) and returns at once (the host's skip rule, expansion_cycle.h).
 // Both words are only written by the LAST kernel of a move, so all kernels of a move decide alike.
 __device__ __forceinline__ bool batch_skips(const int* ctl, int skip_rel)
 {

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/pgx.h"
+#include "expansion_cycle.h"
 #include "move_route.h"
 #include "residuals.hip.h"
 
@@ -103,38 +104,14 @@ struct pgx_ctx {
     pgx::DevBuf kmodels;
     pgx::DevBuf labels; // int32 [n]
     int64_t labels_n = 0;
-    // First-cycle memo of pgx_expansion (capi.hip): PEARL starts every labelling it cannot warm-start from the all-zero labelling
-    // (PEARL.h:507-508, 541-547), so the first cycle's move alpha sees labels < alpha only and is a deterministic function of the
-    // unary columns 0..alpha, lambda, h and the graph.  The labels after each first-cycle move are kept; a later expansion from
-    // zeros whose leading unary columns are THE SAME (exact identity of what pgx_pearl_unary computed them from) restores the
-    // state behind that prefix instead of solving its min-cuts again.
-    struct ExpansionMemo {
-        std::vector<std::string> ident;   // identity of the unary column each kept move was solved with
-        std::vector<int64_t> changed;     // sites the move relabelled
-        int valid = 0;                    // moves 0 .. valid-1 of the last from-zeros expansion are kept
-        pgx::DevBuf snaps;                // [cap][n] int32: labels after move alpha
-        int64_t n = 0, lq = 0, hq = 0, graph_version = -1;
-        int cap = 0;
-    } memo;
-    // The last pgx_expansion that ended on a FIXED POINT (its final cycle relabelled nothing), with what it was computed from: a call
-    // with the same columns, weights, graph and the labels it left is the same deterministic computation - one cycle of no-ops, the same
-    // energy - and is answered from here (capi.hip pgx_expansion).  PEARL ends every run with exactly such a call: the iteration that
-    // finds "nothing changed" labels once more with the models and the warm start of the one before (PEARL.h:429-467).
-    struct ExpansionDone {
-        int valid = 0;
-        std::vector<std::string> ident;
-        int64_t lq = 0, hq = 0, n = 0, graph_version = -1, energy_q = 0;
-        int64_t labels_version = -1;   // pgx_ctx::labels_version when the fixed point was recorded (the unary table's identity is `ident`)
-    } last_done;
-    int64_t labels_version = 0;           // bumped by EVERY writer of `labels` (pgx_set_labels, every expansion move, the greedy labelling): the
-                                          // identical-call shortcut compares it instead of trusting each writer to clear last_done
-    int mf_done_verify = 0;               // PGX_MF_DONE_VERIFY=1: on a shortcut hit run the real verifying cycle and check 0 changes + equal energy
-    std::vector<std::string> unary_ident; // per label: what its unary column was computed from (pgx_pearl_unary); empty = unknown (injected table)
-    int64_t points_version = 0;           // bumped by pgx_set_points
-    int labels_all_zero = 0;              // the resident labelling is the all-zero one pgx_set_labels uploaded (no move has run since)
-    int mf_memo = 1;                      // PGX_MF_MEMO=0: no first-cycle memo (A/B)
-    int64_t memo_hits = 0;                // moves restored from the memo (pgx_expansion_paths[1])
-    int labels_max = 0;          // largest label pgx_set_labels uploaded (the moves index per-label tables with the labels: checked against L)
+    // Everything pgx_expansion remembers between calls - the first-cycle memo, the last fixed point, the labels' version, the unary
+    // columns' identities - and the events that change it (expansion_cycle.h ExpansionState: one owner, compiled into the CPU tests too).
+    pgx::ExpansionState expansion;
+    struct MemoSnapshots {        // the memo's device side (expansion.hip): [rows][n] int32, the labels after first-cycle move alpha
+        pgx::DevBuf buf;
+        int rows = 0;
+        int64_t n = 0;
+    } memo_snaps;
     // graph (symmetric CSR)
     int64_t gn = 0, gE = 0;
     int max_degree = 0;
@@ -285,6 +262,10 @@ struct MoveRequest {
 };
 int expand_alpha_launch(pgx_ctx* ctx, MoveRequest& rq);   // a move on the resident problem: fills in the tables (the caller gives lambda_q, h_q, alpha, the batch fields)
 int expand_cycle_l0(pgx_ctx* ctx, int64_t h_q, int64_t* changed, int* evaluated);  // lambda = 0: all labels, one read-back
+// expansion.hip: pgx_expansion on the resident problem, the cycles driven by expansion_cycle.h run_expansion.  allow_shortcut = false: the
+// cycle runs even when the call could be answered from the last fixed point (what PGX_MF_DONE_VERIFY compares the answer with)
+int expansion_launch(pgx_ctx* ctx, int64_t lambda_q, int64_t h_q, int max_cycles, bool allow_shortcut, int64_t* energy_q, int* cycles);
+void expansion_points_changed(pgx_ctx* ctx);   // pgx_set_points: the event, and the memo's snapshots of the old point set released
 int run_move(pgx_ctx* ctx, MoveRequest& rq);              // lambda > 0, any tables
 void maxflow_free(pgx_ctx* ctx);
 int maxflow_schedule_stats(pgx_ctx* ctx, int64_t out[8]);   // maxflow.hip

@@ -543,7 +543,7 @@ int sampler_prosac_set(pgx_ctx* ctx, const int32_t* tops, int count)
     PGX_HIP(ctx, hipMemcpyAsync(ctx->prosac_tops.p, tops, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the caller's buffer is free on return)
     ctx->prosac_count = count;
-    ctx->prosac_points_version = ctx->points_version;
+    ctx->prosac_points_version = ctx->expansion.points_version;
     return PGX_OK;
 }
 
@@ -599,9 +599,9 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
 int solve_minimal_sampled_launch(pgx_ctx* ctx, int sampler, uint64_t key, uint32_t batch, int S, int32_t* samples_out, double* models_out)
 {
     if (sampler < 0 || sampler > 2) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: sampler %d (0 uniform, 1 NAPSAC, 2 PROSAC)", sampler);
-    if (sampler == 2 && (ctx->prosac_count < S || ctx->prosac_points_version != ctx->points_version))
+    if (sampler == 2 && (ctx->prosac_count < S || ctx->prosac_points_version != ctx->expansion.points_version))
         return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: PROSAC needs pgx_sampler_prosac_set for the resident points with at least %d entries (has %d)", S,
-                    ctx->prosac_points_version == ctx->points_version ? ctx->prosac_count : 0);
+                    ctx->prosac_points_version == ctx->expansion.points_version ? ctx->prosac_count : 0);
     if (sampler == 1 && (ctx->gn != ctx->n || ctx->gE <= 0)) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: NAPSAC needs the neighbourhood graph of the resident points (pgx_graph_build / pgx_set_graph)");
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: points not set");
     if (S <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal_sampled: empty sample batch");

@@ -30,3 +30,7 @@ ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/pnapsac_san
 g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 \
     -o build/san/move_route_san tests/emu/move_route_driver.cpp
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/move_route_san
+# csrc/expansion_cycle.h (which moves of pgx_expansion's cycles run, are skipped, restored or run again: host code of libpgx.so, no HIP in it) under tests/emu/expansion_cycle_driver.cpp
+g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 \
+    -o build/san/expansion_cycle_san tests/emu/expansion_cycle_driver.cpp
+ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/expansion_cycle_san

@@ -10,8 +10,10 @@
 #include <cstdlib>
 #include <numeric>
 #include <random>
+#include <string>
 #include <vector>
 
+#include "../../progressive-x_amd/csrc/expansion_cycle.h"
 #include "../../progressive-x_amd/csrc/maxflow_driver.inl"
 #include "../../progressive-x_amd/csrc/maxflow_l0.hip.h"
 #include "../../progressive-x_amd/csrc/move_route.h"
@@ -368,4 +370,170 @@ extern "C" void emu_plan_move(int mf_tile, int mf_tile_batch, int mf_region, int
     for (int k = 0; k < 3; ++k) out[k] = (int32_t)r.order[k];
     out[3] = r.flip ? 1 : 0;
     out[4] = r.batched ? 1 : 0;
+}
+
+// ---- the cycle driver of csrc/expansion_cycle.h (run_expansion, as libpgx.so compiles it) over a CPU backend: tests/test_expansion_cycle.py,
+// tests/emu/expansion_cycle_driver.cpp.  Moves are solved by emu_expand_alpha above, snapshots are array copies, and a batch has the
+// device's semantics as maxflow_tile.hip states them: enqueued moves execute in order; a move with skip_rel >= 0 does not run when
+// exactly that many earlier moves of the batch relabelled something (status 2); a move the script declines leaves the labels untouched
+// (status 1) and nothing behind it in the batch runs (status 2).
+namespace {
+
+struct EmuProblem {
+    int64_t n;
+    int L;
+    const int64_t* Dq;   // point-major [n][L]
+    const int32_t *off, *idx, *mult;
+    int64_t lq, hq;
+};
+
+// sum of the unary costs + lambda-weighted Potts over the CSR with multiplicities (every pair once) + h per label in use
+int64_t emu_energy(const EmuProblem& p, const int32_t* labels)
+{
+    int64_t e = 0;
+    std::vector<char> used((size_t)p.L, 0);
+    for (int64_t i = 0; i < p.n; ++i) {
+        e += p.Dq[i * p.L + labels[i]];
+        used[(size_t)labels[i]] = 1;
+        if (p.lq > 0 && p.off)
+            for (int32_t a = p.off[i]; a < p.off[i + 1]; ++a)
+                if (p.idx[a] < i && labels[p.idx[a]] != labels[i]) e += p.lq * (int64_t)p.mult[a];
+    }
+    for (int l = 0; l < p.L; ++l) if (used[(size_t)l]) e += p.hq;
+    return e;
+}
+
+struct EmuCycleCtx {   // what a context keeps between calls: the state of expansion_cycle.h and the memo's snapshots
+    ExpansionState st;
+    std::vector<int32_t> snaps;
+    int rows = 0;
+    int64_t n = 0;
+};
+
+enum { kDeclineNone = 0, kDeclineEveryFirstAttempt = 1, kDeclineRandom = 2, kDeclineFirstOfBatch = 3,
+       kBreakNotEnqueued = 4, kBreakDidNotRun = 5 };   // (4, 5: a backend that breaks the batch protocol - the driver must end with its error)
+
+struct EmuCycle {
+    const EmuProblem& p;
+    int32_t* labels;
+    EmuCycleCtx& cx;
+    int decline_mode;
+    std::mt19937_64 rng;
+    int batch_changes = 0;   // ctl[1]: moves of the batch that relabelled something
+    bool poisoned = false;   // ctl[0]
+    std::vector<int> status;
+    std::vector<int64_t> changed;
+    int64_t declines = 0, device_skips = 0;
+    std::string err;
+
+    int solve(int alpha, int64_t* ch) { return emu_expand_alpha(p.n, p.L, p.Dq, p.off, p.idx, p.mult, p.lq, p.hq, alpha, labels, 0, 0, ch, nullptr); }
+    int energy(int64_t* e) { *e = emu_energy(p, labels); return 0; }
+    int move(int alpha, bool, int64_t* ch) { return solve(alpha, ch); }
+    int batch_begin() { batch_changes = 0; poisoned = false; status.clear(); changed.clear(); return 0; }
+    int batch_enqueue(int alpha, int slot, int skip_rel, bool* enqueued)
+    {
+        *enqueued = decline_mode != kBreakNotEnqueued;
+        if ((int)status.size() != slot) return error("emu: slot %d out of order", slot);
+        status.push_back(2);
+        changed.push_back(0);
+        if (poisoned || decline_mode == kBreakDidNotRun) return 0;
+        if (skip_rel >= 0 && batch_changes == skip_rel) { ++device_skips; return 0; }
+        const bool decline = decline_mode == kDeclineEveryFirstAttempt || (decline_mode == kDeclineRandom && rng() % 3 == 0) ||
+                             (decline_mode == kDeclineFirstOfBatch && slot == 0);
+        if (decline) { status[(size_t)slot] = 1; poisoned = true; ++declines; return 0; }
+        status[(size_t)slot] = 0;
+        const int rc = solve(alpha, &changed[(size_t)slot]);
+        if (changed[(size_t)slot] > 0) ++batch_changes;
+        return rc;
+    }
+    int batch_fetch(int slots) { return slots == (int)status.size() ? 0 : error("emu: fetch of %d slots", slots); }
+    int batch_result(int slot, int, int* st, int64_t* ch) { *st = status[(size_t)slot]; *ch = changed[(size_t)slot]; return 0; }
+    int cycle_l0(int64_t* ch)
+    {
+        for (int alpha = 0; alpha < p.L; ++alpha) {
+            int64_t c1 = 0;
+            const int rc = solve(alpha, &c1);
+            if (rc != 0) return rc;
+            *ch += c1;
+        }
+        return 0;
+    }
+    int reserve_snapshots(int prefix)
+    {
+        if (cx.rows >= p.L && cx.n == p.n) return 0;
+        std::vector<int32_t> grown((size_t)p.L * (size_t)p.n);
+        std::copy(cx.snaps.begin(), cx.snaps.begin() + (size_t)prefix * (size_t)p.n, grown.begin());
+        cx.snaps.swap(grown);
+        cx.rows = p.L;
+        cx.n = p.n;
+        return 0;
+    }
+    int snapshot(int alpha) { std::copy(labels, labels + p.n, cx.snaps.begin() + (size_t)alpha * (size_t)p.n); return 0; }
+    int restore(int prefix) { std::copy(cx.snaps.begin() + (size_t)(prefix - 1) * (size_t)p.n, cx.snaps.begin() + (size_t)prefix * (size_t)p.n, labels); return 0; }
+    int error(const char* format, int alpha)
+    {
+        char buf[256];
+        std::snprintf(buf, sizeof buf, format, alpha);
+        err = buf;
+        return -20;
+    }
+};
+
+}  // namespace
+
+extern "C" int64_t emu_cycle_energy(int64_t n, int L, const int64_t* Dq, const int32_t* off, const int32_t* idx, const int32_t* mult,
+                                    int64_t lambda_q, int64_t h_q, const int32_t* labels)
+{
+    const EmuProblem p{n, L, Dq, off, idx, mult, lambda_q, h_q};
+    return emu_energy(p, labels);
+}
+
+extern "C" void* emu_cycle_new(int mf_memo)
+{
+    EmuCycleCtx* cx = new EmuCycleCtx();
+    cx->st.mf_memo = mf_memo;
+    return cx;
+}
+
+extern "C" void emu_cycle_free(void* h) { delete (EmuCycleCtx*)h; }
+
+// the events of ExpansionState: 0 labels written | 1 labels uploaded (arg = their largest) | 2 a table without identity injected |
+// 3 the point set changed | 4 a unary table of these L columns is resident (ids: one number per column; with the points' version its identity)
+extern "C" void emu_cycle_event(void* h, int event, int arg, const int64_t* ids, int L)
+{
+    EmuCycleCtx& cx = *(EmuCycleCtx*)h;
+    if (event == 0) cx.st.labels_written();
+    if (event == 1) cx.st.labels_uploaded(arg);
+    if (event == 2) cx.st.unary_injected();
+    if (event == 3) { cx.st.points_changed(); cx.snaps.clear(); cx.rows = 0; cx.n = 0; }
+    if (event == 4) {
+        std::vector<std::string> ident;
+        for (int l = 0; l < L; ++l) ident.push_back(std::to_string(cx.st.points_version) + "|" + std::to_string(ids[l]));
+        cx.st.unary_resident(std::move(ident));
+    }
+}
+
+// One pgx_expansion call as expansion.hip makes it: the identical-call answer, else the cycles.  counts: solved | skipped on the host |
+// skipped on the device | restored | declined | batches opened behind a decline | declines the backend scripted | skips the backend
+// applied | 1 when the call was answered from the fixed point | the state's memo_hits
+extern "C" int emu_cycle_run(void* h, int64_t n, int L, const int64_t* Dq, const int32_t* off, const int32_t* idx, const int32_t* mult,
+                             int64_t lambda_q, int64_t h_q, int32_t* labels, int max_cycles, int batched, int64_t graph_version,
+                             int decline_mode, uint64_t decline_seed, int64_t* energy_q, int* cycles, int64_t counts[10])
+{
+    EmuCycleCtx& cx = *(EmuCycleCtx*)h;
+    const EmuProblem p{n, L, Dq, off, idx, mult, lambda_q, h_q};
+    ExpansionCall c;
+    c.L = L; c.n = n; c.labels_n = n; c.lq = lambda_q; c.hq = h_q; c.graph_version = graph_version;
+    c.max_cycles = max_cycles;
+    c.batched = batched != 0;
+    CycleCounts cnt;
+    EmuCycle be{p, labels, cx, decline_mode, std::mt19937_64(decline_seed)};
+    int rc = 0;
+    const bool answered = cx.st.answers(c);
+    if (answered) cx.st.answer(c, cnt, energy_q, cycles);
+    else rc = run_expansion(cx.st, c, be, cnt, energy_q, cycles);
+    const int64_t out[10] = {cnt.solved, cnt.skipped_host, cnt.skipped_device, cnt.restored, cnt.declined, cnt.batches_after_decline,
+                             be.declines, be.device_skips, answered ? 1 : 0, cx.st.memo_hits};
+    for (int k = 0; k < 10; ++k) counts[k] = out[k];
+    return rc;
 }
