@@ -139,12 +139,20 @@ void pgx_pnapsac_destroy(pgx_pnapsac *sampler);
 int pgx_host_rows_with_duplicates(const int64_t *s, int64_t count, int m, uint8_t *out_bad);
 int pgx_host_fisher_yates_rows(const int64_t *draws, const int64_t *rows, int64_t k, int m, int64_t *s);
 int pgx_score_launch(pgx_ctx *ctx, double T2, int has_compound, int want_masks);   /* asynchronous */
+/* Results belong to a batch.  A launch scores the resident batch; pgx_score_upload, pgx_solve_minimal(_sampled) and pgx_set_points
+ * make another batch (or none) resident.  pgx_score_fetch, pgx_score_inliers, pgx_score_allgather, pgx_score_allgather_begin and
+ * pgx_score_fetch_all hand out the last launch's results only while the batch it scored is still the resident one: after one of
+ * those calls and before the next launch they are refused (PGX_ERR_INVALID, "the hypothesis batch (or the points) changed since the
+ * last launch") - as pgx_score_allreduce(_begin) has always refused the launch's accumulators (it still enters its collective and
+ * raises on every rank).  A refused or failed upload / solve changes nothing: the previous batch stays resident and its launch
+ * fetchable.  Tables already handed to an exchange slot (_begin) are the slot's and are collected with _end whatever happens to
+ * the batch meanwhile. */
 int pgx_score_fetch(pgx_ctx *ctx, int exponent, int64_t *counts, double *values, double *shared,
                     double *scores, uint64_t *masks);
 /* The inlier set of hypothesis `row` of the last launch that produced masks (pgx_score with masks / pgx_score_launch with
  * want_masks), as ascending point indices - the `inliers` vector getScore fills (scoring_function_with_compound_model.h:88) -
- * compacted on the device.  index: room for n entries.  A later launch without masks, or pgx_set_points, ends that launch: the call is
- * then refused (PGX_ERR_INVALID) - it never returns a row of an earlier launch. */
+ * compacted on the device.  index: room for n entries.  A later launch without masks, a new batch (above) or pgx_set_points ends that
+ * launch: the call is then refused (PGX_ERR_INVALID) - it never returns a row of an earlier launch. */
 int pgx_score_inliers(pgx_ctx *ctx, int row, int32_t *index, int64_t *count);
 /* what one pgx_score_launch reads+writes at minimum (points + models + compound + results), for rooflines */
 int pgx_score_algorithmic_bytes(pgx_ctx *ctx, int want_masks, int64_t *bytes, int64_t *pairs);

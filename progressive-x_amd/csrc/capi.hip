@@ -78,16 +78,50 @@ int sync_deliver(pgx_ctx* ctx)
     return PGX_OK;
 }
 
+int grow_pinned(pgx_ctx* ctx, PinnedBuf& b, size_t bytes, unsigned flags)
+{
+    if (b.cap >= bytes) return PGX_OK;
+    release(b);
+    PGX_HIP(ctx, hipHostMalloc(&b.p, bytes * 2, flags));
+    b.cap = bytes * 2;
+    return PGX_OK;
+}
+
+void release(PinnedBuf& b)
+{
+    if (b.p) (void)hipHostFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
 int host_staging(pgx_ctx* ctx, size_t bytes, void** p)
 {
-    if (ctx->h_res_cap < bytes) {
-        if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-        ctx->h_res = nullptr; ctx->h_res_cap = 0;
-        PGX_HIP(ctx, hipHostMalloc(&ctx->h_res, bytes * 2, hipHostMallocDefault));
-        ctx->h_res_cap = bytes * 2;
-    }
-    *p = ctx->h_res;
+    PGX_TRY(grow_pinned(ctx, ctx->h_res, bytes));
+    *p = ctx->h_res.p;
     return PGX_OK;
+}
+
+int PinnedStage::acquire(pgx_ctx* ctx, size_t bytes)
+{
+    if (busy) { PGX_HIP(ctx, hipEventSynchronize(ev)); busy = 0; }
+    PGX_TRY(grow_pinned(ctx, buf, bytes));
+    if (!ev) PGX_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return PGX_OK;
+}
+
+int PinnedStage::submitted(pgx_ctx* ctx, hipStream_t stream)
+{
+    PGX_HIP(ctx, hipEventRecord(ev, stream));
+    busy = 1;
+    return PGX_OK;
+}
+
+void PinnedStage::free()
+{
+    release(buf);
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr;
+    busy = 0;
 }
 
 }  // namespace pgx
@@ -139,15 +173,15 @@ int pgx_create(int device_id, pgx_ctx** out)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) ctx->cu_count = prop.multiProcessorCount;
     const char* nf = std::getenv("PGX_NO_FILTER");
-    ctx->filter_enabled = (nf && nf[0] == '1') ? 0 : ((nf && nf[0] == '2') ? 2 : 1);
+    ctx->score_sw.filter_enabled = (nf && nf[0] == '1') ? 0 : ((nf && nf[0] == '2') ? 2 : 1);
     if (const char* ns = std::getenv("PGX_NO_SORT")) ctx->score_sort = (ns[0] == '1') ? 0 : 1;
     if (const char* b = std::getenv("PGX_SP_KD")) { const int v = std::atoi(b); ctx->sp_kd = v < 0 ? 0 : (v > 2 ? 2 : v); }
     if (const char* b = std::getenv("PGX_SETPOINTS_HOST")) ctx->setpoints_host = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_GC_FLIP")) ctx->route.gc_flip = std::atoi(b) ? 1 : 0;
-    if (const char* b = std::getenv("PGX_SCORE_MIRROR")) ctx->score_mirror = std::atoi(b) != 0;
-    if (const char* b = std::getenv("PGX_SCORE_NO_CULL")) ctx->score_cull = std::atoi(b) ? 0 : 1;
+    if (const char* b = std::getenv("PGX_SCORE_MIRROR")) ctx->score_sw.mirror = std::atoi(b) != 0;
+    if (const char* b = std::getenv("PGX_SCORE_NO_CULL")) ctx->score_sw.cull = std::atoi(b) ? 0 : 1;
     if (const char* b = std::getenv("PGX_NO_GROUP")) ctx->group_filter = std::atoi(b) ? 0 : 1;
-    if (const char* b = std::getenv("PGX_VERIFY")) ctx->verify = std::atoi(b) ? 1 : 0;
+    if (const char* b = std::getenv("PGX_VERIFY")) ctx->score_sw.verify = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_TILE")) ctx->route.mf_tile = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_TILE_BATCH")) ctx->route.mf_tile_batch = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_REGION")) ctx->route.mf_region = std::atoi(b) ? 1 : 0;
@@ -183,13 +217,11 @@ void pgx_destroy(pgx_ctx* ctx)
                       &ctx->weights, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops};
     for (DevBuf* b : bufs) release(*b);
     for (DevBuf& b : ctx->slots) release(b);
-    if (ctx->h_res) (void)hipHostFree(ctx->h_res);
+    release(ctx->h_res);
+    release(ctx->h_mirror);
+    ctx->h_samples.free();
+    ctx->h_models.free();
     if (ctx->h_rb) (void)hipHostFree(ctx->h_rb);
-    if (ctx->h_mirror) (void)hipHostFree(ctx->h_mirror);
-    if (ctx->h_samples) (void)hipHostFree(ctx->h_samples);
-    if (ctx->h_models) (void)hipHostFree(ctx->h_models);
-    if (ctx->ev_models) (void)hipEventDestroy(ctx->ev_models);
-    if (ctx->ev_samples) (void)hipEventDestroy(ctx->ev_samples);
     for (int k = 0; k < 5; ++k) if (ctx->kev[k]) (void)hipEventDestroy(ctx->kev[k]);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -308,7 +340,7 @@ static int set_points_host(pgx_ctx* ctx, const ModelInfo& mi, const double* poin
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->point_sort = 0;
     ctx->comp_dirty = 1;
-    if (obs0 >= 0 && ctx->group_filter && ctx->filter_enabled == 1 && std::isfinite(umax))
+    if (obs0 >= 0 && ctx->group_filter && ctx->score_sw.filter_enabled == 1 && std::isfinite(umax))
         PGX_TRY(score_sort_points(ctx, mi, points, p32.data(), pmax.data()));
     return PGX_OK;
 }
@@ -321,14 +353,15 @@ int pgx_set_points(pgx_ctx* ctx, int model_type, const double* points, int64_t n
     if (!points || n <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: empty input");
     if (n >= ((int64_t)1 << 31)) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: n must be < 2^31");
     ctx->model_type = model_type; ctx->D = mi.D; ctx->P = mi.P; ctx->n = n;
-    ctx->M = 0; ctx->last_acc = nullptr; ctx->dq_n = 0; ctx->L = 0; ctx->labels_n = 0;
+    ctx->batch.points_changed();   // (before the fallible work: the old points are gone whether or not the new ones arrive)
+    ctx->dq_n = 0; ctx->L = 0; ctx->labels_n = 0;
     ctx->weights_n = 0;  // weights belong to a point set
     ctx->score_global_n = 0;   // the fixed-point scale of a sharded job belongs to that job's point set
     expansion_points_changed(ctx);
     // upload + every derived copy on the device (setpoints.hip): filter scales, f32 rows, Morton order, group bounds
     const int rc = !ctx->setpoints_host ? set_points_device(ctx, mi, points, n) : set_points_host(ctx, mi, points, n);
     if (rc != PGX_OK) {   // half-built copies (an allocation failed midway): no resident problem, every later call fails cleanly
-        ctx->n = 0; ctx->model_type = -1; ctx->D = 0; ctx->P = 0; ctx->point_sort = 0; ctx->mirror_valid = 0;
+        ctx->n = 0; ctx->model_type = -1; ctx->D = 0; ctx->P = 0; ctx->point_sort = 0;
         return rc;
     }
     for (DevBuf& b : ctx->slots) release(b);
@@ -428,32 +461,20 @@ int pgx_score_upload(pgx_ctx* ctx, const double* models, int M)
     if (ctx->n <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_upload: points not set");
     if (!models || M <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_upload: empty hypothesis batch");
     const int P = ctx->P;
-    // the host mirror of an earlier launch is un-permuted with THAT launch's order: from here on h_perm belongs to this batch, so a
-    // fetch of the earlier launch's results must come from the device copy (the finish kernel scattered it through the device perm)
-    ctx->mirror_valid = 0;
     std::vector<int> perm((size_t)M);
     for (int m = 0; m < M; ++m) perm[(size_t)m] = m;
     std::vector<uint64_t> keys;
     // (M = 64 | 65, and Mpad at 255 .. 257, 511 .. 513, 2049: tests/test_gpu_switches.py test_score_batch_sizes_across_the_reorder_and_the_padding)
     const bool reorder = ctx->score_sort && M > 64 && locality_keys(ctx, models, M, keys);
     if (reorder) radix_perm(keys, perm);   // 33-bit keys (locality_keys)
-    if (!reorder) ctx->h_perm.clear();     // identity
-    else ctx->h_perm.assign(perm.begin(), perm.end());
-    ctx->Mpad = ((M + 255) / 256) * 256;   // (the tail of the permutation below is zero-filled: same test)
+    const int Mpad = ((M + 255) / 256) * 256;   // (the tail of the permutation below is zero-filled: same test)
     // The (reordered) batch and its permutation are assembled in a pinned staging buffer owned by the context: the caller's
     // array is consumed before the call returns, and the copies need no synchronisation - the host goes on to enqueue the
     // scoring kernels behind them.  An event guards the staging buffer against the next upload.
-    const size_t mbytes = (size_t)M * P * sizeof(double), pbytes = (size_t)ctx->Mpad * sizeof(int);
-    if (ctx->h_models_busy) { PGX_HIP(ctx, hipEventSynchronize(ctx->ev_models)); ctx->h_models_busy = 0; }
-    if (ctx->h_models_cap < mbytes + pbytes) {
-        if (ctx->h_models) (void)hipHostFree(ctx->h_models);
-        ctx->h_models = nullptr; ctx->h_models_cap = 0;
-        PGX_HIP(ctx, hipHostMalloc(&ctx->h_models, (mbytes + pbytes) * 2, hipHostMallocDefault));
-        ctx->h_models_cap = (mbytes + pbytes) * 2;
-    }
-    if (!ctx->ev_models) PGX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_models, hipEventDisableTiming));
-    double* hm = (double*)ctx->h_models;
-    int* hp = (int*)((char*)ctx->h_models + mbytes);
+    const size_t mbytes = (size_t)M * P * sizeof(double), pbytes = (size_t)Mpad * sizeof(int);
+    PGX_TRY(ctx->h_models.acquire(ctx, mbytes + pbytes));
+    double* hm = (double*)ctx->h_models.buf.p;
+    int* hp = (int*)((char*)ctx->h_models.buf.p + mbytes);
     if (reorder)
         for (int m = 0; m < M; ++m) std::memcpy(hm + (size_t)m * P, models + (size_t)perm[(size_t)m] * P, (size_t)P * sizeof(double));
     else
@@ -464,9 +485,11 @@ int pgx_score_upload(pgx_ctx* ctx, const double* models, int M)
     PGX_TRY(ensure(ctx, ctx->perm, pbytes));
     PGX_HIP(ctx, hipMemcpyAsync(ctx->models.p, hm, mbytes, hipMemcpyHostToDevice, ctx->stream));
     PGX_HIP(ctx, hipMemcpyAsync(ctx->perm.p, hp, pbytes, hipMemcpyHostToDevice, ctx->stream));
-    PGX_HIP(ctx, hipEventRecord(ctx->ev_models, ctx->stream));
-    ctx->h_models_busy = 1;
-    ctx->M = M; ctx->last_acc = nullptr;
+    PGX_TRY(ctx->h_models.submitted(ctx, ctx->stream));
+    // From here on the batch is this one: a mirror an earlier launch wrote is in THAT launch's order, and its rows belong to nothing
+    // (ScoreBatch: the launch's generation is not the batch's any more).  Nothing above changed the owner: a failed upload leaves
+    // the previous batch and its launch as they were.
+    ctx->batch.uploaded(M, Mpad, reorder ? perm.data() : nullptr);
     return PGX_OK;
 }
 
@@ -499,9 +522,10 @@ int pgx_score_set_global_n(pgx_ctx* ctx, int64_t n_total)
 int pgx_score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks)
 {
     CTX_GUARD(ctx);
-    ctx->score_has_compound = has_compound != 0;
     return score_launch(ctx, T2, has_compound, want_masks);
 }
+
+static const char* const kBatchChanged = "the hypothesis batch (or the points) changed since the last launch: its results belong to no resident batch - launch again";
 
 static void finish_scores(int n, int has_compound, int exponent, const double* values, const double* shared,
                           double* scores)
@@ -523,34 +547,31 @@ int pgx_score_fetch(pgx_ctx* ctx, int exponent, int64_t* counts, double* values,
                     uint64_t* masks)
 {
     CTX_GUARD(ctx);
-    const int M = ctx->M;
-    if (M <= 0 || !ctx->counts.p) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch: nothing launched");
-    const size_t Mp = (size_t)ctx->Mpad;
+    const ScoreBatch& sb = ctx->batch;
+    if (sb.table() == ScoreTable::None) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch: nothing launched");
+    if (sb.table() == ScoreTable::Changed) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch: %s", kBatchChanged);
+    const int M = sb.resident.M;
+    const size_t Mp = (size_t)sb.resident.Mpad;
     const size_t need = Mp * 24;
-    if (ctx->h_res_cap < need) {
-        if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-        ctx->h_res = nullptr; ctx->h_res_cap = 0;
-        PGX_HIP(ctx, hipHostMalloc(&ctx->h_res, need * 2, hipHostMallocDefault));
-        ctx->h_res_cap = need * 2;
-    }
-    int64_t* c = (int64_t*)ctx->h_res;
-    double* v = (double*)ctx->h_res + Mp;
-    double* s = (double*)ctx->h_res + 2 * Mp;
-    const bool mirrored = ctx->mirror_valid && ctx->h_mirror_cap >= need;
+    void* stage = nullptr;
+    PGX_TRY(host_staging(ctx, need, &stage));
+    int64_t* c = (int64_t*)stage;
+    double* v = (double*)stage + Mp;
+    double* s = (double*)stage + 2 * Mp;
+    const bool mirrored = sb.from_mirror();
     // counts | values | shared are one allocation of 3 x Mpad words (score_launch): one copy - or none, when the last
     // kernel of the launch has already written them to the host mirror
     if (!mirrored) PGX_HIP(ctx, hipMemcpyAsync(c, ctx->counts.p, need, hipMemcpyDeviceToHost, ctx->stream));
     if (masks) {
-        if (!ctx->have_masks) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch: masks were not requested at launch");
-        PGX_TRY(d2h(ctx, masks, ctx->masks.p, (size_t)M * (size_t)ctx->words * sizeof(uint64_t)));
+        if (!sb.last.masks) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch: masks were not requested at launch");
+        PGX_TRY(d2h(ctx, masks, ctx->masks.p, (size_t)M * (size_t)sb.last.words * sizeof(uint64_t)));
     }
     PGX_TRY(sync_deliver(ctx));
     if (mirrored) {   // device order -> the caller's order
-        const int64_t* mc = (const int64_t*)ctx->h_mirror;
-        const double* mv = (const double*)ctx->h_mirror + Mp;
-        const double* ms = (const double*)ctx->h_mirror + 2 * Mp;
-        if (ctx->h_perm.size() >= (size_t)M) {
-            const int* pm = ctx->h_perm.data();
+        const int64_t* mc = (const int64_t*)ctx->h_mirror.p;
+        const double* mv = (const double*)ctx->h_mirror.p + Mp;
+        const double* ms = (const double*)ctx->h_mirror.p + 2 * Mp;
+        if (const int* pm = sb.unpermute()) {
             for (int m = 0; m < M; ++m) { const int o = pm[m]; c[o] = mc[m]; v[o] = mv[m]; s[o] = ms[m]; }
         } else {
             memcpy(c, mc, (size_t)M * sizeof(int64_t));
@@ -561,7 +582,7 @@ int pgx_score_fetch(pgx_ctx* ctx, int exponent, int64_t* counts, double* values,
     if (counts) memcpy(counts, c, (size_t)M * sizeof(int64_t));
     if (values) memcpy(values, v, (size_t)M * sizeof(double));
     if (shared) memcpy(shared, s, (size_t)M * sizeof(double));
-    finish_scores(M, ctx->score_has_compound, exponent, v, s, scores);
+    finish_scores(M, sb.last.has_compound, exponent, v, s, scores);
     return PGX_OK;
 }
 
@@ -575,15 +596,16 @@ int pgx_score(pgx_ctx* ctx, const double* models, int M, double T2, int has_comp
 
 int pgx_score_algorithmic_bytes(pgx_ctx* ctx, int want_masks, int64_t* bytes, int64_t* pairs)
 {
-    if (!ctx || ctx->n <= 0 || ctx->M <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_algorithmic_bytes: nothing to score");
+    if (!ctx || ctx->n <= 0 || ctx->batch.resident.M <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_algorithmic_bytes: nothing to score");
+    const int64_t M = ctx->batch.resident.M;
     // the inputs once and the outputs once - N d 8 (points) + M p 8 (hypotheses) + M 16 (count, score), plus
     // the compound preference vector (N 8) when the compound term is on.  Derived copies this library keeps (f32 shadow rows,
     // sorted copies, group bounds) are NOT algorithmic bytes.
-    int64_t b = ctx->n * ctx->D * 8 + (int64_t)ctx->M * ctx->P * 8 + (int64_t)ctx->M * 16;
-    if (ctx->score_has_compound) b += ctx->n * 8;
-    if (want_masks) b += (int64_t)ctx->M * ((ctx->n + 63) / 64) * 8;
+    int64_t b = ctx->n * ctx->D * 8 + M * ctx->P * 8 + M * 16;
+    if (ctx->batch.last.has_compound) b += ctx->n * 8;
+    if (want_masks) b += M * ((ctx->n + 63) / 64) * 8;
     if (bytes) *bytes = b;
-    if (pairs) *pairs = ctx->n * (int64_t)ctx->M;
+    if (pairs) *pairs = ctx->n * M;
     return PGX_OK;
 }
 
@@ -591,11 +613,11 @@ int pgx_score_debug_geometry(pgx_ctx* ctx, int what, int value)
 {
     CTX_GUARD(ctx);
     switch (what) {
-    case 0: if (value < 0 || value > 1024) break; ctx->score_split = value; return PGX_OK;
-    case 1: if (value < -1 || value > 1) break; ctx->score_group_xcd = value; return PGX_OK;
-    case 2: if (value < 0 || value > 1024 || value % 8) break; ctx->score_nrep = value; return PGX_OK;
-    case 3: if (value < 1 || value > 65) break; ctx->score_dense_min = value; return PGX_OK;
-    case 4: if (value < 1 || value > 65535) break; ctx->score_cull_segs = value; return PGX_OK;
+    case 0: if (value < 0 || value > 1024) break; ctx->score_sw.split = value; return PGX_OK;
+    case 1: if (value < -1 || value > 1) break; ctx->score_sw.group_xcd = value; return PGX_OK;
+    case 2: if (value < 0 || value > 1024 || value % 8) break; ctx->score_sw.nrep = value; return PGX_OK;
+    case 3: if (value < 1 || value > 65) break; ctx->score_sw.dense_min = value; return PGX_OK;
+    case 4: if (value < 1 || value > 65535) break; ctx->score_sw.cull_segs = value; return PGX_OK;
     }
     return fail(ctx, PGX_ERR_INVALID, "pgx_score_debug_geometry: what = %d, value = %d out of range", what, value);
 }
@@ -607,7 +629,7 @@ int pgx_score_debug_fetch(pgx_ctx* ctx, int what, void* out, int64_t bytes)
     if (!ctx->point_sort) return fail(ctx, PGX_ERR_INVALID, "pgx_score_debug_fetch: no sorted copies for the resident points");
     const int64_t groups = (ctx->n + 63) / 64, supers = (groups + kSuper - 1) / kSuper;
     if (what == 5) {   // the last launch's integer accumulators, replicas summed, caller's order: [3][Mpad] u64 (score.hip score_acc_export)
-        const int64_t want = (int64_t)3 * ctx->Mpad * 8;
+        const int64_t want = (int64_t)3 * ctx->batch.resident.Mpad * 8;
         if (bytes != want) return fail(ctx, PGX_ERR_INVALID, "pgx_score_debug_fetch: buffer 5 holds %lld bytes, asked for %lld", (long long)want, (long long)bytes);
         PGX_TRY(ensure(ctx, ctx->g_counts, (size_t)want));
         PGX_TRY(score_acc_export(ctx, (unsigned long long*)ctx->g_counts.p, ctx->stream));
@@ -643,10 +665,10 @@ int pgx_score_profile(pgx_ctx* ctx, int on)
 int pgx_score_kernel_times(pgx_ctx* ctx, float ms[4])
 {
     CTX_GUARD(ctx);
-    if (!ms || !ctx->kev[0] || ctx->last_score_path == 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_kernel_times: no profiled launch");
+    if (!ms || !ctx->kev[0] || ctx->batch.last.path == 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_kernel_times: no profiled launch");
     ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
     if (ctx->score_profile == 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_kernel_times: profiling is off");
-    if (ctx->last_score_path == 2) {   // cull + group-major
+    if (ctx->batch.last.path == 2) {   // cull + group-major
         PGX_HIP(ctx, hipEventSynchronize(ctx->score_profile >= 2 ? ctx->kev[3] : ctx->kev[2]));
         PGX_HIP(ctx, hipEventElapsedTime(&ms[1], ctx->kev[1], ctx->kev[2]));
         if (ctx->score_profile >= 2) {
@@ -667,29 +689,26 @@ int pgx_score_stats(pgx_ctx* ctx, double T2, int has_compound, int64_t stats[8])
     CTX_GUARD(ctx);
     if (!stats) return fail(ctx, PGX_ERR_INVALID, "pgx_score_stats: stats is NULL");
     for (int k = 0; k < 8; ++k) stats[k] = 0;
-    ctx->score_stats = 1;
-    ctx->score_has_compound = has_compound != 0;
-    const int rc = score_launch(ctx, T2, has_compound, 0);
-    ctx->score_stats = 0;
-    if (rc != PGX_OK) return rc;
-    const int64_t groups = (ctx->n + 63) / 64;
-    stats[0] = ctx->n * (int64_t)ctx->M;   // (point, hypothesis) pairs of the batch
-    stats[6] = ctx->last_score_path;
-    stats[7] = ctx->last_score_filtered;
-    if (ctx->last_score_path == 2) {
+    PGX_TRY(score_launch(ctx, T2, has_compound, 0, true));
+    const int64_t groups = (ctx->n + 63) / 64, M = ctx->batch.resident.M;
+    const ScoreBatch::Launch& last = ctx->batch.last;
+    stats[0] = ctx->n * M;   // (point, hypothesis) pairs of the batch
+    stats[6] = last.path;
+    stats[7] = last.filter;
+    if (last.path == 2) {
         unsigned long long h[8];
         PGX_TRY(d2h(ctx, h, ctx->stats_buf.p, sizeof(h)));
         PGX_TRY(sync_deliver(ctx));
-        stats[1] = groups * (int64_t)ctx->M;  // (hypothesis, group) bound tests an un-hierarchical cull would run
+        stats[1] = groups * M;  // (hypothesis, group) bound tests an un-hierarchical cull would run
         stats[2] = (int64_t)h[0];             // surviving (hypothesis, group) steps: 64 f32 filter evaluations each
         stats[3] = (int64_t)h[1];             // exact FP64 residual evaluations
         stats[4] = (int64_t)h[2];             // inlier pairs
         // PGX_VERIFY=1: inlier pairs (by the exact residual over EVERY pair) that the group bound or the f32 filter discarded
         // (+ the difference between the exhaustive pass's inlier count and the scoring path's: equal unless something else is wrong)
-        stats[5] = ctx->verify ? (int64_t)(h[4] + h[5]) + ((int64_t)h[6] > stats[4] ? (int64_t)h[6] - stats[4] : stats[4] - (int64_t)h[6]) : -1;
+        stats[5] = ctx->score_sw.verify ? (int64_t)(h[4] + h[5]) + ((int64_t)h[6] > stats[4] ? (int64_t)h[6] - stats[4] : stats[4] - (int64_t)h[6]) : -1;
     } else {
         PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        stats[3] = ctx->last_score_filtered ? -1 : stats[0];  // unfiltered chunked kernel: every pair is evaluated exactly
+        stats[3] = last.filter ? -1 : stats[0];  // unfiltered chunked kernel: every pair is evaluated exactly
     }
     return PGX_OK;
 }

@@ -63,8 +63,7 @@ static int load_rccl(pgx_ctx* ctx)
 // the context's stream, all-gathered and copied into pinned memory on the EXCHANGE stream, so the next batch is scored meanwhile.
 struct ExchangeSlot {
     DevBuf stage, gathered;
-    void* host = nullptr;
-    size_t host_cap = 0;
+    PinnedBuf host;
     hipEvent_t scored = nullptr, done = nullptr;
     int M = 0, Mpad = 0, has_compound = 0, busy = 0;
     int reduced = 0;   // begun by pgx_score_allreduce_begin: `host` holds ONE block counts | values | shared, not one per rank
@@ -103,7 +102,7 @@ void comm_free(pgx_ctx* ctx)
     for (ExchangeSlot& e : ctx->comm->slot) {
         release(e.stage);
         release(e.gathered);
-        if (e.host) (void)hipHostFree(e.host);
+        release(e.host);
         if (e.scored) (void)hipEventDestroy(e.scored);
         if (e.done) (void)hipEventDestroy(e.done);
     }
@@ -183,10 +182,22 @@ int pgx_comm_allreduce_max_f64(pgx_ctx* ctx, double* value)
 
 // common head of the two pipelined exchanges: the slot's stream, events and buffers (stage: what leaves this rank, gathered: what
 // comes back, host: its pinned copy)
-static int slot_prepare(pgx_ctx* ctx, const char* who, int slot, size_t stage_bytes, size_t result_bytes, ExchangeSlot** out)
+// what the exchanges of a launch's table ask of the batch's owner first.  The all-gathers send the table itself and refuse one that
+// belongs to no resident batch; the all-reduces only need a block size to agree on - a launch of another batch enters the collective
+// poisoned (export_or_poison), it must not skip it
+static const char* const kBatchChanged = "the hypothesis batch (or the points) changed since the last launch: its results belong to no resident batch - launch again";
+static int table_ready(pgx_ctx* ctx, const char* who, bool current)
+{
+    const ScoreTable t = ctx->batch.table();
+    if (t == ScoreTable::None) return fail(ctx, PGX_ERR_INVALID, "%s: nothing launched", who);
+    if (current && t == ScoreTable::Changed) return fail(ctx, PGX_ERR_INVALID, "%s: %s", who, kBatchChanged);
+    return PGX_OK;
+}
+
+static int slot_prepare(pgx_ctx* ctx, const char* who, bool current, int slot, size_t stage_bytes, size_t result_bytes, ExchangeSlot** out)
 {
     if (slot < 0 || slot > 1) return fail(ctx, PGX_ERR_INVALID, "%s: slot %d (0 or 1)", who, slot);
-    if (ctx->M <= 0 || !ctx->counts.p) return fail(ctx, PGX_ERR_INVALID, "%s: nothing launched", who);
+    PGX_TRY(table_ready(ctx, who, current));
     PGX_HIP(ctx, hipSetDevice(ctx->device));
     CommState* cs = ctx->comm;
     ExchangeSlot& e = cs->slot[slot];
@@ -196,12 +207,7 @@ static int slot_prepare(pgx_ctx* ctx, const char* who, int slot, size_t stage_by
     if (!e.done) PGX_HIP(ctx, hipEventCreateWithFlags(&e.done, hipEventDisableTiming));
     PGX_TRY(ensure(ctx, e.stage, stage_bytes));
     PGX_TRY(ensure(ctx, e.gathered, result_bytes));
-    if (e.host_cap < result_bytes) {
-        if (e.host) (void)hipHostFree(e.host);
-        e.host = nullptr; e.host_cap = 0;
-        PGX_HIP(ctx, hipHostMalloc(&e.host, result_bytes * 2, hipHostMallocDefault));
-        e.host_cap = result_bytes * 2;
-    }
+    PGX_TRY(grow_pinned(ctx, e.host, result_bytes));
     *out = &e;
     return PGX_OK;
 }
@@ -230,9 +236,9 @@ int pgx_score_allgather(pgx_ctx* ctx)
 {
     if (!ctx || !ctx->comm) return fail(ctx, PGX_ERR_INVALID, "pgx_score_allgather: communicator not initialised");
     PGX_NO_EXCHANGE(ctx, "pgx_score_allgather");
-    if (ctx->M <= 0 || !ctx->counts.p) return fail(ctx, PGX_ERR_INVALID, "pgx_score_allgather: nothing launched");
+    PGX_TRY(table_ready(ctx, "pgx_score_allgather", true));
     PGX_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t W = (size_t)3 * (size_t)ctx->Mpad, G = (size_t)ctx->comm->nranks;
+    const size_t W = (size_t)3 * (size_t)ctx->batch.resident.Mpad, G = (size_t)ctx->comm->nranks;
     PGX_TRY(ensure(ctx, ctx->g_counts, G * W * 8));
     PGX_NCCL(ctx, g_rccl.AllGather(ctx->counts.p, ctx->g_counts.p, W, ncclInt64, ctx->comm->comm, ctx->stream));
     return PGX_OK;
@@ -242,19 +248,16 @@ int pgx_score_fetch_all(pgx_ctx* ctx, int exponent, int64_t* counts, double* val
 {
     if (!ctx || !ctx->comm) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch_all: communicator not initialised");
     PGX_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t M = (size_t)ctx->M, Mp = (size_t)ctx->Mpad, G = (size_t)ctx->comm->nranks;
+    const size_t M = (size_t)ctx->batch.resident.M, Mp = (size_t)ctx->batch.resident.Mpad, G = (size_t)ctx->comm->nranks;
     const size_t T = M * G, need = G * 3 * Mp * 8;
     if (T == 0 || !ctx->g_counts.p || ctx->g_counts.cap < need) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch_all: nothing gathered");
-    if (ctx->h_res_cap < need) {
-        if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-        ctx->h_res = nullptr; ctx->h_res_cap = 0;
-        PGX_HIP(ctx, hipHostMalloc(&ctx->h_res, need * 2, hipHostMallocDefault));
-        ctx->h_res_cap = need * 2;
-    }
-    PGX_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->g_counts.p, need, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->batch.table() == ScoreTable::Changed) return fail(ctx, PGX_ERR_INVALID, "pgx_score_fetch_all: %s", kBatchChanged);
+    void* stage = nullptr;
+    PGX_TRY(host_staging(ctx, need, &stage));
+    PGX_HIP(ctx, hipMemcpyAsync(stage, ctx->g_counts.p, need, hipMemcpyDeviceToHost, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t r = 0; r < G; ++r)   // rank-major [M] rows out of [rank][3][Mpad]
-        unpack_block((const int64_t*)ctx->h_res + r * 3 * Mp, M, Mp, ctx->score_has_compound, exponent, counts ? counts + r * M : nullptr,
+        unpack_block((const int64_t*)stage + r * 3 * Mp, M, Mp, ctx->batch.last.has_compound, exponent, counts ? counts + r * M : nullptr,
                      values ? values + r * M : nullptr, shared ? shared + r * M : nullptr, scores ? scores + r * M : nullptr);
     return PGX_OK;
 }
@@ -269,17 +272,17 @@ int pgx_score_allgather_begin(pgx_ctx* ctx, int slot)
 {
     if (!ctx || !ctx->comm) return fail(ctx, PGX_ERR_INVALID, "pgx_score_allgather_begin: communicator not initialised");
     CommState* cs = ctx->comm;
-    const size_t W = (size_t)3 * (size_t)ctx->Mpad, need = (size_t)cs->nranks * W * 8;
+    const size_t W = (size_t)3 * (size_t)ctx->batch.resident.Mpad, need = (size_t)cs->nranks * W * 8;
     ExchangeSlot* ep = nullptr;
-    PGX_TRY(slot_prepare(ctx, "pgx_score_allgather_begin", slot, W * 8, need, &ep));
+    PGX_TRY(slot_prepare(ctx, "pgx_score_allgather_begin", true, slot, W * 8, need, &ep));
     ExchangeSlot& e = *ep;
     PGX_HIP(ctx, hipMemcpyAsync(e.stage.p, ctx->counts.p, W * 8, hipMemcpyDeviceToDevice, ctx->stream));
     PGX_HIP(ctx, hipEventRecord(e.scored, ctx->stream));
     PGX_HIP(ctx, hipStreamWaitEvent(cs->xstream, e.scored, 0));
     PGX_NCCL(ctx, g_rccl.AllGather(e.stage.p, e.gathered.p, W, ncclInt64, cs->comm, cs->xstream));
-    PGX_HIP(ctx, hipMemcpyAsync(e.host, e.gathered.p, need, hipMemcpyDeviceToHost, cs->xstream));
+    PGX_HIP(ctx, hipMemcpyAsync(e.host.p, e.gathered.p, need, hipMemcpyDeviceToHost, cs->xstream));
     PGX_HIP(ctx, hipEventRecord(e.done, cs->xstream));
-    e.M = ctx->M; e.Mpad = ctx->Mpad; e.has_compound = ctx->score_has_compound; e.busy = 1; e.reduced = 0;
+    e.M = ctx->batch.resident.M; e.Mpad = ctx->batch.resident.Mpad; e.has_compound = ctx->batch.last.has_compound; e.busy = 1; e.reduced = 0;
     return PGX_OK;
 }
 
@@ -294,7 +297,7 @@ int pgx_score_allgather_end(pgx_ctx* ctx, int slot, int exponent, int64_t* count
     e.busy = 0;
     const size_t M = (size_t)e.M, Mp = (size_t)e.Mpad, G = (size_t)ctx->comm->nranks;
     for (size_t r = 0; r < G; ++r)   // rank-major [M] rows out of [rank][3][Mpad]
-        unpack_block((const int64_t*)e.host + r * 3 * Mp, M, Mp, e.has_compound, exponent, counts ? counts + r * M : nullptr,
+        unpack_block((const int64_t*)e.host.p + r * 3 * Mp, M, Mp, e.has_compound, exponent, counts ? counts + r * M : nullptr,
                      values ? values + r * M : nullptr, shared ? shared + r * M : nullptr, scores ? scores + r * M : nullptr);
     return PGX_OK;
 }
@@ -317,7 +320,7 @@ static int export_or_poison(pgx_ctx* ctx, unsigned long long* blk, size_t W, hip
 {
     *local_fail = 0;
     *local_rc = PGX_OK;
-    if (ctx->last_acc != nullptr && ctx->last_score_path == 2 && ctx->last_acc_M == ctx->M && ctx->last_acc_Mpad == ctx->Mpad) {
+    if (ctx->batch.acc_exportable()) {
         int rc = score_acc_export(ctx, blk, stream);
         if (rc == PGX_OK && hipMemsetAsync(blk + W, 0, 64, stream) != hipSuccess) rc = fail(ctx, PGX_ERR_HIP, "score exchange: clearing the poison word failed");
         if (rc == PGX_OK) return PGX_OK;
@@ -340,9 +343,10 @@ int pgx_score_allreduce(pgx_ctx* ctx)
 {
     if (!ctx || !ctx->comm) return fail(ctx, PGX_ERR_INVALID, "pgx_score_allreduce: communicator not initialised");
     PGX_NO_EXCHANGE(ctx, "pgx_score_allreduce");
-    if (ctx->M <= 0 || !ctx->counts.p) return fail(ctx, PGX_ERR_INVALID, "pgx_score_allreduce: nothing launched");
+    PGX_TRY(table_ready(ctx, "pgx_score_allreduce", false));
     PGX_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t W = (size_t)3 * (size_t)ctx->Mpad;
+    const ScoreBatch::Resident& rb = ctx->batch.resident;
+    const size_t W = (size_t)3 * (size_t)rb.Mpad;
     PGX_TRY(ensure(ctx, ctx->g_counts, (W + 8) * 8));
     unsigned long long* blk = (unsigned long long*)ctx->g_counts.p;
     int local_fail = 0, local_rc = PGX_OK;
@@ -353,9 +357,9 @@ int pgx_score_allreduce(pgx_ctx* ctx)
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (local_rc != PGX_OK) return local_rc;     // (this rank's own failure, reported after the collective every rank was waiting in)
     if (bad) return poisoned(ctx, "pgx_score_allreduce", bad, local_fail);
-    PGX_TRY(score_acc_import(ctx, blk, ctx->M, ctx->Mpad, ctx->last_qscale, ctx->counts.as<long long>(), ctx->values.as<double>(),
+    PGX_TRY(score_acc_import(ctx, blk, rb.M, rb.Mpad, ctx->batch.last.qscale, ctx->counts.as<long long>(), ctx->values.as<double>(),
                              ctx->shared.as<double>(), ctx->stream));
-    ctx->mirror_valid = 0;   // the host mirror holds this rank's partial table
+    ctx->batch.table_reduced();   // the host mirror holds this rank's partial table
     return PGX_OK;
 }
 
@@ -366,9 +370,10 @@ int pgx_score_allreduce_begin(pgx_ctx* ctx, int slot)
 {
     if (!ctx || !ctx->comm) return fail(ctx, PGX_ERR_INVALID, "pgx_score_allreduce_begin: communicator not initialised");
     CommState* cs = ctx->comm;
-    const size_t W = (size_t)3 * (size_t)ctx->Mpad, need = W * 8;
+    const ScoreBatch::Resident& rb = ctx->batch.resident;
+    const size_t W = (size_t)3 * (size_t)rb.Mpad, need = W * 8;
     ExchangeSlot* ep = nullptr;
-    PGX_TRY(slot_prepare(ctx, "pgx_score_allreduce_begin", slot, need + 64, need + 64, &ep));
+    PGX_TRY(slot_prepare(ctx, "pgx_score_allreduce_begin", false, slot, need + 64, need + 64, &ep));
     ExchangeSlot& e = *ep;
     unsigned long long* blk = (unsigned long long*)e.stage.p;
     int local_fail = 0, local_rc = PGX_OK;
@@ -377,12 +382,12 @@ int pgx_score_allreduce_begin(pgx_ctx* ctx, int slot)
     PGX_HIP(ctx, hipStreamWaitEvent(cs->xstream, e.scored, 0));
     PGX_NCCL(ctx, g_rccl.AllReduce(blk, blk, W + 8, ncclUint64, ncclSum, cs->comm, cs->xstream));
     long long* res = (long long*)e.gathered.p;
-    PGX_TRY(score_acc_import(ctx, blk, ctx->M, ctx->Mpad, local_fail ? 1.0 : ctx->last_qscale, res, (double*)res + ctx->Mpad,
-                             (double*)res + 2 * (size_t)ctx->Mpad, cs->xstream));
-    PGX_HIP(ctx, hipMemcpyAsync(e.host, e.gathered.p, need, hipMemcpyDeviceToHost, cs->xstream));
-    PGX_HIP(ctx, hipMemcpyAsync((char*)e.host + need, blk + W, 8, hipMemcpyDeviceToHost, cs->xstream));
+    PGX_TRY(score_acc_import(ctx, blk, rb.M, rb.Mpad, local_fail ? 1.0 : ctx->batch.last.qscale, res, (double*)res + rb.Mpad,
+                             (double*)res + 2 * (size_t)rb.Mpad, cs->xstream));
+    PGX_HIP(ctx, hipMemcpyAsync(e.host.p, e.gathered.p, need, hipMemcpyDeviceToHost, cs->xstream));
+    PGX_HIP(ctx, hipMemcpyAsync((char*)e.host.p + need, blk + W, 8, hipMemcpyDeviceToHost, cs->xstream));
     PGX_HIP(ctx, hipEventRecord(e.done, cs->xstream));
-    e.M = ctx->M; e.Mpad = ctx->Mpad; e.has_compound = ctx->score_has_compound; e.busy = 1; e.reduced = 1; e.local_fail = local_fail;
+    e.M = rb.M; e.Mpad = rb.Mpad; e.has_compound = ctx->batch.last.has_compound; e.busy = 1; e.reduced = 1; e.local_fail = local_fail;
     return local_rc;     // (a failed export is reported here, AFTER the collective was entered; _end then reports the poisoned table on every rank)
 }
 
@@ -395,9 +400,9 @@ int pgx_score_allreduce_end(pgx_ctx* ctx, int slot, int exponent, int64_t* count
     ExchangeSlot& e = ctx->comm->slot[slot];
     PGX_HIP(ctx, hipEventSynchronize(e.done));
     e.busy = 0; e.reduced = 0;
-    const unsigned long long bad = *(const unsigned long long*)((const char*)e.host + (size_t)3 * (size_t)e.Mpad * 8);
+    const unsigned long long bad = *(const unsigned long long*)((const char*)e.host.p + (size_t)3 * (size_t)e.Mpad * 8);
     if (bad) return poisoned(ctx, "pgx_score_allreduce_end", bad, e.local_fail);
-    unpack_block(e.host, (size_t)e.M, (size_t)e.Mpad, e.has_compound, exponent, counts, values, shared, scores);
+    unpack_block(e.host.p, (size_t)e.M, (size_t)e.Mpad, e.has_compound, exponent, counts, values, shared, scores);
     return PGX_OK;
 }
 

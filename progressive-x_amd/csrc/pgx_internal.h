@@ -11,6 +11,7 @@
 #include "expansion_cycle.h"
 #include "move_route.h"
 #include "residuals.hip.h"
+#include "score_plan.h"
 
 namespace pgx {
 
@@ -20,6 +21,18 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// growable pinned host buffer (grow_pinned) / ... used as the staging of an asynchronous upload: the caller's array is consumed before
+// the call returns, the copies need no synchronisation, and an event guards the buffer against the next call
+struct PinnedBuf { void* p = nullptr; size_t cap = 0; };
+struct PinnedStage {
+    PinnedBuf buf;
+    hipEvent_t ev = nullptr;
+    int busy = 0;
+    int acquire(pgx_ctx* ctx, size_t bytes);       // waits for the copies of the last submission, then buf.p holds at least `bytes`
+    int submitted(pgx_ctx* ctx, hipStream_t stream);   // the copies out of buf.p are enqueued on `stream`
+    void free();
 };
 
 struct MaxflowState;  // maxflow.hip
@@ -46,12 +59,8 @@ struct pgx_ctx {
     double umax = 0.0;       // max |observed image coordinate| over all points
     double fscale = 0.0;     // max(1, max |coordinate|) over all points: isotropic pre-scaling of the minimal solvers
     double rmin = 0.0, rmax = __builtin_inf();   // pgx_set_radius_range: the sphere solver's accepted radii (context state)
-    int filter_enabled = 1;  // PGX_NO_FILTER: 1 = no rejection filter, 2 = FP64 filter only (A/B, debugging)
-    int last_score_filtered = 0;
-    int last_score_path = 0;       // 1 = chunked kernel (every pair visited), 2 = cull + group-major
-    int score_stats = 0;           // set by pgx_score_stats for one launch: work counters in stats_buf
-    int verify = 0;                // PGX_VERIFY=1: pgx_score_stats also re-decides every pair exactly and counts contradictions (score.hip)
-    pgx::DevBuf stats_buf;
+    pgx::ScoreSwitches score_sw;   // PGX_NO_FILTER, PGX_SCORE_NO_CULL, PGX_SCORE_MIRROR, PGX_VERIFY and pgx_score_debug_geometry: what plan_score reads (score_plan.h)
+    pgx::DevBuf stats_buf;         // work counters of a pgx_score_stats launch
     // spatially sorted copies for the score kernel (group-level rejection); aliases of the originals
     // when point_sort is off
     int point_sort = 0;          // 1: pts_s / pts32_s / pmax_s / comp_s hold the points in Morton order, pperm maps back
@@ -60,33 +69,19 @@ struct pgx_ctx {
     pgx::DevBuf pts_s, pts32_s, pmax_s, comp_s, pperm, gbounds, masks_s;
     pgx::DevBuf pts_g, p32_g;    // group-blocked SoA copies of the sorted rows: [group][coordinate][64] (group-major kernel)
     int setpoints_host = 0;      // PGX_SETPOINTS_HOST=1: round 1's host preprocessing in pgx_set_points (A/B, cross-check)
-    int score_dense_min = 32;    // steps with at least this many candidates of 64 are evaluated in place, not queued (PGX_SCORE_DENSE; 65 = never)
-    int score_cull_segs = 256;   // segments of groups per hypothesis word in the cull kernel (PGX_SCORE_CULL_SEGS; 8192 waves at M = 2048)
-    int score_nrep = 0;         // replicas of the integer accumulators (PGX_SCORE_NREP, multiple of 8); 0 = automatic: 8 when a group's waves share an XCD, else 1
-    int score_cull = 1;          // cull + survivor kernels instead of in-kernel group skipping (PGX_SCORE_NO_CULL=1: A/B)
-    double sp_kd_weight = 0.25;  // PGX_SP_KD_W: weight of the 3-D part against the observed pair in the k-d order (1 = box normalisation)
+    double sp_kd_weight = 0.25;  // weight of the 3-D part against the observed pair in the k-d order (1 = box normalisation); no switch sets it
     int sp_kd = 1;               // PGX_SP_KD=0: Morton order of the points of a pose problem instead of the k-d order (setpoints.hip)
     pgx::DevBuf weights_scratch; // scratch of the k-d build (64-bit keys, sort workspace, per-node extents)
-    int score_group_xcd = -1;    // PGX_SCORE_GROUP_XCD: 1 = a group's workgroups on one XCD (8x less row fetch, per-XCD accumulator replicas), 0 = part p on XCD p;
-                                 // -1 (default) = 1 for a locality-ordered batch (few hypothesis words per group have survivors), 0 otherwise (score.hip)
-    int score_split = 0;         // waves per 64-point group in the group-major kernel (PGX_SCORE_SPLIT); 0 = 8 with the spread mapping, 5 co-located (score.hip)
     pgx::DevBuf cull_lists, cull_counts;
     pgx::DevBuf gc;          // inlier/outlier graph cut: e[n] | dq[2][n] | wq[E] | labels[n]
     pgx::DevBuf gc_sel;      // ... the inliers' indices (pgx_gc_inliers): index[n] | count | select scratch
-    int score_xcd_map = 1;       // XCD-aware block mapping of the score kernel (PGX_SCORE_NO_XCD=1 disables)
-    int score_blocks_per_cu = 64;  // grid over-decomposition of the score kernel (PGX_SCORE_BLOCKS_PER_CU)
 
     // scoring
-    int M = 0, Mpad = 0, chunks = 0;
-    int64_t chunk = 0, words = 0;
-    bool have_masks = false;
-    int score_has_compound = 0;
+    // The resident hypothesis batch and what the last launch produced of it: one owner, changed only by its events (score_plan.h
+    // ScoreBatch; compiled into the CPU tests too).  Every entry point that reads results asks it whether they belong to the batch.
+    pgx::ScoreBatch batch;
     int64_t score_global_n = 0;  // pgx_score_set_global_n: the fixed-point scale of the sums is taken from max(n, this) - the ranks of a
                                  // point-sharded job (pgx_score_allreduce) then add integers of the SAME scale: bitwise the unsharded sums
-    unsigned long long* last_acc = nullptr;   // integer accumulators [nrep][3][Mpad] of the last group-major launch (device order), or nullptr
-    int last_nrep = 0;
-    double last_qscale = 0.0;
-    int last_acc_M = 0, last_acc_Mpad = 0;    // the batch the accumulators belong to (an upload / solve after the launch makes them stale)
     pgx::DevBuf models, pcnt, pval, psh, counts, values, shared, masks;
     pgx::DevBuf perm;        // perm[sorted position] = caller's hypothesis index (locality ordering, capi.hip)
     int score_sort = 1;      // PGX_NO_SORT=1 keeps the caller's order (A/B)
@@ -145,24 +140,13 @@ struct pgx_ctx {
     void* h_rb = nullptr;       // pinned ring of d2h() / sync_deliver()
     size_t h_rb_used = 0;
     std::vector<pgx::StagedCopy> rb;
-    void* h_res = nullptr;      // pinned host staging for result read-backs (pageable targets make the copies synchronous)
-    size_t h_res_cap = 0;
+    pgx::PinnedBuf h_res;       // pinned host staging for result read-backs (pageable targets make the copies synchronous): host_staging
+    pgx::PinnedStage h_models;  // pgx_score_upload's (reordered) batch + permutation
+    pgx::PinnedStage h_samples; // pgx_solve_minimal's sample indices (solve.hip upload_samples)
     // Host mirror of the score triples: score_finish_kernel also writes (count, value, shared) in the batch's device order
     // straight into this pinned, device-mapped allocation (coalesced 512 B runs over PCIe), so pgx_score_fetch needs no
-    // copy command on the stream - it waits for the kernel and un-permutes on the host (h_perm; empty = identity).
-    void* h_models = nullptr;    // pinned staging of pgx_score_upload's (reordered) batch + permutation
-    size_t h_models_cap = 0;
-    hipEvent_t ev_models = nullptr;
-    int h_models_busy = 0;
-    void* h_samples = nullptr;   // pinned staging of pgx_solve_minimal's sample indices (solve.hip upload_samples)
-    size_t h_samples_cap = 0;
-    hipEvent_t ev_samples = nullptr;
-    int h_samples_busy = 0;
-    void* h_mirror = nullptr;
-    size_t h_mirror_cap = 0;
-    int mirror_valid = 0;        // the last launch wrote the mirror
-    int score_mirror = 1;        // PGX_SCORE_MIRROR=0: read the triples back with a copy instead
-    std::vector<int> h_perm;     // host copy of `perm` for an uploaded, locality-sorted batch
+    // copy command on the stream - it waits for the kernel and un-permutes on the host (batch.unpermute()).
+    pgx::PinnedBuf h_mirror;
     pgx::DevBuf fit_scratch;  // pgx_gram: partials | result | counters | index list
     pgx::DevBuf weights;      // resident per-point weights of the weighted refits (pgx_set_weights), weights_n == n when valid
     int64_t weights_n = 0;
@@ -181,6 +165,8 @@ int ensure(pgx_ctx* ctx, DevBuf& b, size_t bytes);
 // every entry point starts with an empty list (CTX_GUARD).
 int d2h(pgx_ctx* ctx, void* dst, const void* src, size_t bytes);
 int sync_deliver(pgx_ctx* ctx);
+int grow_pinned(pgx_ctx* ctx, PinnedBuf& b, size_t bytes, unsigned flags = hipHostMallocDefault);   // b.p holds at least `bytes` (twice that when it grows; the old contents are not kept)
+void release(PinnedBuf& b);
 int host_staging(pgx_ctx* ctx, size_t bytes, void** p);   // ctx->h_res grown to at least `bytes` (pinned: a copy into it is one asynchronous command; a pageable target makes every copy a blocking one)
 void release(DevBuf& b);
 
@@ -205,11 +191,10 @@ inline int64_t quantize_lambda(double lambda) { return 2 * (int64_t)__builtin_ne
 // group bounds of the score path (score.hip consumes them, setpoints.hip / score_sort_points build them)
 constexpr double kGroupInflate = 1.00001;
 constexpr int kGroupRow = 12;  // floats per group: c[3], rho, ub, vb, ru, rv, scale, pad[3]
-constexpr int kSuper = 8;      // groups per super-group (512 points): first level of the cull kernel
 
 // launchers implemented in the .hip translation units
 int set_points_device(pgx_ctx* ctx, const ModelInfo& mi, const double* points, int64_t n);  // setpoints.hip: upload + all preprocessing
-int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks);
+int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks, bool want_counters = false);   // score.hip: plan_score -> buffers -> launches -> batch.launched
 int score_inliers_launch(pgx_ctx* ctx, int row, int32_t* index, int64_t* count);   // pointwise.hip
 // point-sharded exchange (comm.hip): the last launch's integer accumulators, replicas summed, in the caller's hypothesis order
 // ([3][Mpad] words) / counts | values | shared from such a block

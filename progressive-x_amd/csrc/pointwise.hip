@@ -357,7 +357,7 @@ int gc_labeling_launch(pgx_ctx* ctx, const double* model, double T2, double lamb
     const bool have_small = rq.pre_sync_ran;
     const int64_t inliers = flip ? rq.changed : n - rq.changed;
     if (have_small) {
-        const int* hs = (const int*)ctx->h_res;
+        const int* hs = (const int*)ctx->h_res.p;
         if (hs[0] != (int)inliers) return fail(ctx, PGX_ERR_INVALID, "pgx_gc_inliers (internal): %d indices for %lld inliers", hs[0], (long long)inliers);
         memcpy(flags, hs + 1, (size_t)inliers * sizeof(int32_t));
         if (count) *count = inliers;
@@ -397,12 +397,15 @@ __global__ __launch_bounds__(kPwBlock) void mask_flags_kernel(const unsigned lon
 int score_inliers_launch(pgx_ctx* ctx, int row, int32_t* index, int64_t* count)
 {
     const int64_t n = ctx->n;
-    if (!ctx->have_masks || ctx->M <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score_inliers: the last launch produced no masks");
-    if (row < 0 || row >= ctx->M) return fail(ctx, PGX_ERR_INVALID, "pgx_score_inliers: row %d of %d", row, ctx->M);
+    const ScoreBatch& sb = ctx->batch;
+    if (sb.mask_rows() == ScoreTable::None) return fail(ctx, PGX_ERR_INVALID, "pgx_score_inliers: the last launch produced no masks");
+    if (sb.mask_rows() == ScoreTable::Changed)
+        return fail(ctx, PGX_ERR_INVALID, "pgx_score_inliers: the hypothesis batch (or the points) changed since the last launch: its mask rows belong to no resident batch - launch again");
+    if (row < 0 || row >= sb.resident.M) return fail(ctx, PGX_ERR_INVALID, "pgx_score_inliers: row %d of %d", row, sb.resident.M);
     if (n <= kCompactSmall) {   // one launch, one copy, one synchronisation
-        PGX_TRY(compact_small_enqueue<true>(ctx, ctx->masks.as<unsigned long long>() + (size_t)row * (size_t)ctx->words, nullptr, n));
+        PGX_TRY(compact_small_enqueue<true>(ctx, ctx->masks.as<unsigned long long>() + (size_t)row * (size_t)sb.last.words, nullptr, n));
         PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const int* hs = (const int*)ctx->h_res;
+        const int* hs = (const int*)ctx->h_res.p;
         memcpy(index, hs + 1, (size_t)hs[0] * sizeof(int32_t));
         *count = hs[0];
         return PGX_OK;
@@ -417,7 +420,7 @@ int score_inliers_launch(pgx_ctx* ctx, int row, int32_t* index, int64_t* count)
     int* d_num = (int*)((char*)ctx->gc_sel.p + 2 * arr);
     void* d_temp = (void*)((char*)ctx->gc_sel.p + 2 * arr + 256);
     hipLaunchKernelGGL(mask_flags_kernel, dim3((unsigned)((n + kPwBlock - 1) / kPwBlock)), dim3(kPwBlock), 0, ctx->stream,
-                       ctx->masks.as<unsigned long long>() + (size_t)row * (size_t)ctx->words, n, d_flags);
+                       ctx->masks.as<unsigned long long>() + (size_t)row * (size_t)sb.last.words, n, d_flags);
     PGX_HIP(ctx, hipGetLastError());
     PGX_HIP(ctx, hipcub::DeviceSelect::Flagged(d_temp, temp_bytes, ids, d_flags, d_sel, d_num, (int)n, ctx->stream));
     int num = 0;

@@ -12,6 +12,8 @@
 
 #include <type_traits>
 
+#include "score_plan.h"   // GroupBound: the planner of a scoring launch reads it too, without HIP
+
 namespace pgx {
 
 enum ModelType : int {
@@ -22,14 +24,6 @@ enum ModelType : int {
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
 __device__ __forceinline__ double cv_max(double a, double b) { return a < b ? b : a; }
 __device__ __forceinline__ double cv_min(double a, double b) { return a > b ? b : a; }
-
-// What the group bound of the sorted points is made of (setpoints.hip builds the rows, score.hip's cull kernel tests them).
-enum GroupBound : int {
-    kBoundBox,        // box of the observed pair + box and ball of the coordinates the projective map multiplies
-    kBoundBoxAll,     // box of all coordinates (Sampson)
-    kBoundBall,       // ball of all coordinates about the box centre (D = 2 or 3)
-    kBoundVanishing   // rows of the normalised segment features
-};
 
 // Residual<MT> is the one description of a model type: every per-type fact the library needs is a member here, and
 // with_model_type() below is the one list of types.  Besides the two residual functions:

@@ -22,7 +22,7 @@
 
 namespace pgx {
 
-constexpr int kScoreBlock = 256;
+// (kScoreBlock = 256, hypotheses per workgroup of the chunked kernel: score_plan.h)
 
 // FILT: 0 = no filter, 1 = FP64 filter, 2 = FP32 pre-filter
 template <int MT, bool MASK, int FILT>
@@ -600,14 +600,14 @@ __global__ __launch_bounds__(256) void score_acc_import_kernel(const unsigned lo
 
 int score_acc_export(pgx_ctx* ctx, unsigned long long* out, hipStream_t stream)
 {
-    if (ctx->last_acc != nullptr && (ctx->last_acc_M != ctx->M || ctx->last_acc_Mpad != ctx->Mpad))
-        return fail(ctx, PGX_ERR_INVALID, "integer accumulators are stale: the batch changed (upload / solve) since the last launch (%d of %d then, %d of %d now)",
-                    ctx->last_acc_M, ctx->last_acc_Mpad, ctx->M, ctx->Mpad);
-    if (ctx->last_acc == nullptr || ctx->last_score_path != 2)
+    const ScoreBatch& b = ctx->batch;
+    if (b.acc_stale())
+        return fail(ctx, PGX_ERR_INVALID, "integer accumulators are stale: the batch changed (upload / solve) since the last launch");
+    if (!b.acc_exportable())
         return fail(ctx, PGX_ERR_INVALID, "point-sharded exchange: the last launch did not run the group-major path (integer accumulators); "
                                           "it needs sorted points, the f32 filter and the cull (the defaults)");
-    hipLaunchKernelGGL(score_acc_export_kernel, dim3((unsigned)((ctx->Mpad + 255) / 256)), dim3(256), 0, stream, ctx->last_acc, ctx->M, ctx->Mpad,
-                       ctx->last_nrep, ctx->perm.as<int>(), out);
+    hipLaunchKernelGGL(score_acc_export_kernel, dim3((unsigned)((b.resident.Mpad + 255) / 256)), dim3(256), 0, stream, b.last.acc, b.resident.M, b.resident.Mpad,
+                       b.last.nrep, ctx->perm.as<int>(), out);
     PGX_HIP(ctx, hipGetLastError());
     return PGX_OK;
 }
@@ -652,179 +652,126 @@ __global__ __launch_bounds__(64 * kReduceWaves) void score_reduce_kernel(
     }
 }
 
-template <int MT, bool MASK, int FILT>
-static void score_launch_one(pgx_ctx* ctx, double T2, int has_compound, double guard, double guard32 = 0.0)
+// What plan_score (score_plan.h) needs to know of a model type.
+template <int MT>
+constexpr ScoreTraits score_traits()
 {
-    const unsigned groups = (unsigned)(ctx->Mpad / kScoreBlock);
-    dim3 grid(groups, (unsigned)ctx->chunks);
-    if (ctx->score_xcd_map) grid = dim3(groups * (((unsigned)ctx->chunks + 7u) / 8u * 8u), 1);
+    return ScoreTraits{Filter<MT>::enabled, Filter32<MT>::enabled, Residual<MT>::bound, std::is_base_of_v<Filter32<kHomography>, Filter32<MT>>};
+}
+
+// the planner tells the types apart by these traits alone (the automatic split: poses 5, vanishing points and Sampson 16)
+static_assert(score_traits<kPnP>().bound == kBoundBox && !score_traits<kPnP>().homography, "the only box-bounded type outside the homography family");
+static_assert(score_traits<kHomography>().homography && score_traits<kHomographySym>().homography && !score_traits<kLine2D>().homography, "");
+static_assert(score_traits<kVanishingPoint>().bound == kBoundVanishing && score_traits<kFundamental>().bound == kBoundBoxAll, "");
+
+template <int MT, bool MASK, int FILT>
+static void score_launch_one(pgx_ctx* ctx, const ScorePlan& pl, double T2, int has_compound)
+{
+    const ScoreBatch::Resident& rb = ctx->batch.resident;
+    const unsigned groups = (unsigned)(rb.Mpad / kScoreBlock);
+    dim3 grid(groups, (unsigned)pl.chunks);
+    if (kScoreXcdMap) grid = dim3(groups * (((unsigned)pl.chunks + 7u) / 8u * 8u), 1);
     const bool srt = ctx->point_sort != 0;  // spatially sorted copies (score_sort_points); masks come out in sorted bit order
     hipLaunchKernelGGL((score_kernel<MT, MASK, FILT>), grid, dim3(kScoreBlock), 0, ctx->stream,
-                       (srt ? ctx->pts_s : ctx->pts).as<double>(), ctx->n, ctx->models.as<double>(), ctx->M, ctx->Mpad, T2,
-                       (srt ? ctx->comp_s : ctx->comp).as<double>(), has_compound, ctx->chunk,
-                       (srt ? ctx->pmax_s : ctx->pmax).as<double>(), guard, (srt ? ctx->pts32_s : ctx->pts32).as<float>(), guard32,
+                       (srt ? ctx->pts_s : ctx->pts).as<double>(), ctx->n, ctx->models.as<double>(), rb.M, rb.Mpad, T2,
+                       (srt ? ctx->comp_s : ctx->comp).as<double>(), has_compound, pl.chunk,
+                       (srt ? ctx->pmax_s : ctx->pmax).as<double>(), pl.guard, (srt ? ctx->pts32_s : ctx->pts32).as<float>(), FILT == 2 ? pl.guard32 : 0.0,
                        ctx->pcnt.as<unsigned>(), ctx->pval.as<double>(), ctx->psh.as<double>(),
                        MASK ? (srt ? ctx->masks_s : ctx->masks).as<unsigned long long>() : (unsigned long long*)nullptr,
-                       ctx->words, ctx->perm.as<int>(), ctx->chunks, ctx->score_xcd_map,
+                       pl.words, ctx->perm.as<int>(), pl.chunks, kScoreXcdMap,
                        (srt && FILT == 2) ? ctx->gbounds.as<float>() : (const float*)nullptr);
 }
 
+// cull, then score group-major, then finish: the plan's path 2.  *acc_out: the integer accumulators the launch leaves behind
 template <int MT>
-static int score_dispatch(pgx_ctx* ctx, double T2, int has_compound, int want_masks)
+static int score_group_path(pgx_ctx* ctx, const ScorePlan& pl, double T2, int has_compound, int want_masks, unsigned long long** acc_out)
 {
-    // filter guard (see Filter<> above): usable iff Umax / T <= 2^28 and everything is finite
-    const double T = std::sqrt(T2);
-    double guard = 0.0;
-    bool filt = Filter<MT>::enabled && ctx->filter_enabled && T > 0.0 && std::isfinite(T) && std::isfinite(ctx->umax) &&
-                ctx->umax <= T * 268435456.0;
-    if (filt) {
-        guard = 4.5 * 1.1102230246251565e-16 * (1.0 + ctx->umax + T) * 16777216.0 / T;
-        filt = std::isfinite(guard);
+    const int M = ctx->batch.resident.M, Mpad = ctx->batch.resident.Mpad;
+    const int groups = pl.groups, W = pl.W, nrep = pl.nrep, split = pl.split, xcd_local = pl.group_xcd ? 1 : 0;
+    PGX_TRY(ensure(ctx, ctx->cull_lists, (size_t)groups * W * sizeof(unsigned long long)));             // keep[g][w]
+    PGX_TRY(ensure(ctx, ctx->cull_counts, (size_t)Mpad * (kHypRow * sizeof(float) + (size_t)nrep * 3 * sizeof(long long) + Residual<MT>::P * sizeof(double))));  // hyp32 | acc[nrep] | models_t
+    float* hyp32 = ctx->cull_counts.as<float>();
+    unsigned long long* acc = (unsigned long long*)(ctx->cull_counts.as<char>() + (size_t)Mpad * kHypRow * sizeof(float));
+    double* models_t = (double*)(acc + (size_t)nrep * 3 * (size_t)Mpad);
+    const double* pts_g = ctx->pts_g.p ? ctx->pts_g.as<double>() : (const double*)nullptr;   // group-blocked SoA copies of the rows
+    const float* p32_g = ctx->pts_g.p ? ctx->p32_g.as<float>() : (const float*)nullptr;
+    unsigned long long* stats = nullptr;
+    if (pl.counters) {
+        PGX_TRY(ensure(ctx, ctx->stats_buf, 8 * sizeof(unsigned long long)));
+        stats = ctx->stats_buf.as<unsigned long long>();
     }
-    // FP32 pre-filter: tau = 2^-10, needs Umax / T <= tau * 2^24 = 2^14
-    double guard32 = 0.0;
-    bool filt32 = filt && ctx->filter_enabled == 1 && ctx->umax <= T * 16384.0;
-    if (filt32) {
-        guard32 = 5.5 * 5.9604644775390625e-8 * (1.0 + ctx->umax + T) * 1024.0 / T;
-        filt32 = std::isfinite(guard32) && guard32 < 1e30;
+    long long* mirror = nullptr;
+    if (pl.mirror) {
+        const size_t need = (size_t)Mpad * 24;
+        if (ctx->h_mirror.cap < need) PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier launch may still be writing the old one
+        PGX_TRY(grow_pinned(ctx, ctx->h_mirror, need, hipHostMallocMapped | hipHostMallocCoherent));
+        mirror = (long long*)ctx->h_mirror.p;
     }
-    if constexpr (Residual<MT>::bound == kBoundVanishing)   // its own trust test per pair, no global guard (Filter32<kVanishingPoint>)
-        filt32 = ctx->filter_enabled == 1 && T > 0.0 && std::isfinite(T) && T2 < 1e30;
-    if constexpr (std::is_base_of_v<Filter32<kHomography>, Filter32<MT>>)   // explicit per-pair error terms, no global guard (Filter32<kHomography>)
-        filt32 = ctx->filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24;
-    if constexpr (Residual<MT>::bound == kBoundBall) {   // per-pair error term, no global guard; T'' must be an ordinary f32
-        filt32 = ctx->filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24 && std::isfinite(ctx->fscale);
-        guard32 = ctx->fscale;             // Filter32<kLine2D / kPlane3D / kSphere3D>::prep: overflow guard (fscale >= 1)
+    if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[0], ctx->stream));
+    // (the accumulators are zeroed by the cull kernel, which runs before their first use)
+    hipLaunchKernelGGL((score_cull_kernel<MT>), dim3((unsigned)((W + kCullWaves - 1) / kCullWaves), pl.cull_segs), dim3(64 * kCullWaves), 0,
+                       ctx->stream, ctx->models.as<double>(), M, T2, pl.guard32, ctx->gbounds.as<float>(), groups, pl.gps, W,
+                       ctx->cull_lists.as<unsigned long long>(), hyp32, models_t, acc, pl.zero_words);
+    PGX_HIP(ctx, hipGetLastError());
+    if (ctx->score_profile) PGX_HIP(ctx, hipEventRecord(ctx->kev[1], ctx->stream));
+    auto group_launch = [&](auto kernel, unsigned long long* masks_s) {
+        hipLaunchKernelGGL(kernel, dim3(pl.gblocks), dim3(64 * kGroupWaves), 0, ctx->stream,
+                           ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->comp_s.as<double>(), ctx->n, groups,
+                           ctx->models.as<double>(), W, T2, has_compound, ctx->cull_lists.as<unsigned long long>(), hyp32,
+                           pl.qscale, acc, Mpad, masks_s, pl.words, ctx->perm.as<int>(), split, xcd_local, models_t,
+                           stats, pts_g, p32_g, nrep, pl.dense_min);
+    };
+    if (want_masks) {
+        PGX_HIP(ctx, hipMemsetAsync(ctx->masks_s.p, 0, (size_t)M * (size_t)pl.words * sizeof(uint64_t), ctx->stream));
+        group_launch(score_group_kernel<MT, true>, ctx->masks_s.as<unsigned long long>());
+    } else if (pl.counters) {  // pgx_score_stats: the same launch with work counters (never timed)
+        PGX_HIP(ctx, hipMemsetAsync(ctx->stats_buf.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
+        group_launch(score_group_kernel<MT, false, true>, nullptr);
+        if (pl.verify)   // PGX_VERIFY=1: stats_buf[4..6] = inliers the group bound removed / the f32 filter removed / all inlier pairs
+            hipLaunchKernelGGL((score_verify_kernel<MT>), dim3((unsigned)groups, (unsigned)W), dim3(64), 0, ctx->stream,
+                               ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->n, ctx->models.as<double>(), M, W, T2,
+                               ctx->cull_lists.as<unsigned long long>(), hyp32, stats + 4);
+    } else {
+        group_launch(score_group_kernel<MT, false>, nullptr);
     }
-    if constexpr (Residual<MT>::bound == kBoundBoxAll) {    // likewise; the bounds on T keep T2 * D~^2 (D~ >= 1e-12) inside the f32 normal range
-        filt32 = ctx->filter_enabled == 1 && T2 > 1e-12 && T2 < 1e12 && std::isfinite(ctx->fscale);
-        guard32 = ctx->fscale * ctx->fscale;   // Filter32<kFundamental>::prep: overflow guard of the f32 terms (fscale >= 1)
-    }
-    // every filter's proof takes the exact path's f64 arithmetic as overflow-free: coordinates up to 1e30 with the
-    // per-hypothesis band of pow2_normaliser keep it so
-    if (!(ctx->fscale <= 1e30)) filt = filt32 = false;
-    ctx->last_score_filtered = filt32 ? 2 : (filt ? 1 : 0);
-    if constexpr (Filter32<MT>::enabled) {
-        if (filt32 && ctx->point_sort && ctx->score_cull) {
-            // ---- cull, then score group-major
-            const int groups = (int)((ctx->n + 63) / 64);
-            const int kCullSegs = ctx->score_cull_segs;
-            const int gps = ((groups + kCullSegs - 1) / kCullSegs + kSuper - 1) / kSuper * kSuper;  // whole super-groups per segment
-            const int W = ctx->Mpad / 64;
-            PGX_TRY(ensure(ctx, ctx->cull_lists, (size_t)groups * W * sizeof(unsigned long long)));             // keep[g][w]
-            // Where the waves of a group run.  Part p of every group on XCD p spreads a group's work over the chip but makes every
-            // XCD fetch every row; all parts of a group on one XCD fetches a row once (FETCH_SIZE 8x lower) and needs a replica of
-            // the accumulators per XCD.  Measured on the final code: the co-located mapping is 9 % faster (group kernel 215 -> 196 us)
-            // on a locality-ordered batch, where only a few of a group's hypothesis words have survivors, and 19 % slower (step
-            // 0.42 -> 0.50 ms) on a batch in arbitrary order, where all of them do - so the order of the batch decides.
-            const int group_xcd = ctx->score_group_xcd >= 0 ? ctx->score_group_xcd : (ctx->h_perm.empty() ? 0 : 1);
-            const int nrep = ctx->score_nrep > 0 ? ctx->score_nrep : (group_xcd ? 8 : 1);
-            const int xcd_local = group_xcd ? 1 : 0;   // per-XCD replicas of the accumulators when a group's waves share an XCD
-            PGX_TRY(ensure(ctx, ctx->cull_counts, (size_t)ctx->Mpad * (kHypRow * sizeof(float) + (size_t)nrep * 3 * sizeof(long long) + Residual<MT>::P * sizeof(double))));  // hyp32 | acc[nrep] | models_t
-            float* hyp32 = ctx->cull_counts.as<float>();
-            unsigned long long* acc = (unsigned long long*)(ctx->cull_counts.as<char>() + (size_t)ctx->Mpad * kHypRow * sizeof(float));
-            double* models_t = (double*)(acc + (size_t)nrep * 3 * (size_t)ctx->Mpad);
-            const double* pts_g = ctx->pts_g.p ? ctx->pts_g.as<double>() : (const double*)nullptr;   // group-blocked SoA copies of the rows
-            const float* p32_g = ctx->pts_g.p ? ctx->p32_g.as<float>() : (const float*)nullptr;
-            int lg = 0;
-            const int64_t n_scale = ctx->score_global_n > ctx->n ? ctx->score_global_n : ctx->n;   // pgx_score_set_global_n
-            while (((int64_t)1 << lg) < n_scale + 1) ++lg;
-            const double qscale = std::ldexp(1.0, 62 - lg < 50 ? 62 - lg : 50);  // every sum is <= n < 2^lg; terms < 2^51 (to_fixed)
-            // the accumulators are zeroed by the cull kernel, which runs before their first use
-            const int64_t zero_words = (int64_t)nrep * ctx->Mpad * 3;
-            if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[0], ctx->stream));
-            hipLaunchKernelGGL((score_cull_kernel<MT>), dim3((unsigned)((W + kCullWaves - 1) / kCullWaves), kCullSegs), dim3(64 * kCullWaves), 0,
-                               ctx->stream, ctx->models.as<double>(), ctx->M, T2, guard32, ctx->gbounds.as<float>(), groups, gps, W,
-                               ctx->cull_lists.as<unsigned long long>(), hyp32, models_t, acc, zero_words);
-            PGX_HIP(ctx, hipGetLastError());
-            if (ctx->score_profile) PGX_HIP(ctx, hipEventRecord(ctx->kev[1], ctx->stream));
-            // waves per group.  Spread mapping: 8 (part p = XCD p).  Co-located mapping: 5 - fewer, longer waves load a group's rows
-            // less often, and an ODD count keeps the heavy workgroups (a locality-ordered batch puts a group's survivors into two or
-            // three neighbouring hypothesis words) from falling into a period of the dispatch order: group kernel 169 (8), 157 (4),
-            // 146 (6), 140 (2) against 135-140 us (1, 3, 5, 7) on the metric batch.
-            // (pose problems take 5 with the spread mapping as well: RANSAC-like batch 0.371 -> 0.353 ms; Sampson and vanishing-point
-            // batches lose 15-20 % there and keep 8)
-            // Round 6 (scripts/sweep_vp_geometry.py, after the Hough ordering of the segments): vanishing-point and Sampson batches take 16 -
-            // group kernel 301 -> 280 us and 123 -> 114 us against 8 (12: 284 / 118, 24: 284 / 115, 32: 296 / 119).
-            const int split_cfg = ctx->score_split > 0 ? ctx->score_split
-                                  : ((group_xcd || MT == kPnP) ? 5 : ((MT == kVanishingPoint || MT == kFundamental) ? 16 : 8));
-            const int split = split_cfg < W ? split_cfg : W;
-            const unsigned gblocks = (xcd_local & 1) ? (unsigned)((int64_t)((groups + 7) / 8) * 8 * split) : (unsigned)((int64_t)groups * split);
-            if (want_masks) {
-                PGX_HIP(ctx, hipMemsetAsync(ctx->masks_s.p, 0, (size_t)ctx->M * (size_t)ctx->words * sizeof(uint64_t), ctx->stream));
-                hipLaunchKernelGGL((score_group_kernel<MT, true>), dim3(gblocks), dim3(64 * kGroupWaves), 0, ctx->stream,
-                                   ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->comp_s.as<double>(), ctx->n, groups,
-                                   ctx->models.as<double>(), W, T2, has_compound, ctx->cull_lists.as<unsigned long long>(), hyp32,
-                                   qscale, acc, ctx->Mpad, ctx->masks_s.as<unsigned long long>(), ctx->words, ctx->perm.as<int>(), split, xcd_local, models_t,
-                                   (unsigned long long*)nullptr, pts_g, p32_g, nrep, 65);
-            } else if (ctx->score_stats) {  // pgx_score_stats: the same launch with work counters (never timed)
-                PGX_TRY(ensure(ctx, ctx->stats_buf, 8 * sizeof(unsigned long long)));
-                PGX_HIP(ctx, hipMemsetAsync(ctx->stats_buf.p, 0, 8 * sizeof(unsigned long long), ctx->stream));
-                hipLaunchKernelGGL((score_group_kernel<MT, false, true>), dim3(gblocks), dim3(64 * kGroupWaves), 0, ctx->stream,
-                                   ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->comp_s.as<double>(), ctx->n, groups,
-                                   ctx->models.as<double>(), W, T2, has_compound, ctx->cull_lists.as<unsigned long long>(), hyp32,
-                                   qscale, acc, ctx->Mpad, (unsigned long long*)nullptr, ctx->words, ctx->perm.as<int>(), split, xcd_local, models_t,
-                                   ctx->stats_buf.as<unsigned long long>(), pts_g, p32_g, nrep, ctx->score_dense_min);
-                if (ctx->verify)   // PGX_VERIFY=1: stats_buf[4..6] = inliers the group bound removed / the f32 filter removed / all inlier pairs
-                    hipLaunchKernelGGL((score_verify_kernel<MT>), dim3((unsigned)groups, (unsigned)W), dim3(64), 0, ctx->stream,
-                                       ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->n, ctx->models.as<double>(), ctx->M, W, T2,
-                                       ctx->cull_lists.as<unsigned long long>(), hyp32, ctx->stats_buf.as<unsigned long long>() + 4);
-            } else {
-                hipLaunchKernelGGL((score_group_kernel<MT, false>), dim3(gblocks), dim3(64 * kGroupWaves), 0, ctx->stream,
-                                   ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->comp_s.as<double>(), ctx->n, groups,
-                                   ctx->models.as<double>(), W, T2, has_compound, ctx->cull_lists.as<unsigned long long>(), hyp32,
-                                   qscale, acc, ctx->Mpad, (unsigned long long*)nullptr, ctx->words, ctx->perm.as<int>(), split, xcd_local, models_t,
-                                   (unsigned long long*)nullptr, pts_g, p32_g, nrep, ctx->score_dense_min);
-            }
-            PGX_HIP(ctx, hipGetLastError());
-            if (ctx->score_profile) PGX_HIP(ctx, hipEventRecord(ctx->kev[2], ctx->stream));
-            if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[4], ctx->stream));
-            long long* mirror = nullptr;
-            if (ctx->score_mirror && !want_masks) {
-                const size_t need = (size_t)ctx->Mpad * 24;
-                if (ctx->h_mirror_cap < need) {
-                    PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier launch may still be writing the old one
-                    if (ctx->h_mirror) (void)hipHostFree(ctx->h_mirror);
-                    ctx->h_mirror = nullptr; ctx->h_mirror_cap = 0;
-                    PGX_HIP(ctx, hipHostMalloc(&ctx->h_mirror, need * 2, hipHostMallocMapped | hipHostMallocCoherent));
-                    ctx->h_mirror_cap = need * 2;
-                }
-                mirror = (long long*)ctx->h_mirror;
-            }
-            hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((ctx->M + 255) / 256)), dim3(256), 0, ctx->stream, acc, ctx->M,
-                               ctx->Mpad, qscale, ctx->perm.as<int>(), ctx->counts.as<long long>(), ctx->values.as<double>(),
-                               ctx->shared.as<double>(), nrep, mirror);
-            PGX_HIP(ctx, hipGetLastError());
-            ctx->mirror_valid = mirror != nullptr;
-            ctx->last_acc = acc; ctx->last_nrep = nrep; ctx->last_qscale = qscale; ctx->last_acc_M = ctx->M; ctx->last_acc_Mpad = ctx->Mpad;
-            if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[3], ctx->stream));
-            ctx->last_score_path = 2;
-            return PGX_OK;
-        }
-    }
-    ctx->last_score_path = 1;
-    ctx->last_acc = nullptr;
+    PGX_HIP(ctx, hipGetLastError());
+    if (ctx->score_profile) PGX_HIP(ctx, hipEventRecord(ctx->kev[2], ctx->stream));
+    if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[4], ctx->stream));
+    hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, acc, M,
+                       Mpad, pl.qscale, ctx->perm.as<int>(), ctx->counts.as<long long>(), ctx->values.as<double>(),
+                       ctx->shared.as<double>(), nrep, mirror);
+    PGX_HIP(ctx, hipGetLastError());
+    if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[3], ctx->stream));
+    *acc_out = acc;
+    return PGX_OK;
+}
+
+// the chunked kernel, then the reduction of its partials: the plan's path 1
+template <int MT>
+static int score_chunked_path(pgx_ctx* ctx, const ScorePlan& pl, double T2, int has_compound, int want_masks)
+{
+    const int M = ctx->batch.resident.M, Mpad = ctx->batch.resident.Mpad;
     if (ctx->score_profile) PGX_HIP(ctx, hipEventRecord(ctx->kev[0], ctx->stream));
     if constexpr (Filter<MT>::enabled) {
         if (want_masks) {
-            if (filt32) score_launch_one<MT, true, 2>(ctx, T2, has_compound, guard, guard32);
-            else if (filt) score_launch_one<MT, true, 1>(ctx, T2, has_compound, guard);
-            else score_launch_one<MT, true, 0>(ctx, T2, has_compound, guard);
+            if (pl.filter == 2) score_launch_one<MT, true, 2>(ctx, pl, T2, has_compound);
+            else if (pl.filter == 1) score_launch_one<MT, true, 1>(ctx, pl, T2, has_compound);
+            else score_launch_one<MT, true, 0>(ctx, pl, T2, has_compound);
         } else {
-            if (filt32) score_launch_one<MT, false, 2>(ctx, T2, has_compound, guard, guard32);
-            else if (filt) score_launch_one<MT, false, 1>(ctx, T2, has_compound, guard);
-            else score_launch_one<MT, false, 0>(ctx, T2, has_compound, guard);
+            if (pl.filter == 2) score_launch_one<MT, false, 2>(ctx, pl, T2, has_compound);
+            else if (pl.filter == 1) score_launch_one<MT, false, 1>(ctx, pl, T2, has_compound);
+            else score_launch_one<MT, false, 0>(ctx, pl, T2, has_compound);
         }
     } else {
-        if (want_masks) score_launch_one<MT, true, 0>(ctx, T2, has_compound, guard);
-        else score_launch_one<MT, false, 0>(ctx, T2, has_compound, guard);
+        if (want_masks) score_launch_one<MT, true, 0>(ctx, pl, T2, has_compound);
+        else score_launch_one<MT, false, 0>(ctx, pl, T2, has_compound);
     }
     PGX_HIP(ctx, hipGetLastError());
     if (ctx->score_profile) PGX_HIP(ctx, hipEventRecord(ctx->kev[1], ctx->stream));
     if (ctx->score_profile >= 2) { PGX_HIP(ctx, hipEventRecord(ctx->kev[2], ctx->stream)); PGX_HIP(ctx, hipEventRecord(ctx->kev[4], ctx->stream)); }
-    hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)((ctx->M + 63) / 64)), dim3(64 * kReduceWaves), 0,
+    hipLaunchKernelGGL(score_reduce_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64 * kReduceWaves), 0,
                        ctx->stream, ctx->pcnt.as<unsigned>(), ctx->pval.as<double>(), ctx->psh.as<double>(),
-                       ctx->chunks, ctx->Mpad, ctx->M, ctx->perm.as<int>(), ctx->counts.as<long long>(),
+                       pl.chunks, Mpad, M, ctx->perm.as<int>(), ctx->counts.as<long long>(),
                        ctx->values.as<double>(), ctx->shared.as<double>());
     PGX_HIP(ctx, hipGetLastError());
     if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[3], ctx->stream));
@@ -983,45 +930,26 @@ int score_sort_points(pgx_ctx* ctx, const ModelInfo& mi, const double* points, c
     return PGX_OK;
 }
 
-static int score_launch_typed(pgx_ctx* ctx, double T2, int has_compound, int want_masks);
-
-// Chooses the point chunking so that the grid has >= ~8 blocks per CU (all 32 wave slots of every CU filled)
-// while chunks stay multiples of 64 points (mask words never straddle blocks).
-int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks)
+// plan (score_plan.h) -> buffers -> launches -> one event on the batch's owner.  A refused call changes nothing; an accepted one that
+// fails midway (an allocation) tells the owner so.
+template <int MT>
+static int score_launch_typed(pgx_ctx* ctx, double T2, int has_compound, int want_masks, bool want_counters)
 {
-    ctx->mirror_valid = 0;   // set by the path whose last kernel writes the host mirror
-    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score: points not set");
-    if (ctx->M <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score: no hypotheses uploaded");
-    const int groups = ctx->Mpad / kScoreBlock;
-    // Work per (hypothesis, point) pair is data dependent (exact path only for candidates), so the grid is over-
-    // decomposed: ~blocks_per_cu blocks per CU keep the tail behind the slowest block short.
-    const int target_blocks = (ctx->cu_count > 0 ? ctx->cu_count : 256) * ctx->score_blocks_per_cu;
-    int64_t chunks = (target_blocks + groups - 1) / groups;
-    int64_t chunk = (ctx->n + chunks - 1) / chunks;
-    chunk = ((chunk + 63) / 64) * 64;
-    if (chunk < 64) chunk = 64;
-    if (chunk > 65472) chunk = 65472;  // queue entries of the deferred kernel are 16-bit offsets into the chunk
-    chunks = (ctx->n + chunk - 1) / chunk;
-    if (chunks > 65535) {  // gridDim.y limit
-        chunks = 65535;
-        chunk = (((ctx->n + chunks - 1) / chunks + 63) / 64) * 64;
-        chunks = (ctx->n + chunk - 1) / chunk;
-    }
-    ctx->chunk = chunk;
-    ctx->chunks = (int)chunks;
-    ctx->words = (ctx->n + 63) / 64;
-    const size_t np = (size_t)chunks * (size_t)ctx->Mpad;
+    const ScoreBatch::Resident& rb = ctx->batch.resident;
+    const ScorePlan pl = plan_score(score_traits<MT>(), ctx->score_sw, ctx->cu_count, ctx->n, rb.M, rb.Mpad, rb.ordered, ctx->point_sort != 0, T2,
+                                    ctx->umax, ctx->fscale, ctx->score_global_n, want_masks != 0, want_counters);
+    const size_t np = (size_t)pl.chunks * (size_t)rb.Mpad;
     PGX_TRY(ensure(ctx, ctx->pcnt, np * sizeof(unsigned)));
     PGX_TRY(ensure(ctx, ctx->pval, np * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->psh, np * sizeof(double)));
     // counts | values | shared live in ONE allocation (values / shared are views into it): pgx_score_fetch brings all three
     // back with a single copy (three small copies cost ~5 us each on the critical path of a 0.3 ms step)
-    PGX_TRY(ensure(ctx, ctx->counts, (size_t)3 * ctx->Mpad * sizeof(long long)));
-    ctx->values.p = ctx->counts.as<char>() + (size_t)ctx->Mpad * 8;
-    ctx->shared.p = ctx->counts.as<char>() + (size_t)2 * ctx->Mpad * 8;
+    PGX_TRY(ensure(ctx, ctx->counts, (size_t)3 * rb.Mpad * sizeof(long long)));
+    ctx->values.p = ctx->counts.as<char>() + (size_t)rb.Mpad * 8;
+    ctx->shared.p = ctx->counts.as<char>() + (size_t)2 * rb.Mpad * 8;
     ctx->values.cap = ctx->shared.cap = 0;  // not owned
-    if (want_masks) PGX_TRY(ensure(ctx, ctx->masks, (size_t)ctx->M * (size_t)ctx->words * sizeof(uint64_t)));
-    ctx->have_masks = want_masks != 0;
+    const size_t mask_bytes = (size_t)rb.M * (size_t)pl.words * sizeof(uint64_t);
+    if (want_masks) PGX_TRY(ensure(ctx, ctx->masks, mask_bytes));
     if (ctx->point_sort) {
         if (has_compound && ctx->comp_dirty) {  // the kernel reads the compound vector in sorted point order
             hipLaunchKernelGGL(gather_f64_kernel, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream,
@@ -1029,25 +957,33 @@ int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks)
             PGX_HIP(ctx, hipGetLastError());
             ctx->comp_dirty = 0;
         }
-        if (want_masks) PGX_TRY(ensure(ctx, ctx->masks_s, (size_t)ctx->M * (size_t)ctx->words * sizeof(uint64_t)));
+        if (want_masks) PGX_TRY(ensure(ctx, ctx->masks_s, mask_bytes));
     }
-    const int rc = score_launch_typed(ctx, T2, has_compound, want_masks);
-    if (rc == PGX_OK && ctx->point_sort && want_masks) {
-        const int64_t total = (int64_t)ctx->M * ctx->words;
-        PGX_HIP(ctx, hipMemsetAsync(ctx->masks.p, 0, (size_t)total * sizeof(uint64_t), ctx->stream));
+    unsigned long long* acc = nullptr;
+    if constexpr (Filter32<MT>::enabled) {
+        if (pl.path == 2) PGX_TRY(score_group_path<MT>(ctx, pl, T2, has_compound, want_masks, &acc));
+    }
+    if (pl.path != 2) PGX_TRY(score_chunked_path<MT>(ctx, pl, T2, has_compound, want_masks));
+    if (ctx->point_sort && want_masks) {
+        const int64_t total = (int64_t)rb.M * pl.words;
+        PGX_HIP(ctx, hipMemsetAsync(ctx->masks.p, 0, mask_bytes, ctx->stream));
         hipLaunchKernelGGL(mask_unpermute_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ctx->masks_s.as<unsigned long long>(), ctx->pperm.as<int>(), ctx->n, ctx->words, ctx->M,
+                           ctx->masks_s.as<unsigned long long>(), ctx->pperm.as<int>(), ctx->n, pl.words, rb.M,
                            ctx->masks.as<unsigned long long>());
         PGX_HIP(ctx, hipGetLastError());
     }
-    return rc;
+    ctx->batch.launched(pl, has_compound != 0, want_masks != 0, acc);
+    return PGX_OK;
 }
 
-static int score_launch_typed(pgx_ctx* ctx, double T2, int has_compound, int want_masks)
+int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks, bool want_counters)
 {
+    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score: points not set");
+    if (ctx->batch.resident.M <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score: no hypotheses uploaded");
     int rc = PGX_OK;
-    if (!with_model_type(ctx->model_type, [&](auto mt) { rc = score_dispatch<decltype(mt)::value>(ctx, T2, has_compound, want_masks); }))
+    if (!with_model_type(ctx->model_type, [&](auto mt) { rc = score_launch_typed<decltype(mt)::value>(ctx, T2, has_compound, want_masks, want_counters); }))
         return fail(ctx, PGX_ERR_INVALID, "pgx_score: bad model type %d", ctx->model_type);
+    if (rc != PGX_OK) ctx->batch.launch_failed();
     return rc;
 }
 

@@ -596,7 +596,7 @@ int set_points_device(pgx_ctx* ctx, const ModelInfo& mi, const double* points, i
     ctx->fscale = fs > 1.0 ? fs : 1.0;   // NaN coordinates leave it at what the finite ones give; the solvers then produce NaN models
     ctx->point_sort = 0;
     ctx->comp_dirty = 1;
-    if (mi.bound == kBoundVanishing && ctx->group_filter && ctx->filter_enabled == 1 && !(flags & 1u) && n >= 1) {
+    if (mi.bound == kBoundVanishing && ctx->group_filter && ctx->score_sw.filter_enabled == 1 && !(flags & 1u) && n >= 1) {
         // ---- segments: f32 feature rows, Hough order of the segments' lines (sp_vp_rows_kernel), group rows of the normalised features
         const double xa = std::fmin(key_f64(st[0]), key_f64(st[2])), xb = std::fmax(key_f64(st[5]), key_f64(st[7]));
         const double ya = std::fmin(key_f64(st[1]), key_f64(st[3])), yb = std::fmax(key_f64(st[6]), key_f64(st[8]));
@@ -640,7 +640,7 @@ int set_points_device(pgx_ctx* ctx, const ModelInfo& mi, const double* points, i
     }
     const bool line = mi.bound == kBoundBall;            // ball bounds about the box centre (d = 2 or 3)
     const bool fund = mi.bound == kBoundBoxAll || line;   // model types whose f32 rows / boxes are built from ALL coordinates
-    if (!((obs0 >= 0 || fund) && ctx->group_filter && ctx->filter_enabled == 1 && std::isfinite(ctx->umax)) || (flags & 1u)) return PGX_OK;
+    if (!((obs0 >= 0 || fund) && ctx->group_filter && ctx->score_sw.filter_enabled == 1 && std::isfinite(ctx->umax)) || (flags & 1u)) return PGX_OK;
     if (fund) {   // f32 rows of the Sampson / line filter (the prep kernel left them zero) + the scales
         hipLaunchKernelGGL(sp_fund_rows_kernel, dim3(blocks), dim3(kSpBlock), 0, ctx->stream, ctx->pts.as<double>(), n, d, ctx->pts32.as<float>(),
                            ctx->pmax.as<double>());

@@ -485,20 +485,11 @@ __global__ __launch_bounds__(64) void solve_f7_kernel(const double* __restrict__
 // the staging buffer against the next call.
 static int upload_samples(pgx_ctx* ctx, const int32_t* samples, size_t bytes)
 {
-    if (ctx->h_samples_busy) { PGX_HIP(ctx, hipEventSynchronize(ctx->ev_samples)); ctx->h_samples_busy = 0; }
-    if (ctx->h_samples_cap < bytes) {
-        if (ctx->h_samples) (void)hipHostFree(ctx->h_samples);
-        ctx->h_samples = nullptr; ctx->h_samples_cap = 0;
-        PGX_HIP(ctx, hipHostMalloc(&ctx->h_samples, bytes * 2, hipHostMallocDefault));
-        ctx->h_samples_cap = bytes * 2;
-    }
-    if (!ctx->ev_samples) PGX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_samples, hipEventDisableTiming));
-    std::memcpy(ctx->h_samples, samples, bytes);
+    PGX_TRY(ctx->h_samples.acquire(ctx, bytes));
+    std::memcpy(ctx->h_samples.buf.p, samples, bytes);
     PGX_TRY(ensure(ctx, ctx->scratch, bytes));
-    PGX_HIP(ctx, hipMemcpyAsync(ctx->scratch.p, ctx->h_samples, bytes, hipMemcpyHostToDevice, ctx->stream));
-    PGX_HIP(ctx, hipEventRecord(ctx->ev_samples, ctx->stream));
-    ctx->h_samples_busy = 1;
-    return PGX_OK;
+    PGX_HIP(ctx, hipMemcpyAsync(ctx->scratch.p, ctx->h_samples.buf.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return ctx->h_samples.submitted(ctx, ctx->stream);
 }
 
 // ---- samples drawn on the device (rng.hip.h): one lane per sample, straight into the buffer the solvers read -----------------
@@ -559,38 +550,36 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     // fscale, which pgx_set_points computes from the caller-visible data: umax is not kept either)
     const bool scaled = mt == kFundamental || mt == kHomography;
     if (scaled && !(ctx->fscale >= 1.0)) return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: coordinate scale not available");
-    // Device-generated batches stay in the caller's order (the kernels below write the identity permutation), so the host copy of an
-    // uploaded batch's locality order and the mirror of its launch end HERE - for pgx_solve_minimal and pgx_solve_minimal_sampled
-    // alike, and only once the call is accepted: a refused call leaves the uploaded batch resident, and its order with it.  (The sampled
-    // entry point used to keep the stale order: the next mirrored fetch came back shuffled by it.  tests/test_gpu_switches.py
-    // test_device_generated_batches_come_back_in_sample_order_after_a_reordered_upload)
-    ctx->h_perm.clear();
-    ctx->mirror_valid = 0;
     const int Mtot = mi.slots * S;
-    ctx->Mpad = ((Mtot + 255) / 256) * 256;   // (255 .. 257 and the other edges of the rounding: test_score_batch_sizes_across_the_reorder_and_the_padding)
+    const int Mpad = ((Mtot + 255) / 256) * 256;   // (255 .. 257 and the other edges of the rounding: test_score_batch_sizes_across_the_reorder_and_the_padding)
     PGX_TRY(ensure(ctx, ctx->models, (size_t)Mtot * mi.P * sizeof(double)));
-    PGX_TRY(ensure(ctx, ctx->perm, (size_t)ctx->Mpad * sizeof(int)));
+    PGX_TRY(ensure(ctx, ctx->perm, (size_t)Mpad * sizeof(int)));
     if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * mi.sample * sizeof(int32_t)));
     const double* pts = ctx->pts.as<double>();
     const int* smp = ctx->scratch.as<int>();
     double* models = ctx->models.as<double>();
     int* perm = ctx->perm.as<int>();
     const dim3 gs((unsigned)((S + 63) / 64)), bs(64);                                            // one lane per sample
-    const dim3 gm((unsigned)((ctx->Mpad + kSolveBlock - 1) / kSolveBlock)), bm(kSolveBlock);      // one lane per padded model
-    if (mt == kFundamental) hipLaunchKernelGGL(solve_f7_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, ctx->Mpad);
-    else if (mt == kHomography) hipLaunchKernelGGL(solve_h4_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, ctx->Mpad);
-    else if (mt == kPnP) hipLaunchKernelGGL(solve_p3p_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
-    else if (mt == kPlane3D) hipLaunchKernelGGL(solve_plane_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
-    else if (mt == kSphere3D) hipLaunchKernelGGL(solve_sphere_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, ctx->Mpad);
-    else if (mt == kLine2D) hipLaunchKernelGGL((solve_kernel<kLine2D>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
-    else if (mt == kVanishingPoint) hipLaunchKernelGGL((solve_kernel<kVanishingPoint>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, ctx->Mpad);
+    const dim3 gm((unsigned)((Mpad + kSolveBlock - 1) / kSolveBlock)), bm(kSolveBlock);      // one lane per padded model
+    if (mt == kFundamental) hipLaunchKernelGGL(solve_f7_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
+    else if (mt == kHomography) hipLaunchKernelGGL(solve_h4_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
+    else if (mt == kPnP) hipLaunchKernelGGL(solve_p3p_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
+    else if (mt == kPlane3D) hipLaunchKernelGGL(solve_plane_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
+    else if (mt == kSphere3D) hipLaunchKernelGGL(solve_sphere_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
+    else if (mt == kLine2D) hipLaunchKernelGGL((solve_kernel<kLine2D>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
+    else if (mt == kVanishingPoint) hipLaunchKernelGGL((solve_kernel<kVanishingPoint>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
     else return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal (internal): model type %d declares a solver that has no launch line", mt);
     PGX_HIP(ctx, hipGetLastError());
     if (models_out) {
         PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)Mtot * mi.P * sizeof(double)));
         PGX_TRY(sync_deliver(ctx));
     }
-    ctx->M = Mtot; ctx->last_acc = nullptr;
+    // Device-generated batches stay in the caller's order (the kernels above wrote the identity permutation), so an uploaded batch's
+    // locality order and the mirror of its launch end HERE - for pgx_solve_minimal and pgx_solve_minimal_sampled alike, and only once
+    // the call has succeeded: a refused or failed call leaves the uploaded batch resident, and its order with it.  (The sampled entry
+    // point used to keep the stale order: the next mirrored fetch came back shuffled by it.  tests/test_gpu_switches.py
+    // test_device_generated_batches_come_back_in_sample_order_after_a_reordered_upload)
+    ctx->batch.generated(Mtot, Mpad);
     return PGX_OK;
 }
 

@@ -34,3 +34,7 @@ ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/move_route_san
 g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 \
     -o build/san/expansion_cycle_san tests/emu/expansion_cycle_driver.cpp
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/expansion_cycle_san
+# csrc/score_plan.h (what a scoring launch looks like and who owns the batch and the last launch's results: host code of libpgx.so, no HIP in it) under tests/emu/score_plan_driver.cpp
+g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 \
+    -o build/san/score_plan_san tests/emu/score_plan_driver.cpp
+ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 build/san/score_plan_san

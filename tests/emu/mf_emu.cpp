@@ -17,6 +17,7 @@
 #include "../../progressive-x_amd/csrc/maxflow_driver.inl"
 #include "../../progressive-x_amd/csrc/maxflow_l0.hip.h"
 #include "../../progressive-x_amd/csrc/move_route.h"
+#include "../../progressive-x_amd/csrc/score_plan.h"
 
 using namespace pgx;
 
@@ -370,6 +371,59 @@ extern "C" void emu_plan_move(int mf_tile, int mf_tile_batch, int mf_region, int
     for (int k = 0; k < 3; ++k) out[k] = (int32_t)r.order[k];
     out[3] = r.flip ? 1 : 0;
     out[4] = r.batched ? 1 : 0;
+}
+
+// The planner of csrc/score_plan.h as libpgx.so compiles it (tests/test_score_plan.py).
+//   in_i = traits (filter64, filter32, bound, homography) | switches (filter_enabled, cull, mirror, verify, split, group_xcd, nrep, dense_min,
+//          cull_segs) | cu_count, M, Mpad, ordered, point_sort, want_masks, want_counters, blocks_per_cu
+//   in_l = n, score_global_n;  in_d = T2, umax, fscale
+//   out_l = path, filter, chunk, chunks, words, groups, cull_segs, gps, W, group_xcd, nrep, split, gblocks, zero_words, dense_min, counters,
+//           verify, mirror;  out_d = guard, guard32, qscale
+extern "C" void emu_plan_score(const int32_t in_i[21], const int64_t in_l[2], const double in_d[3], int64_t out_l[18], double out_d[3])
+{
+    pgx::ScoreTraits tr;
+    tr.filter64 = in_i[0] != 0; tr.filter32 = in_i[1] != 0; tr.bound = in_i[2]; tr.homography = in_i[3] != 0;
+    pgx::ScoreSwitches sw;
+    sw.filter_enabled = in_i[4]; sw.cull = in_i[5]; sw.mirror = in_i[6]; sw.verify = in_i[7]; sw.split = in_i[8]; sw.group_xcd = in_i[9];
+    sw.nrep = in_i[10]; sw.dense_min = in_i[11]; sw.cull_segs = in_i[12];
+    const pgx::ScorePlan p = pgx::plan_score(tr, sw, in_i[13], in_l[0], in_i[14], in_i[15], in_i[16] != 0, in_i[17] != 0, in_d[0], in_d[1], in_d[2],
+                                             in_l[1], in_i[18] != 0, in_i[19] != 0, in_i[20]);
+    const int64_t l[18] = {p.path, p.filter, p.chunk, p.chunks, p.words, p.groups, p.cull_segs, p.gps, p.W, p.group_xcd, p.nrep, p.split,
+                           (int64_t)p.gblocks, p.zero_words, p.dense_min, p.counters, p.verify, p.mirror};
+    for (int k = 0; k < 18; ++k) out_l[k] = l[k];
+    out_d[0] = p.guard; out_d[1] = p.guard32; out_d[2] = p.qscale;
+}
+
+// The batch owner of csrc/score_plan.h (ScoreBatch) under its events: 0 points changed | 1 uploaded (a = M, b = Mpad, perm or NULL) |
+// 2 generated (a = M, b = Mpad) | 3 launched (plan = path, filter, words, nrep, mirror; a = has_compound, b = masks, acc = a token for the
+// accumulators' address, q = qscale) | 4 launch failed | 5 table replaced by a reduction.  A refused or failed upload / solve is no event.
+extern "C" void* emu_batch_new() { return new pgx::ScoreBatch(); }
+extern "C" void emu_batch_free(void* h) { delete (pgx::ScoreBatch*)h; }
+extern "C" void emu_batch_event(void* h, int event, int a, int b, const int32_t* perm, const int64_t plan[5], uint64_t acc, double q)
+{
+    pgx::ScoreBatch& sb = *(pgx::ScoreBatch*)h;
+    if (event == 0) sb.points_changed();
+    else if (event == 1) sb.uploaded(a, b, perm);
+    else if (event == 2) sb.generated(a, b);
+    else if (event == 3) {
+        pgx::ScorePlan p;
+        p.path = (int)plan[0]; p.filter = (int)plan[1]; p.words = plan[2]; p.nrep = (int)plan[3]; p.mirror = plan[4] != 0; p.qscale = q;
+        sb.launched(p, a != 0, b != 0, (unsigned long long*)(uintptr_t)acc);
+    } else if (event == 4) sb.launch_failed();
+    else if (event == 5) sb.table_reduced();
+}
+// out = table (0 ready, 1 none, 2 changed) | mask rows (likewise) | from mirror | ordered | accumulators exportable | ... stale | M | Mpad |
+//       last: has_compound, masks, words, path, filter, nrep, accumulator token;  perm_out: the order to un-permute with, when ordered
+extern "C" double emu_batch_query(void* h, int64_t out[15], int32_t* perm_out)
+{
+    const pgx::ScoreBatch& sb = *(const pgx::ScoreBatch*)h;
+    const int64_t o[15] = {(int64_t)sb.table(), (int64_t)sb.mask_rows(), sb.from_mirror(), sb.unpermute() != nullptr, sb.acc_exportable(), sb.acc_stale(),
+                           sb.resident.M, sb.resident.Mpad, sb.last.has_compound, sb.last.masks, sb.last.words, sb.last.path, sb.last.filter,
+                           sb.last.nrep, (int64_t)(uintptr_t)sb.last.acc};
+    for (int k = 0; k < 15; ++k) out[k] = o[k];
+    if (const int* pm = sb.unpermute())
+        for (int m = 0; m < sb.resident.M; ++m) perm_out[m] = pm[m];
+    return sb.last.qscale;
 }
 
 // ---- the cycle driver of csrc/expansion_cycle.h (run_expansion, as libpgx.so compiles it) over a CPU backend: tests/test_expansion_cycle.py,

@@ -18,7 +18,7 @@ SO = os.environ.get("PGX_EMU_SO") or os.path.join(HERE, "emu", "libmf_emu.so")  
 def emu():
     src = os.path.join(HERE, "emu", "mf_emu.cpp")
     deps = [src] + [os.path.join(HERE, "..", "progressive-x_amd", "csrc", f)
-                    for f in ("maxflow_body.hip.h", "maxflow_driver.inl", "move_route.h", "expansion_cycle.h")]
+                    for f in ("maxflow_body.hip.h", "maxflow_driver.inl", "move_route.h", "expansion_cycle.h", "score_plan.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SO, src])
     return C.CDLL(SO)
