@@ -19,6 +19,7 @@
 
 #include "pgx_internal.h"
 #include "score_filters.hip.h"
+#include "score_runs.h"
 
 namespace pgx {
 
@@ -165,25 +166,75 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
 //                       bit-reproducible although the accumulation order is not fixed.  q = 62 - ceil(log2 n): the
 //                       quantisation error of a sum is < (#groups with inliers) * 2^-(q+1), ~1e-13 relative.
 //   score_finish_kernel accumulators -> counts / values / shared in the caller's hypothesis order.
-constexpr int kHypRow = 20;    // floats per hypothesis: Filter32<MT>::Lane, padded
+// Three independent trims of the group-major kernel, each behind one bit so that two builds of the library can be compared
+// (make EXTRA=-DPGX_SCORE_TRIM=<mask>; docs/lab-notebook.md, "Trimming the group-major step loop"):
+//   1  a hypothesis' row holds the staged form only (StagedVals: the floats reject() reads) instead of the whole lane
+//   2  drain() carries count and value in one word and takes the run boundaries from one head mask (score_runs.h)
+//   4  direct() leaves out the tree and the atomic of the shared sum when no lane shares anything with the compound instance
+#ifndef PGX_SCORE_TRIM
+#define PGX_SCORE_TRIM 7
+#endif
+constexpr bool kTrimRows = (PGX_SCORE_TRIM & 1) != 0, kTrimDrain = (PGX_SCORE_TRIM & 2) != 0, kTrimDirect = (PGX_SCORE_TRIM & 4) != 0;
 
-template <class LaneT>
-__device__ __forceinline__ void lane_store(const LaneT& ln, float* __restrict__ row)
-{
-    static_assert(sizeof(LaneT) % 4 == 0 && sizeof(LaneT) / 4 <= kHypRow, "Filter32 lane constants must fit a row");
-    const float* src = reinterpret_cast<const float*>(&ln);
+// A hypothesis' f32 constants as the cull kernel stores them (hyp32) and the group kernel stages them (LDS): the first kVals
+// floats of Filter32<MT>::Lane in float4 chunks.  Rows of hyp32 are kStride floats apart - 16-byte aligned, 64 bytes for the pose
+// family (14 floats: one cache-line sector per hypothesis).
+template <int MT> struct HypRow {
+    using LaneT = typename Filter32<MT>::Lane;
+    static_assert(sizeof(LaneT) % sizeof(float) == 0, "Filter32 lane constants are floats");
+    static constexpr int kLaneVals = (int)(sizeof(LaneT) / sizeof(float));
+    static constexpr int kVals = kTrimRows ? StagedVals<Filter32<MT>>::value : kLaneVals;
+    static_assert(kVals <= kLaneVals, "the staged form is a prefix of the lane");
+    static constexpr int kChunks = (kVals + 3) / 4;
+    static constexpr int kStride = 4 * kChunks;
+
+    static __device__ __forceinline__ void store(const LaneT& ln, float* __restrict__ row)   // the cull kernel
+    {
+        const float* src = reinterpret_cast<const float*>(&ln);
 #pragma unroll
-    for (int k = 0; k < (int)(sizeof(LaneT) / 4); ++k) row[k] = src[k];
-}
-template <class LaneT>
-__device__ __forceinline__ LaneT lane_load(const float* __restrict__ row)
-{
-    LaneT ln;
-    float* dst = reinterpret_cast<float*>(&ln);
+        for (int k = 0; k < kVals; ++k) row[k] = src[k];
+    }
+    // The rest of the lane stays unset: reject() does not read it (StagedVals).
+    static __device__ __forceinline__ LaneT load(const float* __restrict__ row)              // the verify kernel
+    {
+        LaneT ln;
+        float* dst = reinterpret_cast<float*>(&ln);
 #pragma unroll
-    for (int k = 0; k < (int)(sizeof(LaneT) / 4); ++k) dst[k] = row[k];
-    return ln;
-}
+        for (int k = 0; k < kVals; ++k) dst[k] = row[k];
+        return ln;
+    }
+    // LDS image of a word's 64 hypotheses: [chunk][hypothesis][4].  The owning lanes write consecutive 16-byte slots (rows 80 bytes
+    // apart collided on the banks), the step loop reads chunk c of hypothesis h at the same address in every lane.
+    static __device__ __forceinline__ void stage(const float* __restrict__ row0, float (*lds)[64][4], int lane)
+    {
+        const float* __restrict__ row = static_cast<const float*>(__builtin_assume_aligned(row0, 16));
+#pragma unroll
+        for (int c = 0; c < kChunks; ++c) {
+            if (4 * c + 4 <= kVals) {
+                *reinterpret_cast<float4*>(&lds[c][lane][0]) = *reinterpret_cast<const float4*>(row + 4 * c);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kVals - 4 * c; ++k) lds[c][lane][k] = row[4 * c + k];
+            }
+        }
+    }
+    static __device__ __forceinline__ LaneT staged(const float (*lds)[64][4], int h)
+    {
+        LaneT ln;
+        float* dst = reinterpret_cast<float*>(&ln);
+#pragma unroll
+        for (int c = 0; c < kChunks; ++c) {
+            if (4 * c + 4 <= kVals) {
+                const float4 v = *reinterpret_cast<const float4*>(&lds[c][h][0]);
+                dst[4 * c] = v.x; dst[4 * c + 1] = v.y; dst[4 * c + 2] = v.z; dst[4 * c + 3] = v.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < kVals - 4 * c; ++k) dst[4 * c + k] = lds[c][h][k];
+            }
+        }
+        return ln;
+    }
+};
 
 constexpr int kCullWaves = 4;   // hypothesis words (waves) per workgroup of the cull kernel
 constexpr int kCullTile = 64;   // group bounds staged in LDS per step
@@ -214,7 +265,7 @@ __global__ __launch_bounds__(64 * kCullWaves) void score_cull_kernel(
     for (int k = 0; k < R::P; ++k) mdl[k] = live ? models[(int64_t)m * R::P + k] : __builtin_nan("");
     const typename F32::Lane flane32 = F32::prep(mdl, guard32, T2);
     if (seg == 0 && w < W) {
-        lane_store(flane32, hyp32 + (int64_t)m * kHypRow);
+        HypRow<MT>::store(flane32, hyp32 + (int64_t)m * HypRow<MT>::kStride);
 #pragma unroll
         for (int k = 0; k < R::P; ++k) models_t[(int64_t)k * W * 64 + m] = mdl[k];
     }
@@ -274,6 +325,7 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
     using R = Residual<MT>;
     using F32 = Filter32<MT>;
     using LaneT = typename F32::Lane;
+    using Row = HypRow<MT>;
     const int lane = (int)(threadIdx.x & 63);
     // One item (group, part) per wave, one wave per workgroup.  Measured alternatives at M = 2048, N = 1e6: 4-wave workgroups
     // (a workgroup retires with its slowest wave; 0.32 ms), 2-wave (0.30), persistent waves striding over the items
@@ -339,7 +391,7 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
     // round trip per 64 hypotheses) and read back as broadcasts: one scalar-memory round trip per hypothesis (~1 us
     // when the scalar cache misses) left the kernel latency-bound (37 % VALU utilisation).  The f64 model is fetched
     // only by pairs that have candidates (staging it as well costs occupancy or compaction work: measured slower).
-    __shared__ float s_h32[kGroupWaves][64][kHypRow];
+    __shared__ __attribute__((aligned(16))) float s_h32[kGroupWaves][Row::kChunks][64][4];
     __shared__ unsigned s_queue[kGroupWaves][128];
     int qn = 0;  // queued candidate pairs of this wave (wave-uniform)
     unsigned long long st_steps = 0, st_exact = 0, st_inl = 0;  // STATS only (wave-uniform / per-lane partials)
@@ -357,7 +409,7 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
 #pragma unroll
         for (int k = 0; k < R::D; ++k) q_pt[k] = __shfl(pt[k], src, 64);
         const double q_cmp = has_comp ? __shfl(cmp, src, 64) : 0.0;
-        long long cnt = 0, val = 0, shq = 0;
+        long long cnt = 0, val = 0, shq = 0;  // (kTrimDrain: val = run_pack(count, value), cnt is only the lane's own 0 / 1)
         if (act) {  // exact path: oracle operation order, no contraction
             double mdl[R::P];
 #pragma unroll
@@ -372,15 +424,38 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
                 if (has_comp) shq = to_fixed(cv_min(q_cmp, sc) * qscale);           // :115-117
             }
         }
-        for (int off = 1; off < 64; off <<= 1) {  // segmented sums: lane i ends with the total of i .. end of its run
-            const int mo = __shfl_down(m, off, 64);
-            const bool same = lane + off < 64 && mo == m;
-            if (__ballot(same) == 0) break;  // runs are contiguous: none reaches `off` lanes, none reaches further
-            const long long c2 = __shfl_down(cnt, off, 64), v2 = __shfl_down(val, off, 64), s2 = __shfl_down(shq, off, 64);
-            if (same) { cnt += c2; val += v2; shq += s2; }
-        }
         const int mp = __shfl_up(m, 1, 64);
-        if (act && (lane == 0 || mp != m) && cnt > 0) {
+        const bool head = lane == 0 || mp != m;
+        if constexpr (kTrimDrain) {
+            // Runs are contiguous, so the mask of their first lanes says how far every lane's run reaches (score_runs.h): no
+            // shuffle of m per round; and the count rides in the top bits of the value word (a drain's value sum is < 2^57):
+            // two 64-bit shuffles per round (one without a compound instance) where there were an int and three.  The fields
+            // are split again below - the same integers go into the same atomics.
+            const int dist = run_dist(__ballot(head), lane);
+            unsigned long long pv = run_pack((unsigned)cnt, (unsigned long long)val);
+#pragma unroll 1   // (unrolled, the six rounds cost the pose instance 6 VGPRs and with them a wave per SIMD)
+            for (int off = 1; off < 64; off <<= 1) {  // segmented sums: lane i ends with the total of i .. end of its run
+                const bool same = off < dist;
+                if (__ballot(same) == 0) break;  // none reaches `off` lanes, none reaches further
+                const unsigned long long p2 = __shfl_down(pv, off, 64);
+                if (same) pv += p2;
+                if (has_comp) {
+                    const long long s2 = __shfl_down(shq, off, 64);
+                    if (same) shq += s2;
+                }
+            }
+            cnt = (long long)run_count(pv);
+            val = (long long)run_value(pv);
+        } else {
+            for (int off = 1; off < 64; off <<= 1) {  // segmented sums: lane i ends with the total of i .. end of its run
+                const int mo = __shfl_down(m, off, 64);
+                const bool same = lane + off < 64 && mo == m;
+                if (__ballot(same) == 0) break;  // runs are contiguous: none reaches `off` lanes, none reaches further
+                const long long c2 = __shfl_down(cnt, off, 64), v2 = __shfl_down(val, off, 64), s2 = __shfl_down(shq, off, 64);
+                if (same) { cnt += c2; val += v2; shq += s2; }
+            }
+        }
+        if (act && head && cnt > 0) {
             atomicAdd(&acc[m], (unsigned long long)cnt);
             atomicAdd(&acc[(int64_t)Mpad + m], (unsigned long long)val);
             if (has_comp) atomicAdd(&acc[2 * (int64_t)Mpad + m], (unsigned long long)shq);
@@ -410,15 +485,24 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
         if (bm == 0) return;
         // per-lane fixed point first (the same integers the queued path adds up), then an exact integer tree
         long long val = inl ? to_fixed(sc * qscale) : 0, shq = (inl && has_comp) ? to_fixed(shv * qscale) : 0;
+        // Nothing shared with the compound instance (no instance, or min(compound, score) is 0 in every inlier lane - most
+        // hypotheses of a batch): every shq is to_fixed(0) = 0, the tree would add zeros and the atomic would add 0.
+        // (shv != 0 holds for NaN: such a step takes the full path.)
+        const bool shares = kTrimDirect ? (has_comp && __ballot(inl && shv != 0.0) != 0) : (has_comp != 0);
+        if (shares) {
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            val += __shfl_down(val, off, 64);
-            shq += __shfl_down(shq, off, 64);
+            for (int off = 32; off > 0; off >>= 1) {
+                val += __shfl_down(val, off, 64);
+                shq += __shfl_down(shq, off, 64);
+            }
+        } else {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) val += __shfl_down(val, off, 64);
         }
         if (lane == 0) {
             atomicAdd(&acc[m], (unsigned long long)__popcll(bm));
             atomicAdd(&acc[(int64_t)Mpad + m], (unsigned long long)val);
-            if (has_comp) atomicAdd(&acc[2 * (int64_t)Mpad + m], (unsigned long long)shq);
+            if (shares) atomicAdd(&acc[2 * (int64_t)Mpad + m], (unsigned long long)shq);
             if (MASK) masks[(int64_t)perm[m] * words + g] = bm;  // rows start zeroed
         }
     };
@@ -429,15 +513,14 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
         __builtin_amdgcn_wave_barrier();  // the previous word's reads are done (LDS ops of a wave execute in order)
         if ((todo >> lane) & 1ull) {
             const int64_t ml = (int64_t)w * 64 + lane;
-#pragma unroll
-            for (int k = 0; k < kHypRow; ++k) s_h32[wv][lane][k] = hyp32[ml * kHypRow + k];
+            Row::stage(hyp32 + ml * Row::kStride, s_h32[wv], lane);
         }
         __builtin_amdgcn_wave_barrier();
         while (todo != 0) {
             const int h = __builtin_ctzll(todo);
             todo &= todo - 1;
             const int m = w * 64 + h;
-            const LaneT ln = lane_load<LaneT>(&s_h32[wv][h][0]);  // same address in every lane: LDS broadcast
+            const LaneT ln = Row::staged(s_h32[wv], h);  // same address in every lane: LDS broadcast
             const bool cand = valid && !F32::reject(p32, ln, T2d32);
             const unsigned long long cm = __ballot(cand);
             if (cm == 0) continue;
@@ -515,7 +598,7 @@ __global__ __launch_bounds__(64) void score_verify_kernel(const double* __restri
         for (int k = 0; k < R::P; ++k) mdl[k] = models[(int64_t)m * R::P + k];
         const bool inl = valid && R::squared(pt, mdl) < T2;
         const bool kept = (todo >> h) & 1ull;
-        const LaneT ln = lane_load<LaneT>(hyp32 + (int64_t)m * kHypRow);
+        const LaneT ln = HypRow<MT>::load(hyp32 + (int64_t)m * HypRow<MT>::kStride);
         const bool rej = F32::reject(p32, ln, T2d32);
         c_inl += inl;
         c_cull += inl && !kept;
@@ -689,9 +772,9 @@ static int score_group_path(pgx_ctx* ctx, const ScorePlan& pl, double T2, int ha
     const int M = ctx->batch.resident.M, Mpad = ctx->batch.resident.Mpad;
     const int groups = pl.groups, W = pl.W, nrep = pl.nrep, split = pl.split, xcd_local = pl.group_xcd ? 1 : 0;
     PGX_TRY(ensure(ctx, ctx->cull_lists, (size_t)groups * W * sizeof(unsigned long long)));             // keep[g][w]
-    PGX_TRY(ensure(ctx, ctx->cull_counts, (size_t)Mpad * (kHypRow * sizeof(float) + (size_t)nrep * 3 * sizeof(long long) + Residual<MT>::P * sizeof(double))));  // hyp32 | acc[nrep] | models_t
+    PGX_TRY(ensure(ctx, ctx->cull_counts, (size_t)Mpad * (HypRow<MT>::kStride * sizeof(float) + (size_t)nrep * 3 * sizeof(long long) + Residual<MT>::P * sizeof(double))));  // hyp32 | acc[nrep] | models_t
     float* hyp32 = ctx->cull_counts.as<float>();
-    unsigned long long* acc = (unsigned long long*)(ctx->cull_counts.as<char>() + (size_t)Mpad * kHypRow * sizeof(float));
+    unsigned long long* acc = (unsigned long long*)(ctx->cull_counts.as<char>() + (size_t)Mpad * HypRow<MT>::kStride * sizeof(float));
     double* models_t = (double*)(acc + (size_t)nrep * 3 * (size_t)Mpad);
     const double* pts_g = ctx->pts_g.p ? ctx->pts_g.as<double>() : (const double*)nullptr;   // group-blocked SoA copies of the rows
     const float* p32_g = ctx->pts_g.p ? ctx->p32_g.as<float>() : (const float*)nullptr;

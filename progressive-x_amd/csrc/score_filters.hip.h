@@ -7,6 +7,8 @@
 // Replaces nothing in the reference (its getScore evaluates every pair: scoring_function_with_compound_model.h:78-121).
 #pragma once
 #include <cmath>
+#include <cstddef>
+#include <type_traits>
 
 #include "pgx_internal.h"
 
@@ -132,6 +134,12 @@ template <int MT> struct Filter32 {
     static __device__ __forceinline__ bool group_reject(const float*, const Lane&, float) { return false; }
 };
 
+// The staged form of a hypothesis: the leading floats of Filter32<MT>::Lane that reject() reads.  The cull kernel stores them per
+// hypothesis, the group-major kernel stages them in LDS and rebuilds a Lane from them for reject() (the rest of the lane is not
+// touched there).  A type says so with `kStagedVals`; without it the whole lane is staged.
+template <class F, class = void> struct StagedVals { static constexpr int value = (int)(sizeof(typename F::Lane) / sizeof(float)); };
+template <class F> struct StagedVals<F, std::void_t<decltype(F::kStagedVals)>> { static constexpr int value = F::kStagedVals; };
+
 // ---- group-level rejection ---------------------------------------------------------------------------
 // The points are kept in Morton order of all their coordinates, so 64 consecutive points form a compact group: centre c
 // and radius rho of the part the projective map multiplies, centre (ub, vb) and half extents (ru, rv) of the observed
@@ -148,6 +156,10 @@ template <> struct Filter32<kPnP> {
     static constexpr bool enabled = true;
     static constexpr int kRowVals = 6, kGroupVals = 9;
     struct Lane { float m[12]; float c1, c0; float n0, n1, n2; float nanh; };
+    // reject() reads m, c1, c0 and nothing behind them (n0, n1, n2, nanh belong to group_reject, which the cull kernel runs from
+    // registers): the staged form of a hypothesis - what the cull kernel stores and the group kernel stages - is this prefix
+    static constexpr int kStagedVals = 14;
+    static_assert(offsetof(Lane, c0) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, n0) == kStagedVals * sizeof(float), "m, c1, c0 lead the lane");
     template <class MD> static __device__ __forceinline__ Lane prep(const MD& m0, double guard32, double) {
         Lane ln;
         bool nan = false;
