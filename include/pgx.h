@@ -41,8 +41,9 @@ enum pgx_model_type {
     PGX_VANISHING_POINT = 4,  /* point (xs,ys,xe,ye);    model (v0,v1,v2)                     findVanishingPoints  */
     PGX_HOMOGRAPHY_SYM = 5,   /* point (x1,y1,x2,y2);    model [H | H^-1], symmetric transfer error               */
     PGX_PLANE3D = 6,          /* point (x,y,z);          model (a,b,c,d), (a,b,c) unit normal findPlanes           */
-    PGX_SPHERE3D = 8          /* point (x,y,z);          model (cx,cy,cz,r)                   findSpheres          */
-    /* 7 is not assigned: pgx_model_dims(7) and pgx_set_points(7, ...) fail with PGX_ERR_INVALID */
+    PGX_SPHERE3D = 8,         /* point (x,y,z);          model (cx,cy,cz,r)                   findSpheres          */
+    PGX_CIRCLE2D = 10         /* point (x,y);            model (cx,cy,r)                      findCircles          */
+    /* 7 and 9 are not assigned: pgx_model_dims(7 or 9) and pgx_set_points(7 or 9, ...) fail with PGX_ERR_INVALID */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -88,15 +89,16 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * caller's order), so pgx_score_launch can follow without a model upload; models_out (may be NULL) copies them out.
  * Built: the 2-segment vanishing point solver (solver_vanishing_point_two_lines.h:147-185) and the 2-point line solver
  * [U-4] (samples[S][2], S x 3 models), the 3-point plane solver (samples[S][3], S x 4, findPlanes), the 4-point sphere solver
- * (samples[S][4], S x 4, findSpheres; radii outside pgx_set_radius_range give NaN), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
+ * (samples[S][4], S x 4, findSpheres; radii outside pgx_set_radius_range give NaN), the 3-point circle solver
+ * (samples[S][3], S x 3, findCircles; the same radius range), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
  * FOUR slots per sample: 4S x 12 [R|t], DefaultPnPEstimator progressivex_python.cpp:119, absent upstream); a degenerate sample
  * or an absent root yields a NaN model (never an inlier).  Other model types: PGX_ERR_INVALID.  `samples` is consumed before the
  * call returns; with models_out == NULL the call does not wait for the solver (the batch stays on the device). */
 int pgx_solve_minimal(pgx_ctx *ctx, const int32_t *samples, int S, double *models_out);
-/* The radii the sphere solver accepts (context state, [0, +inf] at pgx_create; only the sphere solver reads it): a sample whose
- * sphere has r outside [rmin, rmax] yields a NaN model.  NaN, rmin < 0 or rmax < rmin: PGX_ERR_INVALID.  rmax = +inf is allowed. */
+/* The radii the sphere and the circle solver accept (context state, [0, +inf] at pgx_create; those two solvers read it): a sample whose
+ * sphere or circle has r outside [rmin, rmax] yields a NaN model.  NaN, rmin < 0 or rmax < rmin: PGX_ERR_INVALID.  rmax = +inf is allowed. */
 int pgx_set_radius_range(pgx_ctx *ctx, double rmin, double rmax);
 /* The same with the samples DRAWN ON THE DEVICE by the in-repo counter-based generator (csrc/rng.hip.h: Philox4x32-10; sample s
  * of batch `batch` under `key` is a pure function of (key, batch, s); m = the resident model type's minimal sample size).
@@ -280,9 +282,10 @@ int pgx_one_workgroup_launches(pgx_ctx *ctx, int64_t out[2]);
  *   PGX_GRAM_VP       solver_vanishing_point_two_lines.h:212-217                               q = 3
  *   PGX_GRAM_PNP_GN   Gauss-Newton rows (J_u, r_u), (J_v, r_v) at the pose params = [R|t] 3x4  q = 7
  *   PGX_GRAM_SPHERE   (1, u, v, w, (u u + v v) + w w), (u, v, w) = (p - o) / s, params = (ox,oy,oz,s), 3-D points    q = 5
+ *   PGX_GRAM_CIRCLE   (1, u, v, u u + v v), (u, v) = (p - o) / s, params = (ox,oy,s), 2-D points                          q = 4
  * Selection: PGX_SEL_INDEX (index[m], host) or PGX_SEL_LABEL (label == `label` on the resident labelling).
  * count = selected points, bad = points skipped because the row is undefined (PnP: depth ~ 0). */
-enum { PGX_GRAM_AFFINE = 0, PGX_GRAM_DLT_H = 1, PGX_GRAM_EPI_F = 2, PGX_GRAM_VP = 3, PGX_GRAM_PNP_GN = 4, PGX_GRAM_SPHERE = 5 };
+enum { PGX_GRAM_AFFINE = 0, PGX_GRAM_DLT_H = 1, PGX_GRAM_EPI_F = 2, PGX_GRAM_VP = 3, PGX_GRAM_PNP_GN = 4, PGX_GRAM_SPHERE = 5, PGX_GRAM_CIRCLE = 6 };
 enum { PGX_SEL_INDEX = 0, PGX_SEL_LABEL = 1 };
 int pgx_set_weights(pgx_ctx *ctx, const double *weights, int64_t len);
 int pgx_gram(pgx_ctx *ctx, int kind, const double *params, int nparams, int sel, const int32_t *index, int64_t m,

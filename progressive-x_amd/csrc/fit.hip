@@ -66,6 +66,7 @@ struct GenEpiF { static constexpr int Q = 9, D = 4; };
 struct GenVp { static constexpr int Q = 3, D = 4; };
 struct GenPnpGn { static constexpr int Q = 7, D = 5; };
 struct GenSphere { static constexpr int Q = 5, D = 3; };
+struct GenCircle { static constexpr int Q = 4, D = 2; };
 
 template <class G>
 __device__ __forceinline__ void emit(const double* pt, const FitParams& prm, Acc<G::Q>& acc, double w, int& bad);
@@ -148,6 +149,15 @@ __device__ __forceinline__ void emit<GenSphere>(const double* pt, const FitParam
 {
     const double u = (pt[0] - prm.v[0]) / prm.v[3], v = (pt[1] - prm.v[1]) / prm.v[3], z = (pt[2] - prm.v[2]) / prm.v[3];
     const double a[5] = {1.0, u, v, z, (u * u + v * v) + z * z};
+    acc.add(a, w);
+}
+
+// prm = (ox, oy, s): the algebraic circle row (1, u, v, u u + v v) of (u, v) = (p - o) / s
+template <>
+__device__ __forceinline__ void emit<GenCircle>(const double* pt, const FitParams& prm, Acc<4>& acc, double w, int&)
+{
+    const double u = (pt[0] - prm.v[0]) / prm.v[2], v = (pt[1] - prm.v[1]) / prm.v[2];
+    const double a[4] = {1.0, u, v, u * u + v * v};
     acc.add(a, w);
 }
 
@@ -561,6 +571,7 @@ static int gram_row_length(pgx_ctx* ctx, const char* who, int kind, int nparams,
     case PGX_GRAM_VP: *q = 3; if (D != 4) return fail(ctx, PGX_ERR_INVALID, "%s: needs 4-D segments", who); break;
     case PGX_GRAM_PNP_GN: *q = 7; if (D != 5 || nparams != 12) return fail(ctx, PGX_ERR_INVALID, "%s: needs 5-D 2D-3D rows and a 3x4 pose", who); break;
     case PGX_GRAM_SPHERE: *q = 5; if (D != 3 || nparams != 4) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 4 parameters (ox, oy, oz, s)", who); break;
+    case PGX_GRAM_CIRCLE: *q = 4; if (D != 2 || nparams != 3) return fail(ctx, PGX_ERR_INVALID, "%s: needs 2-D points and 3 parameters (ox, oy, s)", who); break;
     default: return fail(ctx, PGX_ERR_INVALID, "%s: unknown row kind %d", who, kind);
     }
     return PGX_OK;
@@ -581,6 +592,7 @@ static void with_gram_generator(int kind, int D, F&& f)
     case PGX_GRAM_EPI_F: f(GenEpiF{}); break;
     case PGX_GRAM_VP: f(GenVp{}); break;
     case PGX_GRAM_SPHERE: f(GenSphere{}); break;
+    case PGX_GRAM_CIRCLE: f(GenCircle{}); break;
     default: f(GenPnpGn{}); break;
     }
 }

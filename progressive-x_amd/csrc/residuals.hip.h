@@ -1,4 +1,4 @@
-// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types, 3-D planes and spheres, gfx950 device code.
+// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types, 3-D planes and spheres, 2-D circles, gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -18,7 +18,7 @@ namespace pgx {
 
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
-    kSphere3D = 8, kNumModelTypes = 9   // 7 is not assigned (pgx_model_dims(7) is an error)
+    kSphere3D = 8, kCircle2D = 10, kNumModelTypes = 11   // 7 and 9 are not assigned (pgx_model_dims(7) and (9) are errors)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -178,6 +178,23 @@ template <> struct Residual<kSphere3D> : NoProjectiveMap {
     }
 };
 
+// 2-D circles (findCircles; no reference counterpart - the sphere one dimension down): model (cx, cy, r), dx = x - cx, dy = y - cy,
+// r = |sqrt(dx dx + dy dy) - cr|, plain IEEE sqrt (no intrinsic, no contraction).  This operation order is the contract of every
+// circle check (tests restate it in numpy).
+template <> struct Residual<kCircle2D> : NoProjectiveMap {
+    static constexpr int D = 2, P = 3, sample = 3, slots = 1, bound = kBoundBall;
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        const double dx = p[0] - m[0], dy = p[1] - m[1];
+        return fabs(sqrt(dx * dx + dy * dy) - m[2]);
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double r = plain(p, m);
+        return r * r;
+    }
+};
+
 // The one list of model types: calls f(std::integral_constant<int, MT>{}) for the runtime type mt; false if mt is not a type.
 template <class F> inline bool with_model_type(int mt, F&& f) {
     switch (mt) {
@@ -189,6 +206,7 @@ template <class F> inline bool with_model_type(int mt, F&& f) {
     case kHomographySym: f(std::integral_constant<int, kHomographySym>{}); return true;
     case kPlane3D: f(std::integral_constant<int, kPlane3D>{}); return true;
     case kSphere3D: f(std::integral_constant<int, kSphere3D>{}); return true;
+    case kCircle2D: f(std::integral_constant<int, kCircle2D>{}); return true;
     default: return false;
     }
 }

@@ -618,4 +618,77 @@ template <> struct Filter32<kSphere3D> {
     }
 };
 
+// ---- 2-D circles: r = |sqrt(dx dx + dy dy) - cr| (Residual<kCircle2D>), inlier iff r^2 < T2 --------------------------------------
+// The sphere filter one dimension down, on the 2-D rows the line filter reads.  No scaling of the model; the f32 copies are its
+// entries rounded once.  Per point, in f32: d~ = p~ - c~, q~ = fma(dx, dx, dy dy), s~ = sqrtf(q~), n~ = s~ - r~.  With u = 2^-24,
+// eta = 2^-126, s* = |p - c| (exact), P = max(|x|, |y|, 1) rounded up, |.| the Euclidean norm, every coefficient re-derived for the
+// two-term case and set against the sphere's:
+//   inputs     |p~ - p| <= u |p| <= sqrt(2) u P  (sphere: sqrt(3) u P),  |c~ - c| <= u |c|,  |r~ - cr| <= u |cr|;  s is 1-Lipschitz
+//              in p and in c, so these move s by at most sqrt(2) u P + u |c|, and n by u |cr| more
+//   d~         one rounding per component: |d~ - (p~ - c~)| <= u |p~ - c~| <= u s* + O(u^2)                              (as the sphere)
+//   q~         two non-negative terms: dy dy is rounded as a product and again by the fma (2 roundings), dx dx by the fma alone
+//              (1): q~ = |d~|^2 (1 + t), |t| <= 2 u + O(u^2) -> sqrt: 1 u                                          (sphere: 3 u -> 1.5 u)
+//   sqrtf      v_sqrt_f32's documented 1 ulp = 2 u, whatever correction the lowering adds                               (as the sphere)
+//   exact path d (1 rounding), dx dx + dy dy (2 on the larger term -> 1 after the root), sqrt (1): <= 3 * 2^-53 s* < 0.01 u s*, and
+//              2^-53 |s_c - cr| for the final subtraction, which is part of the T'' margin below            (sphere: 3.5 * 2^-53 s*)
+//   n~         the subtraction s~ - r~ is rounded once, relatively: n~ = (s~ - r~)(1 + t), |t| <= u.  It is charged to the T'' margin
+//              and not to E: m > T'' gives |s~ - r~| >= (T'' + E) (1 - u), and T (1 + 2^-6)(1 - u) > T (1 + 2^-7), E (1 - u) >= the sum
+//              of the terms above as soon as E carries a relative margin of u over them (it carries > 40 %)
+// so |(s~ - r~) - (s_c - cr)| <= sqrt(2) u P + u (|c| + |cr|) + (1 + 1 + 2 + 0.01) u s* + O(u^2).  Underflow: the product dy dy and the
+// fma below 2^-126 carry absolute errors <= eta each (even with denormals flushed), and a subnormal difference d~ is exact (flushed: off by
+// < eta, which moves s by < 2 eta); 2 eta under the root move it by <= sqrt(2 eta) < 1.6e-19                                         (sphere: sqrt(4 eta) < 2.2e-19)
+// The sphere's coefficients are reused, and each bounds its 2-D counterpart with room for evaluating E itself in f32 (three
+// roundings, < 4 u relative) and for writing s~ for s* (the difference is O(u) s*):
+//   E = e1 P + e0 + e2 s~     e1 = 2 u                          >= 1.41 * sqrt(2) u
+//                             e0 = 2 u (|c| + |cr|) + 1e-18     >= 2 * u (|c| + |cr|) + 6 * 1.6e-19     (|c| is inflated by 1.001 on top)
+//                             e2 = 8 u                          >= 1.99 * 4.01 u
+//   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  m is rounded once and monotonically, so |s_c - cr| > T (1 + 2^-7), and the
+//   computed r_c^2 = fl(fl(|s_c - cr|)^2) > T2.
+// Group test on the 2-D ball (stored centre g, radius rho, Pmax) of 64 Morton-consecutive points (sp_line_bounds_kernel<SPAN, 2>,
+// the rows of Filter32<kLine2D>): every member's distance to the circle's centre lies in [s_g - rho, s_g + rho], s_g = |g - c| (g is
+// an f32 value: no input rounding, the e1 Pmax term is kept all the same), so its residual is at least |s_g - cr| - rho less the
+// errors above with P = Pmax and s* <= s_g + rho:
+//   reject the group  <=>  |s~_g - r~| - E(Pmax, s~_g + rho) - 1.001 rho > 1.001 T''.
+// One rule for points outside the circle, inside it, for r = 0 (the residual is s) and for r < 0 (every residual is s + |r|).  A NaN
+// entry culls the hypothesis (all three enter every residual).  A set with coordinates beyond 1e17, a centre or radius beyond 1e17
+// (q~ must stay below the f32 overflow) or a threshold outside the ordinary f32 range gives E = inf: never rejected, the exact path
+// decides (r = inf included: inf - inf is NaN, and a NaN comparison is false).  Scenes far from the origin lose the filter's
+// precision (e1 P grows with the offset, not with the scene): correct, only slower.
+template <> struct Filter32<kCircle2D> {
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 4;
+    struct Lane { float cx, cy, r, e1, e0, e2, tpp, nanh; };
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        ln.cx = (float)m[0]; ln.cy = (float)m[1]; ln.r = (float)m[2];
+        ln.nanh = (m[0] == m[0] && m[1] == m[1] && m[2] == m[2]) ? 0.0f : 1.0f;
+        const double Ts = sqrt(T2);
+        const double cn = sqrt(m[0] * m[0] + m[1] * m[1]) * 1.001;
+        const bool big = !(pscale <= 1e17) || !(cn <= 1e17) || !(fabs(m[2]) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30);
+        const double u = 5.9604644775390625e-8;
+        ln.e1 = f32_up(2.0 * u);
+        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * (cn + fabs(m[2])) + 1e-18);
+        ln.e2 = f32_up(8.0 * u);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        return ln;
+    }
+    static __device__ __forceinline__ float dist(const float* p, const Lane& ln) {
+        const float dx = p[0] - ln.cx, dy = p[1] - ln.cy;
+        return sqrtf(__builtin_fmaf(dx, dx, dy * dy));
+    }
+    // p = (x, y, -, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        const float s = dist(p, ln);
+        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, p[5], ln.e0) + ln.e2 * s);
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (cx, cy, rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;
+        const float s = dist(g, ln);
+        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, g[3], ln.e0) + ln.e2 * (s + g[2])) - g[2] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
 }  // namespace pgx

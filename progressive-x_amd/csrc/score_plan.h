@@ -98,7 +98,8 @@ inline ScorePlan plan_score(const ScoreTraits& tr, const ScoreSwitches& sw, int 
         filt32 = sw.filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24;
     if (tr.bound == kBoundBall) {      // per-pair error term, no global guard; T'' must be an ordinary f32
         filt32 = sw.filter_enabled == 1 && T2 > 1e-24 && T2 < 1e24 && std::isfinite(fscale);
-        p.guard32 = fscale;            // Filter32<kLine2D / kPlane3D / kSphere3D>::prep: overflow guard (fscale >= 1)
+        p.guard32 = fscale;            // Filter32<kLine2D / kPlane3D / kSphere3D / kCircle2D>::prep: overflow guard (fscale >= 1);
+                                       // the plan keys on `bound`: a ball-bounded type needs no line of its own here
     }
     if (tr.bound == kBoundBoxAll) {    // likewise; the bounds on T keep T2 * D~^2 (D~ >= 1e-12) inside the f32 normal range
         filt32 = sw.filter_enabled == 1 && T2 > 1e-12 && T2 < 1e12 && std::isfinite(fscale);

@@ -434,7 +434,7 @@ __global__ __launch_bounds__(SPAN) void sp_vp_bounds_kernel(const double* __rest
 
 // ---- fundamental matrices: f32 rows (x_a, y_a, x_b, y_b, 0, P, P^2, 0) and group rows of the 4-D boxes ---------------------
 // (score.hip Filter32<kFundamental>: P = max(|coordinates|, 1) rounded up)
-__global__ __launch_bounds__(kSpBlock) void sp_fund_rows_kernel(const double* __restrict__ pts, int64_t n, int d /* 4, 2 for lines, 3 for planes and spheres */,
+__global__ __launch_bounds__(kSpBlock) void sp_fund_rows_kernel(const double* __restrict__ pts, int64_t n, int d /* 4, 2 for lines and circles, 3 for planes and spheres */,
                                                                 float* __restrict__ p32, double* __restrict__ pmax)
 {
     const int64_t i = (int64_t)blockIdx.x * kSpBlock + threadIdx.x;
@@ -513,8 +513,8 @@ __global__ __launch_bounds__(SPAN) void sp_fund_bounds_kernel(const double* __re
     }
 }
 
-// 2-D lines, 3-D planes and spheres: group rows (centre[DIM], R, Pmax, 0 ...) - score.hip Filter32<kLine2D> (DIM = 2),
-// Filter32<kPlane3D> and Filter32<kSphere3D> (DIM = 3): the box centre in f64 -> f32, the radius of the ball about the STORED centre, inflated
+// 2-D lines and circles, 3-D planes and spheres: group rows (centre[DIM], R, Pmax, 0 ...) - score.hip Filter32<kLine2D> and
+// Filter32<kCircle2D> (DIM = 2), Filter32<kPlane3D> and Filter32<kSphere3D> (DIM = 3): the box centre in f64 -> f32, the radius of the ball about the STORED centre, inflated
 template <int SPAN, int DIM>
 __global__ __launch_bounds__(SPAN) void sp_line_bounds_kernel(const double* __restrict__ sp, int64_t n, float* __restrict__ rows)
 {

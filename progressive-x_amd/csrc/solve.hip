@@ -25,6 +25,10 @@
 //                                       solves a_i . e = |a_i|^2 / 2 (a_i = p_i - p0) by Cramer's rule on cross products;
 //                                       coplanar points (det == 0), non-finite values and radii outside the context's
 //                                       pgx_set_radius_range give NaN
+//   2-D circle through three points     findCircles' minimal solver (no reference counterpart): the sphere solver one dimension
+//                                       down, a_i . e = |a_i|^2 / 2 (a_i = p_i - p0) by Cramer's rule on the 2x2 system;
+//                                       collinear points (det == 0), non-finite values and radii outside the context's
+//                                       pgx_set_radius_range give NaN
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
 // inlier; the caller drops it (the reference's solvers return "no model").
@@ -163,6 +167,39 @@ __global__ __launch_bounds__(kSolveBlock) void solve_sphere_kernel(const double*
         }
     }
     for (int k = 0; k < 4; ++k) models[(int64_t)s * 4 + k] = m[k];
+}
+
+// 3-point circle: samples[S][3] -> S x 3 models (cx, cy, r).  Operation order (the contract; CircleEstimator.minimal restates it):
+//   a_i = p_i - p0 (componentwise, i = 1, 2), h_i = 0.5 (a_i0 a_i0 + a_i1 a_i1), det = a_10 a_21 - a_11 a_20,
+//   e_0 = (h_1 a_21 - h_2 a_11) / det, e_1 = (a_10 h_2 - a_20 h_1) / det, r = sqrt(e_0 e_0 + e_1 e_1), c = p0 + e.
+// An index outside 0 .. n-1, det == 0 (collinear or coincident points), a non-finite centre or radius, or r outside [rmin, rmax]
+// gives a NaN model.
+__global__ __launch_bounds__(kSolveBlock) void solve_circle_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
+                                                                   int S, double rmin, double rmax, double* __restrict__ models,
+                                                                   int* __restrict__ perm, int Mpad)
+{
+    const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
+    if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
+    if (s >= S) return;
+    const int i0 = samples[3 * s], i1 = samples[3 * s + 1], i2 = samples[3 * s + 2];
+    double m[3];
+    const double nan = __builtin_nan("");
+    m[0] = m[1] = m[2] = nan;
+    if (i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < n && i1 < n && i2 < n) {
+        const double* p0 = pts + (int64_t)i0 * 2;
+        const double* p1 = pts + (int64_t)i1 * 2;
+        const double* p2 = pts + (int64_t)i2 * 2;
+        const double a10 = p1[0] - p0[0], a11 = p1[1] - p0[1], a20 = p2[0] - p0[0], a21 = p2[1] - p0[1];
+        const double h1 = 0.5 * (a10 * a10 + a11 * a11), h2 = 0.5 * (a20 * a20 + a21 * a21);
+        const double det = a10 * a21 - a11 * a20;
+        const double e0 = (h1 * a21 - h2 * a11) / det, e1 = (a10 * h2 - a20 * h1) / det;
+        const double r = sqrt(e0 * e0 + e1 * e1);
+        const double c0 = p0[0] + e0, c1 = p0[1] + e1;
+        if (det != 0.0 && isfinite(c0) && isfinite(c1) && isfinite(r) && r >= rmin && r <= rmax) {
+            m[0] = c0; m[1] = c1; m[2] = r;
+        }
+    }
+    for (int k = 0; k < 3; ++k) models[(int64_t)s * 3 + k] = m[k];
 }
 
 // ---- P3P -------------------------------------------------------------------------------------------------------------
@@ -545,7 +582,7 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     const int mt = ctx->model_type;
     ModelInfo mi;
     if (!model_info(mt, &mi) || mi.slots == 0)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 4-point homography, 7-point fundamental matrix, P3P)", mt);
     // isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1 for these model types, so the solvers take
     // fscale, which pgx_set_points computes from the caller-visible data: umax is not kept either)
     const bool scaled = mt == kFundamental || mt == kHomography;
@@ -566,6 +603,7 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     else if (mt == kPnP) hipLaunchKernelGGL(solve_p3p_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
     else if (mt == kPlane3D) hipLaunchKernelGGL(solve_plane_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
     else if (mt == kSphere3D) hipLaunchKernelGGL(solve_sphere_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
+    else if (mt == kCircle2D) hipLaunchKernelGGL(solve_circle_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
     else if (mt == kLine2D) hipLaunchKernelGGL((solve_kernel<kLine2D>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
     else if (mt == kVanishingPoint) hipLaunchKernelGGL((solve_kernel<kVanishingPoint>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
     else return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal (internal): model type %d declares a solver that has no launch line", mt);

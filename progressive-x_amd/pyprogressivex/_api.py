@@ -1,4 +1,4 @@
-"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres, the same pipeline on 3-D point clouds), same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -305,12 +305,13 @@ def findLines(points, weights, w, h, threshold=2.0, conf=0.5, spatial_coherence_
     return _stack(est, models, 3), labels
 
 
-def _point_cloud(points, weights, n_min):
-    """the input checks of the 3-D point-cloud calls: points [n, 3] with n >= n_min, weights [n] or None; and Progressive NAPSAC's
-    grid, which starts at the corner of the bounding box of the finite coordinates and spans its extents.  Returns (points, weights, grid points, extents)."""
+def _point_cloud(points, weights, n_min, dim=3):
+    """the input checks of the point-cloud calls (3-D; dim=2: findCircles' point sets): points [n, dim] with n >= n_min, weights [n] or
+    None; and Progressive NAPSAC's grid, which starts at the corner of the bounding box of the finite coordinates and spans its
+    extents.  Returns (points, weights, grid points, extents)."""
     points = _as_f64(points)
-    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < n_min:
-        raise ValueError(f"points should be an array with dims [n,3], n>={n_min}")
+    if points.ndim != 2 or points.shape[1] != dim or points.shape[0] < n_min:
+        raise ValueError(f"points should be an array with dims [n,{dim}], n>={n_min}")
     w = None if weights is None else _weights(weights, points.shape[0])
     finite = np.isfinite(points)
     if finite.all():
@@ -322,6 +323,19 @@ def _point_cloud(points, weights, n_min):
         lo = np.where(np.isfinite(lo), lo, 0.0)
     ext = np.where(np.isfinite(ext) & (ext > 0), ext, 1.0)
     return points, w, np.ascontiguousarray(points - lo), ext
+
+
+def _radius_range(radius_range):
+    """radius_range=None or (rmin, rmax) of findSpheres / findCircles -> (rmin, rmax), checked"""
+    if radius_range is None:
+        return 0.0, np.inf
+    try:
+        rmin, rmax = (float(v) for v in radius_range)
+    except (TypeError, ValueError):
+        raise ValueError("radius_range should be a pair (rmin, rmax)") from None
+    if not (rmin >= 0.0 and rmax >= rmin):
+        raise ValueError("radius_range should satisfy 0 <= rmin <= rmax (no NaN)")
+    return rmin, rmax
 
 
 def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
@@ -356,6 +370,21 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
     return _stack(est, models, 4), labels
 
 
+def _find_round(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
+    """findSpheres / findCircles behind their signatures: the estimator says the point dimension (its model type's), the sample size
+    (= the fewest points accepted) and the columns of a model; the radius range goes to the estimator and, per call, to the context."""
+    points, w, grid_pts, ext = _point_cloud(points, weights, est.sample_size, dim=_lib.POINT_DIM[est.model_type])
+    rmin, rmax = _radius_range(radius_range)
+    if do_logging and sampler_id == 1:
+        print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
+    est.radius_range = (rmin, rmax)
+    models, labels, _ = _run(est, points, points, radius,
+                             _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
+                                              est.sample_size),
+                             do_logging=bool(do_logging), weights=w, setup=lambda ctx: ctx.set_radius_range(rmin, rmax), **run_kw)
+    return _stack(est, models, est.cols), labels
+
+
 def findSpheres(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
                 neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
                 minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
@@ -370,30 +399,37 @@ def findSpheres(points, weights=None, threshold=0.05, conf=0.5, spatial_coherenc
     is close to random; the grid's cells span caps with usable curvature.  Samplers 3 and 1 take the points as ordered by quality (every
 proposal starts from the first points): shuffle a cloud that comes in scan order.  Like findPlanes, minimum_point_number has to exceed the
     outliers a shell of width 3 x threshold holds."""
-    points, w, grid_pts, ext = _point_cloud(points, weights, 4)
-    if radius_range is None:
-        rmin, rmax = 0.0, np.inf
-    else:
-        try:
-            rmin, rmax = (float(v) for v in radius_range)
-        except (TypeError, ValueError):
-            raise ValueError("radius_range should be a pair (rmin, rmax)") from None
-        if not (rmin >= 0.0 and rmax >= rmin):
-            raise ValueError("radius_range should satisfy 0 <= rmin <= rmax (no NaN)")
-    if do_logging and sampler_id == 1:
-        print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
-    est = _estimators.SphereEstimator()
-    est.radius_range = (rmin, rmax)
-    models, labels, _ = _run(est, points, points, neighborhood_ball_radius,
-                             _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
-                                              est.sample_size),
-                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                             scoring_exponent=scoring_exponent, do_logging=bool(do_logging), weights=w, seed=seed,
-                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver,
-                             setup=lambda ctx: ctx.set_radius_range(rmin, rmax))
-    return _stack(est, models, 4), labels
+    return _find_round(_estimators.SphereEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
+                       threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                       maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                       minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                       scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                       neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                       distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+
+
+def findCircles(points, weights=None, threshold=2.0, conf=0.5, spatial_coherence_weight=0.0,
+                neighborhood_ball_radius=200.0, maximum_tanimoto_similarity=0.4, max_iters=1000,
+                minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
+                do_logging=False, *, radius_range=None, seed=None, max_outer_iterations=10, neighborhood="flann_like",
+                local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+    """Multi-circle fitting of a 2-D point set (no reference counterpart: findSpheres one dimension down, with a 3-point circle solver
+    and an algebraic refit).  points [n, 2]; returns (circles[K, 3] float64 (cx, cy, r), labels[n] int32) in findPlanes' labelling
+    convention.  threshold bounds the distance from the circle, abs(|p - c| - r); it and neighborhood_ball_radius default to findLines'
+    pixel-scale values (edge points of round parts, fiducials, arcs).  `weights` [n], when given, weight the least-squares refits.
+    radius_range=(rmin, rmax) (keyword-only; default: any radius) drops hypotheses and refits whose radius lies outside it - with straight
+    edges in the scene, an rmax of the order of the image size keeps near-lines out.  Sampler ids as findSpheres': 0 uniform, 1 PROSAC,
+    2 NAPSAC on the neighbourhood graph, 3 (the default) Progressive NAPSAC on a grid over the bounding box; any other id prints to
+    stderr and returns zero models.  Samplers 3 and 1 take the points as ordered by quality (every proposal starts from the first
+    points): shuffle a set that comes in contour order.  minimum_point_number has to exceed the outliers an annulus of width
+    3 x threshold holds."""
+    return _find_round(_estimators.CircleEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
+                       threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                       maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                       minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                       scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                       neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                       distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
 
 
 def find6DPoses(x1y1, x2y2z2, K, threshold=4.0, conf=0.90, spatial_coherence_weight=0.1,

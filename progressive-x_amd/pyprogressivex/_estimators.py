@@ -355,6 +355,71 @@ class SphereEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 2-D circle (findCircles; no reference counterpart): the sphere estimator one dimension down
+# ---------------------------------------------------------------------------------------------------------------------
+class CircleEstimator(Estimator):
+    model_type = _lib.CIRCLE2D
+    sample_size = 3
+    nonminimal_sample_size = 3
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
+    cols = 3
+    radius_range = (0.0, np.inf)   # the radii a model may have (findCircles sets it; the device solver reads pgx_set_radius_range)
+
+    def _in_range(self, r):
+        return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
+
+    def minimal(self, pts, samples):
+        """samples [S, 3] -> circles (cx, cy, r), bitwise csrc/solve.hip's solve_circle_kernel: a_i = p_i - p0,
+        h_i = 0.5 (a_i0 a_i0 + a_i1 a_i1), det = a_10 a_21 - a_11 a_20, e_0 = (h_1 a_21 - h_2 a_11) / det,
+        e_1 = (a_10 h_2 - a_20 h_1) / det, r = sqrt(e_0 e_0 + e_1 e_1), c = p0 + e.  Collinear or coincident samples (det == 0),
+        non-finite values and radii outside radius_range give no model."""
+        p0 = pts[samples[:, 0]]
+        a1, a2 = pts[samples[:, 1]] - p0, pts[samples[:, 2]] - p0
+        h1 = 0.5 * (a1[:, 0] * a1[:, 0] + a1[:, 1] * a1[:, 1])
+        h2 = 0.5 * (a2[:, 0] * a2[:, 0] + a2[:, 1] * a2[:, 1])
+        det = a1[:, 0] * a2[:, 1] - a1[:, 1] * a2[:, 0]
+        with np.errstate(all="ignore"):
+            e0 = (h1 * a2[:, 1] - h2 * a1[:, 1]) / det
+            e1 = (a1[:, 0] * h2 - a2[:, 0] * h1) / det
+            r = np.sqrt(e0 * e0 + e1 * e1)
+            models = np.column_stack([p0[:, 0] + e0, p0[:, 1] + e1, r])
+            ok = (det != 0) & np.isfinite(models).all(axis=1) & self._in_range(r)
+        return models[ok], np.nonzero(ok)[0]
+
+    def _fit(self, init):
+        """Algebraic circle fit in two Gram passes (SphereEstimator._fit one dimension down): the weighted mean o and the RMS
+        distance s from it (GRAM_AFFINE), then the smallest eigenvector theta of the Gram matrix of the rows (1, u, v, u u + v v),
+        (u, v) = (p - o) / s (GRAM_CIRCLE): theta0 + theta1..2 . q + theta3 |q|^2 = 0 is the circle |q + b|^2 = |b|^2 - theta0 / theta3
+        with b = theta1..2 / (2 theta3), so c = o - s b and r = s sqrt(|b|^2 - theta0 / theta3).  `init` is not used."""
+        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,x,y][1,x,y]^T
+        W = G[0, 0]
+        if cnt < 3 or not W > 0:
+            return []
+        o = G[0, 1:] / W
+        scatter = G[1:, 1:] - W * np.outer(o, o)
+        with np.errstate(invalid="ignore"):        # (coincident points: the trace may round below zero; the guard below catches the NaN)
+            s = np.sqrt(np.trace(scatter) / W)
+        if not (np.isfinite(o).all() and s > 0 and np.isfinite(s)):
+            return []
+        G, _, _ = yield (_lib.GRAM_CIRCLE, np.array([o[0], o[1], s]), True, 1)
+        if not np.isfinite(G).all():
+            return []
+        th = self._smallest(G[None])[0]
+        A = th[3]
+        if A == 0:
+            return []
+        b = th[1:3] / (2.0 * A)
+        rad = b @ b - th[0] / A
+        if not rad > 0:
+            return []
+        r = s * np.sqrt(rad)
+        c = o - s * b
+        if not (np.isfinite(c).all() and np.isfinite(r) and self._in_range(r)):
+            return []
+        return [np.array([c[0], c[1], r])]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # vanishing point: solver_vanishing_point_two_lines.h (in-tree, exact restatement)
 # ---------------------------------------------------------------------------------------------------------------------
 class VanishingPointEstimator(Estimator):

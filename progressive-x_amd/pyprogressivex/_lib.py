@@ -18,10 +18,12 @@ LIB_PATH = os.environ.get("PGX_LIBPGX") or os.path.join(_HERE, "libpgx.so")   # 
 
 LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM, PLANE3D = range(7)
 SPHERE3D = 8                   # (7 is not assigned: include/pgx.h)
+CIRCLE2D = 10                  # (9 is not assigned either)
 # per model type: (doubles per point, doubles per model, minimal sample size, hypotheses per sample of the device solver);
 # sample size 0 = no device solver (pgx_solve_minimal fails).  The numbers of csrc/residuals.hip.h; tests/test_abi.py compares.
 MODEL_TABLE = {LINE2D: (2, 3, 2, 1), HOMOGRAPHY: (4, 9, 4, 1), FUNDAMENTAL: (4, 9, 7, 3), PNP: (5, 12, 3, 4),
-               VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1)}
+               VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1),
+               CIRCLE2D: (2, 3, 3, 1)}
 POINT_DIM = {t: row[0] for t, row in MODEL_TABLE.items()}
 PARAM_DIM = {t: row[1] for t, row in MODEL_TABLE.items()}
 FIXED_ONE = float(1 << 32)
@@ -45,8 +47,8 @@ ABI_SYMBOLS = [
 
 
 GRAPH_KNN_IN_BALL, GRAPH_BALL, GRAPH_KNN = 0, 1, 2
-GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE = 0, 1, 2, 3, 4, 5
-GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5}   # GRAM_AFFINE: point dimension + 1
+GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE = 0, 1, 2, 3, 4, 5, 6
+GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5, GRAM_CIRCLE: 4}   # GRAM_AFFINE: point dimension + 1
 
 
 _TRIU = {}
@@ -275,7 +277,7 @@ class Context:
         self._w_obj = weights
 
     def set_radius_range(self, rmin=0.0, rmax=float("inf")):
-        """pgx_set_radius_range: the radii the 4-point sphere solver accepts (context state; [0, inf] at creation)"""
+        """pgx_set_radius_range: the radii the 4-point sphere and the 3-point circle solver accept (context state; [0, inf] at creation)"""
         self._ck(self._lib.pgx_set_radius_range(self._h, C.c_double(float(rmin)), C.c_double(float(rmax))), "pgx_set_radius_range")
 
     def _use_weights(self, weights):
@@ -488,7 +490,7 @@ class Context:
         return off, idx[:arcs], mult[:arcs]
 
     def solve_minimal(self, samples, fetch=True):
-        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, ...), generated from the
+        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, ...), generated from the
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)

@@ -121,6 +121,37 @@ def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, s
     return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(spheres).reshape(-1, 4)
 
 
+def make_circles(n_per_circle=2000, n_circles=4, n_outliers=8000, sigma=0.5, size=1000.0, radius=(40.0, 150.0), coverage=1.0, seed=0):
+    """findCircles' workload (make_spheres in 2-D, pixel scale): K non-overlapping circles with radii uniform in `radius` and centres
+    inside the box [0, size]^2 (each circle lies wholly inside it); the inliers of circle k are uniform on it - or, with coverage < 1,
+    on the arc of that fraction of the circumference around a random direction - with Gaussian noise of `sigma` along the radius;
+    the outliers are uniform in the box.  Returns (points [n, 2], labels [n] (k + 1 = circle k, 0 = outlier),
+    gt_circles [K, 3] = (cx, cy, r))."""
+    rng = np.random.default_rng(seed)
+    if not 0.0 < coverage <= 1.0:
+        raise ValueError("coverage should lie in (0, 1]")
+    circles = []
+    for _ in range(100000):
+        if len(circles) == n_circles:
+            break
+        r = rng.uniform(radius[0], radius[1])
+        c = rng.uniform(r, size - r, 2)
+        if all(np.linalg.norm(c - g[:2]) > r + g[2] for g in circles):
+            circles.append(np.array([c[0], c[1], r]))
+    if len(circles) < n_circles:
+        raise ValueError("cannot place that many non-overlapping circles in the box")
+    pts, labels = [], []
+    for k, g in enumerate(circles):
+        mid = rng.uniform(0.0, 2.0 * np.pi)
+        phi = mid + rng.uniform(-np.pi * coverage, np.pi * coverage, n_per_circle)
+        d = np.column_stack([np.cos(phi), np.sin(phi)])
+        pts.append(g[:2] + d * (g[2] + rng.normal(0, sigma, n_per_circle))[:, None])
+        labels.append(np.full(n_per_circle, k + 1))
+    pts.append(rng.uniform(0, size, (n_outliers, 2)))
+    labels.append(np.zeros(n_outliers, dtype=int))
+    return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(circles).reshape(-1, 3)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # C2  multi-homography
 # ---------------------------------------------------------------------------------------------------------------------
@@ -335,4 +366,4 @@ def misclassification_models(preferences, annotation, K_annot):
 
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
-                   vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D)
+                   vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D)
