@@ -57,44 +57,47 @@ struct Acc {
 };
 
 // row generators: Q = row length, emit(pt, prm, acc, w, bad)
-struct GenAffine2 { static constexpr int Q = 3, D = 2; };
-struct GenAffine3 { static constexpr int Q = 4, D = 3; };
-struct GenAffine4 { static constexpr int Q = 5, D = 4; };
-struct GenAffine5 { static constexpr int Q = 6, D = 5; };
 struct GenDltH { static constexpr int Q = 9, D = 4; };
 struct GenEpiF { static constexpr int Q = 9, D = 4; };
 struct GenVp { static constexpr int Q = 3, D = 4; };
 struct GenPnpGn { static constexpr int Q = 7, D = 5; };
-struct GenSphere { static constexpr int Q = 5, D = 3; };
-struct GenCircle { static constexpr int Q = 4, D = 2; };
 
+// the affine row (1, p[0], .., p[DIM - 1]) of a DIM-D point: lines (2), planes (3) and the 4- and 5-D rows
+template <int DIM> struct GenAffine {
+    static constexpr int Q = DIM + 1, D = DIM;
+    static __device__ __forceinline__ void row(const double* pt, const FitParams&, double (&a)[Q])
+    {
+        a[0] = 1.0;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) a[k + 1] = pt[k];
+    }
+};
+
+// the round family, prm = (o[DIM], s): the algebraic circle (DIM = 2) / sphere (3) row (1, u[DIM], u . u) of u = (p - o) / s,
+// the last entry a left fold: u u + v v, (u u + v v) + w w
+template <int DIM> struct GenRound {
+    static constexpr int Q = DIM + 2, D = DIM;
+    static __device__ __forceinline__ void row(const double* pt, const FitParams& prm, double (&a)[Q])
+    {
+        a[0] = 1.0;
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) a[k + 1] = (pt[k] - prm.v[k]) / prm.v[DIM];
+        double q = a[1] * a[1];
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) q = q + a[k + 1] * a[k + 1];
+        a[Q - 1] = q;
+    }
+};
+
+// one row per point for the templated generators above; the others are specialisations
 template <class G>
-__device__ __forceinline__ void emit(const double* pt, const FitParams& prm, Acc<G::Q>& acc, double w, int& bad);
+__device__ __forceinline__ void emit(const double* pt, const FitParams& prm, Acc<G::Q>& acc, double w, int&)
+{
+    double a[G::Q];
+    G::row(pt, prm, a);
+    acc.add(a, w);
+}
 
-template <>
-__device__ __forceinline__ void emit<GenAffine2>(const double* pt, const FitParams&, Acc<3>& acc, double w, int&)
-{
-    const double a[3] = {1.0, pt[0], pt[1]};
-    acc.add(a, w);
-}
-template <>
-__device__ __forceinline__ void emit<GenAffine3>(const double* pt, const FitParams&, Acc<4>& acc, double w, int&)
-{
-    const double a[4] = {1.0, pt[0], pt[1], pt[2]};
-    acc.add(a, w);
-}
-template <>
-__device__ __forceinline__ void emit<GenAffine4>(const double* pt, const FitParams&, Acc<5>& acc, double w, int&)
-{
-    const double a[5] = {1.0, pt[0], pt[1], pt[2], pt[3]};
-    acc.add(a, w);
-}
-template <>
-__device__ __forceinline__ void emit<GenAffine5>(const double* pt, const FitParams&, Acc<6>& acc, double w, int&)
-{
-    const double a[6] = {1.0, pt[0], pt[1], pt[2], pt[3], pt[4]};
-    acc.add(a, w);
-}
 // prm = (s1, cx1, cy1, s2, cx2, cy2): Hartley-normalised coordinates
 template <>
 __device__ __forceinline__ void emit<GenDltH>(const double* pt, const FitParams& prm, Acc<9>& acc, double w, int&)
@@ -141,24 +144,6 @@ __device__ __forceinline__ void emit<GenPnpGn>(const double* pt, const FitParams
     const double jv[7] = {a * (-rz) + c * ry, c * (-rx), a * rx, 0.0, a, c, dv};
     acc.add(ju, w);
     acc.add(jv, w);
-}
-
-// prm = (ox, oy, oz, s): the algebraic sphere row (1, u, v, w, (u u + v v) + w w) of (u, v, w) = (p - o) / s
-template <>
-__device__ __forceinline__ void emit<GenSphere>(const double* pt, const FitParams& prm, Acc<5>& acc, double w, int&)
-{
-    const double u = (pt[0] - prm.v[0]) / prm.v[3], v = (pt[1] - prm.v[1]) / prm.v[3], z = (pt[2] - prm.v[2]) / prm.v[3];
-    const double a[5] = {1.0, u, v, z, (u * u + v * v) + z * z};
-    acc.add(a, w);
-}
-
-// prm = (ox, oy, s): the algebraic circle row (1, u, v, u u + v v) of (u, v) = (p - o) / s
-template <>
-__device__ __forceinline__ void emit<GenCircle>(const double* pt, const FitParams& prm, Acc<4>& acc, double w, int&)
-{
-    const double u = (pt[0] - prm.v[0]) / prm.v[2], v = (pt[1] - prm.v[1]) / prm.v[2];
-    const double a[4] = {1.0, u, v, u * u + v * v};
-    acc.add(a, w);
 }
 
 template <class G>
@@ -583,16 +568,16 @@ static void with_gram_generator(int kind, int D, F&& f)
 {
     switch (kind) {
     case PGX_GRAM_AFFINE:
-        if (D == 2) f(GenAffine2{});
-        else if (D == 3) f(GenAffine3{});
-        else if (D == 4) f(GenAffine4{});
-        else f(GenAffine5{});
+        if (D == 2) f(GenAffine<2>{});
+        else if (D == 3) f(GenAffine<3>{});
+        else if (D == 4) f(GenAffine<4>{});
+        else f(GenAffine<5>{});
         break;
     case PGX_GRAM_DLT_H: f(GenDltH{}); break;
     case PGX_GRAM_EPI_F: f(GenEpiF{}); break;
     case PGX_GRAM_VP: f(GenVp{}); break;
-    case PGX_GRAM_SPHERE: f(GenSphere{}); break;
-    case PGX_GRAM_CIRCLE: f(GenCircle{}); break;
+    case PGX_GRAM_SPHERE: f(GenRound<3>{}); break;
+    case PGX_GRAM_CIRCLE: f(GenRound<2>{}); break;
     default: f(GenPnpGn{}); break;
     }
 }

@@ -1,4 +1,5 @@
-// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types, 3-D planes and spheres, 2-D circles, gfx950 device code.
+// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the two families of geometric
+// primitives: flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension.  gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -37,12 +38,18 @@ template <int MT> struct Residual;
 
 struct NoProjectiveMap { static constexpr int obs0 = -1, in0 = 0, in1 = -1, box1 = -1; };
 
-// Default2DLineEstimator (progressivex_python.cpp:489) [U-4]: model (a,b,c), r = |a x + b y + c|.
-template <> struct Residual<kLine2D> : NoProjectiveMap {
-    static constexpr int D = 2, P = 3, sample = 2, slots = 1, bound = kBoundBall;
+// The flat family: a hyperplane of DIM-space, model (n[DIM], d), r = |n . p + d| with the sum a left fold -
+//   DIM = 2   |(a x + b y) + c|             2-D lines: Default2DLineEstimator (progressivex_python.cpp:489) [U-4]
+//   DIM = 3   |((a x + b y) + c z) + d|     3-D planes (findPlanes; no reference counterpart), (a, b, c) a unit normal
+// This operation order is the contract of every line and plane check (tests restate it in numpy).
+template <int DIM> struct FlatResidual : NoProjectiveMap {
+    static constexpr int D = DIM, P = DIM + 1, slots = 1, bound = kBoundBall;
     template <class PT, class MD>
     static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
-        return fabs(m[0] * p[0] + m[1] * p[1] + m[2]);
+        double s = m[0] * p[0];
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) s = s + m[k] * p[k];
+        return fabs(s + m[DIM]);
     }
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
@@ -50,6 +57,34 @@ template <> struct Residual<kLine2D> : NoProjectiveMap {
         return r * r;
     }
 };
+template <> struct Residual<kLine2D> : FlatResidual<2> { static constexpr int sample = 2; };
+template <> struct Residual<kPlane3D> : FlatResidual<3> { static constexpr int sample = 3; };
+
+// The round family (no reference counterpart): a sphere of DIM-space, model (c[DIM], cr), d = p - c componentwise,
+// r = |sqrt(d . d) - cr| with the sum a left fold, plain IEEE sqrt (no intrinsic, no contraction) -
+//   DIM = 2   |sqrt(dx dx + dy dy) - cr|               2-D circles (findCircles)
+//   DIM = 3   |sqrt((dx dx + dy dy) + dz dz) - cr|     3-D spheres (findSpheres)
+// This operation order is the contract of every circle and sphere check (tests restate it in numpy).
+template <int DIM> struct RoundResidual : NoProjectiveMap {
+    static constexpr int D = DIM, P = DIM + 1, slots = 1, bound = kBoundBall;
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        double d[DIM];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) d[k] = p[k] - m[k];
+        double q = d[0] * d[0];
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) q = q + d[k] * d[k];
+        return fabs(sqrt(q) - m[DIM]);
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double r = plain(p, m);
+        return r * r;
+    }
+};
+template <> struct Residual<kCircle2D> : RoundResidual<2> { static constexpr int sample = 3; };
+template <> struct Residual<kSphere3D> : RoundResidual<3> { static constexpr int sample = 4; };
 
 // DefaultHomographyEstimator (progressivex_python.cpp:252) [U-1]: one-way forward transfer error,
 // H row-major 3x3 (progressivex_python.cpp:292-300).
@@ -137,56 +172,6 @@ template <> struct Residual<kVanishingPoint> : NoProjectiveMap {
         const double ly = -(mx * v[2] - v[0]);
         const double lz = mx * v[1] - my * v[0];
         return fabs(lx * p[0] + ly * p[1] + lz) / sqrt(lx * lx + ly * ly);
-    }
-    template <class PT, class MD>
-    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
-        const double r = plain(p, m);
-        return r * r;
-    }
-};
-
-// 3-D planes (findPlanes; no reference counterpart - the line construction one dimension up): model (a,b,c,d) with (a,b,c)
-// a unit normal, r = |((a x + b y) + c z) + d|, summed left to right.  This operation order is the contract of every plane
-// check (tests restate it in numpy).
-template <> struct Residual<kPlane3D> : NoProjectiveMap {
-    static constexpr int D = 3, P = 4, sample = 3, slots = 1, bound = kBoundBall;
-    template <class PT, class MD>
-    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
-        return fabs(((m[0] * p[0] + m[1] * p[1]) + m[2] * p[2]) + m[3]);
-    }
-    template <class PT, class MD>
-    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
-        const double r = plain(p, m);
-        return r * r;
-    }
-};
-
-// 3-D spheres (findSpheres; no reference counterpart): model (cx, cy, cz, r), dx = x - cx, dy = y - cy, dz = z - cz,
-// r = |sqrt((dx dx + dy dy) + dz dz) - cr|, summed left to right, plain IEEE sqrt (no intrinsic, no contraction).  This
-// operation order is the contract of every sphere check (tests restate it in numpy).
-template <> struct Residual<kSphere3D> : NoProjectiveMap {
-    static constexpr int D = 3, P = 4, sample = 4, slots = 1, bound = kBoundBall;
-    template <class PT, class MD>
-    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
-        const double dx = p[0] - m[0], dy = p[1] - m[1], dz = p[2] - m[2];
-        return fabs(sqrt((dx * dx + dy * dy) + dz * dz) - m[3]);
-    }
-    template <class PT, class MD>
-    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
-        const double r = plain(p, m);
-        return r * r;
-    }
-};
-
-// 2-D circles (findCircles; no reference counterpart - the sphere one dimension down): model (cx, cy, r), dx = x - cx, dy = y - cy,
-// r = |sqrt(dx dx + dy dy) - cr|, plain IEEE sqrt (no intrinsic, no contraction).  This operation order is the contract of every
-// circle check (tests restate it in numpy).
-template <> struct Residual<kCircle2D> : NoProjectiveMap {
-    static constexpr int D = 2, P = 3, sample = 3, slots = 1, bound = kBoundBall;
-    template <class PT, class MD>
-    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
-        const double dx = p[0] - m[0], dy = p[1] - m[1];
-        return fabs(sqrt(dx * dx + dy * dy) - m[2]);
     }
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& m) {

@@ -455,240 +455,189 @@ template <> struct Filter32<kHomographySym> : Filter32<kHomography> {
     }
 };
 
-// ---- 2-D lines [U-4]: r = |a x + b y + c| (Residual<kLine2D>), inlier iff r^2 < T2 ------------------------------------------------
-// Three f32 FMAs; with P = max(|x|, |y|, 1) rounded up, u = 2^-24, eta = 2^-126:
-//   |n~ - n*| + |n_c - n*| (the exact path's own rounding)  <= E = 4.1 u ((|a| + |b|) P + |c|) + 4 eta P
-//   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  then |n_c| > T (1 + 2^-6) and the computed r_c^2 = fl(n_c^2) > T2.
-// A hypothesis with an entry times the largest P of the set beyond 1e36 gets E = inf (never rejected), one with a NaN entry
-// is culled outright (all three entries enter every residual).  Group test on the 2-D box of 64 Morton-consecutive points
-// (centre, radius R): |n(x)| >= |n(centre)| - ||(a, b)|| R, the error term at the group's largest P.  The dense kernel costs
-// ~10 instructions per pair, so the filter itself buys nothing - the cull does: a line's inliers are a strip of width 2T.
-template <> struct Filter32<kLine2D> {
+// ---- the flat family: 2-D lines [U-4] and 3-D planes, r = |n . p + d| (FlatResidual<DIM>), inlier iff r^2 < T2 ------------------
+// The model is homogeneous: the f32 copies are made from the model after the exact power-of-two scaling and tested against the
+// threshold scaled along (Ts = T sc must be an ordinary f32 as well).  Per point, DIM + 1 inputs and DIM f32 FMAs, right-nested with
+// the constant innermost - this operation order is the contract of the f32 test (tests restate it in numpy):
+//   DIM = 2   n~ = fma(a~, x~, fma(b~, y~, c~))                         P = max(|x|, |y|, 1) rounded up
+//   DIM = 3   n~ = fma(a~, x~, fma(b~, y~, fma(c~, z~, d~)))            P = max(|x|, |y|, |z|, 1) rounded up
+// every input rounded to f32; u = 2^-24, eta = 2^-126.  Relative roundings each term of n* = n . p + d carries in the f32 chain (its
+// two inputs, and every fma from its own outwards):
+//                       DIM = 2                        DIM = 3
+//   a x                 a~, x~, the outer fma     3    a~, x~, the outer fma          3
+//   b y                 b~, y~, both fmas         4    b~, y~, the two outer fmas     4
+//   c z                 -                              c~, z~, all three fmas         5
+//   constant term       c~, both fmas             3    d~, all three fmas             4
+// so |n~ - n*| <= k u (sum |n_j p_j| + |d|) + O(u^2) with k = 4 (DIM = 2), 5 (DIM = 3); the exact path's own f64 chain (product and
+// DIM sums: <= (DIM + 1) * 2^-53 per term) and the O(u^2) terms fit in the extra 0.1 u.  Absolute (subnormal) errors, each < eta: the
+// DIM coefficients times a coordinate (DIM eta P), the DIM coordinates times a coefficient of magnitude < 1 (the normaliser: DIM eta),
+// the DIM fma results and the constant's copy (DIM + 1 eta): 3 eta P + 7 eta <= 6 eta P + 4 eta for P >= 1 (DIM = 3); 2 eta P + 5 eta
+// <= 4 eta P + eta for P >= 2 (DIM = 2), and below that the missing 4 eta vanish in the 0.1 u slack, which is at least 0.05 u: the
+// normaliser leaves the largest entry in [0.5, 1), so S P + |d| >= 0.5 (sc = 1 for an all-zero model, which is switched off below).
+// Hence, with S = sum |n_j|,
+//   |n~ - n*| + |n_c - n*| (the exact path's own rounding)  <=  E = e1 P + e0
+//                 e1                       e0
+//   DIM = 2       4.1 u S + 4 eta          4.1 u |d| + eta
+//   DIM = 3       5.1 u S + 6 eta          5.1 u |d| + 4 eta             (kept as the literals of FlatBudget<DIM>, not computed)
+//   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  then |n_c| > T (1 + 2^-7) (m itself is rounded once) and the computed
+//   r_c^2 = fl(n_c^2) > T2.
+// Group test on the DIM-ball (centre, radius R, Pmax) of 64 Morton-consecutive points (sp_line_bounds_kernel<SPAN, DIM>): for p in
+// the ball |n(p)| >= |n(centre)| - ||n|| R, the error term taken at the group's largest P (which bounds the stored centre too):
+//   reject the group  <=>  |n~(centre)| - ||n|| R - E(Pmax) > T''  (each factor inflated by 1.001).
+// Switch-off: a coefficient times the set's largest P beyond 1e36, a constant term beyond 1e36, a threshold outside the ordinary f32
+// range or a model outside pow2_normaliser's band gives E = inf (never rejected); a NaN entry culls the hypothesis outright (all
+// DIM + 1 entries enter every residual).  The dense kernel costs ~10 instructions per pair, so the filter itself buys nothing - the
+// cull does: a line's inliers are a strip, a plane's a slab of width 2T, and the cull removes most (hypothesis, group) pairs.
+template <int DIM> struct FlatBudget;
+template <> struct FlatBudget<2> { static constexpr double k = 4.1, eta1 = 4.0, eta0 = 1.0; };
+template <> struct FlatBudget<3> { static constexpr double k = 5.1, eta1 = 6.0, eta0 = 4.0; };
+
+template <int DIM> struct FlatFilter32 {
     static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 4;
-    struct Lane { float a, b, c, e1, e0, nrm, tpp, nanh; };
+    static constexpr int kRowVals = 6, kGroupVals = DIM + 2;
+    struct Lane { float n[DIM + 1]; float e1, e0, nrm, tpp, nanh; };   // a row of floats in this order (score.hip HypRow)
+    static_assert(offsetof(Lane, e1) == (DIM + 1) * sizeof(float) && offsetof(Lane, nanh) == (DIM + 5) * sizeof(float) &&
+                  sizeof(Lane) == (DIM + 6) * sizeof(float), "coefficients, e1, e0, nrm, tpp, nanh");
     template <class MD> static __device__ __forceinline__ Lane prep(const MD& m0, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
         Lane ln;
-        // r = |a x + b y + c| scales with the model: the scaled copy is tested against the scaled threshold (sc is a power of two)
+        // r = |n . p + d| scales with the model: the scaled copy is tested against the scaled threshold (sc is a power of two)
         bool off;
-        const double sc = pow2_normaliser<3>(m0, &off);
-        const double m[3] = {m0[0] * sc, m0[1] * sc, m0[2] * sc};
-        ln.a = (float)m[0]; ln.b = (float)m[1]; ln.c = (float)m[2];
-        ln.nanh = (m0[0] == m0[0] && m0[1] == m0[1] && m0[2] == m0[2]) ? 0.0f : 1.0f;
+        const double sc = pow2_normaliser<DIM + 1>(m0, &off);
+        double m[DIM + 1];
+        bool nan = false;
+#pragma unroll
+        for (int k = 0; k <= DIM; ++k) { m[k] = m0[k] * sc; ln.n[k] = (float)m[k]; nan |= !(m0[k] == m0[k]); }
+        ln.nanh = nan ? 1.0f : 0.0f;
         const double Ts = sqrt(T2) * sc;   // the threshold in the scaled model's units: must be an ordinary f32 as well
-        const bool big = !(fabs(m[0]) * pscale <= 1e36) || !(fabs(m[1]) * pscale <= 1e36) || !(fabs(m[2]) <= 1e36) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
+        bool big = !(fabs(m[DIM]) <= 1e36) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
+        double l1 = fabs(m[0]), n2 = m[0] * m[0];
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) { l1 = l1 + fabs(m[k]); n2 = n2 + m[k] * m[k]; }
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) big |= !(fabs(m[k]) * pscale <= 1e36);
+        using B = FlatBudget<DIM>;
         const double u = 5.9604644775390625e-8, eta = 1.1754943508222875e-38;
-        ln.e1 = f32_up(4.1 * u * (fabs(m[0]) + fabs(m[1])) + 4.0 * eta);
-        ln.e0 = big ? __builtin_inff() : f32_up(4.1 * u * fabs(m[2]) + eta);
-        ln.nrm = f32_up(sqrt(m[0] * m[0] + m[1] * m[1]) * 1.001);
+        ln.e1 = f32_up(B::k * u * l1 + B::eta1 * eta);
+        ln.e0 = big ? __builtin_inff() : f32_up(B::k * u * fabs(m[DIM]) + B::eta0 * eta);
+        ln.nrm = f32_up(sqrt(n2) * 1.001);
         ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
         return ln;
     }
-    // p = (x, y, -, -, -, P, -, -) in f32
+    static __device__ __forceinline__ float dot(const float* p, const Lane& ln) {
+        float n = ln.n[DIM];
+#pragma unroll
+        for (int k = DIM - 1; k >= 0; --k) n = __builtin_fmaf(ln.n[k], p[k], n);
+        return n;
+    }
+    // p = (coordinates[DIM], -, .., P, -, -) in f32, P at p[5]
     static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
-        const float n = __builtin_fmaf(ln.a, p[0], __builtin_fmaf(ln.b, p[1], ln.c));
-        const float m = fabsf(n) - __builtin_fmaf(ln.e1, p[5], ln.e0);
+        const float m = fabsf(dot(p, ln)) - __builtin_fmaf(ln.e1, p[5], ln.e0);
         return m > ln.tpp;  // false on NaN / inf - inf
     }
-    // g = (cx, cy, R, Pmax)
+    // g = (centre[DIM], R, Pmax)
     static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
         if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
-        const float n = __builtin_fmaf(ln.a, g[0], __builtin_fmaf(ln.b, g[1], ln.c));
-        const float m = fabsf(n) - __builtin_fmaf(ln.e1, g[3], ln.e0) - ln.nrm * g[2] * 1.001f;
+        const float m = fabsf(dot(g, ln)) - __builtin_fmaf(ln.e1, g[DIM + 1], ln.e0) - ln.nrm * g[DIM] * 1.001f;
         return m > ln.tpp * 1.001f;
     }
 };
+template <> struct Filter32<kLine2D> : FlatFilter32<2> {};
+template <> struct Filter32<kPlane3D> : FlatFilter32<3> {};
 
-// ---- 3-D planes: r = |((a x + b y) + c z) + d| (Residual<kPlane3D>), inlier iff r^2 < T2 -----------------------------------------
-// The line filter one dimension up.  n~ = fma(a~, x~, fma(b~, y~, fma(c~, z~, d~))) with every input rounded to f32 (the model
-// after the exact power-of-two scaling), u = 2^-24, eta = 2^-126, P = max(|x|, |y|, |z|, 1) rounded up.  Relative roundings each
-// term of n* = a x + b y + c z + d carries in the f32 chain:
-//   a x: a~, x~, the outer fma                    3        c z: c~, z~, all three fmas             5
-//   b y: b~, y~, the two outer fmas               4        d:   d~, all three fmas                 4
-// so |n~ - n*| <= 5 u (|a x| + |b y| + |c z| + |d|) + O(u^2); the exact path's own f64 chain (product, three sums: <= 4 * 2^-53
-// per term) and the O(u^2) terms fit in the extra 0.1 u.  Absolute (subnormal) errors, each < eta: the three coefficients a, b, c
-// times a coordinate (3 eta P), the three coordinates times a coefficient of magnitude < 1 (the normaliser: 3 eta), the three fma
-// results and d~ (4 eta) - at most 3 eta P + 7 eta <= 6 eta P + 4 eta for P >= 1.  Hence
-//   |n~ - n*| + |n_c - n*|  <=  E = 5.1 u ((|a| + |b| + |c|) P + |d|) + 6 eta P + 4 eta
-//   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  then |n_c| > T (1 + 2^-7) (m itself is rounded once) and fl(n_c^2) > T2.
-// The group test works on the 3-D ball (centre, radius R) of 64 Morton-consecutive points: for p in the ball
-// |n(p)| >= |n(centre)| - ||(a, b, c)|| R, the error term taken at the group's largest P (which bounds the stored centre too):
-//   reject the group  <=>  |n~(centre)| - ||(a, b, c)|| R - E(Pmax) > T''  (each factor inflated by 1.001).
-// Same switch-off as the line: an entry times the set's largest P beyond 1e36, a threshold outside the ordinary f32 range or a
-// model outside pow2_normaliser's band gives E = inf (never rejected); a NaN entry culls the hypothesis (all four enter every
-// residual).  On a planar scene a plane's inliers are a slab of width 2T, so the cull removes most (hypothesis, group) pairs.
-template <> struct Filter32<kPlane3D> {
-    static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 5;
-    struct Lane { float a, b, c, d, e1, e0, nrm, tpp, nanh; };
-    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m0, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
-        Lane ln;
-        bool off;
-        const double sc = pow2_normaliser<4>(m0, &off);
-        const double m[4] = {m0[0] * sc, m0[1] * sc, m0[2] * sc, m0[3] * sc};
-        ln.a = (float)m[0]; ln.b = (float)m[1]; ln.c = (float)m[2]; ln.d = (float)m[3];
-        ln.nanh = (m0[0] == m0[0] && m0[1] == m0[1] && m0[2] == m0[2] && m0[3] == m0[3]) ? 0.0f : 1.0f;
-        const double Ts = sqrt(T2) * sc;
-        const bool big = !(fabs(m[0]) * pscale <= 1e36) || !(fabs(m[1]) * pscale <= 1e36) || !(fabs(m[2]) * pscale <= 1e36) ||
-                         !(fabs(m[3]) <= 1e36) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
-        const double u = 5.9604644775390625e-8, eta = 1.1754943508222875e-38;
-        ln.e1 = f32_up(5.1 * u * (fabs(m[0]) + fabs(m[1]) + fabs(m[2])) + 6.0 * eta);
-        ln.e0 = big ? __builtin_inff() : f32_up(5.1 * u * fabs(m[3]) + 4.0 * eta);
-        ln.nrm = f32_up(sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) * 1.001);
-        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
-        return ln;
-    }
-    // p = (x, y, z, -, -, P, -, -) in f32
-    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
-        const float n = __builtin_fmaf(ln.a, p[0], __builtin_fmaf(ln.b, p[1], __builtin_fmaf(ln.c, p[2], ln.d)));
-        const float m = fabsf(n) - __builtin_fmaf(ln.e1, p[5], ln.e0);
-        return m > ln.tpp;  // false on NaN / inf - inf
-    }
-    // g = (cx, cy, cz, R, Pmax)
-    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
-        if (ln.nanh != 0.0f) return true;
-        const float n = __builtin_fmaf(ln.a, g[0], __builtin_fmaf(ln.b, g[1], __builtin_fmaf(ln.c, g[2], ln.d)));
-        const float m = fabsf(n) - __builtin_fmaf(ln.e1, g[4], ln.e0) - ln.nrm * g[3] * 1.001f;
-        return m > ln.tpp * 1.001f;
-    }
-};
-
-// ---- 3-D spheres: r = |sqrt((dx dx + dy dy) + dz dz) - cr| (Residual<kSphere3D>), inlier iff r^2 < T2 -------------------------------
+// ---- the round family: 2-D circles and 3-D spheres, r = |sqrt(d . d) - cr| (RoundResidual<DIM>), inlier iff r^2 < T2 ----------------
 // Not homogeneous in the model (the centre is a point, the radius a length): no power-of-two scaling, the f32 copies are the model's
-// entries rounded once.  Per point, in f32: d~ = p~ - c~, q~ = fma(dx, dx, fma(dy, dy, dz dz)), s~ = sqrtf(q~), n~ = s~ - r~.  With
-// u = 2^-24, eta = 2^-126, s* = |p - c| (exact), P = max(|x|, |y|, |z|, 1) rounded up, |.| the Euclidean norm:
-//   inputs     |p~ - p| <= u |p| <= sqrt(3) u P,  |c~ - c| <= u |c|,  |r~ - cr| <= u |cr|
-//   d~         one rounding per component: |d~ - (p~ - c~)| <= u |p~ - c~| <= u s* + O(u^2)
-//   q~         three non-negative terms, at most three roundings each: q~ = |d~|^2 (1 + t), |t| <= 3 u + O(u^2) -> sqrt: 1.5 u
+// entries rounded once.  Per point, in f32, right-nested with the innermost term a plain product - this operation order is the
+// contract of the f32 test (tests restate it in numpy):
+//   d~ = p~ - c~ (componentwise),  s~ = sqrtf(q~),  n~ = s~ - r~,
+//   DIM = 2   q~ = fma(dx, dx, dy dy)                     P = max(|x|, |y|, 1) rounded up
+//   DIM = 3   q~ = fma(dx, dx, fma(dy, dy, dz dz))        P = max(|x|, |y|, |z|, 1) rounded up
+// With u = 2^-24, eta = 2^-126, s* = |p - c| (exact), |.| the Euclidean norm; every coefficient derived for both term counts:
+//   inputs     |p~ - p| <= u |p| <= sqrt(DIM) u P  (sqrt(2) u P | sqrt(3) u P),  |c~ - c| <= u |c|,  |r~ - cr| <= u |cr|;  s is
+//              1-Lipschitz in p and in c, so these move s by at most sqrt(DIM) u P + u |c|, and n by u |cr| more
+//   d~         one rounding per component: |d~ - (p~ - c~)| <= u |p~ - c~| <= u s* + O(u^2)                       (both dimensions)
+//   q~         DIM non-negative terms; the innermost is rounded as a product and again by every fma outside it, the outermost by its
+//              fma alone: at most DIM roundings on a term, q~ = |d~|^2 (1 + t), |t| <= DIM u + O(u^2) -> after the root DIM / 2 u
+//              (DIM = 2: dy dy 2 roundings, dx dx 1, 2 u -> 1 u  |  DIM = 3: at most three each, 3 u -> 1.5 u)
 //   sqrtf      gfx950 lowers sqrtf (no fast-math) to v_sqrt_f32 plus a correction step and a denormal scaling; the budget takes
-//              only v_sqrt_f32's documented 1 ulp = 2 u (correct rounding would be u)
-//   exact path d, q, sqrt and the final subtraction in f64: <= 3.5 * 2^-53 s* + 2^-53 |s_c - cr|  (~0.25 u s*, and the 2^-53 term
-//              is part of the T'' margin below)
-// so |(s~ - r~) - (s_c - cr)| <= sqrt(3) u P + u (|c| + |cr|) + (1 + 1.5 + 2 + 0.25) u s* + O(u^2).  Underflow: the squares and
-// sums below 2^-126 carry absolute errors <= eta each (even with denormals flushed), which move sqrt by <= sqrt(4 eta) < 2.2e-19.
-// The budget rounds every coefficient up by more than 10 % (which also pays for evaluating E itself in f32, and for the rounding of
-// n~, u |s~ - r~| <= u s~ + u |cr|):
-//   E = e1 P + e0 + e2 s~,   e1 = 2 u,   e0 = 2 u (|c| + |cr|) + 1e-18,   e2 = 8 u     (s~ for s*: the difference is O(u))
+//              only v_sqrt_f32's documented 1 ulp = 2 u, whatever correction the lowering adds (correct rounding would be u)
+//   exact path d (1 rounding), the sum of squares (DIM = 2: 2 on the larger term -> 1 after the root), sqrt (1), in f64:
+//              <= 3 * 2^-53 s* < 0.01 u s* (DIM = 2), <= 3.5 * 2^-53 s* (~0.25 u s* is charged, DIM = 3); and 2^-53 |s_c - cr| for the
+//              final subtraction, which is part of the T'' margin below
+//   n~         the subtraction s~ - r~ is rounded once, relatively: n~ = (s~ - r~)(1 + t), |t| <= u (<= u s~ + u |cr|).  It is charged
+//              to the T'' margin and not to E: m > T'' gives |s~ - r~| >= (T'' + E) (1 - u), and T (1 + 2^-6)(1 - u) > T (1 + 2^-7),
+//              E (1 - u) >= the sum of the terms above as soon as E carries a relative margin of u over them (it carries > 10 %)
+// so |(s~ - r~) - (s_c - cr)| <= sqrt(DIM) u P + u (|c| + |cr|) + k_s u s* + O(u^2),
+//              k_s = 1 + 1 + 2 + 0.01 = 4.01 (DIM = 2),   1 + 1.5 + 2 + 0.25 = 4.75 (DIM = 3).
+// Underflow: the products and fmas below 2^-126 carry absolute errors <= eta each (even with denormals flushed), and a subnormal
+// difference d~ is exact (flushed: off by < eta, which moves s by < 2 eta); DIM = 2: 2 eta under the root move it by <= sqrt(2 eta) <
+// 1.6e-19, DIM = 3: 4 eta, sqrt(4 eta) < 2.2e-19.
+// One set of coefficients serves both dimensions; each bounds its term with room (more than 10 % for DIM = 3, more for DIM = 2) for
+// evaluating E itself in f32 (three roundings, < 4 u relative) and for writing s~ for s* (the difference is O(u) s*):
+//   E = e1 P + e0 + e2 s~     e1 = 2 u                          >= 1.41 * sqrt(2) u,  1.15 * sqrt(3) u
+//                             e0 = 2 u (|c| + |cr|) + 1e-18     >= 2 * u (|c| + |cr|) + 6 * 1.6e-19, + 4 * 2.2e-19   (|c| inflated by 1.001 on top)
+//                             e2 = 8 u                          >= 1.99 * 4.01 u,  1.68 * 4.75 u
 //   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  m is rounded once and monotonically, so |s_c - cr| > T (1 + 2^-7), and the
 //   computed r_c^2 = fl(fl(|s_c - cr|)^2) > T2.
-// Group test on the 3-D ball (stored centre g, radius rho, Pmax) of 64 Morton-consecutive points (sp_line_bounds_kernel<SPAN, 3>):
-// every member's distance to the centre lies in [s_g - rho, s_g + rho] with s_g = |g - c| (g is an f32 value, no input rounding),
-// so its residual is at least the distance from r to that interval, |s_g - cr| - rho, less the errors above with P = Pmax and
-// s* <= s_g + rho:
+// Group test on the DIM-ball (stored centre g, radius rho, Pmax) of 64 Morton-consecutive points (sp_line_bounds_kernel<SPAN, DIM>,
+// the rows of the flat family): every member's distance to the model's centre lies in [s_g - rho, s_g + rho], s_g = |g - c| (g is an
+// f32 value: no input rounding, the e1 Pmax term is kept all the same), so its residual is at least the distance from cr to that
+// interval, |s_g - cr| - rho, less the errors above with P = Pmax and s* <= s_g + rho:
 //   reject the group  <=>  |s~_g - r~| - E(Pmax, s~_g + rho) - 1.001 rho > 1.001 T''.
-// One rule for points outside the shell, inside it and for r < 0 (then every residual is s + |r|).  A NaN entry culls the hypothesis
-// (all four enter every residual).  A set with coordinates beyond 1e17, a centre or radius beyond 1e17 (q~ must stay below the f32
-// overflow) or a threshold outside the ordinary f32 range gives E = inf: never rejected, the exact path decides (r = inf included:
-// inf - inf is NaN, and a NaN comparison is false).  Scenes far from the origin lose the filter's precision (e1 P grows with the
-// offset, not with the scene): correct, only slower.
-template <> struct Filter32<kSphere3D> {
-    static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 5;
-    struct Lane { float cx, cy, cz, r, e1, e0, e2, tpp, nanh; };
-    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
-        Lane ln;
-        ln.cx = (float)m[0]; ln.cy = (float)m[1]; ln.cz = (float)m[2]; ln.r = (float)m[3];
-        ln.nanh = (m[0] == m[0] && m[1] == m[1] && m[2] == m[2] && m[3] == m[3]) ? 0.0f : 1.0f;
-        const double Ts = sqrt(T2);
-        const double cn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
-        const bool big = !(pscale <= 1e17) || !(cn <= 1e17) || !(fabs(m[3]) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30);
-        const double u = 5.9604644775390625e-8;
-        ln.e1 = f32_up(2.0 * u);
-        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * (cn + fabs(m[3])) + 1e-18);
-        ln.e2 = f32_up(8.0 * u);
-        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
-        return ln;
-    }
-    static __device__ __forceinline__ float dist(const float* p, const Lane& ln) {
-        const float dx = p[0] - ln.cx, dy = p[1] - ln.cy, dz = p[2] - ln.cz;
-        return sqrtf(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz)));
-    }
-    // p = (x, y, z, -, -, P, -, -) in f32
-    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
-        const float s = dist(p, ln);
-        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, p[5], ln.e0) + ln.e2 * s);
-        return m > ln.tpp;  // false on NaN / inf - inf
-    }
-    // g = (cx, cy, cz, rho, Pmax)
-    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
-        if (ln.nanh != 0.0f) return true;
-        const float s = dist(g, ln);
-        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, g[4], ln.e0) + ln.e2 * (s + g[3])) - g[3] * 1.001f;
-        return m > ln.tpp * 1.001f;
-    }
-};
-
-// ---- 2-D circles: r = |sqrt(dx dx + dy dy) - cr| (Residual<kCircle2D>), inlier iff r^2 < T2 --------------------------------------
-// The sphere filter one dimension down, on the 2-D rows the line filter reads.  No scaling of the model; the f32 copies are its
-// entries rounded once.  Per point, in f32: d~ = p~ - c~, q~ = fma(dx, dx, dy dy), s~ = sqrtf(q~), n~ = s~ - r~.  With u = 2^-24,
-// eta = 2^-126, s* = |p - c| (exact), P = max(|x|, |y|, 1) rounded up, |.| the Euclidean norm, every coefficient re-derived for the
-// two-term case and set against the sphere's:
-//   inputs     |p~ - p| <= u |p| <= sqrt(2) u P  (sphere: sqrt(3) u P),  |c~ - c| <= u |c|,  |r~ - cr| <= u |cr|;  s is 1-Lipschitz
-//              in p and in c, so these move s by at most sqrt(2) u P + u |c|, and n by u |cr| more
-//   d~         one rounding per component: |d~ - (p~ - c~)| <= u |p~ - c~| <= u s* + O(u^2)                              (as the sphere)
-//   q~         two non-negative terms: dy dy is rounded as a product and again by the fma (2 roundings), dx dx by the fma alone
-//              (1): q~ = |d~|^2 (1 + t), |t| <= 2 u + O(u^2) -> sqrt: 1 u                                          (sphere: 3 u -> 1.5 u)
-//   sqrtf      v_sqrt_f32's documented 1 ulp = 2 u, whatever correction the lowering adds                               (as the sphere)
-//   exact path d (1 rounding), dx dx + dy dy (2 on the larger term -> 1 after the root), sqrt (1): <= 3 * 2^-53 s* < 0.01 u s*, and
-//              2^-53 |s_c - cr| for the final subtraction, which is part of the T'' margin below            (sphere: 3.5 * 2^-53 s*)
-//   n~         the subtraction s~ - r~ is rounded once, relatively: n~ = (s~ - r~)(1 + t), |t| <= u.  It is charged to the T'' margin
-//              and not to E: m > T'' gives |s~ - r~| >= (T'' + E) (1 - u), and T (1 + 2^-6)(1 - u) > T (1 + 2^-7), E (1 - u) >= the sum
-//              of the terms above as soon as E carries a relative margin of u over them (it carries > 40 %)
-// so |(s~ - r~) - (s_c - cr)| <= sqrt(2) u P + u (|c| + |cr|) + (1 + 1 + 2 + 0.01) u s* + O(u^2).  Underflow: the product dy dy and the
-// fma below 2^-126 carry absolute errors <= eta each (even with denormals flushed), and a subnormal difference d~ is exact (flushed: off by
-// < eta, which moves s by < 2 eta); 2 eta under the root move it by <= sqrt(2 eta) < 1.6e-19                                         (sphere: sqrt(4 eta) < 2.2e-19)
-// The sphere's coefficients are reused, and each bounds its 2-D counterpart with room for evaluating E itself in f32 (three
-// roundings, < 4 u relative) and for writing s~ for s* (the difference is O(u) s*):
-//   E = e1 P + e0 + e2 s~     e1 = 2 u                          >= 1.41 * sqrt(2) u
-//                             e0 = 2 u (|c| + |cr|) + 1e-18     >= 2 * u (|c| + |cr|) + 6 * 1.6e-19     (|c| is inflated by 1.001 on top)
-//                             e2 = 8 u                          >= 1.99 * 4.01 u
-//   reject  <=>  m := |n~| - E > T'' = T (1 + 2^-6):  m is rounded once and monotonically, so |s_c - cr| > T (1 + 2^-7), and the
-//   computed r_c^2 = fl(fl(|s_c - cr|)^2) > T2.
-// Group test on the 2-D ball (stored centre g, radius rho, Pmax) of 64 Morton-consecutive points (sp_line_bounds_kernel<SPAN, 2>,
-// the rows of Filter32<kLine2D>): every member's distance to the circle's centre lies in [s_g - rho, s_g + rho], s_g = |g - c| (g is
-// an f32 value: no input rounding, the e1 Pmax term is kept all the same), so its residual is at least |s_g - cr| - rho less the
-// errors above with P = Pmax and s* <= s_g + rho:
-//   reject the group  <=>  |s~_g - r~| - E(Pmax, s~_g + rho) - 1.001 rho > 1.001 T''.
-// One rule for points outside the circle, inside it, for r = 0 (the residual is s) and for r < 0 (every residual is s + |r|).  A NaN
-// entry culls the hypothesis (all three enter every residual).  A set with coordinates beyond 1e17, a centre or radius beyond 1e17
+// One rule for points outside the shell, inside it, for r = 0 (the residual is s) and for r < 0 (every residual is s + |r|).  A NaN
+// entry culls the hypothesis (all DIM + 1 enter every residual).  A set with coordinates beyond 1e17, a centre or radius beyond 1e17
 // (q~ must stay below the f32 overflow) or a threshold outside the ordinary f32 range gives E = inf: never rejected, the exact path
 // decides (r = inf included: inf - inf is NaN, and a NaN comparison is false).  Scenes far from the origin lose the filter's
 // precision (e1 P grows with the offset, not with the scene): correct, only slower.
-template <> struct Filter32<kCircle2D> {
+template <int DIM> struct RoundFilter32 {
     static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 4;
-    struct Lane { float cx, cy, r, e1, e0, e2, tpp, nanh; };
+    static constexpr int kRowVals = 6, kGroupVals = DIM + 2;
+    struct Lane { float c[DIM]; float r, e1, e0, e2, tpp, nanh; };   // a row of floats in this order (score.hip HypRow)
+    static_assert(offsetof(Lane, r) == DIM * sizeof(float) && offsetof(Lane, nanh) == (DIM + 5) * sizeof(float) &&
+                  sizeof(Lane) == (DIM + 6) * sizeof(float), "centre, r, e1, e0, e2, tpp, nanh");
     template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
         Lane ln;
-        ln.cx = (float)m[0]; ln.cy = (float)m[1]; ln.r = (float)m[2];
-        ln.nanh = (m[0] == m[0] && m[1] == m[1] && m[2] == m[2]) ? 0.0f : 1.0f;
+        bool nan = !(m[DIM] == m[DIM]);
+        double c2 = m[0] * m[0];
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) c2 = c2 + m[k] * m[k];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) { ln.c[k] = (float)m[k]; nan |= !(m[k] == m[k]); }
+        ln.r = (float)m[DIM];
+        ln.nanh = nan ? 1.0f : 0.0f;
         const double Ts = sqrt(T2);
-        const double cn = sqrt(m[0] * m[0] + m[1] * m[1]) * 1.001;
-        const bool big = !(pscale <= 1e17) || !(cn <= 1e17) || !(fabs(m[2]) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30);
+        const double cn = sqrt(c2) * 1.001;
+        const bool big = !(pscale <= 1e17) || !(cn <= 1e17) || !(fabs(m[DIM]) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30);
         const double u = 5.9604644775390625e-8;
         ln.e1 = f32_up(2.0 * u);
-        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * (cn + fabs(m[2])) + 1e-18);
+        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * (cn + fabs(m[DIM])) + 1e-18);
         ln.e2 = f32_up(8.0 * u);
         ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
         return ln;
     }
     static __device__ __forceinline__ float dist(const float* p, const Lane& ln) {
-        const float dx = p[0] - ln.cx, dy = p[1] - ln.cy;
-        return sqrtf(__builtin_fmaf(dx, dx, dy * dy));
+        float d[DIM];
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) d[k] = p[k] - ln.c[k];
+        float q = d[DIM - 1] * d[DIM - 1];
+#pragma unroll
+        for (int k = DIM - 2; k >= 0; --k) q = __builtin_fmaf(d[k], d[k], q);
+        return sqrtf(q);
     }
-    // p = (x, y, -, -, -, P, -, -) in f32
+    // p = (coordinates[DIM], -, .., P, -, -) in f32, P at p[5]
     static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
         const float s = dist(p, ln);
         const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, p[5], ln.e0) + ln.e2 * s);
         return m > ln.tpp;  // false on NaN / inf - inf
     }
-    // g = (cx, cy, rho, Pmax)
+    // g = (centre[DIM], rho, Pmax)
     static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
         if (ln.nanh != 0.0f) return true;
         const float s = dist(g, ln);
-        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, g[3], ln.e0) + ln.e2 * (s + g[2])) - g[2] * 1.001f;
+        const float m = fabsf(s - ln.r) - (__builtin_fmaf(ln.e1, g[DIM + 1], ln.e0) + ln.e2 * (s + g[DIM])) - g[DIM] * 1.001f;
         return m > ln.tpp * 1.001f;
     }
 };
+template <> struct Filter32<kCircle2D> : RoundFilter32<2> {};
+template <> struct Filter32<kSphere3D> : RoundFilter32<3> {};
 
 }  // namespace pgx

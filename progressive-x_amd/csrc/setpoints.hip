@@ -513,8 +513,9 @@ __global__ __launch_bounds__(SPAN) void sp_fund_bounds_kernel(const double* __re
     }
 }
 
-// 2-D lines and circles, 3-D planes and spheres: group rows (centre[DIM], R, Pmax, 0 ...) - score.hip Filter32<kLine2D> and
-// Filter32<kCircle2D> (DIM = 2), Filter32<kPlane3D> and Filter32<kSphere3D> (DIM = 3): the box centre in f64 -> f32, the radius of the ball about the STORED centre, inflated
+// The flat and the round family (2-D lines and circles, 3-D planes and spheres): group rows (centre[DIM], R, Pmax, 0 ...) that
+// score_filters.hip.h FlatFilter32<DIM> and RoundFilter32<DIM> read, DIM = 2, 3: the box centre in f64 -> f32, the radius of the ball
+// about the STORED centre, inflated
 template <int SPAN, int DIM>
 __global__ __launch_bounds__(SPAN) void sp_line_bounds_kernel(const double* __restrict__ sp, int64_t n, float* __restrict__ rows)
 {

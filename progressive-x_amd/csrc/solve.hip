@@ -18,17 +18,15 @@
 //   absolute pose from 3 points (P3P)   DefaultPnPEstimator's minimal solver (progressivex_python.cpp:119), absent upstream:
 //                                       Grunert's quartic, positive real roots by bisection between the critical points,
 //                                       pose from the orthonormal frames of the two congruent triangles; four slots
-//   3-D plane through three points      findPlanes' minimal solver (no reference counterpart): n = (p1 - p0) x (p2 - p0) in
-//                                       cross3's component order, ln = sqrt(n . n), (a, b, c) = n / ln,
+//   3-D plane through three points      findPlanes' minimal solver (no reference counterpart; the flat family with the line): n =
+//                                       (p1 - p0) x (p2 - p0) in cross3's component order, ln = sqrt(n . n), (a, b, c) = n / ln,
 //                                       d = -((a x0 + b y0) + c z0); collinear or coincident points (ln == 0) give NaN
-//   3-D sphere through four points      findSpheres' minimal solver (no reference counterpart): the centre offset e from p0
-//                                       solves a_i . e = |a_i|^2 / 2 (a_i = p_i - p0) by Cramer's rule on cross products;
-//                                       coplanar points (det == 0), non-finite values and radii outside the context's
-//                                       pgx_set_radius_range give NaN
-//   2-D circle through three points     findCircles' minimal solver (no reference counterpart): the sphere solver one dimension
-//                                       down, a_i . e = |a_i|^2 / 2 (a_i = p_i - p0) by Cramer's rule on the 2x2 system;
-//                                       collinear points (det == 0), non-finite values and radii outside the context's
-//                                       pgx_set_radius_range give NaN
+//   the round family (no reference counterpart): the centre offset e from p0 solves a_i . e = |a_i|^2 / 2 (a_i = p_i - p0);
+//   singular systems (det == 0), non-finite values and radii outside the context's pgx_set_radius_range give NaN
+//     3-D sphere through four points    findSpheres' minimal solver: Cramer's rule on cross products (det == 0: coplanar points)
+//     2-D circle through three points   findCircles' minimal solver: Cramer's rule on the 2x2 system (det == 0: collinear points)
+// The five solvers with one model per sample (line, vanishing point, plane, sphere, circle) share one kernel shell, solve_kernel<MT>;
+// the 7-point, 4-point and P3P solvers run one lane per sample in kernels of their own.
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
 // inlier; the caller drops it (the reference's solvers return "no model").
@@ -36,6 +34,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "pgx_internal.h"
 #include "rng.hip.h"
@@ -53,153 +52,129 @@ __device__ __forceinline__ void cross3(double a1, double b1, double c1, double a
     o[2] = a1 * b2 - b1 * a2;
 }
 
-template <int MT>
-__global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
-                                                            int S, double* __restrict__ models, int* __restrict__ perm, int Mpad)
+// ---- the lane-per-model solvers: one __device__ function per type, one kernel shell ---------------------------------------------
+// solve_minimal(type, p, rmin, rmax, m): p = the sample's Residual<MT>::sample point rows (all inside the point set), m = the model,
+// preset to NaN - a degenerate sample leaves it so.  rmin, rmax: the context's pgx_set_radius_range (the round family reads them).
+template <int MT> using Type = std::integral_constant<int, MT>;
+
+// 2-point line [U-4]: unit normal (-dy, dx) / |d|, offset c = -(n . a); coincident points (ln == 0; also false on NaN) give NaN.
+__device__ __forceinline__ void solve_minimal(Type<kLine2D>, const double* const* p, double, double, double* m)
 {
-    const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
-    if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
-    if (s >= S) return;
-    const int i0 = samples[2 * s], i1 = samples[2 * s + 1];
-    double m[3];
-    const double nan = __builtin_nan("");
-    if (i0 < 0 || i1 < 0 || i0 >= n || i1 >= n) {
-        m[0] = m[1] = m[2] = nan;
-    } else if (MT == kLine2D) {
-        const double ax = pts[(int64_t)i0 * 2], ay = pts[(int64_t)i0 * 2 + 1];
-        const double dx = pts[(int64_t)i1 * 2] - ax, dy = pts[(int64_t)i1 * 2 + 1] - ay;
-        const double ln = sqrt(dx * dx + dy * dy);
-        if (ln > 0.0) {
-            m[0] = -dy / ln;
-            m[1] = dx / ln;
-            m[2] = -(m[0] * ax + m[1] * ay);
-        } else {
-            m[0] = m[1] = m[2] = nan;
-        }
-    } else {
-        const double* a = pts + (int64_t)i0 * 4;
-        const double* b = pts + (int64_t)i1 * 4;
-        double l0[3], l1[3], v[3];
-        cross3(a[0], a[1], 1.0, a[2], a[3], 1.0, l0);
-        cross3(b[0], b[1], 1.0, b[2], b[3], 1.0, l1);
-        cross3(l0[0], l0[1], l0[2], l1[0], l1[1], l1[2], v);
-        const double ln = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        if (ln > 0.0) { m[0] = v[0] / ln; m[1] = v[1] / ln; m[2] = v[2] / ln; }
-        else { m[0] = m[1] = m[2] = nan; }
+    const double ax = p[0][0], ay = p[0][1];
+    const double dx = p[1][0] - ax, dy = p[1][1] - ay;
+    const double ln = sqrt(dx * dx + dy * dy);
+    if (ln > 0.0) {
+        m[0] = -dy / ln;
+        m[1] = dx / ln;
+        m[2] = -(m[0] * ax + m[1] * ay);
     }
-    models[(int64_t)s * 3] = m[0];
-    models[(int64_t)s * 3 + 1] = m[1];
-    models[(int64_t)s * 3 + 2] = m[2];
 }
 
-// 3-point plane: samples[S][3] -> S x 4 models (a, b, c, d).  Operation order (the contract; PlaneEstimator.minimal restates it):
+// vanishing point of two segments (solver_vanishing_point_two_lines.h:174-182); parallel or identical lines give NaN.
+__device__ __forceinline__ void solve_minimal(Type<kVanishingPoint>, const double* const* p, double, double, double* m)
+{
+    const double *a = p[0], *b = p[1];
+    double l0[3], l1[3], v[3];
+    cross3(a[0], a[1], 1.0, a[2], a[3], 1.0, l0);
+    cross3(b[0], b[1], 1.0, b[2], b[3], 1.0, l1);
+    cross3(l0[0], l0[1], l0[2], l1[0], l1[1], l1[2], v);
+    const double ln = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (ln > 0.0) { m[0] = v[0] / ln; m[1] = v[1] / ln; m[2] = v[2] / ln; }
+}
+
+// 3-point plane -> (a, b, c, d).  Operation order (the contract; PlaneEstimator.minimal restates it):
 //   u = p1 - p0, v = p2 - p0 (componentwise), n = cross3(u, v), ln = sqrt((n0 n0 + n1 n1) + n2 n2),
 //   a = n0 / ln, b = n1 / ln, c = n2 / ln, d = -((a x0 + b y0) + c z0).
-// An index outside 0 .. n-1, or ln == 0 (coincident or collinear points; also false on NaN) gives a NaN model.
-__global__ __launch_bounds__(kSolveBlock) void solve_plane_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
-                                                                  int S, double* __restrict__ models, int* __restrict__ perm, int Mpad)
+// ln == 0 (coincident or collinear points; also false on NaN) gives a NaN model.
+__device__ __forceinline__ void solve_minimal(Type<kPlane3D>, const double* const* p, double, double, double* m)
 {
-    const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
-    if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
-    if (s >= S) return;
-    const int i0 = samples[3 * s], i1 = samples[3 * s + 1], i2 = samples[3 * s + 2];
-    double m[4];
-    const double nan = __builtin_nan("");
-    m[0] = m[1] = m[2] = m[3] = nan;
-    if (i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < n && i1 < n && i2 < n) {
-        const double* p0 = pts + (int64_t)i0 * 3;
-        const double* p1 = pts + (int64_t)i1 * 3;
-        const double* p2 = pts + (int64_t)i2 * 3;
-        double nv[3];
-        cross3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2], p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2], nv);
-        const double ln = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
-        if (ln > 0.0) {
-            m[0] = nv[0] / ln;
-            m[1] = nv[1] / ln;
-            m[2] = nv[2] / ln;
-            m[3] = -((m[0] * p0[0] + m[1] * p0[1]) + m[2] * p0[2]);
-        }
+    const double *p0 = p[0], *p1 = p[1], *p2 = p[2];
+    double nv[3];
+    cross3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2], p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2], nv);
+    const double ln = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
+    if (ln > 0.0) {
+        m[0] = nv[0] / ln;
+        m[1] = nv[1] / ln;
+        m[2] = nv[2] / ln;
+        m[3] = -((m[0] * p0[0] + m[1] * p0[1]) + m[2] * p0[2]);
     }
-    for (int k = 0; k < 4; ++k) models[(int64_t)s * 4 + k] = m[k];
 }
 
-// 4-point sphere: samples[S][4] -> S x 4 models (cx, cy, cz, r).  Operation order (the contract; SphereEstimator.minimal restates it):
+// The tail both round solvers share: the model (c, r) counts only if the system was regular (det != 0: no coplanar / collinear or
+// coincident points), centre and radius are finite and rmin <= r <= rmax; otherwise it stays NaN.
+template <int DIM>
+__device__ __forceinline__ void accept_round(double det, const double* c, double r, double rmin, double rmax, double* m)
+{
+    bool ok = det != 0.0 && isfinite(r) && r >= rmin && r <= rmax;
+    for (int k = 0; k < DIM; ++k) ok = ok && isfinite(c[k]);
+    if (!ok) return;
+    for (int k = 0; k < DIM; ++k) m[k] = c[k];
+    m[DIM] = r;
+}
+
+// 4-point sphere -> (cx, cy, cz, r).  Operation order (the contract; SphereEstimator.minimal restates it):
 //   a_i = p_i - p0 (componentwise, i = 1..3), h_i = 0.5 ((a_i0 a_i0 + a_i1 a_i1) + a_i2 a_i2),
 //   n1 = cross3(a2, a3), n2 = cross3(a3, a1), n3 = cross3(a1, a2), det = (a1_0 n1_0 + a1_1 n1_1) + a1_2 n1_2,
 //   e_k = ((h1 n1_k + h2 n2_k) + h3 n3_k) / det, r = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2), c = p0 + e.
-// An index outside 0 .. n-1, det == 0 (coplanar or coincident points), a non-finite centre or radius, or r outside [rmin, rmax]
-// gives a NaN model.
-__global__ __launch_bounds__(kSolveBlock) void solve_sphere_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
-                                                                   int S, double rmin, double rmax, double* __restrict__ models,
-                                                                   int* __restrict__ perm, int Mpad)
+__device__ __forceinline__ void solve_minimal(Type<kSphere3D>, const double* const* p, double rmin, double rmax, double* m)
 {
-    const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
-    if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
-    if (s >= S) return;
-    int ix[4];
-    bool inb = true;
-    for (int k = 0; k < 4; ++k) {
-        ix[k] = samples[4 * s + k];
-        inb = inb && ix[k] >= 0 && ix[k] < n;
+    const double* p0 = p[0];
+    double a[3][3], h[3];
+    for (int i = 0; i < 3; ++i) {
+        for (int k = 0; k < 3; ++k) a[i][k] = p[i + 1][k] - p0[k];
+        h[i] = 0.5 * ((a[i][0] * a[i][0] + a[i][1] * a[i][1]) + a[i][2] * a[i][2]);
     }
-    double m[4];
-    const double nan = __builtin_nan("");
-    m[0] = m[1] = m[2] = m[3] = nan;
-    if (inb) {
-        const double* p0 = pts + (int64_t)ix[0] * 3;
-        double a[3][3], h[3];
-        for (int i = 0; i < 3; ++i) {
-            const double* pi = pts + (int64_t)ix[i + 1] * 3;
-            for (int k = 0; k < 3; ++k) a[i][k] = pi[k] - p0[k];
-            h[i] = 0.5 * ((a[i][0] * a[i][0] + a[i][1] * a[i][1]) + a[i][2] * a[i][2]);
-        }
-        double n1[3], n2[3], n3[3];
-        cross3(a[1][0], a[1][1], a[1][2], a[2][0], a[2][1], a[2][2], n1);
-        cross3(a[2][0], a[2][1], a[2][2], a[0][0], a[0][1], a[0][2], n2);
-        cross3(a[0][0], a[0][1], a[0][2], a[1][0], a[1][1], a[1][2], n3);
-        const double det = (a[0][0] * n1[0] + a[0][1] * n1[1]) + a[0][2] * n1[2];
-        double e[3];
-        for (int k = 0; k < 3; ++k) e[k] = ((h[0] * n1[k] + h[1] * n2[k]) + h[2] * n3[k]) / det;
-        const double r = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-        const double c[3] = {p0[0] + e[0], p0[1] + e[1], p0[2] + e[2]};
-        if (det != 0.0 && isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(r) && r >= rmin && r <= rmax) {
-            m[0] = c[0]; m[1] = c[1]; m[2] = c[2]; m[3] = r;
-        }
-    }
-    for (int k = 0; k < 4; ++k) models[(int64_t)s * 4 + k] = m[k];
+    double n1[3], n2[3], n3[3];
+    cross3(a[1][0], a[1][1], a[1][2], a[2][0], a[2][1], a[2][2], n1);
+    cross3(a[2][0], a[2][1], a[2][2], a[0][0], a[0][1], a[0][2], n2);
+    cross3(a[0][0], a[0][1], a[0][2], a[1][0], a[1][1], a[1][2], n3);
+    const double det = (a[0][0] * n1[0] + a[0][1] * n1[1]) + a[0][2] * n1[2];
+    double e[3];
+    for (int k = 0; k < 3; ++k) e[k] = ((h[0] * n1[k] + h[1] * n2[k]) + h[2] * n3[k]) / det;
+    const double r = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    const double c[3] = {p0[0] + e[0], p0[1] + e[1], p0[2] + e[2]};
+    accept_round<3>(det, c, r, rmin, rmax, m);
 }
 
-// 3-point circle: samples[S][3] -> S x 3 models (cx, cy, r).  Operation order (the contract; CircleEstimator.minimal restates it):
+// 3-point circle -> (cx, cy, r).  Operation order (the contract; CircleEstimator.minimal restates it):
 //   a_i = p_i - p0 (componentwise, i = 1, 2), h_i = 0.5 (a_i0 a_i0 + a_i1 a_i1), det = a_10 a_21 - a_11 a_20,
 //   e_0 = (h_1 a_21 - h_2 a_11) / det, e_1 = (a_10 h_2 - a_20 h_1) / det, r = sqrt(e_0 e_0 + e_1 e_1), c = p0 + e.
-// An index outside 0 .. n-1, det == 0 (collinear or coincident points), a non-finite centre or radius, or r outside [rmin, rmax]
-// gives a NaN model.
-__global__ __launch_bounds__(kSolveBlock) void solve_circle_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
-                                                                   int S, double rmin, double rmax, double* __restrict__ models,
-                                                                   int* __restrict__ perm, int Mpad)
+__device__ __forceinline__ void solve_minimal(Type<kCircle2D>, const double* const* p, double rmin, double rmax, double* m)
 {
+    const double *p0 = p[0], *p1 = p[1], *p2 = p[2];
+    const double a10 = p1[0] - p0[0], a11 = p1[1] - p0[1], a20 = p2[0] - p0[0], a21 = p2[1] - p0[1];
+    const double h1 = 0.5 * (a10 * a10 + a11 * a11), h2 = 0.5 * (a20 * a20 + a21 * a21);
+    const double det = a10 * a21 - a11 * a20;
+    const double e0 = (h1 * a21 - h2 * a11) / det, e1 = (a10 * h2 - a20 * h1) / det;
+    const double r = sqrt(e0 * e0 + e1 * e1);
+    const double c[2] = {p0[0] + e0, p0[1] + e1};
+    accept_round<2>(det, c, r, rmin, rmax, m);
+}
+
+// The shell: samples[S][sample] -> S x P models, one lane per padded model.  An index outside 0 .. n-1 gives a NaN model.
+template <int MT>
+__global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
+                                                            int S, double rmin, double rmax, double* __restrict__ models,
+                                                            int* __restrict__ perm, int Mpad)
+{
+    using R = Residual<MT>;
     const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
     if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
     if (s >= S) return;
-    const int i0 = samples[3 * s], i1 = samples[3 * s + 1], i2 = samples[3 * s + 2];
-    double m[3];
-    const double nan = __builtin_nan("");
-    m[0] = m[1] = m[2] = nan;
-    if (i0 >= 0 && i1 >= 0 && i2 >= 0 && i0 < n && i1 < n && i2 < n) {
-        const double* p0 = pts + (int64_t)i0 * 2;
-        const double* p1 = pts + (int64_t)i1 * 2;
-        const double* p2 = pts + (int64_t)i2 * 2;
-        const double a10 = p1[0] - p0[0], a11 = p1[1] - p0[1], a20 = p2[0] - p0[0], a21 = p2[1] - p0[1];
-        const double h1 = 0.5 * (a10 * a10 + a11 * a11), h2 = 0.5 * (a20 * a20 + a21 * a21);
-        const double det = a10 * a21 - a11 * a20;
-        const double e0 = (h1 * a21 - h2 * a11) / det, e1 = (a10 * h2 - a20 * h1) / det;
-        const double r = sqrt(e0 * e0 + e1 * e1);
-        const double c0 = p0[0] + e0, c1 = p0[1] + e1;
-        if (det != 0.0 && isfinite(c0) && isfinite(c1) && isfinite(r) && r >= rmin && r <= rmax) {
-            m[0] = c0; m[1] = c1; m[2] = r;
-        }
+    int ix[R::sample];
+    bool inb = true;
+    for (int k = 0; k < R::sample; ++k) {
+        ix[k] = samples[R::sample * s + k];
+        inb = inb && ix[k] >= 0 && ix[k] < n;
     }
-    for (int k = 0; k < 3; ++k) models[(int64_t)s * 3 + k] = m[k];
+    double m[R::P];
+    for (int k = 0; k < R::P; ++k) m[k] = __builtin_nan("");
+    if (inb) {
+        const double* p[R::sample];
+        for (int k = 0; k < R::sample; ++k) p[k] = pts + (int64_t)ix[k] * R::D;
+        solve_minimal(Type<MT>{}, p, rmin, rmax, m);
+    }
+    for (int k = 0; k < R::P; ++k) models[(int64_t)s * R::P + k] = m[k];
 }
 
 // ---- P3P -------------------------------------------------------------------------------------------------------------
@@ -601,12 +576,12 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     if (mt == kFundamental) hipLaunchKernelGGL(solve_f7_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
     else if (mt == kHomography) hipLaunchKernelGGL(solve_h4_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
     else if (mt == kPnP) hipLaunchKernelGGL(solve_p3p_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
-    else if (mt == kPlane3D) hipLaunchKernelGGL(solve_plane_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
-    else if (mt == kSphere3D) hipLaunchKernelGGL(solve_sphere_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
-    else if (mt == kCircle2D) hipLaunchKernelGGL(solve_circle_kernel, gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
-    else if (mt == kLine2D) hipLaunchKernelGGL((solve_kernel<kLine2D>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
-    else if (mt == kVanishingPoint) hipLaunchKernelGGL((solve_kernel<kVanishingPoint>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
-    else return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal (internal): model type %d declares a solver that has no launch line", mt);
+    else   // the lane-per-model solvers: whatever else declares slots has a solve_minimal, or this does not compile
+        with_model_type(mt, [&](auto t) {
+            constexpr int MT = decltype(t)::value;
+            if constexpr (Residual<MT>::slots > 0 && MT != kFundamental && MT != kHomography && MT != kPnP)
+                hipLaunchKernelGGL((solve_kernel<MT>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
+        });
     PGX_HIP(ctx, hipGetLastError());
     if (models_out) {
         PGX_TRY(d2h(ctx, models_out, ctx->models.p, (size_t)Mtot * mi.P * sizeof(double)));

@@ -355,33 +355,30 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
     grows with n and later planes lose to tilted partial ones (six-plane scenes at 10^5 points: scoring_exponent=1 recovers all
     six, 2 three to five - DESIGN.md 4.5); minimum_point_number has to exceed the outliers a slab of width 3 x threshold
     holds, or spurious planes through the outliers are accepted."""
-    points, w, grid_pts, ext = _point_cloud(points, weights, 3)
-    if do_logging and sampler_id == 1:
-        print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
-    est = _estimators.PlaneEstimator()
-    models, labels, _ = _run(est, points, points, neighborhood_ball_radius,
-                             _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
-                                              est.sample_size),
-                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                             scoring_exponent=scoring_exponent, do_logging=bool(do_logging), weights=w, seed=seed,
-                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
-    return _stack(est, models, 4), labels
+    return _find_primitive(_estimators.PlaneEstimator(), points, weights, None, sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
 
 
-def _find_round(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
-    """findSpheres / findCircles behind their signatures: the estimator says the point dimension (its model type's), the sample size
-    (= the fewest points accepted) and the columns of a model; the radius range goes to the estimator and, per call, to the context."""
+def _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
+    """findPlanes / findSpheres / findCircles behind their signatures: the estimator says the point dimension (its model type's), the
+    sample size (= the fewest points accepted) and the columns of a model.  Only an estimator with a radius takes radius_range: it goes
+    to the estimator and, per call, to the context."""
     points, w, grid_pts, ext = _point_cloud(points, weights, est.sample_size, dim=_lib.POINT_DIM[est.model_type])
-    rmin, rmax = _radius_range(radius_range)
+    setup = None
+    if isinstance(est, _estimators.RoundEstimator):
+        rmin, rmax = est.radius_range = _radius_range(radius_range)
+        setup = lambda ctx: ctx.set_radius_range(rmin, rmax)   # noqa: E731
     if do_logging and sampler_id == 1:
         print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
-    est.radius_range = (rmin, rmax)
     models, labels, _ = _run(est, points, points, radius,
                              _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
                                               est.sample_size),
-                             do_logging=bool(do_logging), weights=w, setup=lambda ctx: ctx.set_radius_range(rmin, rmax), **run_kw)
+                             do_logging=bool(do_logging), weights=w, setup=setup, **run_kw)
     return _stack(est, models, est.cols), labels
 
 
@@ -399,13 +396,13 @@ def findSpheres(points, weights=None, threshold=0.05, conf=0.5, spatial_coherenc
     is close to random; the grid's cells span caps with usable curvature.  Samplers 3 and 1 take the points as ordered by quality (every
 proposal starts from the first points): shuffle a cloud that comes in scan order.  Like findPlanes, minimum_point_number has to exceed the
     outliers a shell of width 3 x threshold holds."""
-    return _find_round(_estimators.SphereEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                       threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                       maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                       minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                       scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                       neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                       distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+    return _find_primitive(_estimators.SphereEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
 
 
 def findCircles(points, weights=None, threshold=2.0, conf=0.5, spatial_coherence_weight=0.0,
@@ -423,13 +420,13 @@ def findCircles(points, weights=None, threshold=2.0, conf=0.5, spatial_coherence
     stderr and returns zero models.  Samplers 3 and 1 take the points as ordered by quality (every proposal starts from the first
     points): shuffle a set that comes in contour order.  minimum_point_number has to exceed the outliers an annulus of width
     3 x threshold holds."""
-    return _find_round(_estimators.CircleEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                       threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                       maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                       minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                       scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                       neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                       distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+    return _find_primitive(_estimators.CircleEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
 
 
 def find6DPoses(x1y1, x2y2z2, K, threshold=4.0, conf=0.90, spatial_coherence_weight=0.1,

@@ -219,7 +219,7 @@ class LineEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 3-D plane (findPlanes; no reference counterpart): the line estimator one dimension up
+# 3-D plane (findPlanes; no reference counterpart): the flat family with the line, whose refits differ (see _fit / _fit_many)
 # ---------------------------------------------------------------------------------------------------------------------
 class PlaneEstimator(Estimator):
     model_type = _lib.PLANE3D
@@ -229,7 +229,7 @@ class PlaneEstimator(Estimator):
     cols = 4
 
     def minimal(self, pts, samples):
-        """samples [S, 3] -> unit-normal planes (a, b, c, d), bitwise csrc/solve.hip's solve_plane_kernel: n = u x v in cross3's
+        """samples [S, 3] -> unit-normal planes (a, b, c, d), bitwise csrc/solve.hip's solve_minimal for planes: n = u x v in cross3's
         component order, ln = sqrt((n0 n0 + n1 n1) + n2 n2), (a, b, c) = n / ln, d = -((a x0 + b y0) + c z0).  Collinear or
         coincident samples (ln == 0) give no model."""
         p0, p1, p2 = pts[samples[:, 0]], pts[samples[:, 1]], pts[samples[:, 2]]
@@ -286,26 +286,70 @@ class PlaneEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 3-D sphere (findSpheres; no reference counterpart): 4-point minimal solver, algebraic refit on normalised coordinates
+# The round family (no reference counterpart): 3-D sphere (findSpheres, 4-point minimal solver) and 2-D circle (findCircles, 3-point),
+# one algebraic refit on normalised coordinates
 # ---------------------------------------------------------------------------------------------------------------------
 def _cross3(a, b):
     """csrc/solve.hip cross3's component order on [S, 3] arrays"""
     return (a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], -(a[:, 0] * b[:, 2] - a[:, 2] * b[:, 0]), a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0])
 
 
-class SphereEstimator(Estimator):
-    model_type = _lib.SPHERE3D
-    sample_size = 4
-    nonminimal_sample_size = 4
+class RoundEstimator(Estimator):
+    """What the sphere and the circle share: model (c[DIM], r), DIM = the model type's point dimension, the radius range and the
+    algebraic refit.  A subclass adds its model type, sample size, Gram kind and minimal()."""
     device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
-    cols = 4
-    radius_range = (0.0, np.inf)   # the radii a model may have (findSpheres sets it; the device solver reads pgx_set_radius_range)
+    gram_kind = None           # GRAM_CIRCLE / GRAM_SPHERE: the rows (1, q, |q|^2) of the refit
+    radius_range = (0.0, np.inf)   # the radii a model may have (findSpheres / findCircles set it; the device solver reads pgx_set_radius_range)
 
     def _in_range(self, r):
         return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
 
+    def _fit(self, init):
+        """Algebraic fit in two Gram passes: the weighted mean o and the RMS distance s from it (GRAM_AFFINE), then the smallest
+        eigenvector theta of the Gram matrix of the rows (1, q, |q|^2), q = (p - o) / s, the last entry summed left to right
+        (GRAM_CIRCLE: u u + v v, GRAM_SPHERE: (u u + v v) + w w): theta[0] + theta[1..DIM] . q + theta[-1] |q|^2 = 0 is the sphere
+        |q + b|^2 = |b|^2 - theta[0] / theta[-1] with b = theta[1..DIM] / (2 theta[-1]), so c = o - s b and
+        r = s sqrt(|b|^2 - theta[0] / theta[-1]).  The normalisation keeps the small matrix well conditioned for scenes far from
+        the origin.  `init` is not used."""
+        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,p][1,p]^T
+        W = G[0, 0]
+        if cnt < self.sample_size or not W > 0:
+            return []
+        o = G[0, 1:] / W
+        scatter = G[1:, 1:] - W * np.outer(o, o)
+        var = np.trace(scatter) / W
+        # the guard: the root is taken of a positive, finite variance only (coincident points: the trace may round to zero or below it,
+        # which must give no model and no RuntimeWarning); s > 0 and finite exactly when var is
+        if not (np.isfinite(o).all() and var > 0 and np.isfinite(var)):
+            return []
+        s = np.sqrt(var)
+        G, _, _ = yield (self.gram_kind, np.array([*o.tolist(), s]), True, 1)
+        if not np.isfinite(G).all():
+            return []
+        th = self._smallest(G[None])[0]
+        A = th[-1]
+        if A == 0:
+            return []
+        b = th[1:-1] / (2.0 * A)
+        rad = b @ b - th[0] / A
+        if not rad > 0:
+            return []
+        r = s * np.sqrt(rad)
+        c = o - s * b
+        if not (np.isfinite(c).all() and np.isfinite(r) and self._in_range(r)):
+            return []
+        return [np.array([*c.tolist(), r])]
+
+
+class SphereEstimator(RoundEstimator):
+    model_type = _lib.SPHERE3D
+    sample_size = 4
+    nonminimal_sample_size = 4
+    cols = 4
+    gram_kind = _lib.GRAM_SPHERE
+
     def minimal(self, pts, samples):
-        """samples [S, 4] -> spheres (cx, cy, cz, r), bitwise csrc/solve.hip's solve_sphere_kernel: a_i = p_i - p0,
+        """samples [S, 4] -> spheres (cx, cy, cz, r), bitwise csrc/solve.hip's solve_minimal for spheres: a_i = p_i - p0,
         h_i = 0.5 ((a_i0 a_i0 + a_i1 a_i1) + a_i2 a_i2), n1 = a2 x a3, n2 = a3 x a1, n3 = a1 x a2 in cross3's component order,
         det = (a1_0 n1_0 + a1_1 n1_1) + a1_2 n1_2, e_k = ((h1 n1_k + h2 n2_k) + h3 n3_k) / det, r = sqrt((e0 e0 + e1 e1) + e2 e2),
         c = p0 + e.  Coplanar or coincident samples (det == 0), non-finite values and radii outside radius_range give no model."""
@@ -321,55 +365,19 @@ class SphereEstimator(Estimator):
             ok = (det != 0) & np.isfinite(models).all(axis=1) & self._in_range(r)
         return models[ok], np.nonzero(ok)[0]
 
-    def _fit(self, init):
-        """Algebraic sphere fit in two Gram passes: the weighted mean o and the RMS distance s from it (GRAM_AFFINE), then the
-        smallest eigenvector theta of the Gram matrix of the rows (1, u, v, w, |(u, v, w)|^2), (u, v, w) = (p - o) / s
-        (GRAM_SPHERE): theta0 + theta1..3 . q + theta4 |q|^2 = 0 is the sphere |q + b|^2 = |b|^2 - theta0 / theta4 with
-        b = theta1..3 / (2 theta4), so c = o - s b and r = s sqrt(|b|^2 - theta0 / theta4).  The normalisation keeps the 5x5
-        matrix well conditioned for scenes far from the origin.  `init` is not used."""
-        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,x,y,z][1,x,y,z]^T
-        W = G[0, 0]
-        if cnt < 4 or not W > 0:
-            return []
-        o = G[0, 1:] / W
-        scatter = G[1:, 1:] - W * np.outer(o, o)
-        s = np.sqrt(np.trace(scatter) / W)
-        if not (np.isfinite(o).all() and s > 0 and np.isfinite(s)):
-            return []
-        G, _, _ = yield (_lib.GRAM_SPHERE, np.array([o[0], o[1], o[2], s]), True, 1)
-        if not np.isfinite(G).all():
-            return []
-        th = self._smallest(G[None])[0]
-        A = th[4]
-        if A == 0:
-            return []
-        b = th[1:4] / (2.0 * A)
-        rad = b @ b - th[0] / A
-        if not rad > 0:
-            return []
-        r = s * np.sqrt(rad)
-        c = o - s * b
-        if not (np.isfinite(c).all() and np.isfinite(r) and self._in_range(r)):
-            return []
-        return [np.array([c[0], c[1], c[2], r])]
-
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 2-D circle (findCircles; no reference counterpart): the sphere estimator one dimension down
+# 2-D circle: the round family's other member
 # ---------------------------------------------------------------------------------------------------------------------
-class CircleEstimator(Estimator):
+class CircleEstimator(RoundEstimator):
     model_type = _lib.CIRCLE2D
     sample_size = 3
     nonminimal_sample_size = 3
-    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
     cols = 3
-    radius_range = (0.0, np.inf)   # the radii a model may have (findCircles sets it; the device solver reads pgx_set_radius_range)
-
-    def _in_range(self, r):
-        return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
+    gram_kind = _lib.GRAM_CIRCLE
 
     def minimal(self, pts, samples):
-        """samples [S, 3] -> circles (cx, cy, r), bitwise csrc/solve.hip's solve_circle_kernel: a_i = p_i - p0,
+        """samples [S, 3] -> circles (cx, cy, r), bitwise csrc/solve.hip's solve_minimal for circles: a_i = p_i - p0,
         h_i = 0.5 (a_i0 a_i0 + a_i1 a_i1), det = a_10 a_21 - a_11 a_20, e_0 = (h_1 a_21 - h_2 a_11) / det,
         e_1 = (a_10 h_2 - a_20 h_1) / det, r = sqrt(e_0 e_0 + e_1 e_1), c = p0 + e.  Collinear or coincident samples (det == 0),
         non-finite values and radii outside radius_range give no model."""
@@ -385,38 +393,6 @@ class CircleEstimator(Estimator):
             models = np.column_stack([p0[:, 0] + e0, p0[:, 1] + e1, r])
             ok = (det != 0) & np.isfinite(models).all(axis=1) & self._in_range(r)
         return models[ok], np.nonzero(ok)[0]
-
-    def _fit(self, init):
-        """Algebraic circle fit in two Gram passes (SphereEstimator._fit one dimension down): the weighted mean o and the RMS
-        distance s from it (GRAM_AFFINE), then the smallest eigenvector theta of the Gram matrix of the rows (1, u, v, u u + v v),
-        (u, v) = (p - o) / s (GRAM_CIRCLE): theta0 + theta1..2 . q + theta3 |q|^2 = 0 is the circle |q + b|^2 = |b|^2 - theta0 / theta3
-        with b = theta1..2 / (2 theta3), so c = o - s b and r = s sqrt(|b|^2 - theta0 / theta3).  `init` is not used."""
-        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,x,y][1,x,y]^T
-        W = G[0, 0]
-        if cnt < 3 or not W > 0:
-            return []
-        o = G[0, 1:] / W
-        scatter = G[1:, 1:] - W * np.outer(o, o)
-        with np.errstate(invalid="ignore"):        # (coincident points: the trace may round below zero; the guard below catches the NaN)
-            s = np.sqrt(np.trace(scatter) / W)
-        if not (np.isfinite(o).all() and s > 0 and np.isfinite(s)):
-            return []
-        G, _, _ = yield (_lib.GRAM_CIRCLE, np.array([o[0], o[1], s]), True, 1)
-        if not np.isfinite(G).all():
-            return []
-        th = self._smallest(G[None])[0]
-        A = th[3]
-        if A == 0:
-            return []
-        b = th[1:3] / (2.0 * A)
-        rad = b @ b - th[0] / A
-        if not rad > 0:
-            return []
-        r = s * np.sqrt(rad)
-        c = o - s * b
-        if not (np.isfinite(c).all() and np.isfinite(r) and self._in_range(r)):
-            return []
-        return [np.array([c[0], c[1], r])]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

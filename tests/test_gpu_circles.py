@@ -9,6 +9,7 @@ import pytest
 
 import pyprogressivex as px
 from pyprogressivex import _estimators, _lib, _rng, datasets, parallel
+from primitive_helpers import _check_recovery, _check_scores, _want, ref_score, shuffled
 
 pytestmark = pytest.mark.gpu
 
@@ -25,32 +26,6 @@ def sq_circle(pts, m):
     with np.errstate(invalid="ignore", over="ignore"):
         r = np.abs(dist(pts, m) - m[2])
         return r * r
-
-
-def ref_score(pts, models, T2, comp=None):
-    n = pts.shape[0]
-    q = parallel.fixed_point_scale(n)
-    words = (n + 63) // 64
-    out = dict(counts=[], values=[], shared=[], values_q=[], shared_q=[], masks=np.zeros((len(models), words), np.uint64))
-    for k, m in enumerate(models):
-        sq = sq_circle(pts, m)
-        with np.errstate(invalid="ignore"):
-            inl = sq < T2
-        sc = np.maximum(0.0, 1.0 - sq[inl] / T2)
-        out["counts"].append(int(inl.sum()))
-        out["values"].append(sc.sum())
-        out["values_q"].append(int(np.rint(sc * q).astype(np.int64).sum()))
-        sh = np.minimum(comp[inl], sc) if comp is not None else np.zeros(0)
-        out["shared"].append(sh.sum())
-        out["shared_q"].append(int(np.rint(sh * q).astype(np.int64).sum()))
-        bits = np.zeros(words * 64, dtype=bool)
-        bits[:n] = inl
-        out["masks"][k] = np.packbits(bits, bitorder="little").view("<u8")
-    for key in ("counts", "values_q", "shared_q"):
-        out[key] = np.array(out[key], dtype=np.int64)
-    out["values"] = np.array(out["values"])
-    out["shared"] = np.array(out["shared"])
-    return out
 
 
 def make_problem(n, M, seed):
@@ -81,13 +56,6 @@ def make_problem(n, M, seed):
     return pts, models
 
 
-def _check_scores(got, ref):
-    assert np.array_equal(got["counts"], ref["counts"])
-    assert np.array_equal(got["masks"], ref["masks"])
-    assert np.all(np.abs(got["values"] - ref["values"]) <= 1e-9 * np.maximum(np.abs(ref["values"]), 1e-4))
-    assert np.all(np.abs(got["shared"] - ref["shared"]) <= 1e-9 * np.maximum(np.abs(ref["shared"]), 1e-4))
-
-
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 5000])
 @pytest.mark.parametrize("M", [1, 7, 256])
 def test_circle_scoring_bit_exact(gpu_ctx, n, M):
@@ -102,7 +70,7 @@ def test_circle_scoring_bit_exact(gpu_ctx, n, M):
     gpu_ctx.set_points(_lib.CIRCLE2D, pts)
     gpu_ctx.set_compound(comp)
     got = gpu_ctx.score(models, T2, has_compound=True, exponent=2, want_masks=True)
-    ref = ref_score(pts, models, T2, comp)
+    ref = ref_score(sq_circle, pts, models, T2, comp)
     if n >= 5000 and M >= 7:
         assert not (ref["masks"][0, on >> 6] >> np.uint64(on & 63)) & np.uint64(1)
     _check_scores(got, ref)
@@ -122,7 +90,7 @@ def cull_problem():
     """one problem and its numpy reference for every switch of test_circle_culls_are_invisible"""
     pts, models = make_problem(30011, 300, seed=11)
     comp = np.random.default_rng(2).uniform(0, 1, pts.shape[0])
-    return pts, models, comp, ref_score(pts, models, T2_NOMINAL, comp)
+    return pts, models, comp, ref_score(sq_circle, pts, models, T2_NOMINAL, comp)
 
 
 @pytest.mark.parametrize("switch", [None, "PGX_NO_FILTER", "PGX_SCORE_NO_CULL", "PGX_NO_GROUP", "PGX_NO_SORT", "PGX_SETPOINTS_HOST"])
@@ -194,7 +162,7 @@ def test_circle_filter_proof_near_threshold(monkeypatch):
                     st = ctx.score_stats(T * T)
                     assert st["contradictions"] == 0, (off, tf, radius, scale, st)
                     got = ctx.score(hyps, T * T, want_masks=True)
-                    ref = ref_score(pts, hyps, T * T)
+                    ref = ref_score(sq_circle, pts, hyps, T * T)
                     assert np.array_equal(got["counts"], ref["counts"]) and np.array_equal(got["masks"], ref["masks"])
                     assert ref["counts"][0] > 0
                     f32_seen += st["filter"] == "f32"
@@ -252,14 +220,6 @@ def test_circle_pointwise_kernels_bit_exact(gpu_ctx):
         r = np.sqrt(sq_circle(pts[lab4 == k], finite[k]))
         assert abs(sums[k] - r.sum()) <= 1e-12 * max(abs(r.sum()), 1e-300)
         assert abs(gpu_ctx.residual_sum(finite[k], k) - r.sum()) <= 1e-12 * max(abs(r.sum()), 1e-300)
-
-
-def _want(est, pts, samples, S):
-    ok = (samples >= 0).all(1) & (samples < len(pts)).all(1)
-    ref, src = est.minimal(pts, samples[ok])
-    want = np.full((S, 3), np.nan)
-    want[np.flatnonzero(ok)[src]] = ref
-    return want
 
 
 @pytest.fixture(scope="module")
@@ -384,31 +344,6 @@ def test_circle_refit_grams(gpu_ctx):
     assert np.abs(one[0] - jac[1][0]).max() < 1e-10 * 1000.0
     batch = est.nonminimal_batch(gpu_ctx, idx)               # the batched form drives the same coroutine
     assert len(batch) == 4
-
-
-def _check_recovery(circles, labels, pts, gen_labels, gt, thr, sigma):
-    """the sphere tests' criterion: every circle within 2 sigma in centre and radius, and a labelling no worse than two points in a
-    hundred above that of the ground-truth circles with the band the labelling uses"""
-    K = len(gt)
-    assert circles.shape == (K, 3) and circles.dtype == np.float64 and labels.dtype == np.int32
-    for g in gt:
-        k = int(np.argmin(np.linalg.norm(circles[:, :2] - g[:2], axis=1)))
-        assert np.linalg.norm(circles[k, :2] - g[:2]) < 2 * sigma, (circles[k], g)
-        assert abs(circles[k, 2] - g[2]) < 2 * sigma, (circles[k], g)
-    band = 1.5 * thr
-    res = np.abs(np.linalg.norm(pts[:, None, :] - gt[None, :, :2], axis=2) - gt[None, :, 2])
-    near = np.argmin(res, axis=1)
-    floor_labels = np.where(res[np.arange(len(pts)), near] < band, near + 1, 0)
-    floor = float(np.mean(floor_labels != gen_labels))
-    me = datasets.misclassification(np.where(labels == K, 0, labels + 1), gen_labels)
-    assert me <= floor + 0.02, (me, floor)
-
-
-def shuffled(pts, gen, seed=0):
-    """Progressive NAPSAC (the default sampler) takes the points as ordered by quality: in make_circles' order (circle by circle)
-    every proposal would start inside the first circle, so the end-to-end tests put the points in a random order."""
-    order = np.random.default_rng(seed).permutation(len(pts))
-    return np.ascontiguousarray(pts[order]), gen[order]
 
 
 # minimum_point_number: a spurious circle through the uniform outliers collects those inside its annulus of width 3 x threshold = 6

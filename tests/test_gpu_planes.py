@@ -10,6 +10,7 @@ import pytest
 
 import pyprogressivex as px
 from pyprogressivex import _estimators, _lib, _rng, datasets, parallel
+from primitive_helpers import _check_labelling, _check_scores, ref_score
 
 pytestmark = pytest.mark.gpu
 
@@ -17,32 +18,6 @@ pytestmark = pytest.mark.gpu
 def sq_plane(pts, m):
     r = np.abs(((m[0] * pts[:, 0] + m[1] * pts[:, 1]) + m[2] * pts[:, 2]) + m[3])
     return r * r
-
-
-def ref_score(pts, models, T2, comp=None):
-    n = pts.shape[0]
-    q = parallel.fixed_point_scale(n)
-    words = (n + 63) // 64
-    out = dict(counts=[], values=[], shared=[], values_q=[], shared_q=[], masks=np.zeros((len(models), words), np.uint64))
-    for k, m in enumerate(models):
-        sq = sq_plane(pts, m)
-        with np.errstate(invalid="ignore"):
-            inl = sq < T2
-        sc = np.maximum(0.0, 1.0 - sq[inl] / T2)
-        out["counts"].append(int(inl.sum()))
-        out["values"].append(sc.sum())
-        out["values_q"].append(int(np.rint(sc * q).astype(np.int64).sum()))
-        sh = np.minimum(comp[inl], sc) if comp is not None else np.zeros(0)
-        out["shared"].append(sh.sum())
-        out["shared_q"].append(int(np.rint(sh * q).astype(np.int64).sum()))
-        bits = np.zeros(words * 64, dtype=bool)
-        bits[:n] = inl
-        out["masks"][k] = np.packbits(bits, bitorder="little").view("<u8")
-    for key in ("counts", "values_q", "shared_q"):
-        out[key] = np.array(out[key], dtype=np.int64)
-    out["values"] = np.array(out["values"])
-    out["shared"] = np.array(out["shared"])
-    return out
 
 
 def make_problem(n, M, seed, scale=1.0):
@@ -91,11 +66,8 @@ def test_plane_scoring_bit_exact(gpu_ctx, n, M):
     gpu_ctx.set_points(_lib.PLANE3D, pts)
     gpu_ctx.set_compound(comp)
     got = gpu_ctx.score(models, T2, has_compound=True, exponent=2, want_masks=True)
-    ref = ref_score(pts, models, T2, comp)
-    assert np.array_equal(got["counts"], ref["counts"])
-    assert np.array_equal(got["masks"], ref["masks"])
-    assert np.all(np.abs(got["values"] - ref["values"]) <= 1e-9 * np.maximum(np.abs(ref["values"]), 1e-4))
-    assert np.all(np.abs(got["shared"] - ref["shared"]) <= 1e-9 * np.maximum(np.abs(ref["shared"]), 1e-4))
+    ref = ref_score(sq_plane, pts, models, T2, comp)
+    _check_scores(got, ref)
     nomask = gpu_ctx.score(models, T2, has_compound=True, exponent=2)
     assert np.array_equal(nomask["counts"], ref["counts"])
     st = gpu_ctx.score_stats(T2, has_compound=True)
@@ -124,7 +96,7 @@ def test_plane_culls_are_invisible(switch, monkeypatch):
     pts, models = make_problem(30011, 300, seed=11)
     T2 = 2.25 * 0.05 ** 2
     comp = np.random.default_rng(2).uniform(0, 1, pts.shape[0])
-    ref = ref_score(pts, models, T2, comp)
+    ref = ref_score(sq_plane, pts, models, T2, comp)
     if switch:
         monkeypatch.setenv(switch, "1")
     ctx = _lib.Context(0)
@@ -184,7 +156,7 @@ def test_plane_filter_proof_near_threshold(monkeypatch):
                 st = ctx.score_stats(T * T)
                 assert st["contradictions"] == 0, (coord, tf, st)
                 got = ctx.score(hyps, T * T, want_masks=True)
-                ref = ref_score(pts, hyps, T * T)
+                ref = ref_score(sq_plane, pts, hyps, T * T)
                 assert np.array_equal(got["counts"], ref["counts"]) and np.array_equal(got["masks"], ref["masks"])
                 f32_seen |= st["filter"] == "f32"
         assert f32_seen
@@ -337,13 +309,7 @@ def _check_recovery(planes, labels, pts, gen_labels, gt, thr, sigma):
         # offset where the plane's points are (d itself also carries the normal's error times the distance from the origin)
         on = pts[gen_labels == j + 1]
         assert abs(np.mean(on @ planes[k, :3] + planes[k, 3])) < 2 * sigma
-    band = 1.5 * thr
-    res = np.abs(pts @ gt[:, :3].T + gt[:, 3])
-    near = np.argmin(res, axis=1)
-    floor_labels = np.where(res[np.arange(len(pts)), near] < band, near + 1, 0)
-    floor = float(np.mean(floor_labels != gen_labels))
-    me = datasets.misclassification(np.where(labels == K, 0, labels + 1), gen_labels)
-    assert me <= floor + 0.02, (me, floor)
+    _check_labelling(np.abs(pts @ gt[:, :3].T + gt[:, 3]), labels, gen_labels, thr)
 
 
 def test_find_planes_end_to_end():

@@ -11,6 +11,7 @@ import pytest
 
 import pyprogressivex as px
 from pyprogressivex import _estimators, _lib, _rng, datasets, parallel
+from primitive_helpers import _check_recovery, _check_scores, _want, ref_score, shuffled
 
 pytestmark = pytest.mark.gpu
 
@@ -24,32 +25,6 @@ def sq_sphere(pts, m):
     with np.errstate(invalid="ignore", over="ignore"):
         r = np.abs(dist(pts, m) - m[3])
         return r * r
-
-
-def ref_score(pts, models, T2, comp=None):
-    n = pts.shape[0]
-    q = parallel.fixed_point_scale(n)
-    words = (n + 63) // 64
-    out = dict(counts=[], values=[], shared=[], values_q=[], shared_q=[], masks=np.zeros((len(models), words), np.uint64))
-    for k, m in enumerate(models):
-        sq = sq_sphere(pts, m)
-        with np.errstate(invalid="ignore"):
-            inl = sq < T2
-        sc = np.maximum(0.0, 1.0 - sq[inl] / T2)
-        out["counts"].append(int(inl.sum()))
-        out["values"].append(sc.sum())
-        out["values_q"].append(int(np.rint(sc * q).astype(np.int64).sum()))
-        sh = np.minimum(comp[inl], sc) if comp is not None else np.zeros(0)
-        out["shared"].append(sh.sum())
-        out["shared_q"].append(int(np.rint(sh * q).astype(np.int64).sum()))
-        bits = np.zeros(words * 64, dtype=bool)
-        bits[:n] = inl
-        out["masks"][k] = np.packbits(bits, bitorder="little").view("<u8")
-    for key in ("counts", "values_q", "shared_q"):
-        out[key] = np.array(out[key], dtype=np.int64)
-    out["values"] = np.array(out["values"])
-    out["shared"] = np.array(out["shared"])
-    return out
 
 
 def make_problem(n, M, seed, scale=1.0):
@@ -97,11 +72,8 @@ def test_sphere_scoring_bit_exact(gpu_ctx, n, M):
     gpu_ctx.set_points(_lib.SPHERE3D, pts)
     gpu_ctx.set_compound(comp)
     got = gpu_ctx.score(models, T2, has_compound=True, exponent=2, want_masks=True)
-    ref = ref_score(pts, models, T2, comp)
-    assert np.array_equal(got["counts"], ref["counts"])
-    assert np.array_equal(got["masks"], ref["masks"])
-    assert np.all(np.abs(got["values"] - ref["values"]) <= 1e-9 * np.maximum(np.abs(ref["values"]), 1e-4))
-    assert np.all(np.abs(got["shared"] - ref["shared"]) <= 1e-9 * np.maximum(np.abs(ref["shared"]), 1e-4))
+    ref = ref_score(sq_sphere, pts, models, T2, comp)
+    _check_scores(got, ref)
     nomask = gpu_ctx.score(models, T2, has_compound=True, exponent=2)
     assert np.array_equal(nomask["counts"], ref["counts"])
     st = gpu_ctx.score_stats(T2, has_compound=True)
@@ -120,7 +92,7 @@ def test_sphere_culls_are_invisible(switch, monkeypatch):
     pts, models = make_problem(30011, 300, seed=11)
     T2 = 2.25 * 0.05 ** 2
     comp = np.random.default_rng(2).uniform(0, 1, pts.shape[0])
-    ref = ref_score(pts, models, T2, comp)
+    ref = ref_score(sq_sphere, pts, models, T2, comp)
     if switch:
         monkeypatch.setenv(switch, "1")
     ctx = _lib.Context(0)
@@ -185,7 +157,7 @@ def test_sphere_filter_proof_near_threshold(monkeypatch):
                     st = ctx.score_stats(T * T)
                     assert st["contradictions"] == 0, (off, tf, radius, scale, st)
                     got = ctx.score(hyps, T * T, want_masks=True)
-                    ref = ref_score(pts, hyps, T * T)
+                    ref = ref_score(sq_sphere, pts, hyps, T * T)
                     assert np.array_equal(got["counts"], ref["counts"]) and np.array_equal(got["masks"], ref["masks"])
                     assert ref["counts"][0] > 0
                     f32_seen += st["filter"] == "f32"
@@ -258,14 +230,6 @@ def test_sphere_graph_and_expansion_match_the_oracle(gpu_ctx, oracle, kind):
     ref_labels, ref_e, ref_cyc = oracle.expansion(Dq, graph, oracle.quantize_lambda(lam), oracle.quantize(h),
                                                   np.zeros(pts.shape[0], np.int32))
     assert np.array_equal(gpu_ctx.get_labels(), ref_labels) and eq == ref_e and cyc == ref_cyc
-
-
-def _want(est, pts, samples, S):
-    ok = (samples >= 0).all(1) & (samples < len(pts)).all(1)
-    ref, src = est.minimal(pts, samples[ok])
-    want = np.full((S, 4), np.nan)
-    want[np.flatnonzero(ok)[src]] = ref
-    return want
 
 
 def test_sphere_minimal_solvers_bitwise_the_estimator(gpu_ctx):
@@ -359,30 +323,6 @@ def test_sphere_refit_grams(gpu_ctx):
     # the single-selection refit through pgx_gram is the same fit
     one = est.nonminimal(gpu_ctx, ("label", 1), weights=w)
     assert np.abs(one[0] - jac[1][0]).max() < 1e-10
-
-
-def _check_recovery(spheres, labels, pts, gen_labels, gt, thr, sigma):
-    K = len(gt)
-    assert spheres.shape == (K, 4) and labels.dtype == np.int32
-    for g in gt:
-        k = int(np.argmin(np.linalg.norm(spheres[:, :3] - g[:3], axis=1)))
-        assert np.linalg.norm(spheres[k, :3] - g[:3]) < 2 * sigma, (spheres[k], g)
-        assert abs(spheres[k, 3] - g[3]) < 2 * sigma, (spheres[k], g)
-    band = 1.5 * thr
-    res = np.abs(np.linalg.norm(pts[:, None, :] - gt[None, :, :3], axis=2) - gt[None, :, 3])
-    near = np.argmin(res, axis=1)
-    floor_labels = np.where(res[np.arange(len(pts)), near] < band, near + 1, 0)
-    floor = float(np.mean(floor_labels != gen_labels))
-    me = datasets.misclassification(np.where(labels == K, 0, labels + 1), gen_labels)
-    assert me <= floor + 0.02, (me, floor)
-
-
-def shuffled(pts, gen, seed=0):
-    """Progressive NAPSAC (the default sampler) and PROSAC take the points as ordered by quality: their first samples come from the
-    first points, and every proposal restarts the sampler.  In make_spheres' order (sphere by sphere) every proposal would start
-    inside the first sphere, so the end-to-end tests put the points in a random order."""
-    order = np.random.default_rng(seed).permutation(len(pts))
-    return np.ascontiguousarray(pts[order]), gen[order]
 
 
 # minimum_point_number: a spurious sphere through the uniform outliers collects those inside its shell of width 3 x threshold; the
