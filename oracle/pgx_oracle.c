@@ -21,9 +21,9 @@
 
 int pgxo_model_dims(int model_type, int *point_dim, int *param_dim)
 {
-    /* type 7 is not assigned (include/pgx.h): -1 marks it, as pgx_model_dims fails for it */
-    static const int pd[PGXO_MODEL_TYPES] = {2, 4, 4, 5, 4, 4, 3, -1, 3};
-    static const int md[PGXO_MODEL_TYPES] = {3, 9, 9, 12, 3, 18, 4, -1, 4};
+    /* types 7 and 9 are not assigned (include/pgx.h): -1 marks them, as pgx_model_dims fails for them */
+    static const int pd[PGXO_MODEL_TYPES] = {2, 4, 4, 5, 4, 4, 3, -1, 3, -1, 2};
+    static const int md[PGXO_MODEL_TYPES] = {3, 9, 9, 12, 3, 18, 4, -1, 4, -1, 3};
     if (model_type < 0 || model_type >= PGXO_MODEL_TYPES || pd[model_type] < 0) return -1;
     if (point_dim) *point_dim = pd[model_type];
     if (param_dim) *param_dim = md[model_type];
@@ -134,6 +134,17 @@ static double sphere_residual(const double *p, const double *m)
     return fabs(dist - m[3]);
 }
 
+/* 2-D circle (findCircles; no reference counterpart): model (cx,cy,cr).  Distance from the circle
+ * r = |sqrt(dx dx + dy dy) - cr| with d = p - c, IEEE sqrt (include/pgx.h's type table; the DIM = 2 row of the round family's
+ * contract in csrc/residuals.hip.h).  Written out on two coordinates, not as the sphere's sum with a zero third term.  A negative cr
+ * is not special: the formula is evaluated as it stands. */
+static double circle_residual(const double *p, const double *m)
+{
+    const double dx = p[0] - m[0], dy = p[1] - m[1];
+    const double dist = sqrt(dx * dx + dy * dy);
+    return fabs(dist - m[2]);
+}
+
 /* U-14: the F estimator's symmetric-epipolar support (restated from the literature; see include/pgx.h pgx_epipolar_support).
  * out[0] = Sampson inliers (fundamental_sq < T2, strict as the scorer), out[1] = those with r^2 (1/|F x1|^2 + 1/|F^T x2|^2) < S2. */
 void pgxo_epipolar_support(const double *pts, int64_t n, const double *f, double T2, double S2, int64_t *out)
@@ -171,13 +182,14 @@ double pgxo_squared_residual(int model_type, const double *pt, const double *mod
     case PGXO_HOMOGRAPHY_SYM: return homography_sym_sq(pt, model);
     case PGXO_PLANE3D: r = plane_residual(pt, model); return r * r;
     case PGXO_SPHERE3D: r = sphere_residual(pt, model); return r * r;
+    case PGXO_CIRCLE2D: r = circle_residual(pt, model); return r * r;
     default: return NAN;
     }
 }
 
 /* Unsquared residual used by PEARL::parameterEstimation (PEARL.h:371,390).  For the estimators whose
  * source is absent it is restated as sqrt(squaredResidual) [UPSTREAM-MEMORY].  The types whose squared residual is DEFINED as
- * r * r (line, vanishing point, plane, sphere) return r itself: sqrt(r * r) differs from r in the last bit for some r. */
+ * r * r (line, vanishing point, plane, sphere, circle) return r itself: sqrt(r * r) differs from r in the last bit for some r. */
 double pgxo_residual(int model_type, const double *pt, const double *model)
 {
     switch (model_type) {
@@ -185,6 +197,7 @@ double pgxo_residual(int model_type, const double *pt, const double *model)
     case PGXO_VANISHING_POINT: return vp_residual(pt, model);
     case PGXO_PLANE3D: return plane_residual(pt, model);
     case PGXO_SPHERE3D: return sphere_residual(pt, model);
+    case PGXO_CIRCLE2D: return circle_residual(pt, model);
     default: return sqrt(pgxo_squared_residual(model_type, pt, model));
     }
 }
@@ -1157,12 +1170,36 @@ static void solve_sphere4(const double *pts, int64_t n, const int32_t *smp, doub
     out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = r;
 }
 
+/* 3-point circle (include/pgx.h pgx_solve_minimal / pgx_set_radius_range; the operation order csrc/solve.hip states as the contract):
+ * a_i = p_i - p0 (i = 1, 2), h_i = 0.5 (a_i0 a_i0 + a_i1 a_i1), det = a_10 a_21 - a_11 a_20, e_0 = (h_1 a_21 - h_2 a_11) / det,
+ * e_1 = (a_10 h_2 - a_20 h_1) / det, r = sqrt(e_0 e_0 + e_1 e_1), c = p0 + e.  det == 0 (collinear / coincident points), a non-finite
+ * centre or radius and a radius outside the INCLUSIVE range [rmin, rmax] leave the NaN row. */
+static void solve_circle3(const double *pts, int64_t n, const int32_t *smp, double rmin, double rmax, double *out)
+{
+    out[0] = out[1] = out[2] = NAN;
+    for (int k = 0; k < 3; ++k) if (smp[k] < 0 || smp[k] >= n) return;
+    const double *p0 = pts + (size_t)smp[0] * 2, *p1 = pts + (size_t)smp[1] * 2, *p2 = pts + (size_t)smp[2] * 2;
+    const double a10 = p1[0] - p0[0], a11 = p1[1] - p0[1];
+    const double a20 = p2[0] - p0[0], a21 = p2[1] - p0[1];
+    const double h1 = 0.5 * (a10 * a10 + a11 * a11);
+    const double h2 = 0.5 * (a20 * a20 + a21 * a21);
+    const double det = a10 * a21 - a11 * a20;
+    if (!(det != 0.0)) return;                 /* also NaN */
+    const double e0 = (h1 * a21 - h2 * a11) / det;
+    const double e1 = (a10 * h2 - a20 * h1) / det;
+    const double r = sqrt(e0 * e0 + e1 * e1);
+    const double cx = p0[0] + e0, cy = p0[1] + e1;
+    if (!(isfinite(cx) && isfinite(cy) && isfinite(r))) return;
+    if (!(r >= rmin && r <= rmax)) return;
+    out[0] = cx; out[1] = cy; out[2] = r;
+}
+
 int pgxo_solve_minimal(int model_type, const double *pts, int64_t n, const int32_t *samples, int S, double *models_out)
 {
     return pgxo_solve_minimal_range(model_type, pts, n, samples, S, 0.0, INFINITY, models_out);
 }
 
-/* pgxo_solve_minimal with the radius range the sphere solver accepts (pgx_set_radius_range is context state on the device; the
+/* pgxo_solve_minimal with the radius range the sphere and circle solvers accept (pgx_set_radius_range is context state on the device; the
  * oracle has no context, so the caller passes it; the other solvers ignore it).  -2: an invalid range (NaN, rmin < 0, rmax < rmin). */
 int pgxo_solve_minimal_range(int model_type, const double *pts, int64_t n, const int32_t *samples, int S, double rmin, double rmax,
                              double *models_out)
@@ -1174,6 +1211,10 @@ int pgxo_solve_minimal_range(int model_type, const double *pts, int64_t n, const
     }
     if (model_type == PGXO_SPHERE3D) {
         for (int s = 0; s < S; ++s) solve_sphere4(pts, n, samples + (size_t)s * 4, rmin, rmax, models_out + (size_t)s * 4);
+        return 0;
+    }
+    if (model_type == PGXO_CIRCLE2D) {
+        for (int s = 0; s < S; ++s) solve_circle3(pts, n, samples + (size_t)s * 3, rmin, rmax, models_out + (size_t)s * 3);
         return 0;
     }
     if (model_type == PGXO_PNP) {

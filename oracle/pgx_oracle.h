@@ -34,7 +34,8 @@ enum {
     PGXO_HOMOGRAPHY_SYM = 5,  /* pt (x1,y1,x2,y2)    model [H | H^-1] 18 doubles (symmetric transfer) */
     PGXO_PLANE3D = 6,         /* pt (x,y,z)          model (a,b,c,d), (a,b,c) a unit normal  (no reference counterpart) */
     PGXO_SPHERE3D = 8,        /* pt (x,y,z)          model (cx,cy,cz,r)                      (no reference counterpart) */
-    PGXO_MODEL_TYPES = 9      /* one past the largest type number; 7 is not assigned: pgxo_model_dims(7) fails */
+    PGXO_CIRCLE2D = 10,       /* pt (x,y)            model (cx,cy,r)                         (no reference counterpart) */
+    PGXO_MODEL_TYPES = 11     /* one past the largest type number; 7 and 9 are not assigned: pgxo_model_dims fails for them */
 };
 
 #define PGXO_FIXED_SHIFT 32   /* energies are quantised to multiples of 2^-32 for the min-cut */
@@ -113,10 +114,10 @@ void pgxo_epipolar_support(const double *pts, int64_t n, const double *f, double
 double pgxo_residual_sum(int model_type, const double *pts, int64_t n, const double *model,
                          const int32_t *labels, int label);
 
-/* minimal solvers: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 4-point homography,
- * 7-point fundamental matrix, P3P; NaN model for a degenerate sample.  _range: the same with the INCLUSIVE radius range of the
- * sphere solver (the device keeps it as context state, pgx_set_radius_range; [0, +inf] for pgxo_solve_minimal): a sphere whose
- * radius lies outside gives a NaN row; -2 for an invalid range (NaN, rmin < 0, rmax < rmin). */
+/* minimal solvers: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 4-point
+ * homography, 7-point fundamental matrix, P3P; NaN model for a degenerate sample.  _range: the same with the INCLUSIVE radius range of
+ * the sphere and circle solvers (the device keeps it as context state, pgx_set_radius_range; [0, +inf] for pgxo_solve_minimal): a
+ * sphere or circle whose radius lies outside gives a NaN row; -2 for an invalid range (NaN, rmin < 0, rmax < rmin). */
 int pgxo_solve_minimal(int model_type, const double *pts, int64_t n, const int32_t *samples, int S, double *models_out);
 int pgxo_solve_minimal_range(int model_type, const double *pts, int64_t n, const int32_t *samples, int S, double rmin, double rmax,
                              double *models_out);

@@ -14,10 +14,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("PGX_ORACLE_SO") or os.path.join(_HERE, "libpgx_oracle.so")   # (scripts/sanitize.sh points it at the ASAN/UBSAN build)
 
 LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM = range(6)
-PLANE3D, SPHERE3D = 6, 8            # 7 is not assigned (include/pgx.h)
-POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4, PLANE3D: 3, SPHERE3D: 3}
-PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18, PLANE3D: 4, SPHERE3D: 4}
-SAMPLE_SIZE = {0: 2, 1: 4, 2: 7, 3: 3, 4: 2, PLANE3D: 3, SPHERE3D: 4}      # the types with a minimal solver here
+PLANE3D, SPHERE3D, CIRCLE2D = 6, 8, 10            # 7 and 9 are not assigned (include/pgx.h)
+POINT_DIM = {0: 2, 1: 4, 2: 4, 3: 5, 4: 4, 5: 4, PLANE3D: 3, SPHERE3D: 3, CIRCLE2D: 2}
+PARAM_DIM = {0: 3, 1: 9, 2: 9, 3: 12, 4: 3, 5: 18, PLANE3D: 4, SPHERE3D: 4, CIRCLE2D: 3}
+SAMPLE_SIZE = {0: 2, 1: 4, 2: 7, 3: 3, 4: 2, PLANE3D: 3, SPHERE3D: 4, CIRCLE2D: 3}      # the types with a minimal solver here
 FIXED_ONE = 1 << 32
 
 
@@ -350,8 +350,9 @@ def model_dims(model_type):
 
 def solve_minimal(model_type, pts, samples, radius_range=(0.0, np.inf)):
     """[S,3] models of the 2-point line / 2-segment vanishing point solvers, [S,4] of the 3-point plane / 4-point sphere solvers,
-    [3S,9] (three slots per sample) of the 7-point fundamental matrix solver; NaN rows = no model.  radius_range: the inclusive
-    (rmin, rmax) the sphere solver accepts (the device's pgx_set_radius_range), ignored by the other solvers"""
+    [S,3] of the 3-point circle solver, [3S,9] (three slots per sample) of the 7-point fundamental matrix solver; NaN rows = no model.
+    radius_range: the inclusive (rmin, rmax) the sphere and circle solvers accept (the device's pgx_set_radius_range), ignored by
+    the other solvers"""
     pts = _f64(pts); samples = _i32(samples)
     shape = {FUNDAMENTAL: (samples.shape[0] * 3, 9), HOMOGRAPHY: (samples.shape[0], 9), PNP: (samples.shape[0] * 4, 12),
              PLANE3D: (samples.shape[0], 4), SPHERE3D: (samples.shape[0], 4)}.get(model_type, (samples.shape[0], 3))
@@ -535,7 +536,7 @@ def graph_build(points, kind, radius=0.0, k=5):
 # the other estimators' solvers are absent from the snapshot (graph-cut-ransac submodule) and restated from the
 # literature: normalised DLT / 8-point rows, Gauss-Newton rows of the reprojection error at [R|t].
 # ---------------------------------------------------------------------------------------------------------------------
-GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE = 0, 1, 2, 3, 4, 5
+GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE = 0, 1, 2, 3, 4, 5, 6
 
 
 def gram_rows(kind, p, params=None):
@@ -577,6 +578,12 @@ def gram_rows(kind, p, params=None):
         ox, oy, oz, sc = [float(v) for v in params]
         u, v, w = (p[:, 0] - ox) / sc, (p[:, 1] - oy) / sc, (p[:, 2] - oz) / sc
         return [np.column_stack([one, u, v, w, (u * u + v * v) + w * w])], bad
+    if kind == GRAM_CIRCLE:
+        # include/pgx.h PGX_GRAM_CIRCLE: (1, u, v, u u + v v), (u, v) = (p - o) / s, params = (ox, oy, s): the rows of the algebraic
+        # circle fit on coordinates centred at o and scaled by s (2-D points)
+        ox, oy, sc = [float(v) for v in params]
+        u, v = (p[:, 0] - ox) / sc, (p[:, 1] - oy) / sc
+        return [np.column_stack([one, u, v, u * u + v * v])], bad
     raise ValueError(kind)
 
 

@@ -7,7 +7,9 @@ MODEL_CASES = {"line": 0, "homography": 1, "fundamental": 2, "pnp": 3, "vanishin
 # The 3-D point-cloud types live in a table of their own: tests index per-name dictionaries with MODEL_CASES and the soaks pick the
 # type by trial % len(MODEL_CASES), so growing that table would silently change what the committed seeds test.
 MODEL_CASES_3D = {"plane": 6, "sphere": 8}
-ALL_MODEL_CASES = {**MODEL_CASES, **MODEL_CASES_3D}
+# ... and so does the 2-D circle (findCircles, type 10), for the same reason: MODEL_CASES and MODEL_CASES_3D keep their contents and order
+MODEL_CASES_2D = {"circle": 10}
+ALL_MODEL_CASES = {**MODEL_CASES, **MODEL_CASES_3D, **MODEL_CASES_2D}
 
 
 def _fit_n(rng, arr, n):
@@ -48,6 +50,9 @@ def make_case(name, n, M, seed=0):
     elif name == "sphere":
         pts, _, gt = datasets.make_spheres(n_per_sphere=per, n_spheres=3, n_outliers=per, seed=seed)
         thr = 0.05
+    elif name == "circle":            # pixel units (box 1000, radii 40 .. 150, noise 0.5); findCircles' default threshold
+        pts, _, gt = datasets.make_circles(n_per_circle=per, n_circles=3, n_outliers=per, seed=seed)
+        thr = 2.0
     else:
         raise KeyError(name)
     pts = _fit_n(rng, pts, n)
@@ -128,11 +133,12 @@ def fixed_point_accumulators(O, mt, pts, models, T2, comp=None, n_total=None):
     return dict(counts=counts, values_q=values_q, shared_q=shared_q)
 
 
-# ---- 3-D point-cloud scenes shared by the CPU and GPU files of findPlanes / findSpheres ------------------------------------------
+# ---- point-cloud scenes shared by the CPU and GPU files of findPlanes / findSpheres / findCircles ---------------------------------
 def scene_3d(kind, per=800, structures=3, outliers=800, seed=0):
-    """(points [n, 3] in random order, labels, ground truth [K, 4]) of datasets.make_planes / make_spheres.  Shuffled: PROSAC and
-    Progressive NAPSAC read the order as quality, and the generators emit structure by structure."""
-    mk = datasets.make_planes if kind == "plane" else datasets.make_spheres
+    """(points [n, 3] in random order, labels, ground truth [K, 4]) of datasets.make_planes / make_spheres; for kind "circle"
+    (points [n, 2], labels, ground truth [K, 3]) of datasets.make_circles.  Shuffled: PROSAC and Progressive NAPSAC read the order
+    as quality, and the generators emit structure by structure."""
+    mk = {"plane": datasets.make_planes, "sphere": datasets.make_spheres, "circle": datasets.make_circles}[kind]
     pts, gt, models = mk(per, structures, outliers, seed=seed)
     order = np.random.default_rng(seed + 100).permutation(len(pts))
     return np.ascontiguousarray(pts[order]), gt[order], models
@@ -140,7 +146,7 @@ def scene_3d(kind, per=800, structures=3, outliers=800, seed=0):
 
 def match_3d(kind, found, truth):
     """for every ground-truth structure the distance to the nearest found model: planes max(|n x n'| sign-free normal difference,
-    |d - d'|), spheres max(|c - c'|, |r - r'|)"""
+    |d - d'|), spheres and circles max(|c - c'|, |r - r'|)"""
     out = []
     for g in truth:
         best = np.inf
@@ -177,6 +183,33 @@ def edge_clouds_3d(kind):
         "coplanar": (np.column_stack([uv[:, 0], uv[:, 1], 0.25 * uv[:, 0] - 0.5 * uv[:, 1] + 1.0]), kind == "sphere"),
         "outliers_only": (rng.uniform(0.0, 10.0, (300, 3)), False),
         "offset_1e6": (base + np.array([1e6, -1e6, 5e5]), False),
+        "nan_row": (nan_row, False),
+        "inf_row": (inf_row, False),
+        "refused_nan": (refused_nan, False),
+        "refused_inf": (refused_inf, False),
+    }
+
+
+def edge_clouds_2d():
+    """edge_clouds_3d for findCircles (pixel units): name -> (points [n, 2], zero_models).  The degenerate clouds have dyadic
+    coordinates of a few bits, so every difference and product of the 3-point solver is exact and det == 0 exactly (NaN rows); with
+    rounded coordinates a huge circle hugging a line is a legitimate model.  Both columns of a 2-D point are grid coordinates of
+    pgx_graph_build, so every non-finite row is refused there: "nan_row" / "inf_row" are the refused rows of the 2-D table, in the
+    second column, and "refused_nan" / "refused_inf" the same in the first."""
+    rng = np.random.default_rng(23)
+    t = rng.integers(-24, 25, 60) / 8.0
+    base, _, _ = scene_3d("circle", per=150, structures=2, outliers=100, seed=4)
+    nan_row, inf_row, refused_nan, refused_inf = base.copy(), base.copy(), base.copy(), base.copy()
+    nan_row[5, 1] = np.nan
+    inf_row[7, 1] = np.inf
+    refused_nan[5, 0] = np.nan
+    refused_inf[7, 0] = -np.inf
+    return {
+        "n_equals_sample_size": (rng.uniform(0.0, 1000.0, (3, 2)), False),
+        "coincident": (np.tile(np.array([[150.5, -20.25]]), (60, 1)), True),
+        "collinear": (np.array([100.0, 200.0]) + 16.0 * t[:, None] * np.array([0.5, 0.75]), True),
+        "outliers_only": (rng.uniform(0.0, 1000.0, (300, 2)), False),
+        "offset_1e6": (base + np.array([1e6, -1e6]), False),
         "nan_row": (nan_row, False),
         "inf_row": (inf_row, False),
         "refused_nan": (refused_nan, False),

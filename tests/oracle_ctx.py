@@ -77,7 +77,7 @@ class OracleContext:
         self.graph = (np.asarray(off, np.int32), np.asarray(idx, np.int32), np.asarray(mult, np.int32))
 
     def set_radius_range(self, rmin=0.0, rmax=float("inf")):
-        """pgx_set_radius_range: context state that only the sphere solver reads and that set_points leaves alone; NaN, rmin < 0 or
+        """pgx_set_radius_range: context state that only the sphere (type 8) and circle (type 10) solvers read and that set_points leaves alone; NaN, rmin < 0 or
         rmax < rmin are refused (the device returns PGX_ERR_INVALID, which _lib raises as RuntimeError), rmax = +inf is allowed"""
         rmin, rmax = float(rmin), float(rmax)
         if not (rmin >= 0.0 and rmax >= rmin):

@@ -15,8 +15,10 @@ import hashlib
 
 import numpy as np
 
-from helpers import ALL_MODEL_CASES, make_case
+from helpers import make_case
 
+# the eight types the golden file was recorded with, in its order (helpers.ALL_MODEL_CASES has grown since: circles are not recorded)
+PLAN_TYPES = ("line", "homography", "fundamental", "pnp", "vanishing_point", "homography_sym", "plane", "sphere")
 NS = (65, 513, 4097)
 MS = (64, 65, 257)
 # (type, T2 outside the window): kBoundBall | kBoundBoxAll | kBoundVanishing | the homography family | kBoundBox (umax > T * 2^14)
@@ -34,7 +36,7 @@ def _geo_id(geo):
 def cases():
     """{case id: (type, n, M, T2 or None for the case's own threshold, compound + masks, geometry)} in a fixed order"""
     out = {}
-    for name in ALL_MODEL_CASES:
+    for name in PLAN_TYPES:
         for n in NS:
             for M in MS:
                 for full in (False, True):

@@ -167,7 +167,10 @@ def classify(fn, args, kw, gpu, _aligned=False):
 def problem_3d(rng, name, s, K, per, nout, kw):
     """a findPlanes / findSpheres call on a random small cloud (shared with tests/soak_replay.py): (fn, args, kw).  The cloud is
     shuffled (samplers 1 and 3 read the order as quality), a third of them lie far from the origin, half of the calls carry
-    weights, half of the sphere calls a radius range; thresholds and ball radii are in the generators' units (box 10, noise 0.01)."""
+    weights, half of the sphere calls a radius range; thresholds and ball radii are in the generators' units (box 10, noise 0.01).
+    name "circle": problem_2d's findCircles call instead (its draws are its own: the streams of the 3-D seeds do not move)."""
+    if name == "circle":
+        return problem_2d(rng, s, K, per, nout, kw)
     mk = datasets.make_planes if name == "plane" else datasets.make_spheres
     pts, gt, _ = mk(per, K, nout, seed=s)
     pts = np.ascontiguousarray(pts[rng.permutation(len(pts))])
@@ -185,11 +188,32 @@ def problem_3d(rng, name, s, K, per, nout, kw):
     return (px.findPlanes if name == "plane" else px.findSpheres), (pts,), kw
 
 
+def problem_2d(rng, s, K, per, nout, kw):
+    """a findCircles call on a random small 2-D point set in make_circles' pixel units (box 1000, radii 40 .. 150, noise 0.5; shared
+    with tests/soak_replay.py): (fn, args, kw).  Shuffled, a third of the scenes moved by a 2-vector of length 10^U(0, 6), half of the
+    calls with weights and half under a radius range; samplers 0 to 3, both exponents, thresholds and ball radii in pixels (local
+    optimisation, neighbourhood kind and the rest come with the caller's kw)."""
+    pts, gt, _ = datasets.make_circles(per, K, nout, seed=s)
+    pts = np.ascontiguousarray(pts[rng.permutation(len(pts))])
+    if rng.random() < 0.34:
+        t = rng.normal(size=2)
+        pts = pts + t * (10.0 ** rng.uniform(0, 6) / np.linalg.norm(t))
+    kw = dict(kw)
+    kw.update(threshold=float(rng.choice([1.0, 2.0, 4.0])), sampler_id=int(rng.choice([0, 1, 2, 2, 3, 3])),
+              minimum_point_number=int(rng.choice([10, 30])), neighborhood_ball_radius=float(rng.choice([20.0, 60.0, 200.0])),
+              scoring_exponent=int(rng.choice([1, 2])))
+    if rng.random() < 0.5:
+        kw["weights"] = rng.random(len(pts)) + 0.25
+    if rng.random() < 0.5:
+        kw["radius_range"] = (float(rng.choice([0.0, 30.0, 70.0])), float(rng.choice([100.0, 200.0, np.inf])))
+    return px.findCircles, (pts,), kw
+
+
 LAST = {}      # statistics of the last soak() call
 
 
 def soak(seed, trials, verbose=True, only=None, types=None):
-    """types: names of 3-D point-cloud types ("plane", "sphere") to draw instead of the five image-space calls (default: those
+    """types: names of point-cloud types ("plane", "sphere", "circle") to draw instead of the five image-space calls (default: those
     five, trial % 5 - the stream every committed seed was run with)"""
     rng = np.random.default_rng(seed)
     per_type = {}
@@ -216,7 +240,7 @@ def soak(seed, trials, verbose=True, only=None, types=None):
         nout = int(rng.choice([0, 50, 400]))
         if types is not None:
             name3d = list(types)[trial % len(types)]
-            which = 5 if name3d == "plane" else 6
+            which = {"plane": 5, "sphere": 6, "circle": 7}[name3d]
             fn, args, kw = problem_3d(rng, name3d, s, K, per, nout, kw)
         elif which == 0:
             pts, gt, _ = datasets.make_lines(n_per_line=per, n_lines=K, n_outliers=nout, seed=s)
@@ -267,7 +291,7 @@ def soak(seed, trials, verbose=True, only=None, types=None):
             A, B = M.reshape(-1, rows * M.shape[1]), Mr.reshape(-1, rows * M.shape[1])
             tol = 1e-7 * np.abs(B).max(axis=1, keepdims=True) + 1e-9
             same = np.all(np.abs(A - B) <= tol, axis=1)
-            if which not in (4, 6):           # (a pose and a sphere have one sign)
+            if which not in (4, 6, 7):        # (a pose, a sphere and a circle have one sign)
                 same |= np.all(np.abs(A + B) <= tol, axis=1)
             ok = bool(same.all())
         if not ok:

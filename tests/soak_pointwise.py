@@ -10,7 +10,7 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [HERE, os.path.join(HERE, "..", "progressive-x_amd"), os.path.join(HERE, "..", "oracle"), os.path.join(HERE, "..")]
 import numpy as np
-from helpers import MODEL_CASES, MODEL_CASES_3D, make_case
+from helpers import MODEL_CASES, MODEL_CASES_2D, MODEL_CASES_3D, make_case
 from soak_scoring import offset_scene
 from pyprogressivex import _lib
 import pgx_oracle as O
@@ -43,7 +43,8 @@ LAST = {}      # statistics of the last soak() call
 
 def soak(seed, trials, verbose=True, types=None):
     """types: the model types to draw, by name (default: the six of MODEL_CASES - the stream every committed seed was run with); the
-    3-D types also get whole scenes moved far from the origin and, for spheres, a radius range on the solver"""
+    3-D types and the circle also get whole scenes moved far from the origin and, for spheres and circles, a radius range on the
+    solver in half of the cases"""
     rng = np.random.default_rng(seed)
     ctx = _lib.Context(0)
     bad = 0
@@ -72,7 +73,7 @@ def soak(seed, trials, verbose=True, types=None):
             pts *= 10.0 ** rng.uniform(-30, 30)          # the whole data set at an absurd scale
         elif mode == 3 and rng.random() < 0.3:
             pts[rng.integers(0, n, 3)] = rng.choice([np.nan, np.inf, -np.inf, 1e200, 1e-200])
-        if name in MODEL_CASES_3D and rng.random() < 0.34:
+        if (name in MODEL_CASES_3D or name in MODEL_CASES_2D) and rng.random() < 0.34:
             pts, models = offset_scene(rng, name, pts, models)
         T2 = 2.25 * thr * thr * 10.0 ** (rng.uniform(-3, 3) if rng.random() < 0.8 else rng.uniform(-14, 14))
         tag = (name, n, M, mode, trial)
@@ -116,6 +117,10 @@ def soak(seed, trials, verbose=True, types=None):
                 rr = (0.0, np.inf)
                 if name == "sphere" and rng.random() < 0.5:          # pgx_set_radius_range: context state, reset below
                     lo = float(10.0 ** rng.uniform(-2, 1))
+                    rr = (lo, float(lo * 10.0 ** rng.uniform(0, 2))) if rng.random() < 0.8 else (lo, np.inf)
+                    ctx.set_radius_range(*rr)
+                if name == "circle" and rng.random() < 0.5:          # the same for the circle solver, in pixels (radii 40 .. 150)
+                    lo = float(10.0 ** rng.uniform(0, 3))
                     rr = (lo, float(lo * 10.0 ** rng.uniform(0, 2))) if rng.random() < 0.8 else (lo, np.inf)
                     ctx.set_radius_range(*rr)
                 got = ctx.solve_minimal(samples)

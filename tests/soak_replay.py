@@ -74,7 +74,7 @@ LAST = {}      # statistics of the last soak() call
 
 
 def soak(seed, trials, verbose=True, tie=1e-12, types=None):
-    """types: names of 3-D point-cloud types ("plane", "sphere") to draw instead of the five image-space calls (default: those
+    """types: names of point-cloud types ("plane", "sphere", "circle") to draw instead of the five image-space calls (default: those
     five - the stream every committed seed was run with)"""
     rng = np.random.default_rng(seed)
     bad = ties = events = pearl = walks = walk_events = 0

@@ -8,7 +8,7 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [HERE, os.path.join(HERE, "..", "progressive-x_amd"), os.path.join(HERE, "..", "oracle"), os.path.join(HERE, "..")]
 import numpy as np
-from helpers import MODEL_CASES, MODEL_CASES_3D, make_case
+from helpers import MODEL_CASES, MODEL_CASES_2D, MODEL_CASES_3D, make_case
 from pyprogressivex import _lib
 import pgx_oracle as O
 
@@ -17,9 +17,15 @@ LAST = {}      # statistics of the last soak() call: cases, mismatches, contradi
 
 
 def offset_scene(rng, name, pts, models):
-    """3-D types only: the whole scene - points and every hypothesis with them - moved by a vector of length 10^U(0, 8).  A plane
-    (n, d) becomes (n, d - n . t), a sphere (c, r) becomes (c + t, r): the residuals are the same numbers mathematically, the
-    filters' error budgets and the group balls are not."""
+    """point-cloud types only: the whole scene - points and every hypothesis with them - moved by a vector of length 10^U(0, 8).  A
+    plane (n, d) becomes (n, d - n . t), a sphere (c, r) becomes (c + t, r), a circle the same with a 2-vector: the residuals are the
+    same numbers mathematically, the filters' error budgets and the group balls are not."""
+    if name == "circle":          # (draws of its own: the streams of the 3-D seeds do not move)
+        t = rng.normal(size=2)
+        t *= 10.0 ** rng.uniform(0, 8) / np.linalg.norm(t)
+        models = models.copy()
+        models[:, :2] = models[:, :2] + t
+        return pts + t, models
     t = rng.normal(size=3)
     t *= 10.0 ** rng.uniform(0, 8) / np.linalg.norm(t)
     models = models.copy()
@@ -33,7 +39,8 @@ def offset_scene(rng, name, pts, models):
 def soak(seed, trials, verbose=True, verify=True, types=None):
     """types: the model types to draw, by name (default: the six of MODEL_CASES, trial % 6 - the stream every committed seed was
     run with).  For the 3-D types "rescaled by 10^+-160" reads per type: a plane's four numbers scale together; a sphere's centre and
-    radius scale together (the sphere blown up about the origin), and a third of the cases move the whole scene far from the origin.
+    radius scale together (the sphere blown up about the origin), and a third of the cases move the whole scene far from the origin;
+    a circle ("circle", type 10: the DIM = 2 instance of the round family's filter) is treated as a sphere.
     verify: the context is created with PGX_VERIFY=1 and every batch is also re-decided pair by pair on the device
     (pgx_score_stats[5]): a pair the group bound or the f32 filter discarded although the exact residual calls it an inlier is a
     contradiction - a hole in a filter proof - whether or not it happens to change a count."""
@@ -76,7 +83,7 @@ def soak(seed, trials, verbose=True, verify=True, types=None):
         if n >= 500 and trial % 3 == 0:
             pts[rng.integers(0, n, 20)] *= 10.0 ** rng.uniform(-6, 8)
             pts[10:30] = pts[10]
-        if name in MODEL_CASES_3D and rng.random() < 0.34:
+        if (name in MODEL_CASES_3D or name in MODEL_CASES_2D) and rng.random() < 0.34:
             pts, models = offset_scene(rng, name, pts, models)
             gt = models[0].copy()
         sq0 = O.squared_residuals(mt, pts, gt)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import pyprogressivex as px
-from helpers import edge_clouds_3d, match_3d, scene_3d
+from helpers import edge_clouds_2d, edge_clouds_3d, match_3d, scene_3d
 from oracle_ctx import OracleContext
 from pyprogressivex import _api, datasets
 
@@ -121,6 +121,46 @@ def test_spheres_with_radius_range_coherence_and_philox_identical_to_cpu_restate
     for kw in (dict(spatial_coherence_weight=0.1), dict(sampler_rng="philox", sampler_id=0), dict(scoring_exponent=1, sampler_id=1), dict(neighborhood="radius", neighborhood_ball_radius=0.3, spatial_coherence_weight=0.05)):
         (M, lab), (Mr, labr) = _both(monkeypatch, px.findPlanes, pts, seed=2, minimum_point_number=100, **kw)
         assert M.shape == Mr.shape == (3, 4) and np.array_equal(lab, labr) and np.allclose(M, Mr, rtol=1e-8, atol=1e-10), kw
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+@pytest.mark.parametrize("sampler_id", [0, 2, 3])
+def test_circles_identical_to_cpu_restatement(monkeypatch, sampler_id, weighted):
+    """findCircles on the GPU returns the labels (bit for bit) and the models (1e-8) of the same call on the oracle-backed context -
+    whose circle rows are checked against exact arithmetic (tests/test_oracle.py) and whose decisions against the replays
+    (tests/test_api2d_cpu.py) - for the uniform sampler, NAPSAC and Progressive NAPSAC, with and without refit weights; the three
+    circles of the generator are found within 5 sigma = 2.5 px"""
+    pts, gt, truth = scene_3d("circle")
+    w = np.random.default_rng(3).random(len(pts)) + 0.25 if weighted else None
+    (M, lab), (Mr, labr) = _both(monkeypatch, px.findCircles, pts, weights=w, seed=1, sampler_id=sampler_id, minimum_point_number=100)
+    assert M.shape == Mr.shape == (3, 3) and np.array_equal(lab, labr) and np.allclose(M, Mr, rtol=1e-8, atol=1e-10)
+    assert (match_3d("circle", M, truth) <= 2.5).all()
+
+
+def test_circles_with_radius_range_coherence_and_philox_identical_to_cpu_restatement(monkeypatch):
+    pts, gt, truth = scene_3d("circle")
+    for kw in (dict(radius_range=(20.0, 80.0)), dict(spatial_coherence_weight=0.1), dict(sampler_rng="philox"), dict(sampler_rng="philox", sampler_id=0),
+               dict(scoring_exponent=1, sampler_id=2), dict(scoring_exponent=1, sampler_id=1), dict(local_optimization="lsq"),
+               dict(neighborhood="radius", neighborhood_ball_radius=30.0, spatial_coherence_weight=0.05)):
+        (M, lab), (Mr, labr) = _both(monkeypatch, px.findCircles, pts, seed=2, minimum_point_number=100, **kw)
+        assert M.shape == Mr.shape and M.shape[0] >= 1 and np.array_equal(lab, labr) and np.allclose(M, Mr, rtol=1e-8, atol=1e-10), kw
+        if "radius_range" in kw:          # the radii are 110.07, 41.82 and 106.73: the range leaves the small circle whole
+            assert (M[:, 2] >= 20.0).all() and (M[:, 2] <= 80.0).all() and match_3d("circle", M, truth)[1] <= 2.5
+        else:
+            assert M.shape[0] == 3
+
+
+@pytest.mark.parametrize("name", ["nan_row", "inf_row", "refused_nan", "refused_inf"])
+def test_circles_non_finite_rows_are_refused_by_both_contexts(monkeypatch, name):
+    """both columns of a 2-D point are grid coordinates of pgx_graph_build: the device refuses a NaN / Inf in either, as the
+    oracle-backed context does (tests/test_api2d_cpu.py)"""
+    pts, _ = edge_clouds_2d()[name]
+    monkeypatch.setattr(_api, "_ctx", None)
+    with pytest.raises(RuntimeError, match="non-finite"):
+        px.findCircles(pts, seed=1, minimum_point_number=20)
+    monkeypatch.setattr(_api, "_ctx", OracleContext())
+    with pytest.raises(RuntimeError, match="non-finite"):
+        px.findCircles(pts, seed=1, minimum_point_number=20)
 
 
 # ---- the reference's own recorded results (the only reference-held evidence): every bundled scene with EXACTLY the
@@ -271,6 +311,10 @@ def _edge_cases():
         for name in ("n_equals_sample_size", "coincident", "collinear", "coplanar", "outliers_only", "nan_row", "inf_row") + (("offset_1e6",) if kind == "sphere" else ()):
             for sampler_id in (0, 3):
                 cases.append((f"{kind}s_{name}_sampler{sampler_id}", fn, (clouds[name][0],), dict(sampler_id=sampler_id, seed=1, minimum_point_number=20)))
+    clouds = edge_clouds_2d()                                                        # findCircles (helpers.edge_clouds_2d)
+    for name in ("n_equals_sample_size", "coincident", "collinear", "outliers_only", "offset_1e6"):
+        for sampler_id in (0, 3):
+            cases.append((f"circles_{name}_sampler{sampler_id}", px.findCircles, (clouds[name][0],), dict(sampler_id=sampler_id, seed=1, minimum_point_number=20)))
     return cases
 
 
@@ -281,14 +325,14 @@ def test_edge_inputs_identical_to_cpu_restatement(monkeypatch, case, capsys):
     assert M.shape == Mr.shape and lab.shape == (len(args[0]),) and lab.dtype == np.int32
     assert np.array_equal(lab, labr)
     if M.size:
-        rows = {px.findLines: 1, px.findVanishingPoints: 1, px.findPlanes: 1, px.findSpheres: 1}.get(fn, 3)
+        rows = {px.findLines: 1, px.findVanishingPoints: 1, px.findPlanes: 1, px.findSpheres: 1, px.findCircles: 1}.get(fn, 3)
         A, B = M.reshape(-1, rows * M.shape[1]), Mr.reshape(-1, rows * M.shape[1])
         tol = 1e-7 * np.abs(B).max(axis=1, keepdims=True) + 1e-9
         same = np.all(np.abs(A - B) <= tol, axis=1)
-        if fn not in (px.find6DPoses, px.findSpheres):
+        if fn not in (px.find6DPoses, px.findSpheres, px.findCircles):
             same |= np.all(np.abs(A + B) <= tol, axis=1)       # homogeneous models: either sign
         assert same.all(), (name, M, Mr)
-    K = M.shape[0] // {px.findLines: 1, px.findVanishingPoints: 1, px.findPlanes: 1, px.findSpheres: 1}.get(fn, 3)
+    K = M.shape[0] // {px.findLines: 1, px.findVanishingPoints: 1, px.findPlanes: 1, px.findSpheres: 1, px.findCircles: 1}.get(fn, 3)
     assert lab.min() >= 0 and lab.max() <= max(K, 1)            # K = outlier label (0 / 1 with a single model; all 0 with none)
     if fn in (px.findPlanes, px.findSpheres):
         kind = "plane" if fn is px.findPlanes else "sphere"
@@ -297,3 +341,9 @@ def test_edge_inputs_identical_to_cpu_restatement(monkeypatch, case, capsys):
             assert K == 0, name                                 # an exactly degenerate cloud holds no structure of this kind
         bad = np.nonzero(~np.isfinite(args[0]).all(axis=1))[0]
         assert (lab[bad] == K).all() or K == 0                  # a row with a NaN / an Inf is never an inlier
+    if fn is px.findCircles:
+        cloud = name[len("circles_"):name.rindex("_sampler")]
+        if edge_clouds_2d()[cloud][1] or cloud in ("n_equals_sample_size", "outliers_only"):
+            assert K == 0, name                                 # an exactly degenerate point set holds no circle
+        if cloud == "offset_1e6":
+            assert K == 2, name

@@ -404,3 +404,12 @@ def test_find_circles_in_a_mixed_scene():
     assert ((circles[:, 2] >= 20.0) & (circles[:, 2] <= 200.0)).all()
     on = labels < 3
     assert (gen[on] > 0).mean() > 0.9                    # the circles' labels are on the circles' points
+
+
+def test_the_numpy_restatement_and_the_oracle_are_the_same_witness(oracle):
+    """sq_circle above (numpy, written next to the kernels) and the C oracle's squared_residuals (pinned against exact arithmetic in
+    tests/test_oracle.py) agree bit for bit on every point and hypothesis of make_problem(5000, 256, ...), the special models
+    (r = 0, r < 0, r = inf, NaN) included: the two witnesses the circle kernels are held to say the same"""
+    pts, models = make_problem(5000, 256, seed=12)
+    for m in models:
+        assert np.array_equal(sq_circle(pts, m), oracle.squared_residuals(oracle.CIRCLE2D, pts, m), equal_nan=True)

@@ -161,3 +161,52 @@ def test_replay_soak_slice_3d():
     assert soak_replay.soak(2025, 40, verbose=False, types=TYPES_3D) == 0
     print(f"3-D replay soak: {soak_replay.LAST}")
     assert soak_replay.LAST["per_type"] == {"findPlanes": 20, "findSpheres": 20}
+
+
+# ---- the same soaks on the 2-D circle (type 10): new seeds, the `types=` stream, one type's share of the 3-D slices' cases ------------
+TYPES_2D = ("circle",)
+
+
+@pytest.mark.parametrize("seed", [121, 122, 123])
+def test_scoring_soak_slice_circles(oracle, seed):
+    """30 cases per seed of tests/soak_scoring.py on circles: hypotheses a hair from the truth, garbage, rescaled by up to 10^+-160
+    (centre and radius together), entries of wildly different magnitude, a third of the scenes moved up to 1e8 from the origin,
+    outliers blown up inside a group, thresholds on a residual and one ulp either side - counts, masks and values against the oracle,
+    and under PGX_VERIFY=1 no inlier pair that the ball bound or the f32 filter threw away.  The first machine check of the round
+    family's error budget (score_filters.hip.h RoundFilter32) at DIM = 2."""
+    import soak_scoring
+    assert soak_scoring.soak(seed, 30, verbose=False, types=TYPES_2D) == 0
+    st = soak_scoring.LAST
+    print(f"circle scoring soak seed {seed}: {st['per_type']}, {st['verified_pairs']:.3g} verified pairs, {st['contradictions']} contradictions")
+    assert st["contradictions"] == 0 and st["verified_pairs"] > 0 and st["per_type"] == {"circle": 30}
+
+
+@pytest.mark.parametrize("seed", [221, 222])
+def test_pointwise_soak_slice_circles(oracle, seed):
+    """75 cases per seed of tests/soak_pointwise.py on circles: preference vectors, compound maximum, unary table, residual sums, the
+    3-point solver (half of the cases under a radius range), neighbourhood graph, the inlier/outlier cut and the greedy labelling -
+    bit-exact against the oracle on wild hypotheses and point sets"""
+    import soak_pointwise
+    assert soak_pointwise.soak(seed, 75, verbose=False, types=TYPES_2D) == 0
+    print(f"circle pointwise soak seed {seed}: {soak_pointwise.LAST}")
+    assert soak_pointwise.LAST["per_type"] == {"circle": 75} and soak_pointwise.LAST["values_compared"] > 0
+
+
+@pytest.mark.parametrize("seed", [321, 322])
+def test_api_soak_slice_circles(oracle, seed):
+    """15 calls per seed of tests/soak_api.py: findCircles with random arguments (samplers 0 to 3, both exponents, weights, radius
+    ranges, ball radii, neighbourhoods, local optimisation, scenes far from the origin) on the GPU and through the same host code
+    over the CPU oracle; classified as in test_api_soak_slice"""
+    import soak_api
+    assert soak_api.soak(seed, 15, verbose=False, types=TYPES_2D) == 0
+    print(f"circle api soak seed {seed}: {soak_api.LAST}")
+    assert soak_api.LAST["per_type"] == {"findCircles": 15}
+
+
+def test_replay_soak_slice_circles():
+    """20 random findCircles calls through libpgx, every decision against the independent replay and every proposal walk against
+    the proposal replay (tests/soak_replay.py, types=)"""
+    import soak_replay
+    assert soak_replay.soak(2026, 20, verbose=False, types=TYPES_2D) == 0
+    print(f"circle replay soak: {soak_replay.LAST}")
+    assert soak_replay.LAST["per_type"] == {"findCircles": 20} and soak_replay.LAST["proposals"] > 0

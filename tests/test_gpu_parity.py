@@ -8,7 +8,7 @@ compound max) are required to be bit-identical: the kernels use the oracle's ope
 import numpy as np
 import pytest
 
-from helpers import (ALL_MODEL_CASES, MODEL_CASES, MODEL_CASES_3D, csr_from_pairs, make_case, random_sym_graph, realistic_labeling_problem)
+from helpers import (ALL_MODEL_CASES, MODEL_CASES, MODEL_CASES_2D, MODEL_CASES_3D, csr_from_pairs, make_case, random_sym_graph, realistic_labeling_problem)
 from pyprogressivex import _lib, datasets
 
 pytestmark = pytest.mark.gpu
@@ -106,9 +106,9 @@ def test_score_threshold_boundary_is_strict(gpu_ctx, oracle):
     assert np.array_equal(Dq, oracle.unary_q(mt, pts, model, thr, 0.25))
 
 
-@pytest.mark.parametrize("name", ["plane", "sphere"])
+@pytest.mark.parametrize("name", ["plane", "sphere", "circle"])
 def test_score_threshold_boundary_is_strict_3d(gpu_ctx, oracle, name):
-    """the same boundary for the 3-D types: the plane z = 0 / the sphere of radius 3 about the origin, points exactly 2 off it on
+    """the same boundary for the 3-D types and the circle: the plane z = 0 / the sphere (circle) of radius 3 about the origin, points exactly 2 off it on
     both sides (inside and outside the shell), a hair nearer, a hair farther and on it: r^2 == T2 = 4 is no inlier for the scorer
     (strict <) and is within the threshold for PEARL's data term; then the threshold one ulp either side of a residual of a
     realistic cloud, on the group path (n = 20011) as well"""
@@ -116,6 +116,9 @@ def test_score_threshold_boundary_is_strict_3d(gpu_ctx, oracle, name):
     if name == "plane":
         pts = np.array([[7.0, 5.0, 2.0], [-1.0, 1.0, -2.0], [3.0, 0.0, 1.999999], [0.0, 0.0, 0.0], [1.0, 3.0, 2.0000001], [4.0, 4.0, -1.5]])
         model = np.array([[0.0, 0.0, 1.0, 0.0]])
+    elif name == "circle":
+        pts = np.array([[5.0, 0.0], [0.0, -1.0], [4.999999, 0.0], [0.0, 3.0], [0.9999999, 0.0], [0.0, 1.5]])
+        model = np.array([[0.0, 0.0, 3.0]])
     else:
         pts = np.array([[5.0, 0.0, 0.0], [0.0, -1.0, 0.0], [0.0, 0.0, 4.999999], [0.0, 3.0, 0.0], [0.0, 0.0, 0.9999999], [0.0, 1.5, 0.0]])
         model = np.array([[0.0, 0.0, 0.0, 3.0]])
@@ -141,9 +144,10 @@ def test_score_threshold_boundary_is_strict_3d(gpu_ctx, oracle, name):
         assert oracle.score(mt, pts, models[:1], float(np.nextafter(sq[n // 5], np.inf)))["counts"][0] == int((sq <= sq[n // 5]).sum()) > c
 
 
-@pytest.mark.parametrize("name", ["plane", "sphere"])
+@pytest.mark.parametrize("name", ["plane", "sphere", "circle"])
 def test_3d_filters_adversarial(oracle, name, monkeypatch):
-    """The f32 filter and the ball bound of the 3-D types (score_filters.hip.h Filter32<kPlane3D> / <kSphere3D>) must never change
+    """The f32 filter and the ball bound of the 3-D types and of the circle (score_filters.hip.h FlatFilter32<3>, RoundFilter32<3> and
+    its DIM = 2 instance; the circle's scene is in pixels: box 1000, radii 40 .. 150) must never change
     a result: hypotheses at relative distance 1e-13 .. 1e-3 from the truth, thresholds exactly on residuals, scenes moved 1e3 .. 1e8
     from the origin (the budget's |d| and |c| terms), outliers blown up by 1e8 inside a group, spheres with r = 0, r < 0, a centre
     far outside the cloud and a radius that swallows it, whole-scene scales 1e-6 and 1e6, NaN / Inf rows.  Counts and masks equal
@@ -166,6 +170,13 @@ def test_3d_filters_adversarial(oracle, name, monkeypatch):
                 models[50] = [gt[0] + 1e4, gt[1], gt[2], 1e4 + gt[3]]          # the cloud's side of a huge sphere: nearly a plane
                 models[51] = [5.0, 5.0, 5.0, 40.0]                              # swallows the box: every point deep inside
                 models[52] = [5.0, 5.0, 5.0, 1e-300]
+            elif name == "circle":
+                models[48] = [gt[0], gt[1], 0.0]
+                models[49] = [gt[0], gt[1], -gt[2]]
+                models[50] = [gt[0] + 1e6, gt[1], 1e6 + gt[2]]                  # the point set's side of a huge circle: nearly a line
+                models[51] = [500.0, 500.0, 4000.0]                             # swallows the box: every point deep inside
+                models[52] = [500.0, 500.0, 1e-300]
+                models[53] = [gt[0], gt[1], np.inf]
             else:
                 models[48] = [gt[0], gt[1], gt[2], gt[3] + 1e3]                 # a parallel plane far away
                 models[49] = gt * 1e-8                                         # not a unit normal
@@ -173,13 +184,14 @@ def test_3d_filters_adversarial(oracle, name, monkeypatch):
                 models[51] = [0.0, 0.0, 0.0, 0.01]                              # no normal at all: r = |d| for every point
             scale = 1.0
             if variant.startswith("offset"):
-                t = rng.normal(size=3)
+                D = pts.shape[1]
+                t = rng.normal(size=D)
                 t *= float(variant[7:]) / np.linalg.norm(t)
                 models2 = models.copy()
                 if name == "plane":
                     models2[:, 3] = models[:, 3] - models[:, :3] @ t
                 else:
-                    models2[:, :3] = models[:, :3] + t
+                    models2[:, :D] = models[:, :D] + t
                 pts, models = pts + t, models2
             elif variant.startswith("scaled"):
                 scale = 1e6 if variant == "scaled_up" else 1e-6
@@ -192,7 +204,7 @@ def test_3d_filters_adversarial(oracle, name, monkeypatch):
                 pts[rng.integers(0, len(pts), 40)] *= 1e8
                 pts[100:130] = pts[100]
             elif variant == "non_finite":
-                pts[rng.integers(0, len(pts), 6), rng.integers(0, 3, 6)] = [np.nan, np.inf, -np.inf, 1e200, -1e200, 1e-200]
+                pts[rng.integers(0, len(pts), 6), rng.integers(0, pts.shape[1], 6)] = [np.nan, np.inf, -np.inf, 1e200, -1e200, 1e-200]
             ctx.set_points(mt, pts)
             comp = rng.random(len(pts)) * (rng.random(len(pts)) < 0.5)
             ctx.set_compound(comp)
@@ -672,7 +684,7 @@ def test_residual_sum(gpu_ctx, oracle, name):
         assert abs(got - ref) <= REL * max(abs(ref), 1e-300), name
 
 
-@pytest.mark.parametrize("name", ["plane", "sphere"])
+@pytest.mark.parametrize("name", ["plane", "sphere", "circle"])
 def test_residual_sum_at_the_ends_of_the_range_3d(gpu_ctx, oracle, name):
     """PEARL's refit sums add the plain residual r, not sqrt(r * r).  In range the two are the same double; they part where r * r
     under- or overflows (r = 1e-170: r * r = 0; r = 1e200: r * r = inf).  Device and oracle both return r + r there - an oracle left on
@@ -681,6 +693,8 @@ def test_residual_sum_at_the_ends_of_the_range_3d(gpu_ctx, oracle, name):
     for r in (1e-170, 1e200):
         if name == "plane":      # the plane z = 0, two points r above it
             pts, model = np.array([[0.0, 0.0, r], [1.0, 2.0, r], [3.0, 3.0, 1.0]]), np.array([0.0, 0.0, 1.0, 0.0])
+        elif name == "circle":   # two points at the centre of a circle of radius r
+            pts, model = np.array([[1.0, 2.0], [1.0, 2.0], [9.0, 9.0]]), np.array([1.0, 2.0, r])
         else:                    # two points at the centre of a sphere of radius r
             pts, model = np.array([[1.0, 2.0, 3.0], [1.0, 2.0, 3.0], [9.0, 9.0, 9.0]]), np.array([1.0, 2.0, 3.0, r])
         labels = np.array([0, 0, 1], np.int32)
@@ -1239,17 +1253,17 @@ def test_graph_build_error_paths(gpu_ctx):
 # ----------------------------------------------------------------------------------------------------------------------
 # SURVEY 8f rank 1 (first slice): minimal solvers on the GPU — bit-exact models, then scored where they are
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["line", "vanishing_point", "homography", "fundamental", "pnp", "plane", "sphere"])
+@pytest.mark.parametrize("name", ["line", "vanishing_point", "homography", "fundamental", "pnp", "plane", "sphere", "circle"])
 def test_solve_minimal_matches_oracle_and_scores_in_place(gpu_ctx, oracle, name):
     mt, pts, models, thr = make_case(name, 5000, 4, seed=9)
     rng = np.random.default_rng(4)
-    m = {"fundamental": 7, "homography": 4, "pnp": 3, "plane": 3, "sphere": 4}.get(name, 2)
+    m = {"fundamental": 7, "homography": 4, "pnp": 3, "plane": 3, "sphere": 4, "circle": 3}.get(name, 2)
     slots = {"fundamental": 3, "pnp": 4}.get(name, 1)
     samples = rng.integers(0, 5000, (3000, m)).astype(np.int32)
     if name in ("fundamental", "pnp"):                      # some all-inlier samples of one structure as well
         for s in range(100, 400):
             samples[s] = rng.choice(np.nonzero(np.arange(5000) % 5 == s % 3)[0], m, replace=False)
-    if name in MODEL_CASES_3D:                              # samples from the inliers of the three ground-truth structures
+    if name in MODEL_CASES_3D or name in MODEL_CASES_2D:    # samples from the inliers of the three ground-truth structures
         inl = [np.flatnonzero(oracle.squared_residuals(mt, pts, models[k]) < thr * thr) for k in range(3)]
         for s in range(100, 400):
             samples[s] = rng.choice(inl[s % 3], m, replace=False)
@@ -1273,12 +1287,13 @@ def test_solve_minimal_matches_oracle_and_scores_in_place(gpu_ctx, oracle, name)
     assert _rel(a["values"], b["values"]) < REL
     up = gpu_ctx.score(ref[ok], T2)                       # the same models through the upload path
     assert np.array_equal(up["counts"], a["counts"][ok])
-    if name in MODEL_CASES_3D:
+    if name in MODEL_CASES_3D or name in MODEL_CASES_2D:
         assert a["counts"][100:400].max() > 500           # the all-inlier samples found their structure
-    if name == "sphere":
+    if name in ("sphere", "circle"):
         # pgx_set_radius_range (context state): inclusive at both ends - the upper end IS a radius of the batch - and the rows it
         # removes are NaN on both sides; the kept rows are the unrestricted rows bit for bit; invalid ranges are refused
-        radii = np.sort(ref[ok, 3])
+        R = ref.shape[1] - 1                              # the radius column
+        radii = np.sort(ref[ok, R])
         rmin, rmax = float(radii[len(radii) // 4]), float(radii[3 * len(radii) // 4])
         try:
             for rr in ((rmin, rmax), (rmin, np.inf), (0.0, rmax), (rmax, rmax)):
@@ -1287,7 +1302,7 @@ def test_solve_minimal_matches_oracle_and_scores_in_place(gpu_ctx, oracle, name)
                 ref_r = oracle.solve_minimal(mt, pts, samples, radius_range=rr)
                 assert np.array_equal(ranged, ref_r, equal_nan=True), rr
                 keep = ~np.isnan(ranged[:, 0])
-                assert np.array_equal(keep, ok & (ref[:, 3] >= rr[0]) & (ref[:, 3] <= rr[1])) and np.array_equal(ranged[keep], ref[keep])
+                assert np.array_equal(keep, ok & (ref[:, R] >= rr[0]) & (ref[:, R] <= rr[1])) and np.array_equal(ranged[keep], ref[keep])
                 assert 0 < keep.sum() < ok.sum()
                 gpu_ctx.score_launch(T2)
                 assert np.array_equal(gpu_ctx.score_fetch()["counts"], oracle.score(mt, pts, ref_r, T2)["counts"])
@@ -1330,7 +1345,8 @@ def test_gram_matches_oracle(gpu_ctx, oracle, name, n):
              "fundamental": [(_lib.GRAM_EPI_F, np.array([0.01, 300.0, 200.0, 0.012, 310.0, 190.0]))],
              "pnp": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_PNP_GN, models[0][:12])],
              "plane": [(_lib.GRAM_AFFINE, None)],
-             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, np.array([5.1, 4.9, 5.3, 2.5]))]}[name]
+             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, np.array([5.1, 4.9, 5.3, 2.5]))],
+             "circle": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_CIRCLE, np.array([510.0, 490.0, 250.0]))]}[name]
     index = rng.permutation(n)[: max(1, n // 2)]
     for kind, prm in kinds:
         for sel, ref_index in ((("index", index), index), (("label", 1), np.nonzero(labels == 1)[0])):
@@ -1365,7 +1381,8 @@ def test_gram_batch_matches_oracle(gpu_ctx, oracle, name, B, m):
              "fundamental": [(_lib.GRAM_EPI_F, norm)],
              "pnp": [(_lib.GRAM_PNP_GN, lambda: models[0][:12] + 1e-3 * rng.random(12))],
              "plane": [(_lib.GRAM_AFFINE, None)],
-             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, lambda: np.array([5.1, 4.9, 5.3, 2.5]) * (1.0 + 0.1 * rng.random(4)))]}[name]
+             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, lambda: np.array([5.1, 4.9, 5.3, 2.5]) * (1.0 + 0.1 * rng.random(4)))],
+             "circle": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_CIRCLE, lambda: np.array([510.0, 490.0, 250.0]) * (1.0 + 0.1 * rng.random(3)))]}[name]
     index = np.array([rng.choice(n, m, replace=False) for _ in range(B)])
     for kind, make in kinds:
         prm = None if make is None else np.array([make() for _ in range(B)])
@@ -1495,7 +1512,8 @@ def test_label_batched_gram_and_residual_sums_are_bitwise_the_single_label_calls
              "fundamental": [(_lib.GRAM_EPI_F, np.array([norm * (1 + 0.1 * k) for k in range(K)]))],
              "pnp": [(_lib.GRAM_PNP_GN, models[:, :12])],
              "plane": [(_lib.GRAM_AFFINE, None)],
-             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, np.array([np.array([5.1, 4.9, 5.3, 2.5]) * (1 + 0.1 * k) for k in range(K)]))]}[name]
+             "sphere": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_SPHERE, np.array([np.array([5.1, 4.9, 5.3, 2.5]) * (1 + 0.1 * k) for k in range(K)]))],
+             "circle": [(_lib.GRAM_AFFINE, None), (_lib.GRAM_CIRCLE, np.array([np.array([510.0, 490.0, 250.0]) * (1 + 0.1 * k) for k in range(K)]))]}[name]
     for kind, prm in kinds:
         for w, wpow in ((None, 2), (weights, 1), (weights, 2)):
             G, cnt, bad = gpu_ctx.gram_labels(kind, K, params=prm, weights=w, wpow=wpow)
@@ -1756,7 +1774,7 @@ def test_inlier_indices_at_the_one_launch_compaction_limits(gpu_ctx, oracle, n):
         assert np.array_equal(gpu_ctx.gc_inliers(m, T2, 0.2), np.flatnonzero(oracle.gc_labeling(mt, pts, m, T2, 0.2, graph)))
 
 
-@pytest.mark.parametrize("name", ["pnp", "homography", "line", "plane", "sphere"])
+@pytest.mark.parametrize("name", ["pnp", "homography", "line", "plane", "sphere", "circle"])
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 5000, 100003])
 def test_score_inliers_are_the_mask_row(gpu_ctx, oracle, name, n):
     """pgx_score_inliers: the inlier vector of getScore (scoring_function_with_compound_model.h:88) as ascending indices,
@@ -1848,7 +1866,7 @@ def test_point_sharded_accumulators_are_exact(gpu_ctx, oracle):
     point-sharded job all-reduce is bitwise the single-GPU table."""
     from helpers import fixed_point_accumulators
     from pyprogressivex import parallel
-    for name in ("pnp", "fundamental", "vanishing_point", "plane", "sphere"):
+    for name in ("pnp", "fundamental", "vanishing_point", "plane", "sphere", "circle"):
         mt, pts, models, thr = make_case(name, 20011, 96, seed=9)
         T2 = 2.25 * thr * thr
         n = pts.shape[0]
@@ -2116,7 +2134,7 @@ def test_set_points_device_equals_host_preprocessing(name, n, monkeypatch, oracl
 
 
 @pytest.mark.parametrize("name,n", [("plane", 1), ("plane", 63), ("plane", 64), ("plane", 65), ("plane", 5000), ("plane", 100003),
-                                    ("sphere", 513), ("sphere", 20011)])
+                                    ("sphere", 513), ("sphere", 20011), ("circle", 513), ("circle", 20011)])
 def test_set_points_device_preprocessing_of_3d_points(name, n, monkeypatch, oracle):
     """Point dimension 3.  The host preprocessing of round 1 (PGX_SETPOINTS_HOST=1) has no sorted path for the types without a
     projective map: it scores every pair.  That makes it the independent side here: the device preprocessing (Morton order of all
@@ -2151,7 +2169,7 @@ def test_set_points_device_preprocessing_of_3d_points(name, n, monkeypatch, orac
     if order is not None:
         assert np.array_equal(np.sort(order), np.arange(n))
         full = n // 64
-        blocked = pts[order[:full * 64]].reshape(full, 64, 3).transpose(0, 2, 1)
+        blocked = pts[order[:full * 64]].reshape(full, 64, pts.shape[1]).transpose(0, 2, 1)
         assert np.array_equal(rows64[:full], blocked)    # the group-blocked f64 copy: the caller's rows, bit for bit, in that order
         tail = n - full * 64
         if tail:
@@ -2470,3 +2488,42 @@ def test_refit_solver_jacobi_on_the_gpu_equals_the_cpu_restatement(monkeypatch):
     monkeypatch.setattr(_api, "_ctx", OracleContext())
     Fc, lc = px.findTwoViewMotions(p3, 1000, 1000, 1000, 1000, refit_solver="jacobi", **kw)
     assert Fg.shape == Fc.shape and Fg.shape[0] >= 3 and np.array_equal(lg, lc)
+
+
+def test_golden_circle_rows_on_the_device(gpu_ctx):
+    """tests/golden/kat_circles_v1.npz (made from the oracle alone, tests/golden/make_golden_circles.py; tests/test_oracle.py replays
+    it on the CPU) through libpgx: squared residuals (as preferences under a huge threshold), counts, masks, the unary table and the
+    solver rows without and under the radius range bit for bit; score sums and residual sums to 1e-9 max(|ref|, 1e-4); Gram rows to
+    1e-9 of the matrix scale"""
+    import os
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_circles_v1.npz"))
+    mt = MODEL_CASES_2D["circle"]
+    pts, models, thr, comp = g["circle_pts"], g["circle_models"], float(g["circle_thr"][0]), g["circle_comp"]
+    T2 = 2.25 * thr * thr
+    gpu_ctx.set_points(mt, pts)
+    gpu_ctx.set_compound(comp)
+    got = gpu_ctx.score(models, T2, has_compound=True, exponent=2, want_masks=True)
+    assert np.array_equal(got["counts"], g["circle_counts"]) and np.array_equal(got["masks"], g["circle_masks"])
+    for k in ("values", "shared", "scores"):
+        assert np.all(np.abs(got[k] - g[f"circle_{k}"]) <= 1e-9 * np.maximum(np.abs(g[f"circle_{k}"]), 1e-4)), k
+    assert np.array_equal(gpu_ctx.preference(models[0], T2, slot=0, want_pref=True)["pref"], g["circle_pref0"])
+    sq = g["circle_sq0"]
+    big = float(sq.max() * 4 + 1)             # every preference in (0, 1]: bit-equality of 1 - sq / big for every point
+    assert np.array_equal(gpu_ctx.preference(models[0], big, slot=1, want_pref=True)["pref"], np.maximum(0.0, 1.0 - sq / big))
+    assert np.array_equal(gpu_ctx.pearl_unary(models[:3], thr, 0.1, want_table=True), g["circle_unary_q"])
+    gpu_ctx.set_labels(g["circle_labels"])
+    sums = np.array([gpu_ctx.residual_sum(models[k], k) for k in range(3)])
+    assert np.all(np.abs(sums - g["circle_residual_sums"]) <= 1e-9 * np.maximum(np.abs(g["circle_residual_sums"]), 1e-4))
+    assert np.all(np.abs(gpu_ctx.residual_sums(models[:3]) - g["circle_residual_sums"]) <= 1e-9 * np.maximum(np.abs(g["circle_residual_sums"]), 1e-4))
+    assert np.array_equal(gpu_ctx.solve_minimal(g["circle_samples"]), g["circle_solved"], equal_nan=True)
+    rr = g["circle_radius_range"]
+    try:
+        gpu_ctx.set_radius_range(float(rr[0]), float(rr[1]))
+        assert np.array_equal(gpu_ctx.solve_minimal(g["circle_samples"]), g["circle_solved_ranged"], equal_nan=True)
+    finally:
+        gpu_ctx.set_radius_range()
+    for kind in (_lib.GRAM_AFFINE, _lib.GRAM_CIRCLE):
+        prm = g["circle_gram_params"] if kind == _lib.GRAM_CIRCLE else None
+        G, cnt, bad = gpu_ctx.gram(kind, ("index", g["circle_idx"].astype(np.int32)), params=prm, weights=g["circle_w"], wpow=1)
+        ref = g[f"circle_G{kind}"]
+        assert (cnt, bad) == (120, 0) and np.abs(G - ref).max() <= REL * np.abs(ref).max()

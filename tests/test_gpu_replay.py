@@ -222,3 +222,25 @@ def test_c4_full_size_events_match_the_committed_replay_pin(gpu_api):
     assert np.array_equal(np.bincount(np.asarray(labels, dtype=np.int64), minlength=len(pin["label_histogram"])), pin["label_histogram"])
     assert models.shape[0] // 3 == pin["models"].shape[0] == 9
     assert np.array_equal(models.reshape(9, -1), pin["models"].reshape(9, -1))
+
+
+# ---- findCircles (model type 10) ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kw", [
+    dict(sampler_id=3), dict(sampler_id=2), dict(sampler_id=0), dict(sampler_id=1),
+    dict(sampler_id=3, spatial_coherence_weight=0.1, radius_range=(20.0, 300.0)), dict(sampler_id=3, scoring_exponent=1, weights=True),
+    dict(sampler_id=2, scoring_exponent=1)],
+    ids=lambda v: "-".join(f"{k}={x}" for k, x in v.items()))
+def test_circles_gpu_decisions_and_walks_equal_the_replays(gpu_api, kw):
+    """findCircles through libpgx.so on 3 x 800 inliers + 800 outliers (the scene of tests/test_api2d_cpu.py): every accept / reject,
+    PEARL iteration, refit decision and break reason equals oracle/progx_replay.c's (which recomputes them with the ORACLE's circle
+    residuals, pgxo_residual's plain r in the refit sums included), every proposal walk equals oracle/progx_proposal.c's; the three
+    circles come back within 5 sigma = 2.5 px"""
+    pts, gt, truth = scene_3d("circle")
+    kw = dict(kw)
+    if kw.pop("weights", False):
+        kw["weights"] = np.random.default_rng(3).random(len(pts)) + 0.25
+    out, rec, rep = _rr(px.findCircles, pts, seed=1, minimum_point_number=100, **kw)
+    K = H.assert_agree(out, rec, rep, 1)
+    assert K == 3 and (match_3d("circle", out[0], truth) <= 2.5).all()
+    out2, wrec = _walks_agree(px.findCircles, pts, seed=1, minimum_point_number=100, **kw)
+    assert np.array_equal(out2[1], out[1]) and np.array_equal(out2[0], out[0])

@@ -356,7 +356,8 @@ def test_preference_vectors_either_side_of_the_ring(gpu_ctx, oracle, n):
 # A.2  long index lists in pgx_gram: the fused upload of counters | index stops at kFusedIndexMax = 65 536 entries
 # ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,kind,prm", [("line", _lib.GRAM_AFFINE, None), ("plane", _lib.GRAM_AFFINE, None),
-                                           ("homography", _lib.GRAM_DLT_H, NORM), ("sphere", _lib.GRAM_SPHERE, np.array([5.1, 4.9, 5.3, 2.5]))])
+                                           ("homography", _lib.GRAM_DLT_H, NORM), ("sphere", _lib.GRAM_SPHERE, np.array([5.1, 4.9, 5.3, 2.5])),
+                                           ("circle", _lib.GRAM_CIRCLE, np.array([510.0, 490.0, 250.0]))])
 def test_gram_index_lists_either_side_of_the_fused_upload(gpu_ctx, oracle, name, kind, prm):
     """fit.hip gram_launch: up to 65 536 entries the index list is uploaded in one command with the 64 zero bytes of the counters in
     front of it; a longer one is uploaded from the caller's array behind a memset of the two counters in use.  m = 65 536 (fused),
@@ -439,6 +440,8 @@ def _shuffled_family(name, n, M, seed):
         models[:, 3] += 1e-3 * t * np.abs(models[:, 11])
     elif mt == _lib.HOMOGRAPHY:
         models[:, 2] += 1e-3 * t * np.abs(models[:, 8])
+    elif mt == _lib.CIRCLE2D:
+        models[:, 2] += 1e-3 * t                      # (cx, cy, r): the radius
     else:
         models[:, 3] += 1e-3 * t
     models = models[np.random.default_rng(seed + M).permutation(M)]
@@ -447,13 +450,13 @@ def _shuffled_family(name, n, M, seed):
 
 
 @pytest.mark.parametrize("n", [65, 130])
-@pytest.mark.parametrize("name", ["pnp", "homography", "plane"])
+@pytest.mark.parametrize("name", ["pnp", "homography", "plane", "circle"])
 def test_score_batch_sizes_across_the_reorder_and_the_padding(gpu_ctx, oracle, name, n):
     """capi.hip pgx_score_upload: a batch of more than 64 pose or homography hypotheses is reordered by locality key (the results come
     back in the caller's order through the device permutation, or through its host copy when the launch wrote the host mirror); Mpad
     rounds M up to 256 and the tail of the permutation is zero-filled.  M = 64 | 65 (reorder), 255 | 256 | 257 and 511 | 512 | 513
     (padding), 2049 (nine 256-blocks), with and without masks (without: the mirror), with and without the compound vector.  Planes (3-D)
-    are never reordered and take the same sizes."""
+    and circles (2-D) are never reordered and take the same sizes."""
     comp = np.random.default_rng(11).uniform(0, 1, n) * (np.random.default_rng(12).uniform(0, 1, n) < 0.5)
     resident = None
     for M in (64, 65, 255, 256, 257, 511, 512, 513, 2049):
@@ -476,7 +479,7 @@ def test_score_batch_sizes_across_the_reorder_and_the_padding(gpu_ctx, oracle, n
     gpu_ctx.set_compound(None)
 
 
-@pytest.mark.parametrize("name,S", [("pnp", 33), ("homography", 100), ("plane", 100)])
+@pytest.mark.parametrize("name,S", [("pnp", 33), ("homography", 100), ("plane", 100), ("circle", 100)])
 def test_device_generated_batches_come_back_in_sample_order_after_a_reordered_upload(gpu_ctx, oracle, name, S):
     """pgx_solve_minimal / pgx_solve_minimal_sampled leave their hypotheses in sample order (identity permutation on the device).  After
     a REORDERED upload of another M on the same context, a stale host permutation or mirror would shuffle the rows of the fetch: the

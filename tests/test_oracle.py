@@ -12,7 +12,7 @@ from fractions import Fraction as Fr
 import numpy as np
 import pytest
 
-from helpers import ALL_MODEL_CASES, MODEL_CASES, MODEL_CASES_3D, make_case, random_sym_graph
+from helpers import ALL_MODEL_CASES, MODEL_CASES, MODEL_CASES_2D, MODEL_CASES_3D, make_case, random_sym_graph
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_v1.npz")
 
@@ -55,6 +55,13 @@ def test_residual_known_answers(oracle):
     assert O.squared_residuals(O.SPHERE3D, [[4.0, 6.0, 3.0]], [1.0, 2.0, 3.0, 0.0]).tolist() == [25.0]
     assert O.squared_residuals(O.SPHERE3D, [[4.0, 6.0, 3.0]], [1.0, 2.0, 3.0, -2.0]).tolist() == [49.0]
     assert O.residual(O.SPHERE3D, [4.0, 6.0, 3.0], [1.0, 2.0, 3.0, -2.0]) == 7.0
+    # circle of radius 3 about (1, 2): 2 outside it, 2 inside it, on it, and its centre (|0 - 3| = 3); r = 0 and r < 0 as for the sphere
+    cir = [1.0, 2.0, 3.0]
+    assert O.squared_residuals(O.CIRCLE2D, [[6.0, 2.0], [1.0, 1.0], [1.0, -1.0], [1.0, 2.0]], cir).tolist() == [4.0, 4.0, 0.0, 9.0]
+    assert O.residual(O.CIRCLE2D, [6.0, 2.0], cir) == 2.0 and O.residual(O.CIRCLE2D, [1.0, 1.0], cir) == 2.0
+    assert O.squared_residuals(O.CIRCLE2D, [[4.0, 6.0]], [1.0, 2.0, 0.0]).tolist() == [25.0]
+    assert O.squared_residuals(O.CIRCLE2D, [[4.0, 6.0]], [1.0, 2.0, -2.0]).tolist() == [49.0]
+    assert O.residual(O.CIRCLE2D, [4.0, 6.0], [1.0, 2.0, -2.0]) == 7.0
 
 
 def _exact_sq(name, p, m):
@@ -101,6 +108,14 @@ def _exact_sq(name, p, m):
             root = (decimal.Decimal(q.numerator) / decimal.Decimal(q.denominator)).sqrt()
             rq = Fr(*root.as_integer_ratio())
         return q + m[3] ** 2 - 2 * m[3] * rq
+    if name == "circle":
+        # the same on two coordinates: (|p - c| - r)^2 = q + r^2 - 2 r sqrt(q), q = (x - cx)^2 + (y - cy)^2
+        q = (p[0] - m[0]) ** 2 + (p[1] - m[1]) ** 2
+        with decimal.localcontext() as c:
+            c.prec = 80
+            root = (decimal.Decimal(q.numerator) / decimal.Decimal(q.denominator)).sqrt()
+            rq = Fr(*root.as_integer_ratio())
+        return q + m[2] ** 2 - 2 * m[2] * rq
     raise KeyError(name)
 
 
@@ -298,6 +313,7 @@ def test_minimal_solvers_agree_with_the_host_formulas():
 
 
 # ---- committed vectors + hand-checkable cases ------------------------------------------------------------
+GOLDEN_CIRCLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_circles_v1.npz")
 GOLDEN_NEXT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_next_v1.npz")
 
 
@@ -570,11 +586,12 @@ GOLDEN_3D = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "
 
 
 def test_model_dims_agree_with_the_product_table_for_every_type_number(oracle):
-    """pgxo_model_dims against pyprogressivex._lib.MODEL_TABLE (the numbers of csrc/residuals.hip.h) for 0 .. 9: the same types
-    exist on both sides (7 and 9 do not), with the same point and parameter dimensions and, where the oracle has a solver, the
-    same sample size"""
+    """pgxo_model_dims against pyprogressivex._lib.MODEL_TABLE (the numbers of csrc/residuals.hip.h) for 0 .. 10: the same types
+    exist on both sides (10 known; 7 and 9 do not exist), with the same point and parameter dimensions and, where the oracle has a
+    solver, the same sample size"""
     from pyprogressivex import _lib
-    for t in range(10):
+    assert sum(t in _lib.MODEL_TABLE for t in range(11)) == 9 and 7 not in _lib.MODEL_TABLE and 9 not in _lib.MODEL_TABLE
+    for t in range(11):
         dims = oracle.model_dims(t)
         if t in _lib.MODEL_TABLE:
             assert dims == _lib.MODEL_TABLE[t][:2] == (oracle.POINT_DIM[t], oracle.PARAM_DIM[t]), t
@@ -584,9 +601,11 @@ def test_model_dims_agree_with_the_product_table_for_every_type_number(oracle):
     assert oracle.model_dims(-1) is None and np.isnan(oracle.squared_residuals(7, np.zeros((0, 3)), np.zeros(4))).all()
     assert (oracle.PLANE3D, oracle.SPHERE3D) == (_lib.PLANE3D, _lib.SPHERE3D) == (6, 8)
     assert oracle.GRAM_SPHERE == _lib.GRAM_SPHERE and oracle.GRAM_AFFINE == _lib.GRAM_AFFINE
+    assert oracle.CIRCLE2D == _lib.CIRCLE2D == 10 and oracle.GRAM_CIRCLE == _lib.GRAM_CIRCLE == 6
+    assert oracle.model_dims(11) is None and np.isnan(oracle.squared_residuals(9, np.zeros((0, 2)), np.zeros(3))).all()
 
 
-@pytest.mark.parametrize("name", list(MODEL_CASES_3D))
+@pytest.mark.parametrize("name", list(MODEL_CASES_3D) + list(MODEL_CASES_2D))
 def test_plain_residual_of_the_3d_types_is_not_the_root_of_the_square(oracle, name):
     """pgxo_residual (PEARL's refit sums) returns r itself for the types whose squared residual is defined as r * r, as the device's
     Residual<>::plain does.  In binary floating point sqrt(fl(r * r)) == r as long as r * r neither overflows nor underflows, so the
@@ -602,6 +621,8 @@ def test_plain_residual_of_the_3d_types_is_not_the_root_of_the_square(oracle, na
             assert abs(r * r - ex) <= 1e-9 * max(abs(ex), 1e-30) + 1e-18 * max(1.0, abs(ex))
     if name == "plane":      # the plane z = 0 and points 1e-170 / 1e200 above it
         cases = [([0.0, 0.0, 1e-170], [0.0, 0.0, 1.0, 0.0], 1e-170), ([0.0, 0.0, 1e200], [0.0, 0.0, 1.0, 0.0], 1e200)]
+    elif name == "circle":   # the centre of a circle of radius 1e-170 / 1e200
+        cases = [([1.0, 2.0], [1.0, 2.0, 1e-170], 1e-170), ([1.0, 2.0], [1.0, 2.0, 1e200], 1e200)]
     else:                    # the centre of a sphere of radius 1e-170 / 1e200
         cases = [([1.0, 2.0, 3.0], [1.0, 2.0, 3.0, 1e-170], 1e-170), ([1.0, 2.0, 3.0], [1.0, 2.0, 3.0, 1e200], 1e200)]
     for p, m, r in cases:
@@ -853,3 +874,174 @@ def test_golden_3d_rows(oracle):
     out = oracle.solve_minimal(oracle.SPHERE3D, g["sphere_pts"], g["sphere_samples"], radius_range=(float(rr[0]), float(rr[1])))
     assert np.array_equal(out, g["sphere_solved_ranged"], equal_nan=True)
     assert np.isnan(out[:, 0]).sum() > np.isnan(g["sphere_solved"][:, 0]).sum()
+
+
+# ---- the 2-D circle (type 10): the same evidence as the sphere's --------------------------------------------------------------------
+def _exact_circumcircle(P):
+    """centre (Fractions), squared radius (Fraction) and squared conditioning det^2 / (|a1|^2 |a2|^2) of the circle through the three
+    points P [3][2] of doubles, by Cramer's rule in exact rational arithmetic; None for collinear points"""
+    P = [[Fr(float(v)) for v in row] for row in P]
+    a = [[P[i][k] - P[0][k] for k in range(2)] for i in (1, 2)]
+    h = [(ai[0] * ai[0] + ai[1] * ai[1]) / 2 for ai in a]
+    det = a[0][0] * a[1][1] - a[0][1] * a[1][0]
+    if det == 0:
+        return None
+    e = [(h[0] * a[1][1] - h[1] * a[0][1]) / det, (a[0][0] * h[1] - a[1][0] * h[0]) / det]
+    cond2 = det * det / ((a[0][0] ** 2 + a[0][1] ** 2) * (a[1][0] ** 2 + a[1][1] ** 2))
+    return [P[0][0] + e[0], P[0][1] + e[1]], e[0] * e[0] + e[1] * e[1], cond2
+
+
+def test_circle_solver_against_exact_rational_arithmetic(oracle):
+    """The oracle's 3-point circle solver against the circumcircle in exact arithmetic (the centre of three points with double
+    coordinates is a rational number; the radius is the root of one, taken to 60 digits): centre and radius within 1e-9 relative on
+    every sample whose conditioning |det(a1, a2)| / (|a1| |a2|) is at least 1e-3; at most 5 % of the samples may fall under that
+    rule.  400 samples of a four-circle scene, half from one circle and half anywhere."""
+    from pyprogressivex import datasets
+    pts, gt, _ = datasets.make_circles(500, 4, 500, seed=0)
+    rng = np.random.default_rng(0)
+    one = np.nonzero(gt == 1)[0]
+    smp = np.vstack([np.stack([rng.choice(one, 3, replace=False) for _ in range(200)]),
+                     np.stack([rng.choice(len(pts), 3, replace=False) for _ in range(200)])]).astype(np.int32)
+    got = oracle.solve_minimal(oracle.CIRCLE2D, pts, smp)
+    assert got.shape == (400, 3)
+    skipped, worst_c, worst_r = 0, 0.0, 0.0
+    for s in range(len(smp)):
+        ex = _exact_circumcircle(pts[smp[s]])
+        if ex is None or ex[2] < Fr(1, 10 ** 6):
+            skipped += 1
+            continue
+        c, r2, _ = ex
+        r = _sqrt_fraction(r2)
+        assert np.isfinite(got[s]).all(), s
+        ec = max(abs(Fr(float(got[s, k])) - c[k]) for k in range(2)) / max(abs(v) for v in c)
+        er = abs(Fr(float(got[s, 2])) - r) / r
+        worst_c, worst_r = max(worst_c, float(ec)), max(worst_r, float(er))
+        assert ec <= Fr(1, 10 ** 9) and er <= Fr(1, 10 ** 9), (s, float(ec), float(er))
+    print(f"circle solver: {skipped} of {len(smp)} samples under the conditioning rule, worst relative error centre {worst_c:.3g} radius {worst_r:.3g}")
+    assert skipped <= 0.05 * len(smp)
+    # every point of every sample lies on its circle: the exact residual of the oracle's model is at rounding level
+    for s in range(len(smp)):
+        if np.isfinite(got[s]).all():
+            for i in smp[s]:
+                assert float(_exact_sq("circle", pts[i], got[s])) <= (1e-9 * max(1.0, abs(got[s]).max())) ** 2, s
+
+
+def test_circle_solver_hand_checked_degenerate_and_radius_range(oracle):
+    """the solver's NaN cases with dyadic coordinates (every difference and product exact, so det == 0 exactly), the inclusive
+    radius range, rmin == rmax, refused ranges"""
+    O = oracle
+    pts = np.array([[3.0, 2.0], [1.0, 4.0], [-1.0, 2.0], [1.0, 0.0],              # 0-3: the circle of radius 2 about (1, 2)
+                    [0.5, 0.25], [1.5, 0.75], [3.5, 1.75],                       # 4-6: collinear
+                    [np.nan, 0.0], [np.inf, 1.0],                                # 7, 8
+                    [5.0, 0.0], [-5.0, 0.0], [0.0, 5.0],                         # 9-11: radius 5 about the origin
+                    [1e200, 0.0], [0.0, 1e200], [-1e200, 0.0]])                  # 12-14: h overflows: a non-finite centre
+    m = O.solve_minimal(O.CIRCLE2D, pts, np.array([[0, 1, 2], [3, 2, 1], [2, 3, 0]], np.int32))
+    assert m.tolist() == [[1.0, 2.0, 2.0]] * 3
+    # collinear, coincident (twice and three times the same point), out-of-range indices, NaN and Inf coordinates, overflow -> NaN rows
+    bad = O.solve_minimal(O.CIRCLE2D, pts, np.array([[4, 5, 6], [6, 4, 5], [0, 0, 1], [1, 0, 0], [2, 2, 2], [0, 1, 15], [0, -1, 2],
+                                                     [0, 1, 7], [0, 1, 8], [12, 13, 14]], np.int32))
+    assert bad.shape == (10, 3) and np.isnan(bad).all()
+    smp = np.array([[9, 10, 11], [0, 1, 2]], np.int32)            # radii 5 and 2
+    free = O.solve_minimal(O.CIRCLE2D, pts, smp)
+    assert free.tolist() == [[0.0, 0.0, 5.0], [1.0, 2.0, 2.0]]
+    for rng_, keep in (((5.0, 5.0), [True, False]), ((2.0, 2.0), [False, True]), ((2.0, 5.0), [True, True]),
+                       ((2.0, np.nextafter(5.0, 0.0)), [False, True]), ((np.nextafter(2.0, 3.0), np.inf), [True, False]),
+                       ((0.0, 2.0), [False, True]), ((0.0, np.inf), [True, True]), ((3.0, 4.0), [False, False]),
+                       ((6.0, 6.0), [False, False])):
+        out = O.solve_minimal(O.CIRCLE2D, pts, smp, radius_range=rng_)
+        assert (~np.isnan(out[:, 0])).tolist() == keep, rng_
+        assert np.array_equal(out[keep], free[keep]) and np.isnan(out[~np.array(keep)]).all()
+    for bad_range in ((-1.0, 2.0), (2.0, 1.0), (np.nan, 1.0), (0.0, np.nan)):
+        with pytest.raises(ValueError):
+            O.solve_minimal(O.CIRCLE2D, pts, smp, radius_range=bad_range)
+
+
+def test_circle_solver_is_bitwise_the_host_estimator(oracle):
+    """two restatements of the operation order csrc/solve.hip documents (C here, numpy in _estimators.py) return the same bits and
+    the same set of samples without a model, with and without a radius range"""
+    from pyprogressivex import _estimators, datasets
+    rng = np.random.default_rng(6)
+    pts, _, _ = datasets.make_circles(300, 3, 300, seed=2)
+    smp = rng.integers(0, len(pts), (600, 3)).astype(np.int32)
+    smp[:10, 2] = smp[:10, 0]
+    for rr in ((0.0, np.inf), (60.0, 300.0)):
+        est = _estimators.CircleEstimator()
+        est.radius_range = rr
+        ref, src = est.minimal(pts, smp)
+        got = oracle.solve_minimal(oracle.CIRCLE2D, pts, smp, radius_range=rr)
+        # a repeated point: a_2 = 0 exactly, so det = a_10 0 - a_11 0 = 0 exactly (unlike the sphere's 3 x 3 determinant)
+        assert np.isnan(got[:10]).all()
+        assert np.array_equal(np.nonzero(~np.isnan(got[:, 0]))[0], src) and np.array_equal(got[src], ref)
+        assert 10 < len(src) < 590 or rr[1] == np.inf          # the range keeps some samples and removes others
+
+
+def test_gram_circle_rows_hand_checked(oracle):
+    O = oracle
+    pts = np.array([[3.0, 2.0], [1.0, 6.0]])
+    # o = (1, 2), s = 2: rows (1, 1, 0, 1) and (1, 0, 2, 4)
+    blocks, bad = O.gram_rows(O.GRAM_CIRCLE, pts, [1.0, 2.0, 2.0])
+    assert len(blocks) == 1 and not bad.any() and blocks[0].tolist() == [[1.0, 1.0, 0.0, 1.0], [1.0, 0.0, 2.0, 4.0]]
+    G, cnt, nbad = O.gram(O.GRAM_CIRCLE, pts, [0, 1], params=[1.0, 2.0, 2.0])
+    assert cnt == 2 and nbad == 0 and G.tolist() == [[2, 1, 2, 5], [1, 1, 0, 1], [2, 0, 4, 8], [5, 1, 8, 17]]
+    G, cnt, nbad = O.gram(O.GRAM_CIRCLE, pts, [0, 1], params=[1.0, 2.0, 2.0], weights=np.array([2.0, 3.0]), wpow=1)
+    assert G[0].tolist() == [5.0, 2.0, 6.0, 14.0]
+    G, cnt, nbad = O.gram(O.GRAM_AFFINE, pts, [0, 1])
+    assert G.shape == (3, 3) and G[0].tolist() == [2.0, 4.0, 8.0]
+
+
+@pytest.mark.parametrize("offset", [0.0, 1e3, 1e6])
+def test_circle_refit_on_the_oracle_rows_recovers_a_noise_free_circle(oracle, offset):
+    """CircleEstimator driven by the ORACLE's Gram rows (GRAM_AFFINE, then GRAM_CIRCLE on centred and scaled coordinates) recovers
+    a known circle from noise-free points on three quarters of it, also 1e3 and 1e6 from the origin.  Bound as the sphere's
+    (test_refits_on_the_oracle_rows_recover_noise_free_structures): the inputs are rounded to ulp(|o|) and the eigenproblem's
+    condition number on such an arc is of the order 10^2, so the floor is 10^3 ulp(max(r, |o|)); the rows are centred before they
+    are squared, so that floor is the whole bound."""
+    from oracle_ctx import OracleContext
+    from pyprogressivex import _estimators
+    rng = np.random.default_rng(2)
+    ctx = OracleContext()
+    c = np.array([offset + 300.0, -offset + 200.0])
+    phi = rng.uniform(0.0, 1.5 * np.pi, 400)
+    pts = c + 75.0 * np.column_stack([np.cos(phi), np.sin(phi)])
+    floor = 1e3 * np.spacing(max(75.0, offset + 300.0))
+    ctx.set_points(oracle.CIRCLE2D, pts)
+    for w in (None, rng.random(400) + 0.5):
+        fit = _estimators.CircleEstimator().nonminimal(ctx, ("index", np.arange(400)), w)
+        assert len(fit) == 1
+        err_c, err_r = np.abs(fit[0][:2] - c).max(), abs(fit[0][2] - 75.0)
+        print(f"circle refit at offset {offset:g}: centre error {err_c:.3g}, radius error {err_r:.3g} (bound {floor:.3g})")
+        assert err_c <= floor and err_r <= floor
+    ctx.set_labels((np.arange(400) % 2).astype(np.int32))
+    a = _estimators.CircleEstimator().nonminimal(ctx, ("label", 0), None)
+    b = _estimators.CircleEstimator().nonminimal(ctx, ("index", np.arange(0, 400, 2)), None)
+    assert np.array_equal(a[0], b[0])
+
+
+def test_golden_circle_rows(oracle):
+    """the committed known answers of the circle rows (tests/golden/make_golden_circles.py): residuals, score table with masks,
+    preference, unary table, residual sums, solver outputs without and with a radius range bit for bit, Gram matrices to 1e-12"""
+    g = np.load(GOLDEN_CIRCLES)
+    mt = MODEL_CASES_2D["circle"]
+    pts, models, thr, comp = g["circle_pts"], g["circle_models"], float(g["circle_thr"][0]), g["circle_comp"]
+    T2 = 2.25 * thr * thr
+    assert pts.shape == (200, 2) and models.shape == (6, 3) and thr == 2.0
+    assert np.array_equal(oracle.squared_residuals(mt, pts, models[0]), g["circle_sq0"])
+    assert np.array_equal(np.array([oracle.residual(mt, p, models[0]) for p in pts]), g["circle_plain0"])
+    sc = oracle.score(mt, pts, models, T2, compound=comp, has_compound=True, exponent=2, want_masks=True)
+    for k in ("counts", "values", "shared", "scores", "masks"):
+        assert np.array_equal(sc[k], g[f"circle_{k}"]), k
+    assert sc["counts"].max() > 30
+    assert np.array_equal(oracle.preference(mt, pts, models[0], T2), g["circle_pref0"])
+    assert np.array_equal(oracle.unary_q(mt, pts, models[:3], thr, 0.1), g["circle_unary_q"])
+    labels = g["circle_labels"]
+    assert np.array_equal(np.array([oracle.residual_sum(mt, pts, models[k], labels, k) for k in range(3)]), g["circle_residual_sums"])
+    assert np.array_equal(oracle.solve_minimal(mt, pts, g["circle_samples"]), g["circle_solved"], equal_nan=True)
+    rr = g["circle_radius_range"]
+    out = oracle.solve_minimal(mt, pts, g["circle_samples"], radius_range=(float(rr[0]), float(rr[1])))
+    assert np.array_equal(out, g["circle_solved_ranged"], equal_nan=True)
+    assert np.isnan(out[:, 0]).sum() > np.isnan(g["circle_solved"][:, 0]).sum() and (out[:, 2] == rr[1]).any()
+    for kind in (oracle.GRAM_AFFINE, oracle.GRAM_CIRCLE):
+        prm = g["circle_gram_params"] if kind == oracle.GRAM_CIRCLE else None
+        G, cnt, bad = oracle.gram(kind, pts, g["circle_idx"], params=prm, weights=g["circle_w"], wpow=1)
+        ref = g[f"circle_G{kind}"]
+        assert cnt == 120 and bad == 0 and np.abs(G - ref).max() <= 1e-12 * np.abs(ref).max()
