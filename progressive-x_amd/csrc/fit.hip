@@ -12,7 +12,14 @@
 //
 //   out = sum over selected points i of  W_i * sum over the rows a of point i of  a a^T      (upper triangle, row-major)
 //   W_i = w_i^wpow (weights optional).  Selection: an uploaded index list, or label == k on the resident labelling.
-// Fixed reduction tree (lanes -> waves -> per-block partials -> one final block): bit-reproducible run to run.
+// Fixed reduction tree (lanes -> waves -> per-block partials -> one final block per item): bit-reproducible run to run.
+//
+// Each pass is written once.  accumulate() is the per-point body of every kernel; wave_sum / wave_tree / block_tree are the only
+// trees.  gram_kernel + gram_final_kernel serve pgx_gram (one item: an index list or one label) and pgx_gram_labels (blockIdx.y =
+// label), so "entry k of the all-labels call is bitwise the single-label call" - the contract nonminimal_labels rests on once per
+// PEARL iteration - holds because there is no second kernel.  wave_gram() is the one-wave pass of gram_batch_kernel and of every
+// Gauss-Newton step of pnp_refine_batch_kernel.  On the host, check_call / check_index / gram_row_length are the argument checks
+// under the caller's name, carve() lays out fit_scratch, batch_upload() is the prologue of the two one-wave-per-selection calls.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -146,132 +153,120 @@ __device__ __forceinline__ void emit<GenPnpGn>(const double* pt, const FitParams
     acc.add(jv, w);
 }
 
+// ---- the reduction passes, each written once ---------------------------------------------------------------------------------
+// The operation order below IS the contract: the bits of every Gram call are pinned (tests/test_gpu_reductions.py).
+
+// block k of a [items][12] device table of parameter blocks
+__device__ __forceinline__ FitParams load_params(const double* __restrict__ table, int64_t k)
+{
+    FitParams p;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) p.v[j] = table[k * 12 + j];
+    return p;
+}
+
+// the rows of resident point i under prm into acc, weighted by (*w)^wpow (w null: 1); returns 1 for a point without rows (bad)
+template <class G>
+__device__ __forceinline__ int accumulate(const double* __restrict__ pts, int64_t i, const double* __restrict__ w, int wpow,
+                                          const FitParams& prm, Acc<G::Q>& acc)
+{
+    double pt[G::D];
+#pragma unroll
+    for (int k = 0; k < G::D; ++k) pt[k] = pts[i * G::D + k];
+    double wi = 1.0;
+    if (w != nullptr) { wi = *w; if (wpow == 2) wi = wi * wi; }
+    int bad = 0;
+    emit<G>(pt, prm, acc, wi, bad);
+    return bad;
+}
+
+// the 64 lanes of a wave by shuffle, off = 32, 16, .., 1; the sum is valid in lane 0
+template <class T>
+__device__ __forceinline__ T wave_sum(T x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    return x;
+}
+
+// the wave tree over the NV accumulators: sink(k, sum k), the sum valid in lane 0.  (Each sum goes to its consumer before the next
+// tree starts: all NV trees first keep NV more values live - 182 VGPRs instead of 140 on the 9-entry rows.)
+template <int NV, class F>
+__device__ __forceinline__ void wave_tree(const double (&s)[NV], F&& sink)
+{
+#pragma unroll
+    for (int k = 0; k < NV; ++k) sink(k, wave_sum(s[k]));
+}
+
+// a block of kFitBlock threads: the wave tree, lane 0 of each wave to lds [kFitBlock / 64][NV], then the waves 0..3 in order into out[NV]
+template <int NV>
+__device__ __forceinline__ void block_tree(const double (&s)[NV], double* __restrict__ lds, double* __restrict__ out)
+{
+    double* const mine = lds + (threadIdx.x >> 6) * NV;
+    wave_tree(s, [&](int k, double x) { if ((threadIdx.x & 63) == 0) mine[k] = x; });
+    __syncthreads();
+    for (int k = threadIdx.x; k < NV; k += kFitBlock) {
+        double x = lds[k];
+        for (int w2 = 1; w2 < kFitBlock / 64; ++w2) x += lds[w2 * NV + k];
+        out[k] = x;
+    }
+}
+
+// One wave, one selection of m resident points (the inner RANSAC of the local optimisation, DESIGN.md 5.8: m <= 64 in practice,
+// 7 x the minimal sample size): lanes take the points t = lane, lane + 64, ..; sink(k, sum k) and the returned number of bad
+// points are valid in lane 0.
+template <class G, class F>
+__device__ __forceinline__ int wave_gram(const double* __restrict__ pts, const int* __restrict__ index, const double* __restrict__ wsel,
+                                         int m, int wpow, const FitParams& prm, F&& sink)
+{
+    Acc<G::Q> acc;
+    acc.zero();
+    int nbad = 0;
+    for (int t = threadIdx.x; t < m; t += 64) nbad += accumulate<G>(pts, index[t], wsel != nullptr ? wsel + t : nullptr, wpow, prm, acc);
+    wave_tree(acc.s, sink);
+    return wave_sum(nbad);
+}
+
+// The selection pass.  blockIdx.y = item: with an index list the listed points (one item), otherwise the points whose resident label
+// is label0 + item (PEARL::parameterEstimation refits every instance per iteration: all labels in one launch).  The parameters
+// of item k are block k of prm_k, or prm for every item when prm_k is null.  Partials [item][block][NV], counters [2 * item]: the
+// single-selection calls are gridDim.y = 1, so entry k of an all-labels call is bitwise the single-label call by construction.
 template <class G>
 __global__ __launch_bounds__(kFitBlock) void gram_kernel(const double* __restrict__ pts, int64_t n, FitParams prm,
-                                                         const int* __restrict__ index, int64_t m,
-                                                         const int* __restrict__ labels, int label,
+                                                         const double* __restrict__ prm_k, const int* __restrict__ index, int64_t m,
+                                                         const int* __restrict__ labels, int label0,
                                                          const double* __restrict__ weights, int wpow,
-                                                         double* __restrict__ partials, int* __restrict__ counters)
+                                                         int blocks, double* __restrict__ partials, int* __restrict__ counters)
 {
     constexpr int Q = G::Q, NV = Q * (Q + 1) / 2;
     __shared__ double lds[(kFitBlock / 64) * NV];
     __shared__ int s_cnt, s_bad;
     if (threadIdx.x == 0) { s_cnt = 0; s_bad = 0; }
     __syncthreads();
+    const int item = (int)blockIdx.y;
+    if (prm_k != nullptr) prm = load_params(prm_k, item);
     Acc<Q> acc;
     acc.zero();
     const int64_t t = (int64_t)blockIdx.x * kFitBlock + threadIdx.x;
     int64_t i = -1;
     if (index != nullptr) { if (t < m) i = index[t]; }
-    else if (t < n && labels[t] == label) i = t;
-    int bad = 0;
+    else if (t < n && labels[t] == label0 + item) i = t;
     if (i >= 0) {
-        double pt[G::D];
-#pragma unroll
-        for (int k = 0; k < G::D; ++k) pt[k] = pts[i * G::D + k];
-        double w = 1.0;
-        if (weights != nullptr) { w = weights[i]; if (wpow == 2) w = w * w; }
-        emit<G>(pt, prm, acc, w, bad);
+        const int bad = accumulate<G>(pts, i, weights != nullptr ? weights + i : nullptr, wpow, prm, acc);
         atomicAdd(&s_cnt, 1);
         if (bad) atomicAdd(&s_bad, 1);
     }
-    // fixed tree: lanes (shuffle), then waves in order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double x = acc.s[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-        if (lane == 0) lds[wave * NV + k] = x;
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < NV; k += kFitBlock) {
-        double s = lds[k];
-        for (int w2 = 1; w2 < kFitBlock / 64; ++w2) s += lds[w2 * NV + k];
-        partials[(int64_t)blockIdx.x * NV + k] = s;
-    }
+    block_tree<NV>(acc.s, lds, partials + ((int64_t)item * blocks + blockIdx.x) * NV);
     if (threadIdx.x == 0) {
-        if (s_cnt) atomicAdd(&counters[0], s_cnt);
-        if (s_bad) atomicAdd(&counters[1], s_bad);
+        if (s_cnt) atomicAdd(&counters[2 * item], s_cnt);
+        if (s_bad) atomicAdd(&counters[2 * item + 1], s_bad);
     }
 }
 
-// one block: value k is summed by 16 lanes (lane j takes the blocks b = j mod 16 in order), then a fixed xor tree
+// The final pass, one block per item: value k is summed by 16 lanes (lane j takes the blocks b = j mod 16 in order), then a fixed
+// xor tree
 __global__ __launch_bounds__(1024) void gram_final_kernel(const double* __restrict__ partials, int blocks, int nv,
                                                           double* __restrict__ out)
-{
-    const int k = (int)threadIdx.x >> 4, j = (int)threadIdx.x & 15;
-    double s = 0.0;
-    if (k < nv)
-        for (int b = j; b < blocks; b += 16) s += partials[(int64_t)b * nv + k];
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if (k < nv && j == 0) out[k] = s;
-}
-
-template <class G>
-void launch(pgx_ctx* ctx, const FitParams& prm, const int* index, int64_t m, int label, const double* weights, int wpow,
-            int blocks, double* partials, int* counters)
-{
-    hipLaunchKernelGGL((gram_kernel<G>), dim3((unsigned)blocks), dim3(kFitBlock), 0, ctx->stream, ctx->pts.as<double>(), ctx->n,
-                       prm, index, m, ctx->labels.as<int>(), label, weights, wpow, partials, counters);
-}
-
-// All labels in one launch (PEARL::parameterEstimation refits every instance per iteration): blockIdx.y = label, one
-// parameter block per label.  Per-block tree and final pass are those of gram_kernel / gram_final_kernel, so out[k] is
-// bit-identical to the single-label call with label k.
-template <class G>
-__global__ __launch_bounds__(kFitBlock) void gram_labels_kernel(const double* __restrict__ pts, int64_t n, const double* __restrict__ prm_k,
-                                                                const int* __restrict__ labels, const double* __restrict__ weights,
-                                                                int wpow, int blocks, double* __restrict__ partials,
-                                                                int* __restrict__ counters)
-{
-    constexpr int Q = G::Q, NV = Q * (Q + 1) / 2;
-    __shared__ double lds[(kFitBlock / 64) * NV];
-    __shared__ int s_cnt, s_bad;
-    if (threadIdx.x == 0) { s_cnt = 0; s_bad = 0; }
-    __syncthreads();
-    const int label = (int)blockIdx.y;
-    FitParams prm;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) prm.v[k] = prm_k[(int64_t)label * 12 + k];
-    Acc<Q> acc;
-    acc.zero();
-    const int64_t t = (int64_t)blockIdx.x * kFitBlock + threadIdx.x;
-    const int64_t i = (t < n && labels[t] == label) ? t : -1;
-    int bad = 0;
-    if (i >= 0) {
-        double pt[G::D];
-#pragma unroll
-        for (int k = 0; k < G::D; ++k) pt[k] = pts[i * G::D + k];
-        double w = 1.0;
-        if (weights != nullptr) { w = weights[i]; if (wpow == 2) w = w * w; }
-        emit<G>(pt, prm, acc, w, bad);
-        atomicAdd(&s_cnt, 1);
-        if (bad) atomicAdd(&s_bad, 1);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double x = acc.s[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-        if (lane == 0) lds[wave * NV + k] = x;
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < NV; k += kFitBlock) {
-        double s = lds[k];
-        for (int w2 = 1; w2 < kFitBlock / 64; ++w2) s += lds[w2 * NV + k];
-        partials[((int64_t)label * blocks + blockIdx.x) * NV + k] = s;
-    }
-    if (threadIdx.x == 0) {
-        if (s_cnt) atomicAdd(&counters[2 * label], s_cnt);
-        if (s_bad) atomicAdd(&counters[2 * label + 1], s_bad);
-    }
-}
-
-__global__ __launch_bounds__(1024) void gram_final_labels_kernel(const double* __restrict__ partials, int blocks, int nv,
-                                                                 double* __restrict__ out)
 {
     const double* part = partials + (int64_t)blockIdx.x * blocks * nv;
     const int k = (int)threadIdx.x >> 4, j = (int)threadIdx.x & 15;
@@ -283,66 +278,26 @@ __global__ __launch_bounds__(1024) void gram_final_labels_kernel(const double* _
     if (k < nv && j == 0) out[(int64_t)blockIdx.x * nv + k] = s;
 }
 
-template <class G>
-void launch_labels(pgx_ctx* ctx, int K, const double* prm, const double* weights, int wpow, int blocks, double* partials, int* counters)
-{
-    hipLaunchKernelGGL((gram_labels_kernel<G>), dim3((unsigned)blocks, (unsigned)K), dim3(kFitBlock), 0, ctx->stream,
-                       ctx->pts.as<double>(), ctx->n, prm, ctx->labels.as<int>(), weights, wpow, blocks, partials, counters);
-}
-
-// Batched variant for the inner RANSAC of the local optimisation: B small index selections of m points
-// each, one wave per selection (m <= 64 in practice: 7 x the minimal sample size), per-selection parameter blocks.
-// Lanes take the points t = lane, lane + 64, ..; fixed shuffle tree: bit-reproducible.
+// B selections of m points each, one wave per selection, per-selection parameter blocks; fixed shuffle tree: bit-reproducible
 template <class G>
 __global__ __launch_bounds__(64) void gram_batch_kernel(const double* __restrict__ pts, const double* __restrict__ prm,
                                                         const int* __restrict__ index, int m,
                                                         const double* __restrict__ wsel, int wpow,
                                                         double* __restrict__ out, int* __restrict__ bad)
 {
-    constexpr int Q = G::Q, NV = Q * (Q + 1) / 2;
-    const int b = blockIdx.x;
-    FitParams p;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) p.v[k] = prm[(int64_t)b * 12 + k];
-    Acc<Q> acc;
-    acc.zero();
-    int nbad = 0;
-    for (int t = threadIdx.x; t < m; t += 64) {
-        const int64_t i = index[(int64_t)b * m + t];
-        double pt[G::D];
-#pragma unroll
-        for (int k = 0; k < G::D; ++k) pt[k] = pts[i * G::D + k];
-        double w = 1.0;
-        if (wsel != nullptr) { w = wsel[(int64_t)b * m + t]; if (wpow == 2) w = w * w; }
-        int bd = 0;
-        emit<G>(pt, p, acc, w, bd);
-        nbad += bd;
-    }
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double x = acc.s[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-        if (threadIdx.x == 0) out[(int64_t)b * NV + k] = x;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nbad += __shfl_down(nbad, off, 64);
+    constexpr int NV = G::Q * (G::Q + 1) / 2;
+    const int64_t b = blockIdx.x;
+    double* const mine = out + b * NV;
+    const int nbad = wave_gram<G>(pts, index + b * m, wsel != nullptr ? wsel + b * m : nullptr, m, wpow, load_params(prm, b),
+                                  [&](int k, double x) { if (threadIdx.x == 0) mine[k] = x; });
     if (threadIdx.x == 0) bad[b] = nbad;
-}
-
-template <class G>
-void launch_batch(pgx_ctx* ctx, int B, const double* prm, const int* index, int m, const double* wsel, int wpow, double* out,
-                  int* bad)
-{
-    hipLaunchKernelGGL((gram_batch_kernel<G>), dim3((unsigned)B), dim3(64), 0, ctx->stream, ctx->pts.as<double>(), prm, index, m,
-                       wsel, wpow, out, bad);
 }
 
 // ---- Gauss-Newton pose refits of a whole batch in ONE launch --------------------------------------------------------------
 // The local optimisation refits ~50 selections of 21 points per graph-cut round; each Gauss-Newton step used to be one
 // gram_batch launch, a copy back, a stacked 6x6 pseudo-inverse on the host and a copy up (10 steps per round: a third of
-// find6DPoses' proposal time at C4).  Here one wave owns one selection for all its steps: the normal equations by the same
-// rows and the same shuffle tree as gram_batch_kernel (bitwise the same sums), broadcast to every lane, and each lane
+// find6DPoses' proposal time at C4).  Here one wave owns one selection for all its steps: the normal equations by wave_gram(),
+// the pass of gram_batch_kernel (bitwise the same sums by construction), broadcast to every lane, and each lane
 // redundantly runs the small dense part - pseudo-inverse of the symmetric 6x6 through a cyclic Jacobi eigen-decomposition with
 // numpy.linalg.pinv's cut-off (|lambda| <= rcond max|lambda| dropped), Rodrigues update of R, t += dt - exactly the iteration
 // of pyprogressivex/_estimators.py PnPEstimator._fit_many, whose iterates it reproduces up to rounding (tests: 1e-9).
@@ -416,40 +371,15 @@ __global__ __launch_bounds__(64) void pnp_refine_batch_kernel(const double* __re
                                                               const int* __restrict__ index, int m, const double* __restrict__ wsel, int wpow,
                                                               int iterations, double* __restrict__ out, int* __restrict__ status)
 {
-    using G = GenPnpGn;
-    constexpr int Q = 7, NV = 28;
-    const int b = blockIdx.x;
-    FitParams p;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) p.v[k] = inits[(int64_t)b * 12 + k];
+    constexpr int NV = 28;
+    const int64_t b = blockIdx.x;
+    FitParams p = load_params(inits, b);
     bool failed = m < 4;
     for (int it = 0; it < iterations && !failed; ++it) {
-        Acc<Q> acc;
-        acc.zero();
-        int nbad = 0;
-        for (int t = threadIdx.x; t < m; t += 64) {
-            const int64_t i = index[(int64_t)b * m + t];
-            double pt[G::D];
-#pragma unroll
-            for (int k = 0; k < G::D; ++k) pt[k] = pts[i * G::D + k];
-            double w = 1.0;
-            if (wsel != nullptr) { w = wsel[(int64_t)b * m + t]; if (wpow == 2) w = w * w; }
-            int bd = 0;
-            emit<G>(pt, p, acc, w, bd);
-            nbad += bd;
-        }
         double g[NV];
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            double x = acc.s[k];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-            g[k] = __shfl(x, 0, 64);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nbad += __shfl_down(nbad, off, 64);
-        nbad = __shfl(nbad, 0, 64);
-        if (nbad > 0) { failed = true; break; }
+        const int nbad = wave_gram<GenPnpGn>(pts, index + b * m, wsel != nullptr ? wsel + b * m : nullptr, m, wpow, p,
+                                             [&](int k, double x) { g[k] = __shfl(x, 0, 64); });
+        if (__shfl(nbad, 0, 64) > 0) { failed = true; break; }
         // upper triangle, row-major: (r, c) at r * 7 - r (r - 1) / 2 + (c - r)
         double A[6][6], rhs[6];
         bool fin = true;
@@ -513,37 +443,34 @@ __global__ __launch_bounds__(64) void pnp_refine_batch_kernel(const double* __re
 
 }  // namespace
 
-int pnp_refine_batch_launch(pgx_ctx* ctx, const double* inits, const int32_t* index, int B, int m, const double* wsel, int wpow,
-                            int iterations, double* out, int32_t* status)
+// ---- host side: checks, scratch and uploads, each stated once ------------------------------------------------------------------
+
+// what every Gram entry point asks first, under its own name: resident points, the weight power, a parameter block of at most 12
+static int check_call(pgx_ctx* ctx, const char* who, int wpow, const double* params, int nparams)
 {
-    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_pnp_refine_batch: points not set");
-    if (ctx->D != 5) return fail(ctx, PGX_ERR_INVALID, "pgx_pnp_refine_batch: needs 5-D 2D-3D rows");
-    if (wpow != 1 && wpow != 2) return fail(ctx, PGX_ERR_INVALID, "pgx_pnp_refine_batch: weight power must be 1 or 2");
-    if (!inits || !out || !status || B < 0 || m < 0 || iterations < 0 || ((int64_t)B * m > 0 && !index))
-        return fail(ctx, PGX_ERR_INVALID, "pgx_pnp_refine_batch: bad argument");
-    if (B == 0) return PGX_OK;
-    const int64_t tot = (int64_t)B * m;
-    for (int64_t t = 0; t < tot; ++t)
-        if (index[t] < 0 || index[t] >= ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_pnp_refine_batch: index %d out of range", index[t]);
-    // scratch: inits[B][12] | out[B][12] | wsel[B][m] | index[B][m] | status[B]
-    const size_t prm_bytes = (size_t)B * 12 * 8, w_bytes = wsel ? (size_t)tot * 8 : 0;
-    const size_t idx_bytes = ((size_t)tot * 4 + 7) & ~(size_t)7, st_bytes = (size_t)B * 4;
-    PGX_TRY(ensure(ctx, ctx->fit_scratch, 2 * prm_bytes + w_bytes + idx_bytes + st_bytes + 64));
-    char* base = (char*)ctx->fit_scratch.p;
-    double* d_in = (double*)base;
-    double* d_out = (double*)(base + prm_bytes);
-    double* d_w = (double*)(base + 2 * prm_bytes);
-    int* d_idx = (int*)(base + 2 * prm_bytes + w_bytes);
-    int* d_st = (int*)(base + 2 * prm_bytes + w_bytes + idx_bytes);
-    PGX_HIP(ctx, hipMemcpyAsync(d_in, inits, prm_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (tot > 0) PGX_HIP(ctx, hipMemcpyAsync(d_idx, index, (size_t)tot * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (w_bytes) PGX_HIP(ctx, hipMemcpyAsync(d_w, wsel, w_bytes, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(pnp_refine_batch_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, ctx->pts.as<double>(), d_in, d_idx, m,
-                       wsel ? d_w : nullptr, wpow, iterations, d_out, d_st);
-    PGX_HIP(ctx, hipGetLastError());
-    PGX_TRY(d2h(ctx, out, d_out, prm_bytes));
-    PGX_TRY(d2h(ctx, status, d_st, st_bytes));
-    PGX_TRY(sync_deliver(ctx));
+    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "%s: points not set", who);
+    if (wpow != 1 && wpow != 2) return fail(ctx, PGX_ERR_INVALID, "%s: weight power must be 1 or 2", who);
+    if (nparams < 0 || nparams > 12 || (nparams > 0 && !params)) return fail(ctx, PGX_ERR_INVALID, "%s: bad parameter block", who);
+    return PGX_OK;
+}
+
+// every index of a list names a resident point (checked before anything is enqueued: the kernels gather without a bound)
+static int check_index(pgx_ctx* ctx, const char* who, const int32_t* index, int64_t count)
+{
+    for (int64_t t = 0; t < count; ++t)
+        if (index[t] < 0 || index[t] >= ctx->n) return fail(ctx, PGX_ERR_INVALID, "%s: index %d out of range", who, index[t]);
+    return PGX_OK;
+}
+
+// Regions of the given byte sizes one behind the other in ctx->fit_scratch, each from an 8-byte boundary: region[k] = start of
+// region k.  Regions whose sizes are multiples of 8 are adjacent: the fused uploads and read-backs below rely on that.
+template <size_t N>
+static int carve(pgx_ctx* ctx, const size_t (&bytes)[N], char* (&region)[N])
+{
+    size_t off[N], total = 0;
+    for (size_t k = 0; k < N; ++k) { off[k] = total; total += (bytes[k] + 7) & ~(size_t)7; }
+    PGX_TRY(ensure(ctx, ctx->fit_scratch, total + 64));
+    for (size_t k = 0; k < N; ++k) region[k] = (char*)ctx->fit_scratch.p + off[k];
     return PGX_OK;
 }
 
@@ -582,45 +509,6 @@ static void with_gram_generator(int kind, int D, F&& f)
     }
 }
 
-int gram_batch_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, const int32_t* index, int B, int m,
-                      const double* wsel, int wpow, double* out, int32_t* bad)
-{
-    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_batch: points not set");
-    if (wpow != 1 && wpow != 2) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_batch: weight power must be 1 or 2");
-    if (nparams < 0 || nparams > 12 || (nparams > 0 && !params)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_batch: bad parameter block");
-    if (!out || B < 0 || m < 0 || ((int64_t)B * m > 0 && !index)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_batch: bad argument");
-    int q = 0;
-    PGX_TRY(gram_row_length(ctx, "pgx_gram_batch", kind, nparams, &q));
-    const int nv = q * (q + 1) / 2;
-    if (B == 0) return PGX_OK;
-    const int64_t tot = (int64_t)B * m;
-    for (int64_t t = 0; t < tot; ++t)
-        if (index[t] < 0 || index[t] >= ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_batch: index %d out of range", index[t]);
-    // scratch: prm[B][12] | out[B][nv] | wsel[B][m] | index[B][m] | bad[B]
-    const size_t prm_bytes = (size_t)B * 12 * 8, out_bytes = (size_t)B * nv * 8, w_bytes = wsel ? (size_t)tot * 8 : 0;
-    const size_t idx_bytes = ((size_t)tot * 4 + 7) & ~(size_t)7, bad_bytes = (size_t)B * 4;
-    PGX_TRY(ensure(ctx, ctx->fit_scratch, prm_bytes + out_bytes + w_bytes + idx_bytes + bad_bytes + 64));
-    char* base = (char*)ctx->fit_scratch.p;
-    double* d_prm = (double*)base;
-    double* d_out = (double*)(base + prm_bytes);
-    double* d_w = (double*)(base + prm_bytes + out_bytes);
-    int* d_idx = (int*)(base + prm_bytes + out_bytes + w_bytes);
-    int* d_bad = (int*)(base + prm_bytes + out_bytes + w_bytes + idx_bytes);
-    std::vector<double> hp((size_t)B * 12, 0.0);
-    for (int b = 0; b < B; ++b)
-        for (int k = 0; k < nparams; ++k) hp[(size_t)b * 12 + k] = params[(size_t)b * nparams + k];
-    PGX_HIP(ctx, hipMemcpyAsync(d_prm, hp.data(), prm_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (tot > 0) PGX_HIP(ctx, hipMemcpyAsync(d_idx, index, (size_t)tot * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (w_bytes) PGX_HIP(ctx, hipMemcpyAsync(d_w, wsel, w_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const double* ww = wsel ? d_w : nullptr;
-    with_gram_generator(kind, ctx->D, [&](auto gen) { launch_batch<decltype(gen)>(ctx, B, d_prm, d_idx, m, ww, wpow, d_out, d_bad); });
-    PGX_HIP(ctx, hipGetLastError());
-    PGX_TRY(d2h(ctx, out, d_out, out_bytes));
-    if (bad) PGX_TRY(d2h(ctx, bad, d_bad, bad_bytes));
-    PGX_TRY(sync_deliver(ctx));
-    return PGX_OK;
-}
-
 // Per-point weights are RESIDENT (pgx_set_weights checks their length against n and uploads them once): the Gram calls only
 // say whether to use them.  (They used to take a host pointer without a length and copied n doubles from it on every call.)
 static int resident_weights(pgx_ctx* ctx, const char* who, int use_weights, const double** ww)
@@ -633,13 +521,108 @@ static int resident_weights(pgx_ctx* ctx, const char* who, int use_weights, cons
     return PGX_OK;
 }
 
+// the selection pass over blocks x K workgroups and the final pass of its K items: partials -> out [K][nv]
+static int launch_gram(pgx_ctx* ctx, int kind, int K, int blocks, const FitParams& prm, const double* prm_k, const int* index, int64_t m,
+                       int label0, const double* ww, int wpow, double* partials, int* counters, int nv, double* out)
+{
+    with_gram_generator(kind, ctx->D, [&](auto gen) {
+        hipLaunchKernelGGL((gram_kernel<decltype(gen)>), dim3((unsigned)blocks, (unsigned)K), dim3(kFitBlock), 0, ctx->stream,
+                           ctx->pts.as<double>(), ctx->n, prm, prm_k, index, m, ctx->labels.as<int>(), label0, ww, wpow, blocks, partials, counters);
+    });
+    PGX_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(gram_final_kernel, dim3((unsigned)K), dim3(1024), 0, ctx->stream, partials, blocks, nv, out);
+    PGX_HIP(ctx, hipGetLastError());
+    return PGX_OK;
+}
+
+// result [K][nv] | counters [2K], the counters cnt_off bytes behind the result: ONE copy back, into pinned memory
+static int fetch_gram(pgx_ctx* ctx, const void* d_out, size_t cnt_off, int K, int nv, double* out, int64_t* count, int64_t* bad)
+{
+    const size_t bytes = cnt_off + (size_t)2 * K * sizeof(int);
+    void* hs = nullptr;
+    PGX_TRY(host_staging(ctx, bytes, &hs));
+    PGX_TRY(d2h(ctx, hs, d_out, bytes));
+    PGX_TRY(sync_deliver(ctx));
+    memcpy(out, hs, (size_t)K * nv * sizeof(double));
+    const int* cnt = (const int*)((const char*)hs + cnt_off);
+    for (int k = 0; k < K; ++k) {
+        if (count) count[k] = cnt[2 * k];
+        if (bad) bad[k] = cnt[2 * k + 1];
+    }
+    return PGX_OK;
+}
+
+// The one-wave-per-selection calls: scratch prm[B][12] | out[B][out_doubles] | wsel[B][m] | index[B][m] | flags[B], and the uploads
+// of the parameter blocks (host, [B][12]), the index lists and the selections' weights (wsel null: none, d->w null)
+struct BatchBuffers {
+    double *prm, *out, *w;
+    int *index, *flags;
+};
+
+static int batch_upload(pgx_ctx* ctx, const double* prm, int B, int m, const int32_t* index, const double* wsel, size_t out_doubles,
+                        BatchBuffers* d)
+{
+    const size_t tot = (size_t)B * m, prm_bytes = (size_t)B * 12 * 8, w_bytes = wsel ? tot * 8 : 0;
+    char* r[5];
+    PGX_TRY(carve(ctx, {prm_bytes, (size_t)B * out_doubles * 8, w_bytes, tot * 4, (size_t)B * 4}, r));
+    *d = {(double*)r[0], (double*)r[1], wsel ? (double*)r[2] : nullptr, (int*)r[3], (int*)r[4]};
+    PGX_HIP(ctx, hipMemcpyAsync(d->prm, prm, prm_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (tot > 0) PGX_HIP(ctx, hipMemcpyAsync(d->index, index, tot * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (w_bytes) PGX_HIP(ctx, hipMemcpyAsync(d->w, wsel, w_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return PGX_OK;
+}
+
+int pnp_refine_batch_launch(pgx_ctx* ctx, const double* inits, const int32_t* index, int B, int m, const double* wsel, int wpow,
+                            int iterations, double* out, int32_t* status)
+{
+    PGX_TRY(check_call(ctx, "pgx_pnp_refine_batch", wpow, nullptr, 0));
+    if (ctx->D != 5) return fail(ctx, PGX_ERR_INVALID, "pgx_pnp_refine_batch: needs 5-D 2D-3D rows");
+    if (!inits || !out || !status || B < 0 || m < 0 || iterations < 0 || ((int64_t)B * m > 0 && !index))
+        return fail(ctx, PGX_ERR_INVALID, "pgx_pnp_refine_batch: bad argument");
+    if (B == 0) return PGX_OK;
+    PGX_TRY(check_index(ctx, "pgx_pnp_refine_batch", index, (int64_t)B * m));
+    BatchBuffers d;
+    PGX_TRY(batch_upload(ctx, inits, B, m, index, wsel, 12, &d));
+    hipLaunchKernelGGL(pnp_refine_batch_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, ctx->pts.as<double>(), d.prm, d.index, m,
+                       d.w, wpow, iterations, d.out, d.flags);
+    PGX_HIP(ctx, hipGetLastError());
+    PGX_TRY(d2h(ctx, out, d.out, (size_t)B * 12 * 8));
+    PGX_TRY(d2h(ctx, status, d.flags, (size_t)B * 4));
+    PGX_TRY(sync_deliver(ctx));
+    return PGX_OK;
+}
+
+int gram_batch_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, const int32_t* index, int B, int m,
+                      const double* wsel, int wpow, double* out, int32_t* bad)
+{
+    PGX_TRY(check_call(ctx, "pgx_gram_batch", wpow, params, nparams));
+    if (!out || B < 0 || m < 0 || ((int64_t)B * m > 0 && !index)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_batch: bad argument");
+    int q = 0;
+    PGX_TRY(gram_row_length(ctx, "pgx_gram_batch", kind, nparams, &q));
+    const int nv = q * (q + 1) / 2;
+    if (B == 0) return PGX_OK;
+    PGX_TRY(check_index(ctx, "pgx_gram_batch", index, (int64_t)B * m));
+    std::vector<double> hp((size_t)B * 12, 0.0);
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < nparams; ++k) hp[(size_t)b * 12 + k] = params[(size_t)b * nparams + k];
+    BatchBuffers d;
+    PGX_TRY(batch_upload(ctx, hp.data(), B, m, index, wsel, (size_t)nv, &d));
+    with_gram_generator(kind, ctx->D, [&](auto gen) {
+        hipLaunchKernelGGL((gram_batch_kernel<decltype(gen)>), dim3((unsigned)B), dim3(64), 0, ctx->stream, ctx->pts.as<double>(), d.prm,
+                           d.index, m, d.w, wpow, d.out, d.flags);
+    });
+    PGX_HIP(ctx, hipGetLastError());
+    PGX_TRY(d2h(ctx, out, d.out, (size_t)B * nv * 8));
+    if (bad) PGX_TRY(d2h(ctx, bad, d.flags, (size_t)B * 4));
+    PGX_TRY(sync_deliver(ctx));
+    return PGX_OK;
+}
+
 int gram_labels_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int K, int use_weights, int wpow,
                        double* out, int64_t* count, int64_t* bad)
 {
-    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: points not set");
+    PGX_TRY(check_call(ctx, "pgx_gram_labels", wpow, params, nparams));
     if (ctx->labels_n != ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: labels not set");
-    if (wpow != 1 && wpow != 2) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: weight power must be 1 or 2");
-    if (nparams < 0 || nparams > 12 || (nparams > 0 && !params)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: bad parameter block");
     if (!out || K <= 0 || K > kMaxGramLabels) return fail(ctx, PGX_ERR_INVALID, "pgx_gram_labels: bad argument");
     int q = 0;
     PGX_TRY(gram_row_length(ctx, "pgx_gram_labels", kind, nparams, &q));
@@ -648,44 +631,25 @@ int gram_labels_launch(pgx_ctx* ctx, int kind, const double* params, int nparams
     const double* ww = nullptr;
     PGX_TRY(resident_weights(ctx, "pgx_gram_labels", use_weights, &ww));
     // scratch: partials[K][blocks][nv] | out[K][nv] | counters[2K] | prm[K][12]
-    const size_t part_bytes = (size_t)K * blocks * nv * 8, out_bytes = (size_t)K * nv * 8, cnt_bytes = ((size_t)K * 8 + 15) & ~(size_t)15;
-    const size_t prm_bytes = (size_t)K * 12 * 8;
-    PGX_TRY(ensure(ctx, ctx->fit_scratch, part_bytes + out_bytes + cnt_bytes + prm_bytes + 64));
-    char* base = (char*)ctx->fit_scratch.p;
-    double* d_part = (double*)base;
-    double* d_out = (double*)(base + part_bytes);
-    int* d_cnt = (int*)(base + part_bytes + out_bytes);
-    double* d_prm = (double*)(base + part_bytes + out_bytes + cnt_bytes);
+    const size_t out_bytes = (size_t)K * nv * 8, cnt_bytes = ((size_t)K * 8 + 15) & ~(size_t)15, prm_bytes = (size_t)K * 12 * 8;
+    char* r[4];
+    PGX_TRY(carve(ctx, {(size_t)K * blocks * nv * 8, out_bytes, cnt_bytes, prm_bytes}, r));
     // counters (zero) | parameter blocks are adjacent: ONE upload clears the first and fills the second; result | counters are
-    // adjacent too: ONE copy back, into pinned memory.  (A fill, two uploads' worth of commands and two blocking copies into pageable
+    // adjacent too (fetch_gram).  (A fill, two uploads' worth of commands and two blocking copies into pageable
     // memory before: a third of the call on a 300-point scene, scripts/bench_small_calls.py.)
     std::vector<double> hp(cnt_bytes / 8 + (size_t)K * 12, 0.0);
     for (int k = 0; k < K; ++k)
         for (int j = 0; j < nparams; ++j) hp[cnt_bytes / 8 + (size_t)k * 12 + j] = params[(size_t)k * nparams + j];
-    PGX_HIP(ctx, hipMemcpyAsync(d_cnt, hp.data(), cnt_bytes + prm_bytes, hipMemcpyHostToDevice, ctx->stream));
-    with_gram_generator(kind, ctx->D, [&](auto gen) { launch_labels<decltype(gen)>(ctx, K, d_prm, ww, wpow, blocks, d_part, d_cnt); });
-    PGX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(gram_final_labels_kernel, dim3((unsigned)K), dim3(1024), 0, ctx->stream, d_part, blocks, nv, d_out);
-    PGX_HIP(ctx, hipGetLastError());
-    void* hs = nullptr;
-    PGX_TRY(host_staging(ctx, out_bytes + cnt_bytes, &hs));
-    PGX_TRY(d2h(ctx, hs, d_out, out_bytes + (size_t)2 * K * sizeof(int)));
-    PGX_TRY(sync_deliver(ctx));
-    memcpy(out, hs, out_bytes);
-    const int* cnt = (const int*)((const char*)hs + out_bytes);
-    for (int k = 0; k < K; ++k) {
-        if (count) count[k] = cnt[2 * k];
-        if (bad) bad[k] = cnt[2 * k + 1];
-    }
-    return PGX_OK;
+    PGX_HIP(ctx, hipMemcpyAsync(r[2], hp.data(), cnt_bytes + prm_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PGX_TRY(launch_gram(ctx, kind, K, blocks, FitParams{}, (const double*)r[3], nullptr, 0, 0, ww, wpow, (double*)r[0], (int*)r[2], nv,
+                        (double*)r[1]));
+    return fetch_gram(ctx, r[1], out_bytes, K, nv, out, count, bad);
 }
 
 int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int sel, const int32_t* index, int64_t m,
                 int label, int use_weights, int wpow, double* out, int64_t* count, int64_t* bad)
 {
-    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: points not set");
-    if (wpow != 1 && wpow != 2) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: weight power must be 1 or 2");
-    if (nparams < 0 || nparams > 12 || (nparams > 0 && !params)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: bad parameter block");
+    PGX_TRY(check_call(ctx, "pgx_gram", wpow, params, nparams));
     if (!out) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: out is NULL");
     int q = 0;
     PGX_TRY(gram_row_length(ctx, "pgx_gram", kind, nparams, &q));
@@ -693,8 +657,7 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
     int64_t work = 0;
     if (sel == PGX_SEL_INDEX) {
         if (m < 0 || (m > 0 && !index)) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: index list missing");
-        for (int64_t t = 0; t < m; ++t)
-            if (index[t] < 0 || index[t] >= ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: index %d out of range", index[t]);
+        PGX_TRY(check_index(ctx, "pgx_gram", index, m));
         work = m;
     } else if (sel == PGX_SEL_LABEL) {
         if (ctx->labels_n != ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_gram: labels not set");
@@ -713,17 +676,12 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
         if (bad) *bad = 0;
         return PGX_OK;
     }
-    // scratch: partials | out | counters | index
-    const size_t part_bytes = (size_t)blocks * nv * sizeof(double);
+    // scratch: partials | out (64 doubles) | counters (64 bytes) | index
     const size_t idx_bytes = sel == PGX_SEL_INDEX ? (size_t)m * sizeof(int32_t) : 0;
-    const size_t total = part_bytes + 64 * sizeof(double) + 64 + ((idx_bytes + 7) & ~(size_t)7);
-    PGX_TRY(ensure(ctx, ctx->fit_scratch, total));
-    char* base = (char*)ctx->fit_scratch.p;
-    double* d_part = (double*)base;
-    double* d_out = (double*)(base + part_bytes);
-    int* d_cnt = (int*)(base + part_bytes + 64 * sizeof(double));
-    int* d_idx = (int*)(base + part_bytes + 64 * sizeof(double) + 64);
-    // counters (64 bytes, zero) | index list are adjacent: a short list is uploaded together with the zeros (one command instead of two)
+    char* r[4];
+    PGX_TRY(carve(ctx, {(size_t)blocks * nv * 8, 64 * sizeof(double), (size_t)64, idx_bytes}, r));
+    int* d_cnt = (int*)r[2];
+    // counters (zero) | index list are adjacent: a short list is uploaded together with the zeros (one command instead of two)
     std::vector<int32_t> up;   // (alive until the stream has been synchronised below)
     if (idx_bytes && m <= kFusedIndexMax) {
         up.assign(16 + (size_t)m, 0);
@@ -731,23 +689,11 @@ int gram_launch(pgx_ctx* ctx, int kind, const double* params, int nparams, int s
         PGX_HIP(ctx, hipMemcpyAsync(d_cnt, up.data(), 64 + idx_bytes, hipMemcpyHostToDevice, ctx->stream));
     } else {
         PGX_HIP(ctx, hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
-        if (idx_bytes) PGX_HIP(ctx, hipMemcpyAsync(d_idx, index, idx_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (idx_bytes) PGX_HIP(ctx, hipMemcpyAsync(r[3], index, idx_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
-    const int* ix = sel == PGX_SEL_INDEX ? d_idx : nullptr;
-    with_gram_generator(kind, ctx->D, [&](auto gen) { launch<decltype(gen)>(ctx, prm, ix, m, label, ww, wpow, blocks, d_part, d_cnt); });
-    PGX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(gram_final_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_part, blocks, nv, d_out);
-    PGX_HIP(ctx, hipGetLastError());
-    // result (64 doubles) | counters are adjacent: one copy back, into pinned memory
-    void* hs = nullptr;
-    PGX_TRY(host_staging(ctx, 64 * sizeof(double) + 8, &hs));
-    PGX_TRY(d2h(ctx, hs, d_out, 64 * sizeof(double) + 8));
-    PGX_TRY(sync_deliver(ctx));
-    memcpy(out, hs, (size_t)nv * sizeof(double));
-    const int* cnt = (const int*)((const char*)hs + 64 * sizeof(double));
-    if (count) *count = cnt[0];
-    if (bad) *bad = cnt[1];
-    return PGX_OK;
+    PGX_TRY(launch_gram(ctx, kind, 1, blocks, prm, nullptr, sel == PGX_SEL_INDEX ? (const int*)r[3] : nullptr, m, label, ww, wpow,
+                        (double*)r[0], d_cnt, nv, (double*)r[1]));
+    return fetch_gram(ctx, r[1], 64 * sizeof(double), 1, nv, out, count, bad);
 }
 
 

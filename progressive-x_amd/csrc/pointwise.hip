@@ -4,7 +4,7 @@
 //                       ProgressiveX::isPutativeModelValid (progressive_x.h:583-585)
 //   compound_kernel     ProgressiveX::updateCompoundModel (progressive_x.h:597-624)
 //   unary_kernel        pearl::dataEnergyFunctor (PEARL.h:82-128), all (point, label) pairs at once, quantised
-//   residual_sum_kernel PEARL::parameterEstimation's before/after sums (PEARL.h:369-371, 388-390)
+//   residual_sums_kernel PEARL::parameterEstimation's before/after sums (PEARL.h:369-371, 388-390), all labels at once
 //   bucket_*            PEARL::parameterEstimation's label bucketing (PEARL.h:342-352): histogram + stable compaction
 //                       with wave ballot / prefix sums
 //   energy_kernel       GCoptimization::compute_energy (absent upstream, U-5): data + Potts + label costs, exact int64
@@ -25,6 +25,14 @@ struct ModelArg {
 };
 
 constexpr int kPwBlock = 256;
+
+// the resident type's model as a kernel argument: its ctx->P doubles, zero-padded
+static ModelArg model_arg(const pgx_ctx* ctx, const double* model)
+{
+    ModelArg mdl;
+    for (int k = 0; k < 18; ++k) mdl.v[k] = k < ctx->P ? model[k] : 0.0;
+    return mdl;
+}
 
 __device__ __forceinline__ double wave_sum(double x)
 {
@@ -54,22 +62,23 @@ __device__ __forceinline__ void block_sum(double (&x)[NV], double* lds /* >= 4*N
     }
 }
 
-// final pass: one block adds `count` partial NV-tuples in a fixed order
+// final pass: block s adds the `count` partial NV-tuples of segment s in a fixed order
 template <int NV>
 __global__ __launch_bounds__(kPwBlock) void final_sum_kernel(const double* __restrict__ partials, int count,
                                                              double* __restrict__ out)
 {
     __shared__ double lds[4 * NV];
+    const double* part = partials + (int64_t)blockIdx.x * count * NV;
     double acc[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) acc[k] = 0.0;
     for (int b = threadIdx.x; b < count; b += kPwBlock)
 #pragma unroll
-        for (int k = 0; k < NV; ++k) acc[k] += partials[(int64_t)b * NV + k];
+        for (int k = 0; k < NV; ++k) acc[k] += part[(int64_t)b * NV + k];
     block_sum<NV>(acc, lds);
     if (threadIdx.x == 0)
 #pragma unroll
-        for (int k = 0; k < NV; ++k) out[k] = acc[k];
+        for (int k = 0; k < NV; ++k) out[(int64_t)blockIdx.x * NV + k] = acc[k];
 }
 
 template <int MT>
@@ -113,8 +122,7 @@ __global__ __launch_bounds__(kPwBlock) void preference_kernel(const double* __re
 int preference_launch(pgx_ctx* ctx, const double* model, double T2, double* d_pref, double out3[3])
 {
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_preference: points not set");
-    ModelArg mdl;
-    for (int k = 0; k < 18; ++k) mdl.v[k] = k < ctx->P ? model[k] : 0.0;
+    const ModelArg mdl = model_arg(ctx, model);
     const int blocks = (int)((ctx->n + kPwBlock - 1) / kPwBlock);
     PGX_TRY(ensure(ctx, ctx->red_partials, (size_t)blocks * 3 * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->red_out, 8 * sizeof(double)));
@@ -323,10 +331,7 @@ int gc_labeling_launch(pgx_ctx* ctx, const double* model, double T2, double lamb
     long long* dq = (long long*)(e + n);
     long long* wq = dq + 2 * n;
     int* labels = (int*)(wq + (E > 0 ? E : 1));
-    ModelArg mdl;
-    int pd = 0, pp = 0;
-    model_dims(ctx->model_type, &pd, &pp);
-    for (int j = 0; j < 18; ++j) mdl.v[j] = j < pp ? model[j] : 0.0;
+    const ModelArg mdl = model_arg(ctx, model);
     const int blocks = (int)((n + kPwBlock - 1) / kPwBlock);
     dim3 g((unsigned)blocks), b(kPwBlock);
     const double* pts = ctx->pts.as<double>();
@@ -435,64 +440,36 @@ int score_inliers_launch(pgx_ctx* ctx, int row, int32_t* index, int64_t* count)
 }
 
 // ---- a9: residual sums ---------------------------------------------------------------------------------------------
-template <int MT>
-__global__ __launch_bounds__(kPwBlock) void residual_sum_kernel(const double* __restrict__ pts, int64_t n, ModelArg mdl,
-                                                                const int* __restrict__ labels, int label,
-                                                                double* __restrict__ partials)
-{
-    using R = Residual<MT>;
-    __shared__ double lds[4];
-    const int64_t i = (int64_t)blockIdx.x * kPwBlock + threadIdx.x;
-    double acc[1] = {0.0};
-    if (i < n && labels[i] == label) {
-        double pt[R::D];
-        load_point<MT>(pts, i, pt);
-        acc[0] = R::plain(pt, mdl.v);  // PEARL.h:371 / :390  (unsquared residual)
-    }
-    block_sum<1>(acc, lds);
-    if (threadIdx.x == 0) partials[blockIdx.x] = acc[0];
-}
-
-// All K labels in one launch (blockIdx.y = label, model k for label k): the same per-block tree and the same final pass as
-// the single-label kernel, so sums[k] is bit-identical to residual_sum_launch(model k, k).  PEARL::parameterEstimation
-// needs 2K such sums per iteration; one host round trip each made its loop latency-bound.
+// K labels in one launch: blockIdx.y = k sums the unsquared residuals (PEARL.h:371 / :390) of model k over the points labelled
+// label0 + k.  PEARL::parameterEstimation needs 2K such sums per iteration; one host round trip each made its loop latency-bound
+// (DESIGN.md 5.6).  The single-label call is K = 1 of the same kernels, so sums[k] is bitwise pgx_residual_sum(model k, k).
 template <int MT>
 __global__ __launch_bounds__(kPwBlock) void residual_sums_kernel(const double* __restrict__ pts, int64_t n,
                                                                  const double* __restrict__ models,
-                                                                 const int* __restrict__ labels, int blocks,
+                                                                 const int* __restrict__ labels, int label0, int blocks,
                                                                  double* __restrict__ partials)
 {
     using R = Residual<MT>;
     __shared__ double lds[4];
-    const int label = (int)blockIdx.y;
+    const int k = (int)blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * kPwBlock + threadIdx.x;
     double acc[1] = {0.0};
-    if (i < n && labels[i] == label) {
+    if (i < n && labels[i] == label0 + k) {
         double pt[R::D], mdl[R::P];
 #pragma unroll
-        for (int k = 0; k < R::P; ++k) mdl[k] = models[(int64_t)label * R::P + k];
+        for (int j = 0; j < R::P; ++j) mdl[j] = models[(int64_t)k * R::P + j];
         load_point<MT>(pts, i, pt);
         acc[0] = R::plain(pt, mdl);
     }
     block_sum<1>(acc, lds);
-    if (threadIdx.x == 0) partials[(int64_t)label * blocks + blockIdx.x] = acc[0];
+    if (threadIdx.x == 0) partials[(int64_t)k * blocks + blockIdx.x] = acc[0];
 }
 
-__global__ __launch_bounds__(kPwBlock) void final_sums_kernel(const double* __restrict__ partials, int count, double* __restrict__ out)
+static int residual_sums_run(pgx_ctx* ctx, const char* who, const double* models, int K, int label0, double* sums)
 {
-    __shared__ double lds[4];
-    const double* part = partials + (int64_t)blockIdx.x * count;
-    double acc[1] = {0.0};
-    for (int b = threadIdx.x; b < count; b += kPwBlock) acc[0] += part[b];
-    block_sum<1>(acc, lds);
-    if (threadIdx.x == 0) out[blockIdx.x] = acc[0];
-}
-
-int residual_sums_launch(pgx_ctx* ctx, const double* models, int K, double* sums)
-{
-    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_residual_sums: points not set");
-    if (ctx->labels_n != ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_residual_sums: labels not set");
-    if (K <= 0 || K > 65535) return fail(ctx, PGX_ERR_INVALID, "pgx_residual_sums: K = %d out of range", K);
+    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "%s: points not set", who);
+    if (ctx->labels_n != ctx->n) return fail(ctx, PGX_ERR_INVALID, "%s: labels not set", who);
+    if (K <= 0 || K > 65535) return fail(ctx, PGX_ERR_INVALID, "%s: K = %d out of range", who, K);
     const int blocks = (int)((ctx->n + kPwBlock - 1) / kPwBlock);
     PGX_TRY(ensure(ctx, ctx->red_partials, (size_t)blocks * (size_t)(K > 3 ? K : 3) * sizeof(double)));
     PGX_TRY(ensure(ctx, ctx->red_out, (size_t)(K > 8 ? K : 8) * sizeof(double)));
@@ -503,38 +480,24 @@ int residual_sums_launch(pgx_ctx* ctx, const double* models, int K, double* sums
     const double* mdl = ctx->kmodels.as<double>();
     const int* lab = ctx->labels.as<int>();
     double* part = ctx->red_partials.as<double>();
-    if (!with_model_type(ctx->model_type, [&](auto mt) { hipLaunchKernelGGL((residual_sums_kernel<decltype(mt)::value>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, blocks, part); }))
+    if (!with_model_type(ctx->model_type, [&](auto mt) { hipLaunchKernelGGL((residual_sums_kernel<decltype(mt)::value>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label0, blocks, part); }))
         return fail(ctx, PGX_ERR_INVALID, "bad model type");
     PGX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(final_sums_kernel, dim3((unsigned)K), dim3(kPwBlock), 0, ctx->stream, part, blocks, ctx->red_out.as<double>());
+    hipLaunchKernelGGL((final_sum_kernel<1>), dim3((unsigned)K), dim3(kPwBlock), 0, ctx->stream, part, blocks, ctx->red_out.as<double>());
     PGX_HIP(ctx, hipGetLastError());
     PGX_TRY(d2h(ctx, sums, ctx->red_out.p, (size_t)K * sizeof(double)));
     PGX_TRY(sync_deliver(ctx));
     return PGX_OK;
 }
 
+int residual_sums_launch(pgx_ctx* ctx, const double* models, int K, double* sums)
+{
+    return residual_sums_run(ctx, "pgx_residual_sums", models, K, 0, sums);
+}
+
 int residual_sum_launch(pgx_ctx* ctx, const double* model, int label, double* sum)
 {
-    if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_residual_sum: points not set");
-    if (ctx->labels_n != ctx->n) return fail(ctx, PGX_ERR_INVALID, "pgx_residual_sum: labels not set");
-    ModelArg mdl;
-    for (int k = 0; k < 18; ++k) mdl.v[k] = k < ctx->P ? model[k] : 0.0;
-    const int blocks = (int)((ctx->n + kPwBlock - 1) / kPwBlock);
-    PGX_TRY(ensure(ctx, ctx->red_partials, (size_t)blocks * 3 * sizeof(double)));
-    PGX_TRY(ensure(ctx, ctx->red_out, 8 * sizeof(double)));
-    dim3 g((unsigned)blocks), b(kPwBlock);
-    const double* pts = ctx->pts.as<double>();
-    const int* lab = ctx->labels.as<int>();
-    double* part = ctx->red_partials.as<double>();
-    if (!with_model_type(ctx->model_type, [&](auto mt) { hipLaunchKernelGGL((residual_sum_kernel<decltype(mt)::value>), g, b, 0, ctx->stream, pts, ctx->n, mdl, lab, label, part); }))
-        return fail(ctx, PGX_ERR_INVALID, "bad model type");
-    PGX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL((final_sum_kernel<1>), dim3(1), dim3(kPwBlock), 0, ctx->stream, part, blocks,
-                       ctx->red_out.as<double>());
-    PGX_HIP(ctx, hipGetLastError());
-    PGX_TRY(d2h(ctx, sum, ctx->red_out.p, sizeof(double)));
-    PGX_TRY(sync_deliver(ctx));
-    return PGX_OK;
+    return residual_sums_run(ctx, "pgx_residual_sum", model, 1, label, sum);
 }
 
 // ---- U-14: support of a fundamental matrix under the symmetric epipolar distance --------------------------------------------
@@ -579,8 +542,7 @@ int epipolar_support_launch(pgx_ctx* ctx, const double* F, double T2, double S2,
 {
     if (ctx->n <= 0 || ctx->model_type != kFundamental)
         return fail(ctx, PGX_ERR_INVALID, "pgx_epipolar_support: needs the points of a fundamental-matrix problem");
-    ModelArg mdl;
-    for (int k = 0; k < 18; ++k) mdl.v[k] = k < 9 ? F[k] : 0.0;
+    const ModelArg mdl = model_arg(ctx, F);
     PGX_TRY(ensure(ctx, ctx->red_out, 8 * sizeof(double)));
     unsigned long long* out = (unsigned long long*)ctx->red_out.p;
     PGX_HIP(ctx, hipMemsetAsync(out, 0, 16, ctx->stream));

@@ -48,6 +48,7 @@ timeit("gram DLT (110 indices)", lambda: ctx.gram(_lib.GRAM_DLT_H, ("index", idx
 timeit("gram DLT (label 1)", lambda: ctx.gram(_lib.GRAM_DLT_H, ("label", 1), params=norm))
 timeit("gram_labels DLT (4 labels)", lambda: ctx.gram_labels(_lib.GRAM_DLT_H, 4, params=np.tile(norm, (4, 1))))
 timeit("residual_sums (4 models)", lambda: ctx.residual_sums(models))
+timeit("residual_sum (label 1)", lambda: ctx.residual_sum(models[1], 1))
 timeit("gc_inliers", lambda: ctx.gc_inliers(H, T2, 0.05))
 timeit("pearl_unary (4 models)", lambda: ctx.pearl_unary(models, 4.0, 0.05))
 

@@ -116,7 +116,7 @@ def _check_gram_labels(gpu_ctx, oracle, kind, pts, labels, K, populated, prm, w,
     empty = np.ones(K, bool)
     empty[list(populated)] = False
     assert not cnt[empty].any() and not bad[empty].any() and not G[empty].any(), "an empty label came back with a count or a matrix"
-    for k in singles:                                         # the same per-block tree and final pass as the single-label call
+    for k in singles:                                         # the single-label call: the same kernels with one item
         Gk, ck, bk = gpu_ctx.gram(kind, ("label", k), params=None if prm is None else prm[k], weights=w, wpow=wpow)
         assert np.array_equal(G[k], Gk) and (int(cnt[k]), int(bad[k])) == (ck, bk), f"label {k} of {K}, wpow {wpow}"
     for k in populated:
@@ -129,8 +129,8 @@ def test_gram_labels_either_side_of_the_ring(gpu_ctx, oracle, K):
     """pgx_gram_labels reads result and counters back in ONE copy of K * nv * 8 + 2 K * 4 bytes (fit.hip gram_labels_launch).
     GRAM_DLT_H, nv = 45: K = 89: 32 040 + 712 = 32 752 bytes (staged); K = 90: 32 400 + 720 = 33 120 (direct); K = 91: 33 488 and
     K = 92: 33 856 (direct; the sizes at which the result alone crosses).  Most labels are empty, four are populated, label K is the
-    outlier label.  gram_labels_kernel / gram_final_labels_kernel are gram_kernel / gram_final_kernel with blockIdx.y = label: entry
-    k is bitwise the single-label call."""
+    outlier label.  pgx_gram is the one-item call of the same gram_kernel / gram_final_kernel (blockIdx.y = label): entry k is
+    bitwise the single-label call - one kernel compared with itself here; tests/test_gpu_reductions.py pins the bits."""
     assert 89 * (45 * 8 + 8) <= STAGE_MAX < 90 * (45 * 8 + 8) and 91 * 45 * 8 <= STAGE_MAX < 92 * 45 * 8
     n = 3001
     mt, pts, _, _ = _case("homography", n, 1, 4)
@@ -171,8 +171,8 @@ def test_gram_labels_up_to_the_label_limit(gpu_ctx, oracle, K):
 @pytest.mark.parametrize("K", [4096, 4097])
 def test_residual_sums_either_side_of_the_ring(gpu_ctx, oracle, K):
     """pgx_residual_sums reads K doubles back: K = 4096: 32 768 bytes (staged, the largest staged copy there is); K = 4097: 32 776
-    (direct).  blockIdx.y = label with the per-block tree and final pass of the single-label kernel: sums[k] is bitwise
-    pgx_residual_sum(model k, k)."""
+    (direct).  pgx_residual_sum is the K = 1 call of the same kernels (blockIdx.y = label - label0): sums[k] is bitwise
+    pgx_residual_sum(model k, k) - one kernel compared with itself here; tests/test_gpu_reductions.py pins the bits."""
     assert 4096 * 8 <= STAGE_MAX < 4097 * 8
     n = 3001
     mt, pts, base, _ = _case("line", n, 7, 6)
