@@ -76,6 +76,10 @@ struct DeviceCycle {
     }
     int restore(int prefix)
     {
+        // The restored labelling holds what moves 0 .. prefix-1 wrote last time.  Those moves do not run now, so nothing else tells
+        // labels_max: with the whole first cycle restored and max_cycles = 1 it stayed at the uploaded zeros' 0, and a later, smaller
+        // table passed the range check with labels up to prefix-1 resident (found by tests/soak_sequences.py, history "from zeros again").
+        if (prefix - 1 > ctx->expansion.labels_max) ctx->expansion.labels_max = prefix - 1;
         PGX_HIP(ctx, hipMemcpyAsync(ctx->labels.p, (char*)ctx->memo_snaps.buf.p + (size_t)(prefix - 1) * row_bytes(), row_bytes(), hipMemcpyDeviceToDevice, ctx->stream));
         return PGX_OK;
     }

@@ -107,6 +107,14 @@ def test_expansion_soak_slice_through_region_moves(oracle, seed, monkeypatch):
     assert soak(seed, 120, verbose=False, max_n=2500) == 0
 
 
+def test_sequence_soak_slice(oracle):
+    """A bounded slice of tests/soak_sequences.py on seeds of its own (the committed ones are tests/test_gpu_sequences.py's): random
+    call sequences on one context - every single-GPU call that touches resident state, refusals included - against the model of
+    include/pgx.h (tests/ctx_model.py), with up to eight accepted calls per sequence repeated bit for bit on a fresh context."""
+    from soak_sequences import soak
+    assert soak(91, 4, verbose=False) == 0
+
+
 def test_replay_soak_slice():
     """60 random drop-in calls through libpgx, every decision against the independent replay of progressive_x.h / PEARL.h
     (tests/soak_replay.py; the long campaigns are in profiles/)"""
