@@ -7,6 +7,10 @@ Only the vanishing-point solver exists in the snapshot; the line / homography / 
 absent graph-cut-ransac submodule and are restated from the literature [UPSTREAM-MEMORY] — SURVEY.md §8f ranks them
 "next" (GPU versions), so round 1 keeps them on the host: they produce the hypothesis batches that the HIP scorer
 consumes and the refits PEARL asks for.  Residuals are NOT computed here — that is libpgx's job.
+
+Every refit is stated once, as `_fit_many(gram, B, inits)` on [B, ...] stacks; `Estimator.nonminimal` (one selection),
+`nonminimal_labels` (all labels) and `nonminimal_batch` (B index selections) hand it a Gram provider over pgx_gram,
+pgx_gram_labels and pgx_gram_batch.  PnP alone keeps a second, single-item statement (see `PnPEstimator.nonminimal`).
 """
 import numpy as np
 
@@ -54,109 +58,60 @@ class Estimator:
         candidates with the proposal's scoring function.  Default: valid, unchanged."""
         return True, model
 
-    def _fit(self, init):
-        """The refit as a coroutine: yields Gram requests (kind, params, use_weights, wpow), receives (G, count, bad)
-        and returns the list of models.  Written once, driven either by one pgx_gram call per request (`nonminimal`) or
-        in lockstep over a batch of selections with one pgx_gram_batch launch per step (`nonminimal_batch`)."""
+    def _fit_many(self, gram, B, inits):
+        """The least-squares refit of B items at once, stated once per estimator: the data passes go to the Gram provider,
+        gram(kind, params [len(rows), p] | None, use_weights, wpow, rows) -> (G [len(rows), q, q], count [len(rows)],
+        bad [len(rows)]), one request for all the items that still need it (rows = their numbers); the small dense solves run
+        here on stacks.  inits = B start models or None.  Returns a list of B model lists.  The three entry points below
+        differ in the provider alone."""
         raise NotImplementedError
-        yield  # pragma: no cover
 
     def nonminimal(self, ctx, sel, weights=None, init=None):
         """Least-squares fit to the selected resident points -> list of models (the reference accepts the refit only
         if exactly 1).  sel = ("index", indices) or ("label", k); the data pass runs on the device (ctx.gram =
-        pgx_gram: weighted Gram matrix of the design rows), the small dense solve here."""
+        pgx_gram: weighted Gram matrix of the design rows), the small dense solve here: `_fit_many` with one item."""
         self._eig_ctx = ctx
-        gen = self._fit(init)
-        try:
-            req = next(gen)
-            while True:
-                kind, params, use_w, wpow = req
-                req = gen.send(ctx.gram(kind, sel, params=params, weights=weights if use_w else None, wpow=wpow))
-        except StopIteration as done:
-            return done.value
+
+        def gram(kind, prm, use_w, wpow, rows):
+            G, cnt, bad = ctx.gram(kind, sel, params=None if prm is None else prm[0], weights=weights if use_w else None, wpow=wpow)
+            return G[None], np.array([cnt]), np.array([bad])
+        return self._fit_many(gram, 1, [init])[0]
 
     def nonminimal_labels(self, ctx, K, weights=None, inits=None, skip=()):
-        """`nonminimal(ctx, ("label", k), weights, init=inits[k])` for k = 0..K-1 with the coroutines advancing in lockstep:
-        every step is ONE pgx_gram_labels launch for all labels (PEARL refits every instance per iteration; one host round
-        trip per instance and step made that loop latency-bound).  Labels in `skip` are not fitted.  The Gram matrices
-        are bit-identical to the single-label calls, so the results are those of K separate `nonminimal` calls."""
+        """`nonminimal(ctx, ("label", k), weights, init=inits[k])` for k = 0..K-1 at once: every Gram request is ONE
+        pgx_gram_labels launch for all labels (PEARL refits every instance per iteration; one host round trip per instance
+        and request made that loop latency-bound).  Labels in `skip` are not fitted.  The Gram matrices are bit-identical to
+        the single-label calls, so the results are those of K separate `nonminimal` calls."""
         self._eig_ctx = ctx
-        if hasattr(self, "_fit_many"):          # refit vectorised over the instances (same Gram launches, stacked small solves)
-            live = [k for k in range(K) if k not in skip]
-            out = [[] for _ in range(K)]
-            if not live:
-                return out
-
-            def gram(kind, prm, use_w, wpow, rows):
-                sel = [live[r] for r in rows]
-                full = None
-                if prm is not None:
-                    full = np.zeros((K, prm.shape[1]))
-                    full[sel] = prm
-                G, cnt, bad = ctx.gram_labels(kind, K, params=full, weights=weights if use_w else None, wpow=wpow)
-                return G[sel], cnt[sel], bad[sel]
-            res = self._fit_many(gram, len(live), [None if inits is None else inits[k] for k in live])
-            for r, k in enumerate(live):
-                out[k] = res[r]
+        live = [k for k in range(K) if k not in skip]
+        out = [[] for _ in range(K)]
+        if not live:
             return out
-        gens = {k: self._fit(None if inits is None else inits[k]) for k in range(K) if k not in skip}
-        results, pending = {k: [] for k in range(K)}, {}
-        for k, g in gens.items():
-            try:
-                pending[k] = next(g)
-            except StopIteration as done:
-                results[k] = done.value
-        while pending:
-            groups = {}
-            for k, (kind, params, use_w, wpow) in pending.items():
-                groups.setdefault((kind, bool(use_w), wpow, None if params is None else len(np.ravel(params))), []).append(k)
-            for (kind, use_w, wpow, plen), ks in groups.items():
-                prm = None
-                if plen is not None:
-                    prm = np.zeros((K, plen))
-                    for k in ks:
-                        prm[k] = np.asarray(pending[k][1], dtype=np.float64).reshape(-1)
-                G, cnt, bad = ctx.gram_labels(kind, K, params=prm, weights=weights if use_w else None, wpow=wpow)
-                for k in ks:
-                    try:
-                        pending[k] = gens[k].send((G[k], int(cnt[k]), int(bad[k])))
-                    except StopIteration as done:
-                        results[k] = done.value
-                        del pending[k]
-        return [results[k] for k in range(K)]
+
+        def gram(kind, prm, use_w, wpow, rows):
+            sel = [live[r] for r in rows]
+            full = None
+            if prm is not None:                   # labels not asked about get a zero-filled params row
+                full = np.zeros((K, prm.shape[1]))
+                full[sel] = prm
+            G, cnt, bad = ctx.gram_labels(kind, K, params=full, weights=weights if use_w else None, wpow=wpow)
+            return G[sel], cnt[sel], bad[sel]
+        res = self._fit_many(gram, len(live), [None if inits is None else inits[k] for k in live])
+        for r, k in enumerate(live):
+            out[k] = res[r]
+        return out
 
     def nonminimal_batch(self, ctx, index, weights=None, init=None):
-        """`nonminimal` for B index selections of equal size (index [B, m]) sharing `init`: the B coroutines advance in
-        lockstep, each step is ONE pgx_gram_batch launch.  Returns a list of B model lists."""
+        """`nonminimal` for B index selections of equal size (index [B, m]) sharing `init`: every Gram request is ONE
+        pgx_gram_batch launch.  Returns a list of B model lists."""
         index = np.asarray(index)
         B, m = index.shape
         self._eig_ctx = ctx
-        if hasattr(self, "_fit_many"):           # refit vectorised over the batch (same Gram launches, stacked small solves)
-            def gram(kind, prm, use_w, wpow, rows):
-                G, bad = ctx.gram_batch(kind, index[rows], params=prm, weights=weights if use_w else None, wpow=wpow)
-                return G, np.full(len(rows), m, dtype=np.int64), bad
-            return self._fit_many(gram, B, [init] * B)
-        gens = [self._fit(init) for _ in range(B)]
-        results, pending = [None] * B, {}
-        for b, g in enumerate(gens):
-            try:
-                pending[b] = next(g)
-            except StopIteration as done:
-                results[b] = done.value
-        while pending:
-            groups = {}
-            for b, (kind, params, use_w, wpow) in pending.items():
-                groups.setdefault((kind, bool(use_w), wpow, params is None), []).append(b)
-            for (kind, use_w, wpow, no_params), bs in groups.items():
-                prm = None if no_params else np.array([np.asarray(pending[b][1], dtype=np.float64).reshape(-1) for b in bs])
-                G, bad = ctx.gram_batch(kind, index[bs], params=prm, weights=weights if use_w else None, wpow=wpow)
-                for k, b in enumerate(bs):
-                    try:
-                        pending[b] = gens[b].send((G[k], m, int(bad[k])))
-                    except StopIteration as done:
-                        results[b] = done.value
-                        del pending[b]
-        return results
+
+        def gram(kind, prm, use_w, wpow, rows):
+            G, bad = ctx.gram_batch(kind, index[rows], params=prm, weights=weights if use_w else None, wpow=wpow)
+            return G, np.full(len(rows), m, dtype=np.int64), bad
+        return self._fit_many(gram, B, [init] * B)
 
     def descriptor(self, model):
         return np.asarray(model, dtype=np.float64)
@@ -184,19 +139,10 @@ class LineEstimator(Estimator):
         models = np.column_stack([nrm, c])
         return models[ok], np.nonzero(ok)[0]
 
-    def _fit(self, init):
-        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,x,y][1,x,y]^T
-        W = G[0, 0]
-        if cnt < 2 or not W > 0:
-            return []
-        mean = G[0, 1:] / W
-        evals, evecs = np.linalg.eigh(G[1:, 1:] - W * np.outer(mean, mean))     # weighted scatter about the mean
-        nrm = evecs[:, 0]
-        return [np.array([nrm[0], nrm[1], -nrm @ mean])]
-
     def _fit_many(self, gram, B, inits):
-        """`_fit` for B items at once: one Gram launch, stacked 2x2 eigh (LAPACK per matrix: bitwise the single-call models; the
-        coroutine per item was half of a findLines call at C1 - 5 800 fits of ~7 us of Python each)."""
+        """Total least squares: the normal is the smallest eigenvector of the weighted scatter about the mean.  One Gram request
+        (sum w [1,x,y][1,x,y]^T), stacked 2x2 eigh (LAPACK per matrix, so an item's model does not depend on its neighbours; a
+        Python-level fit per item was half of a findLines call at C1 - 5 800 fits of ~7 us each)."""
         out = [[] for _ in range(B)]
         G, cnt, _ = gram(_lib.GRAM_AFFINE, None, True, 1, np.arange(B))
         W = G[:, 0, 0]
@@ -211,15 +157,15 @@ class LineEstimator(Estimator):
         if ok.any():
             evecs[ok] = np.linalg.eigh(scatter[ok])[1]
         for k, b in enumerate(idx):
-            if not ok[k]:                         # (eigh raises on non-finite input: the single-item path would too)
-                np.linalg.eigh(scatter[k])
+            if not ok[k]:                         # (a non-finite scatter gets what eigh on it alone raises or returns, whoever shares the batch)
+                evecs[k] = np.linalg.eigh(scatter[k])[1]
             nrm = evecs[k][:, 0]
             out[b] = [np.array([nrm[0], nrm[1], -nrm @ mean[k]])]
         return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 3-D plane (findPlanes; no reference counterpart): the flat family with the line, whose refits differ (see _fit / _fit_many)
+# 3-D plane (findPlanes; no reference counterpart): the flat family with the line, whose refits differ (see _fit_many)
 # ---------------------------------------------------------------------------------------------------------------------
 class PlaneEstimator(Estimator):
     model_type = _lib.PLANE3D
@@ -251,24 +197,13 @@ class PlaneEstimator(Estimator):
             return self._smallest(scatter)
         return np.linalg.eigh(scatter)[1][:, :, 0]
 
-    def _fit(self, init):
-        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,x,y,z][1,x,y,z]^T
-        W = G[0, 0]
-        if cnt < 3 or not W > 0:
-            return []
-        mean = G[0, 1:] / W
-        scatter = G[1:, 1:] - W * np.outer(mean, mean)                          # weighted scatter about the mean
-        if not np.isfinite(scatter).all():
-            return []
-        nrm = self._normal(scatter[None])[0]
-        return [np.array([nrm[0], nrm[1], nrm[2], -nrm @ mean])]
-
     def _fit_many(self, gram, B, inits):
-        """`_fit` for B items at once: one Gram launch, stacked 3x3 eigen-solves (bitwise the single-call models)."""
+        """The line's fit one dimension up: one Gram request (sum w [1,x,y,z][1,x,y,z]^T), stacked 3x3 eigen-solves; a non-finite
+        scatter gives no model."""
         out = [[] for _ in range(B)]
         G, cnt, _ = gram(_lib.GRAM_AFFINE, None, True, 1, np.arange(B))
         W = G[:, 0, 0]
-        idx = np.nonzero((np.asarray(cnt) >= 3) & (W > 0))[0]
+        idx = np.nonzero((np.asarray(cnt) >= 3) & (W > 0) & np.isfinite(G).all(axis=(1, 2)))[0]
         if idx.size == 0:
             return out
         Wk = W[idx]
@@ -304,41 +239,48 @@ class RoundEstimator(Estimator):
     def _in_range(self, r):
         return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
 
-    def _fit(self, init):
-        """Algebraic fit in two Gram passes: the weighted mean o and the RMS distance s from it (GRAM_AFFINE), then the smallest
+    def _fit_many(self, gram, B, inits):
+        """Algebraic fit in two Gram requests: the weighted mean o and the RMS distance s from it (GRAM_AFFINE), then the smallest
         eigenvector theta of the Gram matrix of the rows (1, q, |q|^2), q = (p - o) / s, the last entry summed left to right
         (GRAM_CIRCLE: u u + v v, GRAM_SPHERE: (u u + v v) + w w): theta[0] + theta[1..DIM] . q + theta[-1] |q|^2 = 0 is the sphere
         |q + b|^2 = |b|^2 - theta[0] / theta[-1] with b = theta[1..DIM] / (2 theta[-1]), so c = o - s b and
         r = s sqrt(|b|^2 - theta[0] / theta[-1]).  The normalisation keeps the small matrix well conditioned for scenes far from
-        the origin.  `init` is not used."""
-        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, True, 1)                    # sum w [1,p][1,p]^T
-        W = G[0, 0]
-        if cnt < self.sample_size or not W > 0:
-            return []
-        o = G[0, 1:] / W
-        scatter = G[1:, 1:] - W * np.outer(o, o)
-        var = np.trace(scatter) / W
+        the origin.  `inits` is not used.  The reductions whose order numpy chooses (the trace, b . b) stay per item, so a model
+        does not depend on its neighbours."""
+        out = [[] for _ in range(B)]
+        G, cnt, _ = gram(_lib.GRAM_AFFINE, None, True, 1, np.arange(B))        # sum w [1,p][1,p]^T
+        W = G[:, 0, 0]
+        rows = np.nonzero((np.asarray(cnt) >= self.sample_size) & (W > 0) & np.isfinite(G).all(axis=(1, 2)))[0]
+        if rows.size == 0:
+            return out
+        W = W[rows]
+        o = G[rows, 0, 1:] / W[:, None]
+        scatter = G[rows][:, 1:, 1:] - W[:, None, None] * (o[:, :, None] * o[:, None, :])
+        var = np.array([np.trace(sc) for sc in scatter]) / W
         # the guard: the root is taken of a positive, finite variance only (coincident points: the trace may round to zero or below it,
         # which must give no model and no RuntimeWarning); s > 0 and finite exactly when var is
-        if not (np.isfinite(o).all() and var > 0 and np.isfinite(var)):
-            return []
-        s = np.sqrt(var)
-        G, _, _ = yield (self.gram_kind, np.array([*o.tolist(), s]), True, 1)
-        if not np.isfinite(G).all():
-            return []
-        th = self._smallest(G[None])[0]
-        A = th[-1]
-        if A == 0:
-            return []
-        b = th[1:-1] / (2.0 * A)
-        rad = b @ b - th[0] / A
-        if not rad > 0:
-            return []
-        r = s * np.sqrt(rad)
-        c = o - s * b
-        if not (np.isfinite(c).all() and np.isfinite(r) and self._in_range(r)):
-            return []
-        return [np.array([*c.tolist(), r])]
+        ok = np.isfinite(o).all(axis=1) & (var > 0) & np.isfinite(var)
+        if not ok.any():
+            return out
+        rows, o, s = rows[ok], o[ok], np.sqrt(var[ok])
+        G, _, _ = gram(self.gram_kind, np.column_stack([o, s]), True, 1, rows)
+        fin = np.isfinite(G).all(axis=(1, 2))
+        if not fin.any():
+            return out
+        rows, o, s = rows[fin], o[fin], s[fin]
+        for k, th in enumerate(self._smallest(G[fin])):
+            A = th[-1]
+            if A == 0:
+                continue
+            b = th[1:-1] / (2.0 * A)
+            rad = b @ b - th[0] / A
+            if not rad > 0:
+                continue
+            r = s[k] * np.sqrt(rad)
+            c = o[k] - s[k] * b
+            if np.isfinite(c).all() and np.isfinite(r) and self._in_range(r):
+                out[rows[k]] = [np.array([*c.tolist(), r])]
+        return out
 
 
 class SphereEstimator(RoundEstimator):
@@ -419,22 +361,9 @@ class VanishingPointEstimator(Estimator):
         v = v / np.where(ok, ln, 1.0)[:, None]
         return v[ok], np.nonzero(ok)[0]
 
-    def _fit(self, init):
-        # rows A = [y0*mz-my, mx-x0*mz, x0*my-y0*mx] * w (:212-218) are generated and accumulated on the device
-        AtA, cnt, _ = yield (_lib.GRAM_VP, None, True, 2)
-        if cnt < 2:
-            return []
-        if self.refit_solver == "jacobi":
-            v = self._smallest(AtA[None])[0]
-        else:
-            evals, evecs = np.linalg.eigh(AtA)                                    # :227 SelfAdjointEigenSolver
-            v = evecs[:, int(np.argmin(evals))]                                   # :230-233
-        n = np.linalg.norm(v)
-        return [v / n] if n > 0 else []
-
     def _fit_many(self, gram, B, inits):
-        """`_fit` for B items at once (gram = the Gram provider of nonminimal_batch / nonminimal_labels): one launch, stacked
-        3x3 eigh (LAPACK per matrix: bitwise the single-call models)."""
+        """Smallest eigenvector of A^T A, rows A = [y0*mz-my, mx-x0*mz, x0*my-y0*mx] * w (:212-218) generated and accumulated on
+        the device: one Gram request, stacked 3x3 eigh (:227 SelfAdjointEigenSolver, :230-233; LAPACK per matrix)."""
         out = [[] for _ in range(B)]
         AtA, cnt, _ = gram(_lib.GRAM_VP, None, True, 2, np.arange(B))
         idx = np.nonzero((cnt >= 2) & np.isfinite(AtA).all(axis=(1, 2)))[0]
@@ -465,43 +394,25 @@ def _dlt_rows(x1, y1, x2, y2):
     return r1, r2
 
 
-def _hartley_from_moments(G, cnt):
-    """Normalising similarities of both images from one pass of first/second moments (the affine Gram matrix G;
-    isotropic scaling to an RMS distance of sqrt(2) from the centroid).  Returns (T1, T2, params for the DLT /
-    epipolar rows, count)."""
-    if cnt < 1:
-        return None, None, None, 0
-    c = G[0, 1:] / cnt
-    var = np.maximum(np.diag(G)[1:] / cnt - c * c, 0.0)
-    Ts, prm = [], []
-    for k in (0, 2):
-        rms = np.sqrt(var[k] + var[k + 1])
-        sc = np.sqrt(2.0) / rms if rms > 0 else 1.0
-        Ts.append(np.array([[sc, 0, -sc * c[k]], [0, sc, -sc * c[k + 1]], [0, 0, 1.0]]))
-        prm += [sc, c[k], c[k + 1]]
-    return Ts[0], Ts[1], np.array(prm), cnt
-
-
 def _hartley_batch(G, cnt):
-    """`_hartley_from_moments` for a stack of Gram matrices G [B, 5, 5] with counts cnt [B] (all >= 1): (T1 [B,3,3],
-    T2 [B,3,3], params [B,6]) - elementwise the same arithmetic, so every item gets bitwise the single-call result."""
+    """Normalising similarities of both images from one pass of first/second moments (the affine Gram matrices G [B, 5, 5] with
+    counts cnt [B], all >= 1; isotropic scaling to an RMS distance of sqrt(2) from the centroid): (T1 [B,3,3], T2 [B,3,3],
+    params [B,6] for the DLT / epipolar rows) - elementwise arithmetic, an item's result does not depend on its neighbours."""
     B = G.shape[0]
     cnt = np.asarray(cnt, dtype=np.float64).reshape(B, 1)
     c = G[:, 0, 1:] / cnt
     var = np.maximum(np.diagonal(G, axis1=1, axis2=2)[:, 1:] / cnt - c * c, 0.0)
-    Ts, prm = [], []
-    for k in (0, 2):
-        rms = np.sqrt(var[:, k] + var[:, k + 1])
-        sc = np.where(rms > 0, np.sqrt(2.0) / np.where(rms > 0, rms, 1.0), 1.0)
-        T = np.zeros((B, 3, 3))
-        T[:, 0, 0] = sc
-        T[:, 0, 2] = -sc * c[:, k]
-        T[:, 1, 1] = sc
-        T[:, 1, 2] = -sc * c[:, k + 1]
-        T[:, 2, 2] = 1.0
-        Ts.append(T)
-        prm += [sc, c[:, k], c[:, k + 1]]
-    return Ts[0], Ts[1], np.stack(prm, axis=1)
+    rms = np.sqrt(var[:, 0::2] + var[:, 1::2])               # [B, 2]: first image, second image
+    pos = rms > 0
+    sc = np.where(pos, np.sqrt(2.0) / np.where(pos, rms, 1.0), 1.0)
+    T = np.zeros((B, 2, 3, 3))
+    T[:, :, 0, 0] = T[:, :, 1, 1] = sc
+    T[:, :, 0, 2] = -sc * c[:, 0::2]
+    T[:, :, 1, 2] = -sc * c[:, 1::2]
+    T[:, :, 2, 2] = 1.0
+    prm = np.empty((B, 6))                                   # (sc, cx, cy) of the first image, then of the second
+    prm[:, 0::3], prm[:, 1::3], prm[:, 2::3] = sc, c[:, 0::2], c[:, 1::2]
+    return T[:, 0], T[:, 1], prm
 
 
 def _dlt_homography(p):
@@ -532,11 +443,6 @@ def _dlt_homography(p):
     return H if np.isfinite(H).all() else None
 
 
-def _smallest_eigenvector(G):
-    evals, evecs = np.linalg.eigh(G)
-    return evecs[:, 0]
-
-
 class HomographyEstimator(Estimator):
     model_type = _lib.HOMOGRAPHY
     sample_size = 4
@@ -563,22 +469,9 @@ class HomographyEstimator(Estimator):
         ok &= np.isfinite(h).all(axis=1)
         return h[ok], np.nonzero(ok)[0]
 
-    def _fit(self, init):
-        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, False, 2)
-        T1, T2, prm, cnt = _hartley_from_moments(G, cnt)
-        if cnt < 4:
-            return []
-        AtA, _, _ = yield (_lib.GRAM_DLT_H, prm, True, 2)                                  # normalised DLT rows
-        Hn = (self._smallest(AtA[None])[0] if self.refit_solver == "jacobi" else _smallest_eigenvector(AtA)).reshape(3, 3)
-        H = np.linalg.inv(T2) @ Hn @ T1
-        if not np.isfinite(H).all() or abs(H[2, 2]) < 1e-300:
-            return []
-        return [(H / H[2, 2]).reshape(-1)]
-
-
     def _fit_many(self, gram, B, inits):
-        """`_fit` for B items at once: two Gram launches, stacked eigh / inv (numpy runs LAPACK per matrix, so each item's
-        model is bitwise the single-call one)."""
+        """Normalised DLT: two Gram requests (the moments for the normalisation, then the normalised DLT rows), stacked eigh /
+        inv (numpy runs LAPACK per matrix, so an item's model does not depend on its neighbours)."""
         out = [[] for _ in range(B)]
         G, cnt, _ = gram(_lib.GRAM_AFFINE, None, False, 2, np.arange(B))
         rows = np.nonzero((cnt >= 4) & np.isfinite(G).all(axis=(1, 2)))[0]
@@ -620,10 +513,6 @@ class SymmetricHomographyEstimator(HomographyEstimator):
         models, src = super().minimal(pts, samples)
         aug, keep = self._augment(models)
         return aug, src[keep]
-
-    def _fit(self, init):
-        res = yield from super()._fit(init)
-        return [m for m in self._augment(np.array(res).reshape(-1, 9))[0]]
 
     def _fit_many(self, gram, B, inits):
         return [[m for m in self._augment(np.array(res).reshape(-1, 9))[0]] for res in super()._fit_many(gram, B, inits)]
@@ -693,8 +582,6 @@ class FundamentalEstimator(Estimator):
         ok = (nrm > 0) & np.isfinite(nrm)
         models = (F[ok] / nrm[ok][:, None, None]).reshape(-1, 9)
         return models, sidx[ok].astype(np.int64)
-
-        return np.array(models).reshape(-1, 9), np.array(src, dtype=np.int64)
 
     # -- validity [U-14] ------------------------------------------------------------------------------------------------------
     # DefaultFundamentalMatrixEstimator (progressivex_python.cpp:616) = gcransac's FundamentalMatrixEstimator, whose source is
@@ -833,25 +720,11 @@ class FundamentalEstimator(Estimator):
             return True, cands[k - 1].copy()
         return True, model
 
-    def _fit(self, init):
-        G, cnt, _ = yield (_lib.GRAM_AFFINE, None, False, 2)
-        T1, T2, prm, cnt = _hartley_from_moments(G, cnt)
-        if cnt < 8:
-            return []
-        AtA, _, _ = yield (_lib.GRAM_EPI_F, prm, True, 2)                                  # normalised 8-point rows
-        F = (self._smallest(AtA[None])[0] if self.refit_solver == "jacobi" else _smallest_eigenvector(AtA)).reshape(3, 3)
-        u, s, v = np.linalg.svd(F)
-        F = u @ np.diag([s[0], s[1], 0.0]) @ v
-        F = T2.T @ F @ T1
-        nrm = np.linalg.norm(F)
-        if not np.isfinite(nrm) or nrm == 0:
-            return []
-        return [(F / nrm).reshape(-1)]
-
     def _fit_many(self, gram, B, inits):
-        """`_fit` for B items at once (a local-optimisation round refits 50 samples, a PEARL iteration every instance: 5 200
-        eigh + svd calls were a third of findTwoViewMotions' proposal time at C3): two Gram launches, stacked eigh / svd -
-        LAPACK per matrix, so each item's model is bitwise the single-call one."""
+        """Normalised 8-point: two Gram requests (the moments for the normalisation, then the normalised epipolar rows), stacked
+        eigh / svd for the rank-2 projection - LAPACK per matrix, so an item's model does not depend on its neighbours (a
+        local-optimisation round refits 50 samples, a PEARL iteration every instance: 5 200 single eigh + svd calls were a third
+        of findTwoViewMotions' proposal time at C3)."""
         out = [[] for _ in range(B)]
         G, cnt, _ = gram(_lib.GRAM_AFFINE, None, False, 2, np.arange(B))
         rows = np.nonzero((cnt >= 8) & np.isfinite(G).all(axis=(1, 2)))[0]
@@ -977,16 +850,20 @@ class PnPEstimator(Estimator):
         o = np.argsort(src, kind="stable")
         return models[o], src[o]
 
-    def _fit(self, init):
+    def nonminimal(self, ctx, sel, weights=None, init=None):
         """Gauss-Newton on the reprojection error from `init` (PEARL and the local optimisation always have one; the
         DLT start of an un-initialised fit is not needed on this path).  Per iteration the device accumulates the
-        normal equations  sum (J,r)^T (J,r)  (rows in fit.hip GenPnpGn), the 6x6 solve and the pose update run here."""
+        normal equations  sum (J,r)^T (J,r)  (rows in fit.hip GenPnpGn, one pgx_gram call), the 6x6 solve and the pose update
+        run here."""
+        # The one refit with two statements.  This single-item one solves with lstsq and the vector forms of norm; `_fit_many`
+        # (labels, batches) solves with pinv on stacks.  The two agree to rounding only (the tests say 1e-9), and the local
+        # optimisation runs this one on the product path, so its bits stay: folding it into `_fit_many` would change results.
         if init is None:
             return []
         P = np.asarray(init, dtype=np.float64).reshape(3, 4).copy()
         R, t = P[:, :3], P[:, 3]
         for _ in range(10):
-            G, cnt, bad = yield (_lib.GRAM_PNP_GN, np.column_stack([R, t]).reshape(-1), True, 2)
+            G, cnt, bad = ctx.gram(_lib.GRAM_PNP_GN, sel, params=np.column_stack([R, t]).reshape(-1), weights=weights, wpow=2)
             if cnt < 4 or bad > 0:
                 return []
             try:
@@ -1005,11 +882,10 @@ class PnPEstimator(Estimator):
         out = np.column_stack([R, t])
         return [out.reshape(-1)] if np.isfinite(out).all() else []
 
-
     def nonminimal_batch(self, ctx, index, weights=None, init=None):
         """The local optimisation's B refits from one start: ONE pgx_pnp_refine_batch launch that runs all Gauss-Newton steps
         on the device when the context offers it (the GPU context); otherwise - the CPU oracle context of the tests - the
-        lockstep iteration of `_fit_many`, whose iterates the kernel reproduces up to rounding."""
+        stacked iteration of `_fit_many`, whose iterates the kernel reproduces up to rounding."""
         refine = getattr(ctx, "pnp_refine_batch", None)
         if refine is None or init is None:
             return super().nonminimal_batch(ctx, index, weights, init)
@@ -1020,10 +896,10 @@ class PnPEstimator(Estimator):
         return [[P[b]] if ok[b] else [] for b in range(B)]
 
     def _fit_many(self, gram, B, inits, iterations=10):
-        """`_fit` for B items at once: the same Gauss-Newton iteration with the 6x6 solves, the rotation updates and the
+        """The Gauss-Newton iteration of `nonminimal` for B items at once, with the 6x6 solves, the rotation updates and the
         convergence tests done on [B, ...] arrays - 50 refits x 10 iterations per graph-cut round were 13 us of lstsq + 15 us
         of small-array numpy each, a third of C4's proposal time.  The solve is the pseudo-inverse with lstsq's cut-off
-        (singular values below eps * 6 * s_max dropped), so an item's iterates are those of `_fit` up to rounding."""
+        (singular values below eps * 6 * s_max dropped), so an item's iterates are those of `nonminimal` up to rounding."""
         out = [[] for _ in range(B)]
         have = np.array([ini is not None for ini in inits], dtype=bool)
         if not have.any():
@@ -1069,6 +945,9 @@ class PnPEstimator(Estimator):
 
 ESTIMATORS = {
     "line": LineEstimator,
+    "plane": PlaneEstimator,
+    "sphere": SphereEstimator,
+    "circle": CircleEstimator,
     "vanishing_point": VanishingPointEstimator,
     "homography": HomographyEstimator,
     "homography_sym": SymmetricHomographyEstimator,

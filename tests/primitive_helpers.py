@@ -1,9 +1,10 @@
 """What the GPU tests of the geometric primitives (test_gpu_planes.py, test_gpu_spheres.py, test_gpu_circles.py) share: the numpy
 reference of a scoring call, its comparison, the expected output of the device's minimal solvers, and the recovery criterion of the
-end-to-end calls.  The per-type arithmetic (sq_*, dist, make_problem) stays with each test file."""
+end-to-end calls; and what their CPU tests share: one refit on numpy Gram matrices.  The per-type arithmetic (sq_*, dist,
+make_problem) stays with each test file."""
 import numpy as np
 
-from pyprogressivex import datasets, parallel
+from pyprogressivex import _lib, datasets, parallel
 
 
 def ref_score(sq_fn, pts, models, T2, comp=None):
@@ -79,3 +80,26 @@ def shuffled(pts, gen, seed=0):
     inside the first model, so the end-to-end tests put the points in a random order."""
     order = np.random.default_rng(seed).permutation(len(pts))
     return np.ascontiguousarray(pts[order]), gen[order]
+
+
+def numpy_refit(est, pts, w=None):
+    """est._fit_many with one item (B = 1) through a numpy Gram provider (the device's rows, summed in float64): the affine rows
+    (1, p), then for the round family the rows (1, q, |q|^2), q = (p - o) / s, the last entry summed left to right.  Returns
+    (models, requests), requests = the (kind, params [1, p] | None, use_weights, wpow) the refit asked for, in order."""
+    w = np.ones(len(pts)) if w is None else w
+    requests = []
+
+    def gram(kind, prm, use_w, wpow, rows):
+        assert list(rows) == [0] and (prm is None or prm.shape[0] == 1)
+        requests.append((kind, prm, use_w, wpow))
+        if kind == _lib.GRAM_AFFINE:
+            A = np.column_stack([np.ones(len(pts)), pts])
+        else:
+            q = (pts - prm[0, :-1]) / prm[0, -1]
+            sq = q[:, 0] * q[:, 0]
+            for k in range(1, q.shape[1]):
+                sq = sq + q[:, k] * q[:, k]
+            A = np.column_stack([np.ones(len(pts)), q, sq])
+        return ((A * w[:, None]).T @ A)[None], np.array([len(pts)]), np.array([0])
+    (models,) = est._fit_many(gram, 1, [None])
+    return models, requests

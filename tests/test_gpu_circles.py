@@ -342,7 +342,7 @@ def test_circle_refit_grams(gpu_ctx):
         assert np.abs(a[0] - gt[k]).max() < 0.5
     one = est.nonminimal(gpu_ctx, ("label", 1), weights=w)
     assert np.abs(one[0] - jac[1][0]).max() < 1e-10 * 1000.0
-    batch = est.nonminimal_batch(gpu_ctx, idx)               # the batched form drives the same coroutine
+    batch = est.nonminimal_batch(gpu_ctx, idx)               # the batched form runs the same statement of the refit
     assert len(batch) == 4
 
 

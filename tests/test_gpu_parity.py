@@ -1399,14 +1399,14 @@ def test_gram_batch_matches_oracle(gpu_ctx, oracle, name, B, m):
 
 
 def test_batched_refits_equal_single_refits(gpu_ctx):
-    """Estimator.nonminimal_batch (coroutines in lockstep over pgx_gram_batch) returns what nonminimal returns per
-    selection (same algebra; only the reduction tree of the Gram pass differs: 1e-9)."""
+    """Estimator.nonminimal_batch (one pgx_gram_batch launch per Gram request of the refit) returns what nonminimal (one
+    pgx_gram call per request) returns per selection (the same statement of the algebra, PnP apart; only the reduction tree
+    of the Gram pass differs: 1e-9)."""
     from pyprogressivex import _estimators
     rng = np.random.default_rng(4)
-    table = dict(_estimators.ESTIMATORS, plane=_estimators.PlaneEstimator, sphere=_estimators.SphereEstimator)
-    for name in ("line", "vanishing_point", "homography", "homography_sym", "fundamental", "pnp", "plane", "sphere"):
+    for name in ("line", "vanishing_point", "homography", "homography_sym", "fundamental", "pnp", "plane", "sphere", "circle"):
         mt, pts, models, thr = make_case(name, 4000, 1, seed=9)
-        est = table[name]()
+        est = _estimators.ESTIMATORS[name]()
         gpu_ctx.set_points(mt, pts)
         m = 7 * est.sample_size
         one = gpu_ctx.score(models[:1], 2.25 * thr * thr, want_masks=True)

@@ -171,8 +171,8 @@ def test_refits_recover_the_generating_models():
 
 
 def test_batched_refits_equal_single_refits_on_the_oracle_context():
-    # the lockstep coroutine driver (nonminimal_batch) must return exactly what per-selection refits return when both
-    # are fed by the same Gram provider
+    # nonminimal_batch (one gram_batch call per Gram request of the refit) must return exactly what per-selection refits
+    # (one gram call per request) return when both are fed by the same Gram provider; PnP's two statements agree to rounding
     from pyprogressivex import _estimators, _lib, datasets
     rng = np.random.default_rng(1)
     pts, gt, _ = datasets.make_homographies(n_per_plane=200, n_planes=2, n_outliers=50, seed=1)

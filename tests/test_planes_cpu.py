@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pyprogressivex as px
+from primitive_helpers import numpy_refit
 from pyprogressivex import _estimators, _lib, datasets
 
 
@@ -85,17 +86,12 @@ def test_plane_minimal_solver_on_hand_made_samples():
 
 
 def _drive_fit(est, pts, w=None):
+    models, requests = numpy_refit(est, pts, w)
+    assert len(requests) == 1, "the refit asked for a second Gram matrix"
+    assert requests[0][0] == _lib.GRAM_AFFINE and requests[0][2] is True
     w = np.ones(len(pts)) if w is None else w
     A = np.column_stack([np.ones(len(pts)), pts])
-    G = (A * w[:, None]).T @ A
-    gen = est._fit(None)
-    req = next(gen)
-    assert req[0] == _lib.GRAM_AFFINE and req[2] is True
-    try:
-        gen.send((G, len(pts), 0))
-    except StopIteration as done:
-        return done.value, G
-    raise AssertionError("the refit asked for a second Gram matrix")
+    return models, (A * w[:, None]).T @ A
 
 
 def test_plane_refit_recovers_a_known_plane():

@@ -1,11 +1,12 @@
-"""RoundEstimator._fit, which SphereEstimator and CircleEstimator share, against the two refit bodies it replaced, restated here as
-they were: bitwise the same models on the inputs of test_spheres_cpu.py / test_circles_cpu.py (known spheres and circles, weights,
+"""RoundEstimator._fit_many, which SphereEstimator and CircleEstimator share, with one item (B = 1) against the two single-item refit
+bodies it replaced, restated here as they were (generators that yield Gram requests): bitwise the same models on the inputs of test_spheres_cpu.py / test_circles_cpu.py (known spheres and circles, weights,
 offsets, radius ranges, too few points, coincident points, no weight), and no RuntimeWarning where the old sphere body gave one."""
 import warnings
 
 import numpy as np
 import pytest
 
+from primitive_helpers import numpy_refit
 from pyprogressivex import _estimators, _lib, datasets
 
 
@@ -67,7 +68,8 @@ def _old_circle_fit(est, init):
 
 
 def _drive(gen, pts, w):
-    """runs a refit coroutine on numpy Gram matrices: the affine rows, then the rows (1, q, |q|^2) summed left to right"""
+    """runs an old refit body on numpy Gram matrices: the affine rows, then the rows (1, q, |q|^2) summed left to right (what
+    primitive_helpers.numpy_refit feeds the shared refit)"""
     req = next(gen)
     try:
         while True:
@@ -118,7 +120,7 @@ def test_shared_round_refit_is_bitwise_the_two_old_bodies(kind, coverage):
             want = _drive(old(est, None), p, w)
         with warnings.catch_warnings():
             warnings.simplefilter("error")                   # the shared one must not
-            got = _drive(est._fit(None), p, w)
+            got, _ = numpy_refit(est, p, w)
         assert len(got) == len(want), name
         for a, b in zip(got, want):
             assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (name, a, b)

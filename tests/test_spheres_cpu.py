@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pyprogressivex as px
+from primitive_helpers import numpy_refit
 from pyprogressivex import _estimators, _lib, datasets
 
 
@@ -103,25 +104,12 @@ def test_sphere_minimal_solver_on_hand_made_samples():
 
 
 def _drive_fit(est, pts, w=None):
-    """runs the refit coroutine on numpy Gram matrices (the device's rows, summed in float64)"""
-    w = np.ones(len(pts)) if w is None else w
-    gen = est._fit(None)
-    req = next(gen)
-    kinds = []
-    try:
-        while True:
-            kind, prm, use_w, wpow = req
-            assert use_w is True and wpow == 1
-            kinds.append(kind)
-            if kind == _lib.GRAM_AFFINE:
-                A = np.column_stack([np.ones(len(pts)), pts])
-            else:
-                assert kind == _lib.GRAM_SPHERE and len(prm) == 4
-                q = (pts - prm[:3]) / prm[3]
-                A = np.column_stack([np.ones(len(pts)), q, (q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]])
-            req = gen.send(((A * w[:, None]).T @ A, len(pts), 0))
-    except StopIteration as done:
-        return done.value, kinds
+    """runs the refit on numpy Gram matrices (the device's rows, summed in float64)"""
+    models, requests = numpy_refit(est, pts, w)
+    for kind, prm, use_w, wpow in requests:
+        assert use_w is True and wpow == 1
+        assert kind == _lib.GRAM_AFFINE or (kind == _lib.GRAM_SPHERE and prm.shape == (1, 4))
+    return models, [r[0] for r in requests]
 
 
 @pytest.mark.parametrize("coverage", [1.0, 0.5])
