@@ -175,12 +175,16 @@ int pgx_score_profile(pgx_ctx *ctx, int on);
  * host version bit for bit): what = 0 sorted order (n int32), 1 group + super-group rows ((groups + supers) x 12 f32),
  * 2 / 3 the group-blocked f64 / f32 row copies, 4 the sorted f32 rows; 5 the integer accumulators of the last launch, replicas
  * summed, in the caller's hypothesis order (3 x Mpad u64: count | value | shared in 2^-q fixed point - what pgx_score_allreduce
- * adds across ranks).  bytes must match exactly. */
+ * adds across ranks); 6 the items the last launch's cull kernel put on the work lists of the group-major kernel, per [XCD g & 7][weight
+ * class] (8 x 4 u32; fails unless that launch took its items from the lists); 7 the survivor words of that cull kernel
+ * (groups x Mpad / 64 u64, the batch in device order).  bytes must match exactly. */
 int pgx_score_debug_fetch(pgx_ctx *ctx, int what, void *out, int64_t bytes);
 /* Test hook: launch geometry of the group-major score path (results must not depend on it - integer accumulation of per-pair
  * fixed point; tests/test_gpu_parity.py).  what = 0 waves per 64-point group (0 = automatic), 1 a group's waves on one XCD
  * (-1 automatic, 0, 1), 2 replicas of the accumulators (0 = automatic, else a multiple of 8), 3 candidates of 64 from which a
- * step is evaluated in place instead of queued (1..65), 4 segments of groups per hypothesis word in the cull kernel.  Not an
+ * step is evaluated in place instead of queued (1..65), 4 segments of groups per hypothesis word in the cull kernel, 5 the work lists
+ * of the group-major kernel (-1 automatic: pose problems on the one-XCD mapping, 0 never, 1 every type on that mapping; also
+ * PGX_SCORE_WORKLIST=0 / 1 at pgx_create), 6 .. 8 the three weight thresholds of the lists' four classes (1 .. 2^30).  Not an
  * environment switch: nothing in the product path calls it. */
 int pgx_score_debug_geometry(pgx_ctx *ctx, int what, int value);
 int pgx_score_kernel_times(pgx_ctx *ctx, float ms[4]);

@@ -180,6 +180,7 @@ int pgx_create(int device_id, pgx_ctx** out)
     if (const char* b = std::getenv("PGX_GC_FLIP")) ctx->route.gc_flip = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_SCORE_MIRROR")) ctx->score_sw.mirror = std::atoi(b) != 0;
     if (const char* b = std::getenv("PGX_SCORE_NO_CULL")) ctx->score_sw.cull = std::atoi(b) ? 0 : 1;
+    if (const char* b = std::getenv("PGX_SCORE_WORKLIST")) ctx->score_sw.worklist = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_NO_GROUP")) ctx->group_filter = std::atoi(b) ? 0 : 1;
     if (const char* b = std::getenv("PGX_VERIFY")) ctx->score_sw.verify = std::atoi(b) ? 1 : 0;
     if (const char* b = std::getenv("PGX_MF_TILE")) ctx->route.mf_tile = std::atoi(b) ? 1 : 0;
@@ -213,7 +214,7 @@ void pgx_destroy(pgx_ctx* ctx)
                       &ctx->masks, &ctx->g_counts, &ctx->g_values, &ctx->g_shared,
                       &ctx->red_partials, &ctx->red_out, &ctx->dq, &ctx->kmodels, &ctx->labels, &ctx->goff,
                       &ctx->gidx, &ctx->gmult, &ctx->grev, &ctx->scratch, &ctx->fit_scratch, &ctx->pts_s, &ctx->pts32_s,
-                      &ctx->pmax_s, &ctx->comp_s, &ctx->pperm, &ctx->gbounds, &ctx->masks_s, &ctx->cull_lists, &ctx->cull_counts, &ctx->gc, &ctx->gc_sel,
+                      &ctx->pmax_s, &ctx->comp_s, &ctx->pperm, &ctx->gbounds, &ctx->masks_s, &ctx->cull_lists, &ctx->cull_counts, &ctx->score_wl, &ctx->gc, &ctx->gc_sel,
                       &ctx->weights, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops};
     for (DevBuf* b : bufs) release(*b);
     for (DevBuf& b : ctx->slots) release(b);
@@ -618,6 +619,10 @@ int pgx_score_debug_geometry(pgx_ctx* ctx, int what, int value)
     case 2: if (value < 0 || value > 1024 || value % 8) break; ctx->score_sw.nrep = value; return PGX_OK;
     case 3: if (value < 1 || value > 65) break; ctx->score_sw.dense_min = value; return PGX_OK;
     case 4: if (value < 1 || value > 65535) break; ctx->score_sw.cull_segs = value; return PGX_OK;
+    case 5: if (value < -1 || value > 1) break; ctx->score_sw.worklist = value; return PGX_OK;
+    case 6: if (value < 1 || value > (1 << 30)) break; ctx->score_sw.wl_t1 = value; return PGX_OK;
+    case 7: if (value < 1 || value > (1 << 30)) break; ctx->score_sw.wl_t2 = value; return PGX_OK;
+    case 8: if (value < 1 || value > (1 << 30)) break; ctx->score_sw.wl_t3 = value; return PGX_OK;
     }
     return fail(ctx, PGX_ERR_INVALID, "pgx_score_debug_geometry: what = %d, value = %d out of range", what, value);
 }
@@ -637,9 +642,23 @@ int pgx_score_debug_fetch(pgx_ctx* ctx, int what, void* out, int64_t bytes)
         PGX_TRY(sync_deliver(ctx));
         return PGX_OK;
     }
+    if (what == 6) {   // the work lists' counts of the last launch, [8 XCDs][4 classes] u32 (score.hip score_finish_kernel keeps the copy)
+        const int64_t want = (int64_t)kWlXcds * kWlClasses * 4;
+        if (bytes != want) return fail(ctx, PGX_ERR_INVALID, "pgx_score_debug_fetch: buffer 6 holds %lld bytes, asked for %lld", (long long)want, (long long)bytes);
+        if (!ctx->batch.current() || ctx->batch.last.path != 2 || !ctx->score_wl_last || !ctx->score_wl.p)
+            return fail(ctx, PGX_ERR_INVALID, "pgx_score_debug_fetch: the last launch did not take its items from work lists");
+        std::vector<unsigned> h((size_t)kWlCountWords);
+        PGX_HIP(ctx, hipMemcpyAsync(h.data(), ctx->score_wl.p, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+        PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int k = 0; k < kWlXcds * kWlClasses; ++k) ((unsigned*)out)[k] = h[(size_t)k * kWlCountStride + 1];
+        return PGX_OK;
+    }
+    if (what == 7 && !(ctx->batch.current() && ctx->batch.last.path == 2))
+        return fail(ctx, PGX_ERR_INVALID, "pgx_score_debug_fetch: the last launch did not run the cull kernel on the resident batch");
     const DevBuf* b = nullptr;
     int64_t have = 0;
     switch (what) {
+    case 7: b = &ctx->cull_lists; have = groups * (ctx->batch.resident.Mpad / 64) * 8; break;   // keep[group][word] of the last launch's cull
     case 0: b = &ctx->pperm; have = ctx->n * 4; break;
     case 1: b = &ctx->gbounds; have = (groups + supers) * kGroupRow * 4; break;
     case 2: b = &ctx->pts_g; have = groups * 64 * ctx->D * 8; break;

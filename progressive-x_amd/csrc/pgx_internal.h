@@ -73,6 +73,9 @@ struct pgx_ctx {
     int sp_kd = 1;               // PGX_SP_KD=0: Morton order of the points of a pose problem instead of the k-d order (setpoints.hip)
     pgx::DevBuf weights_scratch; // scratch of the k-d build (64-bit keys, sort workspace, per-node extents)
     pgx::DevBuf cull_lists, cull_counts;
+    pgx::DevBuf score_wl;        // work lists of the group-major kernel (score_worklist.h): counts | 8 x 4 lists of (group, 4-word) items
+    int score_wl_last = 0;       // the last group-major launch took its items from the lists (their counts: pgx_score_debug_fetch(6))
+    int score_wl_dirty = 0;      // a launch got past its cull kernel but not to its finish kernel: the counts may not be zero
     pgx::DevBuf gc;          // inlier/outlier graph cut: e[n] | dq[2][n] | wq[E] | labels[n]
     pgx::DevBuf gc_sel;      // ... the inliers' indices (pgx_gc_inliers): index[n] | count | select scratch
 

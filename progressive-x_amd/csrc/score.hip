@@ -242,16 +242,23 @@ constexpr int kCullTile = 64;   // group bounds staged in LDS per step
 // The group bounds of a segment are staged in LDS by the whole workgroup (coalesced vector loads, one round trip per 64
 // groups) and read back as broadcasts: with scalar loads a wave paid one ~1 us scalar-cache miss per four groups, and the
 // kernel — a single generation of waves — took as long as that latency chain (43 us for 27 VALU instructions per test).
-template <int MT>
-__global__ __launch_bounds__(64 * kCullWaves) void score_cull_kernel(
+// (waves per SIMD: the budget the kernel had before it weighed items - 72 registers for the two 12-parameter filters, 64 for the rest;
+// the compiler meets it without scratch, and left alone it gives a wave away on four of the nine types)
+template <int MT> constexpr int kCullWavesPerSimd = (MT == kPnP || MT == kHomographySym) ? 7 : 8;
+// LISTS: also weigh the tile's (group, 4-word) items and append the non-empty ones to the work lists (without: the kernel as it was)
+template <int MT, bool LISTS>
+__global__ __launch_bounds__(64 * kCullWaves) __attribute__((amdgpu_waves_per_eu(kCullWavesPerSimd<MT>))) void score_cull_kernel(
     const double* __restrict__ models, int M, double T2, double guard32, const float* __restrict__ gbounds, int groups,
     int gps /* groups per segment */, int W, unsigned long long* __restrict__ keep, float* __restrict__ hyp32,
     double* __restrict__ models_t /* [P][W * 64]: component-major copy for the gathers of the group kernel */,
-    unsigned long long* __restrict__ zero /* the accumulators of the group kernel, zeroed here (one fill command less) */, int64_t zero_words)
+    unsigned long long* __restrict__ zero /* the accumulators of the group kernel, zeroed here (one fill command less) */, int64_t zero_words,
+    unsigned* __restrict__ wl /* LISTS: the work lists of the group kernel, counts | items (score_worklist.h) */, int wl_xb, unsigned wl_cap,
+    unsigned wl_t1, unsigned wl_t2, unsigned wl_t3)
 {
     using R = Residual<MT>;
     using F32 = Filter32<MT>;
     __shared__ __attribute__((aligned(16))) float s_gb[kCullTile + kCullTile / kSuper][kGroupRow];  // groups | their super-groups
+    __shared__ unsigned s_wt[kCullWaves][kCullTile];   // work lists: surviving steps per (word of this workgroup, group of the tile)
     {
         const int64_t nthreads = (int64_t)gridDim.x * gridDim.y * (64 * kCullWaves);
         for (int64_t i = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (64 * kCullWaves) + threadIdx.x; i < zero_words; i += nthreads) zero[i] = 0ull;
@@ -280,23 +287,55 @@ __global__ __launch_bounds__(64 * kCullWaves) void score_cull_kernel(
         for (int e = (int)threadIdx.x; e < scnt * kGroupRow; e += 64 * kCullWaves)
             (&s_gb[kCullTile][0])[e] = gbounds[((int64_t)groups + t0 / kSuper) * kGroupRow + e];
         __syncthreads();
-        if (w >= W) continue;
-        for (int sgi = 0; sgi < scnt; ++sgi) {
-            const int i0 = sgi * kSuper, i1 = i0 + kSuper < cnt ? i0 + kSuper : cnt;
-            float sr[kGroupRow];
+        unsigned steps = 0;   // work lists: lane i holds the surviving steps of (this wave's word, group t0 + i)
+        if (w < W)
+            for (int sgi = 0; sgi < scnt; ++sgi) {
+                const int i0 = sgi * kSuper, i1 = i0 + kSuper < cnt ? i0 + kSuper : cnt;
+                float sr[kGroupRow];
 #pragma unroll
-            for (int k = 0; k < F32::kGroupVals; ++k) sr[k] = s_gb[kCullTile + sgi][k];  // same address in every lane: LDS broadcast
-            if (__ballot(live && !F32::group_reject(sr, flane32, Tup32)) == 0) {  // no hypothesis of the word reaches these 512 points
-                if (lane < i1 - i0) keep[(int64_t)(t0 + i0 + lane) * W + w] = 0;
-                continue;
-            }
-            for (int i = i0; i < i1; ++i) {
-                float gr[kGroupRow];
+                for (int k = 0; k < F32::kGroupVals; ++k) sr[k] = s_gb[kCullTile + sgi][k];  // same address in every lane: LDS broadcast
+                if (__ballot(live && !F32::group_reject(sr, flane32, Tup32)) == 0) {  // no hypothesis of the word reaches these 512 points
+                    if (lane < i1 - i0) keep[(int64_t)(t0 + i0 + lane) * W + w] = 0;
+                    continue;
+                }
+                for (int i = i0; i < i1; ++i) {
+                    float gr[kGroupRow];
 #pragma unroll
-                for (int k = 0; k < F32::kGroupVals; ++k) gr[k] = s_gb[i][k];
-                const unsigned long long bm = __ballot(live && !F32::group_reject(gr, flane32, Tup32));
-                if (lane == 0) keep[(int64_t)(t0 + i) * W + w] = bm;
+                    for (int k = 0; k < F32::kGroupVals; ++k) gr[k] = s_gb[i][k];
+                    const unsigned long long bm = __ballot(live && !F32::group_reject(gr, flane32, Tup32));
+                    if (lane == 0) keep[(int64_t)(t0 + i) * W + w] = bm;
+                    if (LISTS) steps = lane == i ? (unsigned)__popcll(bm) : steps;
+                }
             }
+        if (!LISTS) continue;
+        // ---- the tile's items (group t0 + i, this workgroup's words) onto the work lists: lane i of the first wave weighs item i -
+        // the surviving steps of its live words - and the non-empty ones are appended to list [g & 7][class of the weight].  One
+        // returning atomic per (XCD, class) pair that occurs in the tile: lanes with equal lane & 7 have equal g & 7, so the pair's
+        // lanes are the class' ballot under one byte-lane mask; positions inside the pair's block follow from the lanes below.
+        s_wt[threadIdx.x >> 6][lane] = steps;
+        __syncthreads();
+        if (threadIdx.x >= 64) continue;
+        const int nlive = W - (int)blockIdx.x * kCullWaves < kCullWaves ? W - (int)blockIdx.x * kCullWaves : kCullWaves;
+        unsigned wt = 0;
+        if (lane < cnt)
+            for (int v = 0; v < nlive; ++v) wt += s_wt[v][lane];
+        const int cls = wt != 0 ? wl_class(wt, wl_t1, wl_t2, wl_t3) : -1;
+        unsigned long long mine = 0;   // the lanes of this lane's (XCD, class) pair
+#pragma unroll
+        for (int c = 0; c < kWlClasses; ++c) {
+            const unsigned long long bc = __ballot(cls == c);
+            if (cls == c) mine = bc & (0x0101010101010101ull << (lane & 7));
+        }
+        const int first = cls >= 0 ? __builtin_ctzll(mine) : lane;
+        const unsigned g = (unsigned)(t0 + lane);
+        const int list = (int)(g & 7u) * kWlClasses + (cls >= 0 ? cls : 0);
+        unsigned base = 0;
+        if (cls >= 0 && lane == first) base = atomicAdd(&wl[list * kWlCountStride], (unsigned)__popcll(mine));
+        base = (unsigned)__shfl((int)base, first, 64);
+        if (cls >= 0) {
+            const unsigned pos = base + __builtin_amdgcn_mbcnt_hi((unsigned)(mine >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mine, 0u));
+            if (pos < wl_cap)   // (always: a list holds every item of its XCD's groups, and the counts start from zero)
+                wl[kWlCountWords + (size_t)list * wl_cap + pos] = wl_item(g, blockIdx.x, wl_xb);
         }
     }
 }
@@ -319,9 +358,14 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
     int Mpad, unsigned long long* __restrict__ masks, int64_t words, const int* __restrict__ perm, int split, int xcd_local, const double* __restrict__ models_t,
     unsigned long long* __restrict__ stats /* STATS: [0] surviving (hypothesis, group) steps, [1] exact evaluations, [2] inlier pairs */,
     const double* __restrict__ pts_g /* [groups][D][64]: group-blocked SoA copy of the rows (nullptr: AoS) */,
-    const float* __restrict__ p32_g /* [groups][8][64] */, int nrep, int dense_min)
+    const float* __restrict__ p32_g /* [groups][8][64] */, int nrep, int dense_min,
+    const unsigned* __restrict__ wl /* the cull kernel's work lists (score_worklist.h), or nullptr: (group, part) from the workgroup id */,
+    int wl_xb, unsigned wl_cap)
 {
     // split: waves per group, each takes every split-th word of 64 hypotheses (shorter waves: better tail)
+    // Work lists: workgroup b takes item b >> 3 of the lists of XCD b & 7 instead, the heaviest class first - a group and 4 adjacent
+    // words - and walks exactly the non-empty words the parts would have walked: the same steps, the same integers.  The grid is the
+    // lists' worst case; a workgroup past its XCD's total leaves after four scalar loads, and those come last in dispatch order.
     using R = Residual<MT>;
     using F32 = Filter32<MT>;
     using LaneT = typename F32::Lane;
@@ -333,23 +377,40 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
     // group's workgroups on one XCD (FETCH_SIZE 165 -> 45 MiB but 0.51 ms); one wave per workgroup with 8 parts per
     // group: 0.28 ms (16 parts: 250 k workgroups, the dispatcher limits at ~1.3 ns per workgroup).
     const int wv = 0;
-    int g, part;
-    if (xcd_local) {  // workgroup ids go round-robin over the 8 XCDs: all parts of a group on one XCD (its L2 fetches the rows once)
-        const int slot = (int)(blockIdx.x >> 3);
-        g = (slot / split) * 8 + (int)(blockIdx.x & 7u);
-        part = slot % split;
-        if (g >= groups) return;
+    int g, w0, w1 = W, wstep = 1;   // this wave's words of group g: w0, w0 + wstep, ... below w1
+    if (wl != nullptr) {
+        const int xcd = (int)(blockIdx.x & 7u);
+        unsigned lc[kWlClasses];
+#pragma unroll
+        for (int c = 0; c < kWlClasses; ++c) lc[c] = wl[wl_count_index(xcd, c)];   // wave-uniform -> scalar loads
+        int cls;
+        unsigned pos;
+        if (!wl_locate(lc[0], lc[1], lc[2], lc[3], blockIdx.x >> 3, &cls, &pos)) return;   // past this XCD's lists
+        if (pos >= wl_cap) return;            // (never: a list holds at most its XCD's items)
+        const unsigned item = wl[kWlCountWords + (size_t)(xcd * kWlClasses + cls) * wl_cap + pos];
+        if (wl_item_group(item, wl_xb) >= (unsigned)groups || wl_item_column(item, wl_xb) * kWlItemWords >= (unsigned)W) return;   // (never either)
+        g = (int)wl_item_group(item, wl_xb);
+        w0 = (int)wl_item_column(item, wl_xb) * kWlItemWords;
+        w1 = w0 + kWlItemWords < W ? w0 + kWlItemWords : W;
     } else {
-        g = (int)blockIdx.x / split;
-        part = (int)blockIdx.x % split;
-    }
-    g = __builtin_amdgcn_readfirstlane(g);
-    part = __builtin_amdgcn_readfirstlane(part);
-    {   // nothing survived the cull for this wave's hypotheses: leave before the point rows are requested
+        if (xcd_local) {  // workgroup ids go round-robin over the 8 XCDs: all parts of a group on one XCD (its L2 fetches the rows once)
+            const int slot = (int)(blockIdx.x >> 3);
+            g = (slot / split) * 8 + (int)(blockIdx.x & 7u);
+            w0 = slot % split;
+            if (g >= groups) return;
+        } else {
+            g = (int)blockIdx.x / split;
+            w0 = (int)blockIdx.x % split;
+        }
+        wstep = split;
+        // nothing survived the cull for this wave's hypotheses: leave before the point rows are requested (a listed item has survivors)
         unsigned long long any = 0;
-        for (int w = part; w < W; w += split) any |= keep[(int64_t)g * W + w];
+        for (int w = w0; w < W; w += split) any |= keep[(int64_t)g * W + w];
         if (any == 0) return;
     }
+    g = __builtin_amdgcn_readfirstlane(g);
+    w0 = __builtin_amdgcn_readfirstlane(w0);
+    w1 = __builtin_amdgcn_readfirstlane(w1);
     const int64_t j = (int64_t)g * 64 + lane;
     const bool valid = j < n;
     const int64_t jj = valid ? j : n - 1;
@@ -506,7 +567,7 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
             if (MASK) masks[(int64_t)perm[m] * words + g] = bm;  // rows start zeroed
         }
     };
-    for (int w = part; w < W; w += split) {
+    for (int w = w0; w < w1; w += wstep) {
         unsigned long long todo = keep[(int64_t)g * W + w];  // wave-uniform -> scalar load
         if (todo == 0) continue;
         if (STATS) st_steps += (unsigned long long)__popcll(todo);
@@ -620,8 +681,15 @@ __global__ __launch_bounds__(64) void score_verify_kernel(const double* __restri
 __global__ __launch_bounds__(256) void score_finish_kernel(const unsigned long long* __restrict__ acc, int M, int Mpad, double qscale,
                                                            const int* __restrict__ perm, long long* __restrict__ counts,
                                                            double* __restrict__ values, double* __restrict__ shared, int nrep,
-                                                           long long* __restrict__ mirror /* pinned host memory or nullptr */)
+                                                           long long* __restrict__ mirror /* pinned host memory or nullptr */,
+                                                           unsigned* __restrict__ wl /* the work lists' counts or nullptr */)
 {
+    // the work lists' counts back to zero for the next launch's cull kernel: nothing reads them after the group kernel (a copy stays
+    // in the next word of each count's line for pgx_score_debug_fetch(6))
+    if (wl != nullptr && blockIdx.x == 0 && threadIdx.x < kWlXcds * kWlClasses) {
+        wl[threadIdx.x * kWlCountStride + 1] = wl[threadIdx.x * kWlCountStride];
+        wl[threadIdx.x * kWlCountStride] = 0u;
+    }
     const int m = (int)(blockIdx.x * 256 + threadIdx.x);
     if (m >= M) return;
     const int o = perm[m];  // hypotheses were scored in locality order: results go back to the caller's order
@@ -790,19 +858,34 @@ static int score_group_path(pgx_ctx* ctx, const ScorePlan& pl, double T2, int ha
         PGX_TRY(grow_pinned(ctx, ctx->h_mirror, need, hipHostMallocMapped | hipHostMallocCoherent));
         mirror = (long long*)ctx->h_mirror.p;
     }
+    // The work lists: counts | 8 x 4 lists of wl_cap items.  The counts are zero whenever a cull kernel starts: zeroed when the buffer is
+    // allocated, put back to zero by every finish kernel, and cleared here after a launch that did not get as far as its finish kernel.
+    unsigned* wl = nullptr;
+    if (pl.worklist) {
+        const void* before = ctx->score_wl.p;
+        PGX_TRY(ensure(ctx, ctx->score_wl, ((size_t)kWlCountWords + (size_t)kWlXcds * kWlClasses * pl.wl_cap) * sizeof(unsigned)));
+        if (ctx->score_wl.p != before || ctx->score_wl_dirty) PGX_HIP(ctx, hipMemsetAsync(ctx->score_wl.p, 0, kWlCountWords * sizeof(unsigned), ctx->stream));
+        ctx->score_wl_dirty = 1;   // until the finish kernel is enqueued
+        wl = ctx->score_wl.as<unsigned>();
+    }
     if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[0], ctx->stream));
     // (the accumulators are zeroed by the cull kernel, which runs before their first use)
-    hipLaunchKernelGGL((score_cull_kernel<MT>), dim3((unsigned)((W + kCullWaves - 1) / kCullWaves), pl.cull_segs), dim3(64 * kCullWaves), 0,
-                       ctx->stream, ctx->models.as<double>(), M, T2, pl.guard32, ctx->gbounds.as<float>(), groups, pl.gps, W,
-                       ctx->cull_lists.as<unsigned long long>(), hyp32, models_t, acc, pl.zero_words);
+    auto cull_launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((W + kCullWaves - 1) / kCullWaves), pl.cull_segs), dim3(64 * kCullWaves), 0,
+                           ctx->stream, ctx->models.as<double>(), M, T2, pl.guard32, ctx->gbounds.as<float>(), groups, pl.gps, W,
+                           ctx->cull_lists.as<unsigned long long>(), hyp32, models_t, acc, pl.zero_words, wl, pl.wl_xbits, pl.wl_cap, pl.wl_t[0],
+                           pl.wl_t[1], pl.wl_t[2]);
+    };
+    if (pl.worklist) cull_launch(score_cull_kernel<MT, true>);
+    else cull_launch(score_cull_kernel<MT, false>);
     PGX_HIP(ctx, hipGetLastError());
     if (ctx->score_profile) PGX_HIP(ctx, hipEventRecord(ctx->kev[1], ctx->stream));
     auto group_launch = [&](auto kernel, unsigned long long* masks_s) {
-        hipLaunchKernelGGL(kernel, dim3(pl.gblocks), dim3(64 * kGroupWaves), 0, ctx->stream,
+        hipLaunchKernelGGL(kernel, dim3(pl.worklist ? pl.wl_grid : pl.gblocks), dim3(64 * kGroupWaves), 0, ctx->stream,
                            ctx->pts_s.as<double>(), ctx->pts32_s.as<float>(), ctx->comp_s.as<double>(), ctx->n, groups,
                            ctx->models.as<double>(), W, T2, has_compound, ctx->cull_lists.as<unsigned long long>(), hyp32,
                            pl.qscale, acc, Mpad, masks_s, pl.words, ctx->perm.as<int>(), split, xcd_local, models_t,
-                           stats, pts_g, p32_g, nrep, pl.dense_min);
+                           stats, pts_g, p32_g, nrep, pl.dense_min, (const unsigned*)wl, pl.wl_xbits, pl.wl_cap);
     };
     if (want_masks) {
         PGX_HIP(ctx, hipMemsetAsync(ctx->masks_s.p, 0, (size_t)M * (size_t)pl.words * sizeof(uint64_t), ctx->stream));
@@ -822,8 +905,10 @@ static int score_group_path(pgx_ctx* ctx, const ScorePlan& pl, double T2, int ha
     if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[4], ctx->stream));
     hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, acc, M,
                        Mpad, pl.qscale, ctx->perm.as<int>(), ctx->counts.as<long long>(), ctx->values.as<double>(),
-                       ctx->shared.as<double>(), nrep, mirror);
+                       ctx->shared.as<double>(), nrep, mirror, wl);
     PGX_HIP(ctx, hipGetLastError());
+    ctx->score_wl_dirty = 0;
+    ctx->score_wl_last = pl.worklist ? 1 : 0;
     if (ctx->score_profile >= 2) PGX_HIP(ctx, hipEventRecord(ctx->kev[3], ctx->stream));
     *acc_out = acc;
     return PGX_OK;

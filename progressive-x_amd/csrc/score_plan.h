@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "score_worklist.h"
+
 namespace pgx {
 
 // What the group bound of the sorted points is made of (setpoints.hip builds the rows, score.hip's cull kernel tests them).
@@ -23,6 +25,8 @@ constexpr int kScoreBlocksPerCu = 64;   // grid over-decomposition of the chunke
 constexpr int kScoreXcdMap = 1;         // XCD-aware block mapping of the chunked kernel (no switch sets it)
 constexpr int kScoreMaxChunk = 65472;   // queue entries of the deferred kernel are 16-bit offsets into the chunk
 constexpr int kScoreMaxChunks = 65535;  // gridDim.y limit
+constexpr int kScoreCullSegs = 256;     // the cull kernel's segments per hypothesis word unless pgx_score_debug_geometry(4) says otherwise
+constexpr int64_t kWlMaxItems = (int64_t)1 << 22;   // (group, item column) pairs beyond which the work lists are not built (16 bytes each)
 
 // What the planner needs to know of a model type (score.hip score_traits<MT>() fills it from Residual / Filter / Filter32).
 struct ScoreTraits {
@@ -44,7 +48,11 @@ struct ScoreSwitches {
                              // waves share an XCD, else 1
     int dense_min{32};       // pgx_score_debug_geometry(3): steps with at least this many candidates of 64 are evaluated in place, not
                              // queued (65 = never)
-    int cull_segs{256};      // pgx_score_debug_geometry(4): segments of groups per hypothesis word in the cull kernel
+    int cull_segs{kScoreCullSegs};   // pgx_score_debug_geometry(4): segments of groups per hypothesis word in the cull kernel
+    int worklist{-1};        // pgx_create, PGX_SCORE_WORKLIST=0 | 1 and pgx_score_debug_geometry(5): the group-major kernel takes (group, 4-word)
+                             // items from the cull kernel's work lists; -1 = automatic (pose problems on the co-located mapping), 0 = never,
+                             // 1 = on the co-located mapping for every model type (A/B)
+    int wl_t1{24}, wl_t2{64}, wl_t3{160};   // pgx_score_debug_geometry(6 .. 8): weight thresholds of the four classes (t2 = t3 = 2^30: two classes)
 };
 
 struct ScorePlan {
@@ -69,6 +77,13 @@ struct ScorePlan {
     bool counters = false;     // the group-major instance with work counters (pgx_score_stats)
     bool verify = false;       // ... followed by the exhaustive verification kernel
     bool mirror = false;       // the finish kernel also writes the triples to the host mirror
+    // the work lists (score_worklist.h); all 0 when off: split and gblocks above then describe the launch
+    bool worklist = false;     // the cull kernel appends the non-empty (group, 4-word) items, the group kernel takes them heaviest first
+    int wl_columns = 0;        // items per group: ceil(W / kWlItemWords)
+    int wl_xbits = 0;          // bits of the item column in an item record
+    unsigned wl_cap = 0;       // capacity of each of the 8 x 4 lists: its worst case, every item of the XCD's groups (no overflow path)
+    unsigned wl_t[3] = {0, 0, 0};   // class thresholds
+    unsigned wl_grid = 0;      // workgroups of the group kernel: 8 * wl_cap, slot b >> 3 of XCD b & 7
 };
 
 // The floating-point expressions keep the operation order they always had: guard, guard32 and qscale are compared by their bits.
@@ -165,6 +180,21 @@ inline ScorePlan plan_score(const ScoreTraits& tr, const ScoreSwitches& sw, int 
     p.counters = want_counters && !want_masks;   // pgx_score_stats: the same launch with work counters (never timed)
     p.verify = p.counters && sw.verify;
     p.mirror = sw.mirror && !want_masks;
+    // ---- the work lists.  On for pose problems on the co-located mapping (the step bench.py measures: group kernel, tail and sweep in
+    // docs/lab-notebook.md, "A heavy-first work list"); the other types keep the strided parts until somebody measures them
+    // (sw.worklist = 1 is the switch for that).  Off whenever a debug switch asks for a geometry of its own (split, cull_segs; a forced
+    // spread mapping is not co-located), and for the mask-producing launch, which evaluates every step in place and was not measured.
+    const int columns = (p.W + kWlItemWords - 1) / kWlItemWords;
+    const int64_t cap = (int64_t)((p.groups + kWlXcds - 1) / kWlXcds) * columns;
+    if (p.group_xcd && sw.split == 0 && sw.cull_segs == kScoreCullSegs && !want_masks && (sw.worklist == 1 || (sw.worklist < 0 && pose)) &&
+        wl_fits(p.groups, columns) && (int64_t)p.groups * columns <= kWlMaxItems) {
+        p.worklist = true;
+        p.wl_columns = columns;
+        p.wl_xbits = wl_xbits(columns);
+        p.wl_cap = (unsigned)cap;
+        p.wl_t[0] = (unsigned)sw.wl_t1; p.wl_t[1] = (unsigned)sw.wl_t2; p.wl_t[2] = (unsigned)sw.wl_t3;
+        p.wl_grid = (unsigned)kWlXcds * p.wl_cap;
+    }
     return p;
 }
 

@@ -382,10 +382,27 @@ class Context:
         return out
 
     def score_debug_geometry(self, **kw):
-        """pgx_score_debug_geometry (test hook): split=, group_xcd=, nrep=, dense_min=, cull_segs="""
-        keys = {"split": 0, "group_xcd": 1, "nrep": 2, "dense_min": 3, "cull_segs": 4}
+        """pgx_score_debug_geometry (test hook): split=, group_xcd=, nrep=, dense_min=, cull_segs=, worklist= (-1 automatic | 0 | 1),
+        wl_t1=, wl_t2=, wl_t3= (class thresholds of the work lists)"""
+        keys = {"split": 0, "group_xcd": 1, "nrep": 2, "dense_min": 3, "cull_segs": 4, "worklist": 5, "wl_t1": 6, "wl_t2": 7, "wl_t3": 8}
         for k, v in kw.items():
             self._ck(self._lib.pgx_score_debug_geometry(self._h, C.c_int(keys[k]), C.c_int(int(v))), "pgx_score_debug_geometry")
+
+    def score_keep_words(self, Mpad):
+        """pgx_score_debug_fetch(7): the survivor words the last launch's cull kernel wrote, uint64 [groups, Mpad / 64] (bit h of word w:
+        hypothesis 64 w + h of the batch in device order may have inliers in the group)"""
+        out = np.empty(((self.n + 63) // 64, Mpad // 64), dtype=np.uint64)
+        self._ck(self._lib.pgx_score_debug_fetch(self._h, C.c_int(7), out.ctypes.data_as(C.c_void_p), C.c_int64(out.nbytes)),
+                 "pgx_score_debug_fetch")
+        return out
+
+    def score_worklist_counts(self):
+        """pgx_score_debug_fetch(6): items per [XCD g & 7][weight class] the last launch's cull kernel put on the work lists, uint32 [8, 4]
+        (PgxError if that launch did not take its items from the lists)"""
+        out = np.empty((8, 4), dtype=np.uint32)
+        self._ck(self._lib.pgx_score_debug_fetch(self._h, C.c_int(6), out.ctypes.data_as(C.c_void_p), C.c_int64(out.nbytes)),
+                 "pgx_score_debug_fetch")
+        return out
 
     def score_profile(self, on=1):
         """0 off; 1 = HIP events around the dominant scoring kernel only; 2 (or True) = around every kernel of a launch"""

@@ -6,7 +6,7 @@ import numpy as np
 from pyprogressivex import _lib, datasets
 
 # arguments: plain integers = waves per group of score_group_kernel; key=value sets any geometry knob of pgx_score_debug_geometry
-# for that run (e.g. "transposed=1,tsplit=3,dense_min=24")
+# for that run and the runs after it (e.g. "dense_min=24", "worklist=0", "wl_t1=16,wl_t2=48,wl_t3=128")
 splits = [a for a in sys.argv[1:]] or ["0"]
 x1, x2, K, lab, gt = datasets.make_poses(n_per_object=50000, n_objects=16, n_outliers=200000, seed=0)
 pts, f = datasets.normalize_pnp(x1, x2, K)
