@@ -11,12 +11,15 @@
 //                                       upstream: null space of the 7x9 epipolar system by Gauss-Jordan elimination with
 //                                       full pivoting, det(l F1 + (1-l) F2) = 0 as a cubic, real roots by bisection of
 //                                       one root + the quadratic factor (only + - * / sqrt: identical on CPU and GPU),
-//                                       up to three models per sample (three slots, NaN = no root)
+//                                       where det(F1 - F2) vanishes F1 - F2 itself follows the finite roots (the chart's root at
+//                                       infinity); up to three models per sample (three slots, NaN = no root)
 //   homography from 4 correspondences   DefaultHomographyEstimator's minimal solver (progressivex_python.cpp:252), absent
 //                                       upstream: h33 = 1, the 8x8 DLT system of the isotropically scaled points by
 //                                       Gaussian elimination with partial pivoting (rank test 1e-12), scaling undone
 //   absolute pose from 3 points (P3P)   DefaultPnPEstimator's minimal solver (progressivex_python.cpp:119), absent upstream:
-//                                       Grunert's quartic, positive real roots by bisection between the critical points,
+//                                       Grunert's quartic, positive real roots by bisection between the critical points (a
+//                                       critical point itself where the quartic touches zero), u = s2/s1 from the linear formula
+//                                       or, where that fails its gates (two poses sharing v), from the first side constraint;
 //                                       pose from the orthonormal frames of the two congruent triangles; four slots
 //   3-D plane through three points      findPlanes' minimal solver (no reference counterpart; the flat family with the line): n =
 //                                       (p1 - p0) x (p2 - p0) in cross3's component order, ln = sqrt(n . n), (a, b, c) = n / ln,
@@ -206,11 +209,67 @@ __device__ void cubic_roots(double a, double b, double c, double *r)
 
 __device__ double quartic_eval(const double *m, double x) { return (((x + m[3]) * x + m[2]) * x + m[1]) * x + m[0]; }
 
+__device__ __forceinline__ bool p3p_change(double a, double b) { return (a < 0.0 && b >= 0.0) || (a >= 0.0 && b < 0.0); }
+
+/* the gates of one (u, v) at s1: positive finite depths and the two unused side constraints to 1e-6.  Returns 1 and writes the
+ * depths and |e2|, or 0. */
+__device__ int p3p_gate(double u, double v, double s1, double cg, double ca, double c2, double a2, double *dep, double *e2abs)
+{
+    const double s2 = u * s1, s3 = v * s1;
+    if (!(s1 > 0.0) || !(s2 > 0.0) || !(s3 > 0.0) || !(s1 < 1e300) || !(s2 < 1e300) || !(s3 < 1e300)) return 0;
+    const double e1 = s1 * s1 + s2 * s2 - 2.0 * s1 * s2 * cg - c2;
+    const double e2 = s2 * s2 + s3 * s3 - 2.0 * s2 * s3 * ca - a2;
+    if (!(fabs(e1) < 1e-6 * c2) || !(fabs(e2) < 1e-6 * a2)) return 0;
+    dep[0] = s1; dep[1] = s2; dep[2] = s3;
+    *e2abs = fabs(e2);
+    return 1;
+}
+
+/* the pose of one depth triple: camera-frame points and the two orthonormal frames, R = EY^T EX, t = Y0 - R X0.  Returns 1 and
+ * writes P (12, [R|t] row-major); 0 and P = NaN on a degenerate frame or a non-finite entry. */
+__device__ int p3p_pose(double f[3][3], double X[3][3], const double *dep, double *P)
+{
+    double Y[3][3];
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) Y[r][k] = f[r][k] * dep[r];
+    double EX[3][3], EY[3][3];
+    for (int w = 0; w < 2; ++w) {
+        double (*Q)[3] = w == 0 ? X : Y;
+        double (*E)[3] = w == 0 ? EX : EY;
+        double p1[3], p2[3];
+        for (int k = 0; k < 3; ++k) { p1[k] = Q[1][k] - Q[0][k]; p2[k] = Q[2][k] - Q[0][k]; }
+        const double n1 = sqrt(p1[0] * p1[0] + p1[1] * p1[1] + p1[2] * p1[2]);
+        if (!(n1 > 0.0)) return 0;
+        for (int k = 0; k < 3; ++k) E[0][k] = p1[k] / n1;
+        double cr[3] = {E[0][1] * p2[2] - E[0][2] * p2[1], E[0][2] * p2[0] - E[0][0] * p2[2], E[0][0] * p2[1] - E[0][1] * p2[0]};
+        const double n3 = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
+        if (!(n3 > 0.0)) return 0;
+        for (int k = 0; k < 3; ++k) E[2][k] = cr[k] / n3;
+        E[1][0] = E[2][1] * E[0][2] - E[2][2] * E[0][1];
+        E[1][1] = E[2][2] * E[0][0] - E[2][0] * E[0][2];
+        E[1][2] = E[2][0] * E[0][1] - E[2][1] * E[0][0];
+    }
+    double R[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = EY[0][i] * EX[0][j] + EY[1][i] * EX[1][j] + EY[2][i] * EX[2][j];
+    int fin = 1;
+    for (int i = 0; i < 3; ++i) {
+        const double t = Y[0][i] - (R[i][0] * X[0][0] + R[i][1] * X[0][1] + R[i][2] * X[0][2]);
+        if (!(fabs(t) < 1e300)) fin = 0;
+        for (int j = 0; j < 3; ++j) { if (!(fabs(R[i][j]) < 1e300)) fin = 0; P[4 * i + j] = R[i][j]; }
+        P[4 * i + 3] = t;
+    }
+    if (!fin) for (int k = 0; k < 12; ++k) P[k] = __builtin_nan("");
+    return fin;
+}
+
 /* P3P (Grunert's quartic in v = s3/s1 as in Fischler-Bolles; DefaultPnPEstimator's minimal solver is absent upstream):
  * rows (u, v, X, Y, Z) in normalised image coordinates; positive real roots of the quartic by bisection between the
- * critical points (roots of the derivative cubic) inside (0, Cauchy bound); depths from the two remaining constraints
- * (consistency 1e-6); pose from the orthonormal frames of the two congruent triangles.  out = 4 slots x 12 ([R|t]
- * row-major), NaN = no solution. */
+ * critical points (roots of the derivative cubic) inside (0, Cauchy bound), and a critical point itself where the quartic
+ * vanishes to its evaluation error without a sign change on either side (a double root); u = s2/s1 from the linear combination
+ * of the constraints, or - where that fails its gates, as it does when two poses share v (0 / 0) - from the quadratic
+ * u^2 - 2 cg u + 1 - c2 / s1^2 = 0: at a simple root the u with the smaller |e2|, at a double root both; gates: positive depths,
+ * the two unused side constraints to 1e-6; pose from the orthonormal frames of the two congruent triangles.
+ * out = 4 slots x 12 ([R|t] row-major) in ascending v, NaN = no solution. */
 __device__ void solve_p3p(const double *pts, int64_t n, const int32_t *smp, double *out)
 {
     for (int k = 0; k < 48; ++k) out[k] = __builtin_nan("");
@@ -257,64 +316,54 @@ __device__ void solve_p3p(const double *pts, int64_t n, const int32_t *smp, doub
     }
     bp[nb++] = B;
     int slot = 0;
-    for (int s = 0; s + 1 < nb && slot < 4; ++s) {
-        double lo = bp[s], hi = bp[s + 1];
-        const double plo = quartic_eval(m, lo), phi = quartic_eval(m, hi);
-        if (!((plo < 0.0 && phi >= 0.0) || (plo >= 0.0 && phi < 0.0))) continue;
-        const int rising = plo < 0.0;
-        for (int it = 0; it < 200; ++it) {
-            const double mid = 0.5 * (lo + hi);
-            const bool last = mid == lo || mid == hi;   // (see cubic_roots: the state is a fixed point after this update)
-            const double pv = quartic_eval(m, mid);
-            if ((pv < 0.0) == rising) lo = mid; else hi = mid;
-            if (last) break;
+    /* candidates in ascending order: even c = the interval (bp[c/2], bp[c/2 + 1]), odd c = the critical point between two intervals */
+    for (int c = 0; c <= 2 * (nb - 2) && slot < 4; ++c) {
+        const int s = c >> 1, dbl = c & 1;
+        double v;
+        if (!dbl) {
+            double lo = bp[s], hi = bp[s + 1];
+            const double plo = quartic_eval(m, lo), phi = quartic_eval(m, hi);
+            if (!p3p_change(plo, phi)) continue;
+            const int rising = plo < 0.0;
+            for (int it = 0; it < 200; ++it) {
+                const double mid = 0.5 * (lo + hi);
+                const bool last = mid == lo || mid == hi;   // (see cubic_roots: the state is a fixed point after this update)
+                const double pv = quartic_eval(m, mid);
+                if ((pv < 0.0) == rising) lo = mid; else hi = mid;
+                if (last) break;
+            }
+            v = 0.5 * (lo + hi);
+        } else {
+            /* a double root has no sign change on either side: the critical point counts as a root where |p| is within the
+             * evaluation error of Horner's rule there, 16 eps (((v + |m3|) v + |m2|) v + |m1|) v + |m0|) */
+            v = bp[s + 1];
+            const double pl = quartic_eval(m, bp[s]), pv = quartic_eval(m, v), pr = quartic_eval(m, bp[s + 2]);
+            if (p3p_change(pl, pv) || p3p_change(pv, pr)) continue;
+            const double bound = 0x1p-48 * ((((v + fabs(m[3])) * v + fabs(m[2])) * v + fabs(m[1])) * v + fabs(m[0]));
+            if (!(fabs(pv) <= bound)) continue;
         }
-        const double v = 0.5 * (lo + hi);
         if (!(v > 0.0)) continue;
-        const double den = 2.0 * (cg - v * ca);
-        const double u = ((-1.0 + q) * v * v - 2.0 * q * cb * v + 1.0 + q) / den;
         const double s1 = sqrt(b2 / (1.0 + v * v - 2.0 * v * cb));
-        const double s2 = u * s1, s3 = v * s1;
-        if (!(s1 > 0.0) || !(s2 > 0.0) || !(s3 > 0.0) || !(s1 < 1e300) || !(s2 < 1e300) || !(s3 < 1e300)) continue;
-        const double e1 = s1 * s1 + s2 * s2 - 2.0 * s1 * s2 * cg - c2;
-        const double e2 = s2 * s2 + s3 * s3 - 2.0 * s2 * s3 * ca - a2;
-        if (!(fabs(e1) < 1e-6 * c2) || !(fabs(e2) < 1e-6 * a2)) continue;
-        /* camera-frame points and the two orthonormal frames */
-        const double dep[3] = {s1, s2, s3};
-        double Y[3][3];
-        for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) Y[r][k] = f[r][k] * dep[r];
-        double EX[3][3], EY[3][3];
-        int okf = 1;
-        for (int w = 0; w < 2; ++w) {
-            double (*P)[3] = w == 0 ? X : Y;
-            double (*E)[3] = w == 0 ? EX : EY;
-            double p1[3], p2[3];
-            for (int k = 0; k < 3; ++k) { p1[k] = P[1][k] - P[0][k]; p2[k] = P[2][k] - P[0][k]; }
-            const double n1 = sqrt(p1[0] * p1[0] + p1[1] * p1[1] + p1[2] * p1[2]);
-            if (!(n1 > 0.0)) { okf = 0; break; }
-            for (int k = 0; k < 3; ++k) E[0][k] = p1[k] / n1;
-            double cr[3] = {E[0][1] * p2[2] - E[0][2] * p2[1], E[0][2] * p2[0] - E[0][0] * p2[2], E[0][0] * p2[1] - E[0][1] * p2[0]};
-            const double n3 = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
-            if (!(n3 > 0.0)) { okf = 0; break; }
-            for (int k = 0; k < 3; ++k) E[2][k] = cr[k] / n3;
-            E[1][0] = E[2][1] * E[0][2] - E[2][2] * E[0][1];
-            E[1][1] = E[2][2] * E[0][0] - E[2][0] * E[0][2];
-            E[1][2] = E[2][0] * E[0][1] - E[2][1] * E[0][0];
+        double da[3], db[3], ea = 0.0, eb = 0.0;
+        int oka = 0, okb = 0;
+        if (!dbl) {     /* u from the linear combination of the constraints (0 / 0 where two poses share v) */
+            const double den = 2.0 * (cg - v * ca);
+            const double u = ((-1.0 + q) * v * v - 2.0 * q * cb * v + 1.0 + q) / den;
+            oka = p3p_gate(u, v, s1, cg, ca, c2, a2, da, &ea);
         }
-        if (!okf) continue;
-        double *P = out + 12 * slot;
-        double R[3][3];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) R[i][j] = EY[0][i] * EX[0][j] + EY[1][i] * EX[1][j] + EY[2][i] * EX[2][j];
-        int fin = 1;
-        for (int i = 0; i < 3; ++i) {
-            const double t = Y[0][i] - (R[i][0] * X[0][0] + R[i][1] * X[0][1] + R[i][2] * X[0][2]);
-            if (!(fabs(t) < 1e300)) fin = 0;
-            for (int j = 0; j < 3; ++j) { if (!(fabs(R[i][j]) < 1e300)) fin = 0; P[4 * i + j] = R[i][j]; }
-            P[4 * i + 3] = t;
+        if (!oka) {     /* the second way: u^2 - 2 cg u + 1 - c2 / s1^2 = 0 (the first side constraint over s1^2), both roots through the gates */
+            const double disc = cg * cg - 1.0 + c2 / (s1 * s1);
+            if (disc >= 0.0) {
+                const double sq = sqrt(disc);
+                oka = p3p_gate(cg - sq, v, s1, cg, ca, c2, a2, da, &ea);
+                okb = sq > 0.0 && p3p_gate(cg + sq, v, s1, cg, ca, c2, a2, db, &eb);
+                if (!dbl && oka && okb) {   /* a simple root carries one pose: the u with the smaller |e2| */
+                    if (eb < ea) oka = 0; else okb = 0;
+                }
+            }
         }
-        if (!fin) { for (int k = 0; k < 12; ++k) P[k] = __builtin_nan(""); continue; }
-        ++slot;
+        if (oka && slot < 4) slot += p3p_pose(f, X, da, out + 12 * slot);
+        if (okb && slot < 4) slot += p3p_pose(f, X, db, out + 12 * slot);
     }
 }
 
@@ -441,6 +490,8 @@ __global__ __launch_bounds__(64) void solve_f7_kernel(const double* __restrict__
     }
     double roots[3] = {nan, nan, nan};
     const double cm = fmax(fmax(fabs(c0), fabs(c1)), fmax(fabs(c2), fabs(c3)));
+    // c3 = det(F1 - F2) vanishes: F1 - F2 itself is singular, the root at infinity of this chart (slot qinf, after the finite ones)
+    int qinf = -1;
     if (!(cm > 0.0) || !(cm < 1e300)) return;
     if (fabs(c3) > 1e-14 * cm) {
         const double a = c2 / c3, b = c1 / c3, c = c0 / c3;
@@ -462,6 +513,7 @@ __global__ __launch_bounds__(64) void solve_f7_kernel(const double* __restrict__
             roots[2] = (-qb + sq) / 2.0;
         }
     } else if (fabs(c2) > 1e-14 * cm) {
+        qinf = 2;
         const double disc = c1 * c1 - 4.0 * c2 * c0;
         if (disc >= 0.0) {
             const double sq = sqrt(disc);
@@ -469,14 +521,17 @@ __global__ __launch_bounds__(64) void solve_f7_kernel(const double* __restrict__
             roots[1] = (-c1 + sq) / (2.0 * c2);
         }
     } else if (fabs(c1) > 1e-14 * cm) {
+        qinf = 1;
         roots[0] = -c0 / c1;
+    } else {
+        qinf = 0;
     }
     const double s1 = scale, s2 = scale * scale;
     for (int q = 0; q < 3; ++q) {
         const double l = roots[q];
-        if (!(l == l)) continue;
+        if (q != qinf && !(l == l)) continue;
         double F[9];
-        for (int k = 0; k < 9; ++k) F[k] = l * F1[k] + (1.0 - l) * F2[k];
+        for (int k = 0; k < 9; ++k) F[k] = q == qinf ? D[k] : l * F1[k] + (1.0 - l) * F2[k];
         // undo the isotropic scaling: F <- diag(1/s, 1/s, 1) F diag(1/s, 1/s, 1)
         F[0] = F[0] / s2; F[1] = F[1] / s2; F[2] = F[2] / s1;
         F[3] = F[3] / s2; F[4] = F[4] / s2; F[5] = F[5] / s1;

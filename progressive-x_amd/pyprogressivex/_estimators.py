@@ -451,12 +451,15 @@ class HomographyEstimator(Estimator):
     device_minimal = True      # pgx_solve_minimal: 8x8 Gaussian elimination per sample on the GPU
 
     def minimal(self, pts, samples):
-        scale = max(1.0, float(np.abs(pts).max()))     # isotropic pre-scaling: coordinates O(1) for the 8x8 solve
+        largest = float(np.abs(pts).max())
+        scale = max(1.0, largest)                      # isotropic pre-scaling: coordinates O(1) for the 8x8 solve
         p = pts[samples] / scale                       # [S,4,4]
         r1, r2 = _dlt_rows(p[..., 0], p[..., 1], p[..., 2], p[..., 3])
         A = np.concatenate([r1, r2], axis=1)           # [S,8,9]
         lhs, rhs = A[:, :, :8], -A[:, :, 8]
-        ok = np.abs(np.linalg.det(lhs)) > 1e-14
+        # the determinant of a regular sample scales with the eighth power of the coordinates (four columns linear, two quadratic in
+        # them), so for a point set below 1 - where the pre-scaling does nothing - the threshold follows it (a set that reaches 1: unchanged)
+        ok = np.abs(np.linalg.det(lhs)) > 1e-14 * min(1.0, largest) ** 8
         h = np.zeros((len(samples), 9))
         if ok.any():
             h[ok, :8] = np.linalg.solve(lhs[ok], rhs[ok][..., None])[..., 0]
@@ -543,7 +546,7 @@ class FundamentalEstimator(Estimator):
         p = pts[samples]
         scale = max(1.0, float(np.abs(pts).max()))
         A = self._rows(p / scale)                      # [S,7,9], isotropic pre-scaling for conditioning
-        _, _, vt = np.linalg.svd(A, full_matrices=True)
+        _, sv, vt = np.linalg.svd(A, full_matrices=True)
         F1, F2 = vt[:, 7].reshape(-1, 3, 3), vt[:, 8].reshape(-1, 3, 3)
         # det(l F1 + (1-l) F2) is a cubic in l: interpolate it at 4 nodes
         ls = np.array([0.0, 1.0, -1.0, 2.0])
@@ -553,7 +556,9 @@ class FundamentalEstimator(Estimator):
         D = np.diag([1 / scale, 1 / scale, 1.0])
         # roots of all cubics at once: eigenvalues of the stacked companion matrices (np.roots does the same one by
         # one); samples with a vanishing leading coefficient (a quadratic) take the slow path
-        finite = np.isfinite(coef).all(axis=1)
+        # a rank-deficient sample (a repeated point, seven points of one plane) has no two-dimensional null space to take a pencil
+        # from: no model, as the device's 1e-12 pivot test answers (the last two right singular vectors alone would give arbitrary ones)
+        finite = np.isfinite(coef).all(axis=1) & (sv[:, 6] >= 1e-12)
         lead = np.abs(coef[:, 0]) > 1e-14 * np.abs(coef).max(axis=1)
         reg = np.nonzero(finite & lead)[0]
         sidx, roots = [], []
@@ -828,15 +833,33 @@ class PnPEstimator(Estimator):
             with np.errstate(all="ignore"):
                 u = ((-1 + qq) * vv * vv - 2 * qq * cba * vv + 1 + qq) / (2 * (cga - vv * caa))
                 s1 = np.sqrt(b2s / (1 + vv * vv - 2 * vv * cba))
-            s2, s3 = u * s1, vv * s1
-            good = np.isfinite(s1) & np.isfinite(s2) & (s1 > 0) & (s2 > 0) & (s3 > 0)
-            # consistency with the two unused side constraints
-            e1 = s1 ** 2 + s2 ** 2 - 2 * s1 * s2 * cga - c2s
-            e2 = s2 ** 2 + s3 ** 2 - 2 * s2 * s3 * caa - a2s
-            good &= (np.abs(e1) < 1e-6 * c2s) & (np.abs(e2) < 1e-6 * a2s)
+            s3 = vv * s1
+
+            def gates(u):
+                # positive finite depths and consistency with the two unused side constraints -> (passes, |e2|)
+                with np.errstate(all="ignore"):
+                    s2 = u * s1
+                    e1 = s1 ** 2 + s2 ** 2 - 2 * s1 * s2 * cga - c2s
+                    e2 = s2 ** 2 + s3 ** 2 - 2 * s2 * s3 * caa - a2s
+                    ok = np.isfinite(s1) & np.isfinite(s2) & (s1 > 0) & (s2 > 0) & (s3 > 0)
+                    return ok & (np.abs(e1) < 1e-6 * c2s) & (np.abs(e2) < 1e-6 * a2s), np.abs(e2)
+
+            good, _ = gates(u)
+            if not good.all():
+                # the second way to u where the linear one fails its gates (0 / 0 when two poses share v, solve.hip solve_p3p):
+                # u^2 - 2 cg u + 1 - c2 / s1^2 = 0, of its roots through the gates the one with the smaller |e2|
+                with np.errstate(all="ignore"):
+                    disc = cga * cga - 1 + c2s / (s1 * s1)
+                    sq = np.sqrt(np.where(disc >= 0, disc, np.nan))
+                oka, ea = gates(cga - sq)
+                okb, eb = gates(cga + sq)
+                second = okb & (~oka | (eb < ea))
+                u = np.where(good, u, np.where(second, cga + sq, cga - sq))
+                good = good | oka | okb
             if not good.any():
                 continue
             sidx = sidx[good]
+            s2 = u * s1
             depth = np.stack([s1[good], s2[good], s3[good]], axis=1)
             Y = f[sidx] * depth[..., None]                    # camera-frame points
             R, t = _kabsch(X[sidx], Y)
