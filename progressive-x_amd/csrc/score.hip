@@ -171,10 +171,22 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
 //   1  a hypothesis' row holds the staged form only (StagedVals: the floats reject() reads) instead of the whole lane
 //   2  drain() carries count and value in one word and takes the run boundaries from one head mask (score_runs.h)
 //   4  direct() leaves out the tree and the atomic of the shared sum when no lane shares anything with the compound instance
+// Four more, of the way into the step loop and of the filter step (docs/lab-notebook.md, "A shorter prologue and filter step").  Only
+// 64 is on by default: the three prologue bits take the dependent memory round trips before the first step from about 14 to 5 and
+// measured nothing (the other waves of the SIMD hide them) - they stay for the next A/B.
+//   8   a listed workgroup fetches its XCD's four counts in one round trip and finds its (class, position) by selects
+//       (wl_locate_select) - wl_locate's early exits let the loads sink into its branches, one round trip each
+//   16  the kernel arguments are all requested right after entry: one batch instead of five lazy ones
+//   32  what the item determines is requested together: its (up to) four keep words, the point rows, the compound value
+//   64  the filter runs in every lane and the tail group's lanes beyond n are taken out of the ballot by one mask computed once:
+//       no exec region around the filter in every step, no bool between the comparison and the ballot, and a lane's candidate flag
+//       is its bit of the surviving mask as it stands
 #ifndef PGX_SCORE_TRIM
-#define PGX_SCORE_TRIM 7
+#define PGX_SCORE_TRIM 71
 #endif
 constexpr bool kTrimRows = (PGX_SCORE_TRIM & 1) != 0, kTrimDrain = (PGX_SCORE_TRIM & 2) != 0, kTrimDirect = (PGX_SCORE_TRIM & 4) != 0;
+constexpr bool kTrimLocate = (PGX_SCORE_TRIM & 8) != 0, kTrimArgs = (PGX_SCORE_TRIM & 16) != 0, kTrimItem = (PGX_SCORE_TRIM & 32) != 0,
+               kTrimTail = (PGX_SCORE_TRIM & 64) != 0;
 
 // A hypothesis' f32 constants as the cull kernel stores them (hyp32) and the group kernel stages them (LDS): the first kVals
 // floats of Filter32<MT>::Lane in float4 chunks.  Rows of hyp32 are kStride floats apart - 16-byte aligned, 64 bytes for the pose
@@ -377,6 +389,16 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
     // group's workgroups on one XCD (FETCH_SIZE 165 -> 45 MiB but 0.51 ms); one wave per workgroup with 8 parts per
     // group: 0.28 ms (16 parts: 250 k workgroups, the dispatcher limits at ~1.3 ns per workgroup).
     const int wv = 0;
+    if constexpr (kTrimArgs) {
+        // Left alone the compiler fetches an argument where it is first used: a listed wave waited for five batches of them, one
+        // after the other, between its entry and its first step.  One empty statement that every path needs the result of (W, groups)
+        // and that reads the others makes them one batch of scalar loads.  Not volatile: a statement with side effects counts as a
+        // store, and the uniform loads behind it (counts, item, keep words) would leave the scalar unit.  keep and wl are not named:
+        // a pointer an asm statement has seen counts as escaped, its loads inside the word loop could then alias the atomics and
+        // would leave the scalar unit as well; they sit between named arguments and arrive with them.
+        asm("" : "+s"(W), "+s"(groups) : "s"(wl_xb), "s"(wl_cap), "s"(n), "s"(pts_g), "s"(p32_g), "s"(pts), "s"(pts32),
+            "s"(comp), "s"(has_comp), "s"(nrep), "s"(acc), "s"(Mpad), "s"(hyp32), "s"(dense_min), "s"(models), "s"(models_t), "s"(T2), "s"(qscale), "s"(split), "s"(xcd_local));
+    }
     int g, w0, w1 = W, wstep = 1;   // this wave's words of group g: w0, w0 + wstep, ... below w1
     if (wl != nullptr) {
         const int xcd = (int)(blockIdx.x & 7u);
@@ -385,8 +407,16 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
         for (int c = 0; c < kWlClasses; ++c) lc[c] = wl[wl_count_index(xcd, c)];   // wave-uniform -> scalar loads
         int cls;
         unsigned pos;
-        if (!wl_locate(lc[0], lc[1], lc[2], lc[3], blockIdx.x >> 3, &cls, &pos)) return;   // past this XCD's lists
-        if (pos >= wl_cap) return;            // (never: a list holds at most its XCD's items)
+        if constexpr (kTrimLocate) {
+            // all four counts are in registers before the first is looked at: one round trip, and a workgroup past its lists leaves
+            // after it.  (The never-taken guard on the position shares the exit.)
+            asm("" : "+s"(lc[0]), "+s"(lc[1]), "+s"(lc[2]), "+s"(lc[3]));
+            const bool found = wl_locate_select(lc[0], lc[1], lc[2], lc[3], blockIdx.x >> 3, &cls, &pos);
+            if (!found | (pos >= wl_cap)) return;
+        } else {
+            if (!wl_locate(lc[0], lc[1], lc[2], lc[3], blockIdx.x >> 3, &cls, &pos)) return;   // past this XCD's lists
+            if (pos >= wl_cap) return;            // (never: a list holds at most its XCD's items)
+        }
         const unsigned item = wl[kWlCountWords + (size_t)(xcd * kWlClasses + cls) * wl_cap + pos];
         if (wl_item_group(item, wl_xb) >= (unsigned)groups || wl_item_column(item, wl_xb) * kWlItemWords >= (unsigned)W) return;   // (never either)
         g = (int)wl_item_group(item, wl_xb);
@@ -414,6 +444,24 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
     const int64_t j = (int64_t)g * 64 + lane;
     const bool valid = j < n;
     const int64_t jj = valid ? j : n - 1;
+    // Lanes at or past n exist in the last group only and hold a COPY OF THE LAST POINT on both layouts (AoS: row jj = n - 1; SoA: the
+    // tail group is padded with its last row), so their filter arithmetic is that of a real row.  kTrimTail relies on it: the filter
+    // runs in every lane and these lanes are taken out of each step's ballot by valid_mask.
+    const unsigned long long valid_mask = __ballot(valid);
+    // kTrimItem: a listed item's keep words (adjacent: w0 .. w0 + 3), its point rows and its compound value are requested together
+    // here - one memory round trip; the word loop takes its words from registers.  The four words are ONE 32-byte scalar load
+    // (four loads share their address registers and wait for each other) that stays inside the group's row, also where the row's
+    // last item is short (score_worklist.h wl_words_begin / wl_words_shift): a word at or past W is 0 and is never read.  Rows
+    // shorter than one item (W < 4) keep the word loop's own loads.
+    static_assert(kWlItemWords == 4, "the item's keep words are one 4-word load");
+    typedef unsigned long long keep4_t __attribute__((ext_vector_type(4), aligned(8)));
+    const bool item_words = kTrimItem && wl != nullptr && W >= kWlItemWords;
+    uint64_t kw[kWlItemWords] = {};
+    double cmp = 0.0;
+    const int kwb = wl_words_begin(w0, W);   // (wave-uniform)
+    keep4_t kwv = {};
+    if (item_words) kwv = *reinterpret_cast<const keep4_t*>(keep + (int64_t)g * W + kwb);   // wave-uniform -> one scalar load
+    if (kTrimItem && has_comp) cmp = comp[jj];   // (ahead of the rows: its address and value in registers of their own)
     double pt[R::D];
     float p32[8];
     if (pts_g != nullptr) {
@@ -442,7 +490,8 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
 #pragma unroll
         for (int q = 0; q < 8; ++q) p32[q] = pts32[jj * 8 + q];
     }
-    const double cmp = has_comp ? comp[jj] : 0.0;
+    if (!kTrimItem && has_comp) cmp = comp[jj];
+    if (item_words) wl_words_shift(kwv.x, kwv.y, kwv.z, kwv.w, w0 - kwb, kw);   // (first use of the keep words: behind the requests for the rows)
     // nrep replicas of the integer accumulators, chosen by workgroup id: workgroup ids go round-robin over the XCDs, so with
     // nrep a multiple of 8 a replica is only ever updated from one XCD (its atomics stay in that L2), and the hot
     // hypotheses (thousands of updates) do not serialise on three addresses.  score_finish_kernel adds the replicas (exact).
@@ -568,7 +617,14 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
         }
     };
     for (int w = w0; w < w1; w += wstep) {
-        unsigned long long todo = keep[(int64_t)g * W + w];  // wave-uniform -> scalar load
+        unsigned long long todo;
+        if (item_words) {  // the item's next word: fetched with the rows
+            todo = kw[0];
+#pragma unroll
+            for (int k = 0; k + 1 < kWlItemWords; ++k) kw[k] = kw[k + 1];
+        } else {
+            todo = keep[(int64_t)g * W + w];  // wave-uniform -> scalar load
+        }
         if (todo == 0) continue;
         if (STATS) st_steps += (unsigned long long)__popcll(todo);
         __builtin_amdgcn_wave_barrier();  // the previous word's reads are done (LDS ops of a wave execute in order)
@@ -582,9 +638,19 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
             todo &= todo - 1;
             const int m = w * 64 + h;
             const LaneT ln = Row::staged(s_h32[wv], h);  // same address in every lane: LDS broadcast
-            const bool cand = valid && !F32::reject(p32, ln, T2d32);
-            const unsigned long long cm = __ballot(cand);
-            if (cm == 0) continue;
+            bool cand;
+            unsigned long long cm;
+            if constexpr (kTrimTail) {
+                // every lane runs the filter (the lanes past n on a copy of the last point, see valid_mask); the comparison's lane
+                // mask is the ballot, and a lane is a candidate when its bit survives the mask
+                cm = RejectTerms<F32>::passed(p32, ln, T2d32) & valid_mask;
+                if (cm == 0) continue;
+                cand = __builtin_amdgcn_inverse_ballot_w64(cm);   // lane i: bit i of cm - the mask itself, no shift and compare per lane
+            } else {
+                cand = valid && !F32::reject(p32, ln, T2d32);
+                cm = __ballot(cand);
+                if (cm == 0) continue;
+            }
             if (!MASK && __popcll(cm) < dense_min) {
                 // the exact path with ~3 of 64 lanes busy per (hypothesis, group) was most of this kernel: candidates
                 // are queued instead and evaluated 64 at a time

@@ -140,6 +140,22 @@ template <int MT> struct Filter32 {
 template <class F, class = void> struct StagedVals { static constexpr int value = (int)(sizeof(typename F::Lane) / sizeof(float)); };
 template <class F> struct StagedVals<F, std::void_t<decltype(F::kStagedVals)>> { static constexpr int value = F::kStagedVals; };
 
+// The wave's survivors of one hypothesis: bit i = lane i's pair is NOT rejected.  A filter whose reject() is the conjunction of two
+// comparisons can hand them out one by one (reject_terms): each comparison's lane mask is a ballot as it stands, and the masks are
+// combined on the scalar unit - the ballot of the combined bool goes through a 0 / 1 register and a second comparison in every lane.
+template <class F, class = void> struct RejectTerms {
+    static __device__ __forceinline__ unsigned long long passed(const float* p, const typename F::Lane& ln, float T2d) {
+        return __builtin_amdgcn_ballot_w64(!F::reject(p, ln, T2d));
+    }
+};
+template <class F> struct RejectTerms<F, std::void_t<decltype(&F::reject_terms)>> {
+    static __device__ __forceinline__ unsigned long long passed(const float* p, const typename F::Lane& ln, float T2d) {
+        bool a, b;
+        F::reject_terms(p, ln, T2d, &a, &b);
+        return ~(__builtin_amdgcn_ballot_w64(a) & __builtin_amdgcn_ballot_w64(b));   // (every lane of the wave is active in the step loop)
+    }
+};
+
 // ---- group-level rejection ---------------------------------------------------------------------------
 // The points are kept in Morton order of all their coordinates, so 64 consecutive points form a compact group: centre c
 // and radius rho of the part the projective map multiplies, centre (ub, vb) and half extents (ru, rv) of the observed
@@ -181,6 +197,12 @@ template <> struct Filter32<kPnP> {
     }
     // p = (u, v, X, Y, Z, scale, -, -) in f32
     static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float T2d) {
+        bool trust, over;
+        reject_terms(p, ln, T2d, &trust, &over);
+        return trust && over;
+    }
+    // the two comparisons reject() is the conjunction of, for a caller that wants their lane masks (RejectTerms below)
+    static __device__ __forceinline__ void reject_terms(const float* p, const Lane& ln, float T2d, bool* trust, bool* over) {
         const float* m = ln.m;
         const float px = __builtin_fmaf(m[0], p[2], __builtin_fmaf(m[1], p[3], __builtin_fmaf(m[2], p[4], m[3])));
         const float py = __builtin_fmaf(m[4], p[2], __builtin_fmaf(m[5], p[3], __builtin_fmaf(m[6], p[4], m[7])));
@@ -189,8 +211,8 @@ template <> struct Filter32<kPnP> {
         const float b = __builtin_fmaf(p[1], pz, -py);
         const float lhs = __builtin_fmaf(b, b, a * a);
         const float rhs = (pz * pz) * T2d;
-        const bool trust = __builtin_fmaf(ln.c1, p[5], ln.c0) <= fabsf(pz);  // false on NaN
-        return trust && (lhs > rhs);                                         // false on NaN
+        *trust = __builtin_fmaf(ln.c1, p[5], ln.c0) <= fabsf(pz);  // false on NaN
+        *over = lhs > rhs;                                         // false on NaN
     }
     // g = (cX, cY, cZ, rho, ub, vb, ru, rv, scale, -, -, -)
     static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float Tup) {

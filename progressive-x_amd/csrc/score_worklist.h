@@ -59,4 +59,29 @@ PGX_WL_FN bool wl_locate(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uin
     return false;
 }
 
+// wl_locate without early exits, for the group kernel: every comparison and subtraction is made, selects pick the result, so the
+// four counts can be fetched in one round trip and nothing is loaded behind a branch.  A class' comparison only counts when no
+// heavier class took the slot; then every subtraction before it was of a count <= slot and did not wrap - the same (class, position)
+// as wl_locate for all 32-bit counts (tests/test_score_worklist_locate.py).  When false, *cls and *pos are written but mean nothing.
+PGX_WL_FN bool wl_locate_select(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t slot, int* cls, uint32_t* pos)
+{
+    const uint32_t s3 = slot, s2 = s3 - c3, s1 = s2 - c2, s0 = s1 - c1;
+    const bool in3 = s3 < c3, in2 = !in3 & (s2 < c2), in1 = !in3 & !in2 & (s1 < c1), in0 = !in3 & !in2 & !in1 & (s0 < c0);
+    *cls = in3 ? 3 : in2 ? 2 : in1 ? 1 : 0;
+    *pos = in3 ? s3 : in2 ? s2 : in1 ? s1 : s0;
+    return in3 | in2 | in1 | in0;
+}
+
+// ---- an item's keep words (words w0 .. w0 + 3 of a group's row of W >= 4 words, those at or past W count as 0) as ONE load of four
+// adjacent words that stays inside the row: it begins at wl_words_begin, d = w0 - begin words early when the row's last item is
+// short, and wl_words_shift moves the words down by d.
+PGX_WL_FN int wl_words_begin(int w0, int W) { return w0 + kWlItemWords <= W ? w0 : W - kWlItemWords; }
+PGX_WL_FN void wl_words_shift(uint64_t v0, uint64_t v1, uint64_t v2, uint64_t v3, int d, uint64_t out[kWlItemWords])
+{
+    out[0] = d == 0 ? v0 : d == 1 ? v1 : d == 2 ? v2 : v3;
+    out[1] = d == 0 ? v1 : d == 1 ? v2 : d == 2 ? v3 : 0;
+    out[2] = d == 0 ? v2 : d == 1 ? v3 : 0;
+    out[3] = d == 0 ? v3 : 0;
+}
+
 }  // namespace pgx
