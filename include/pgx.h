@@ -42,8 +42,10 @@ enum pgx_model_type {
     PGX_HOMOGRAPHY_SYM = 5,   /* point (x1,y1,x2,y2);    model [H | H^-1], symmetric transfer error               */
     PGX_PLANE3D = 6,          /* point (x,y,z);          model (a,b,c,d), (a,b,c) unit normal findPlanes           */
     PGX_SPHERE3D = 8,         /* point (x,y,z);          model (cx,cy,cz,r)                   findSpheres          */
-    PGX_CIRCLE2D = 10         /* point (x,y);            model (cx,cy,r)                      findCircles          */
-    /* 7 and 9 are not assigned: pgx_model_dims(7 or 9) and pgx_set_points(7 or 9, ...) fail with PGX_ERR_INVALID */
+    PGX_CIRCLE2D = 10,        /* point (x,y);            model (cx,cy,r)                      findCircles          */
+    PGX_LINE3D = 12           /* point (x,y,z);          model (px,py,pz,dx,dy,dz), a point on the line and a direction
+                                                         (unit from the solver and the refit)  findLines3D          */
+    /* 7, 9 and 11 are not assigned: pgx_model_dims(7, 9 or 11) and pgx_set_points(7, 9 or 11, ...) fail with PGX_ERR_INVALID */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -90,7 +92,8 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * Built: the 2-segment vanishing point solver (solver_vanishing_point_two_lines.h:147-185) and the 2-point line solver
  * [U-4] (samples[S][2], S x 3 models), the 3-point plane solver (samples[S][3], S x 4, findPlanes), the 4-point sphere solver
  * (samples[S][4], S x 4, findSpheres; radii outside pgx_set_radius_range give NaN), the 3-point circle solver
- * (samples[S][3], S x 3, findCircles; the same radius range), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
+ * (samples[S][3], S x 3, findCircles; the same radius range), the 2-point 3-D line solver (samples[S][2], S x 6, findLines3D:
+ * a point and a unit direction; coincident points or a length that is not finite give NaN), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
  * FOUR slots per sample: 4S x 12 [R|t], DefaultPnPEstimator progressivex_python.cpp:119, absent upstream); a degenerate sample

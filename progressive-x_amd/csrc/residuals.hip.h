@@ -1,5 +1,6 @@
-// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the two families of geometric
-// primitives: flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension.  gfx950 device code.
+// residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the geometric primitives: the two
+// families flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension, and the 3-D line
+// (distance to an axis).  gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -19,7 +20,8 @@ namespace pgx {
 
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
-    kSphere3D = 8, kCircle2D = 10, kNumModelTypes = 11   // 7 and 9 are not assigned (pgx_model_dims(7) and (9) are errors)
+    kSphere3D = 8, kCircle2D = 10, kLine3D = 12,
+    kNumModelTypes = 13   // 7, 9 and 11 are not assigned (pgx_model_dims(7), (9) and (11) are errors)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -85,6 +87,27 @@ template <int DIM> struct RoundResidual : NoProjectiveMap {
 };
 template <> struct Residual<kCircle2D> : RoundResidual<2> { static constexpr int sample = 3; };
 template <> struct Residual<kSphere3D> : RoundResidual<3> { static constexpr int sample = 4; };
+
+// 3-D line (findLines3D; no reference counterpart): model (p[3], d[3]), a point on the line and a direction.  e = x - p componentwise,
+// c = e x d in solve.hip cross3's component order,
+//   c0 = e1 d2 - e2 d1,   c1 = -(e0 d2 - e2 d0),   c2 = e0 d1 - e1 d0,   r^2 = (c0 c0 + c1 c1) + c2 c2,   r = sqrt(r^2).
+// squared() is primary and has no root in it.  The direction is taken as given: r is the distance to the axis times |d| (the solver
+// and the refit return unit directions), there is no division by |d|.  The cross-product form, not |e|^2 - (e . d)^2, which cancels
+// for points far along the line.  Every entry of the model enters at least two components of c: one NaN entry makes every residual
+// NaN; d = 0 makes every residual 0.  This operation order is the contract of every 3-D line check (tests restate it in numpy).
+template <> struct Residual<kLine3D> : NoProjectiveMap {
+    static constexpr int D = 3, P = 6, sample = 2, slots = 1, bound = kBoundBall;
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double e0 = p[0] - m[0], e1 = p[1] - m[1], e2 = p[2] - m[2];
+        const double c0 = e1 * m[5] - e2 * m[4];
+        const double c1 = -(e0 * m[5] - e2 * m[3]);
+        const double c2 = e0 * m[4] - e1 * m[3];
+        return (c0 * c0 + c1 * c1) + c2 * c2;
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) { return sqrt(squared(p, m)); }
+};
 
 // DefaultHomographyEstimator (progressivex_python.cpp:252) [U-1]: one-way forward transfer error,
 // H row-major 3x3 (progressivex_python.cpp:292-300).
@@ -192,6 +215,7 @@ template <class F> inline bool with_model_type(int mt, F&& f) {
     case kPlane3D: f(std::integral_constant<int, kPlane3D>{}); return true;
     case kSphere3D: f(std::integral_constant<int, kSphere3D>{}); return true;
     case kCircle2D: f(std::integral_constant<int, kCircle2D>{}); return true;
+    case kLine3D: f(std::integral_constant<int, kLine3D>{}); return true;
     default: return false;
     }
 }

@@ -662,4 +662,117 @@ template <int DIM> struct RoundFilter32 {
 template <> struct Filter32<kCircle2D> : RoundFilter32<2> {};
 template <> struct Filter32<kSphere3D> : RoundFilter32<3> {};
 
+// ---- 3-D lines: r = |(x - p) x d| (Residual<kLine3D>), inlier iff r^2 < T2 ------------------------------------------------------------
+// Homogeneous in the direction d only (p is a point): the f32 copy of d is made from d after the exact power-of-two scaling
+// sc = pow2_normaliser<3>(d), which leaves its largest entry in [0.5, 1) and |d| in [0.5, sqrt(3)), and is tested against the threshold
+// scaled along, Ts = T sc (must be an ordinary f32 as well).  p is rounded once and not scaled.  Below d is the scaled direction and
+// r* = |(x - p) x d| in exact arithmetic on the f64 inputs.  Per point, in f32 - this operation order is the contract of the f32 test
+// (tests restate it with fma as one rounding):
+//   e~_k = x~_k - p~_k                                                            P = max(|x|, |y|, |z|, 1) rounded up
+//   c~_0 = fma(e~_1, d~_2, -(e~_2 d~_1)),  c~_1 = fma(e~_2, d~_0, -(e~_0 d~_2)),  c~_2 = fma(e~_0, d~_1, -(e~_1 d~_0))
+//   q~ = fma(c~_0, c~_0, fma(c~_1, c~_1, c~_2 c~_2)),  s~ = sqrtf(q~),  l~ = (|e~_0| + |e~_1|) + |e~_2|
+// (c~_1 has the sign of the exact path's c1 reversed: only its square is used.)  With u = 2^-24, eta = 2^-126, |.| the Euclidean norm
+// unless marked |.|_1, and e^ = x~ - p~ exactly:
+//   inputs     e -> e x d is |d|-Lipschitz in e and |e|-Lipschitz in d: |x~ - x| <= u |x| <= sqrt(3) u P and |p~ - p| <= u |p| move c by
+//              at most |d| (sqrt(3) u P + u |p|); |d~ - d| <= u |d| moves it by u |d| |e^|
+//   e~         one rounding per component, |e~ - e^| <= u |e^|: moves c by at most u |d~| |e^|
+//   c~_k       the inner product is rounded once and the fma once: |c~_k - c_k(e~, d~)| <= u |e~_j d~_i| + u |c_k| + O(u^2); the three
+//              inner products are three different entries of the outer product e~ d~^T, so their vector is at most |e~| |d~| long:
+//              u |e~| |d~| + u |c~|
+//   q~         three non-negative terms; the innermost is rounded as a product and by both fmas outside it, the outermost by its fma
+//              alone: at most 3 roundings on a term, q~ = |c~|^2 (1 + t), |t| <= 3 u + O(u^2) -> 1.5 u |c~| after the root
+//   sqrtf      v_sqrt_f32's documented 1 ulp = 2 u |c~|, whatever correction the lowering adds (as the round family charges it)
+//   exact path three differences, six products, three differences of products, then three squares and two sums, in f64 without
+//              contraction: |c_c - c*| <= 4 * 2^-53 |e| |d| + O(2^-106), absolute and not relative to r; the sum of squares adds a
+//              relative 2 * 2^-53 after the root.  Together < 2^-50 |e| |d| = u 2^-26 |e| |d|
+// and |c~| <= |e~| |d~| (1 + O(u)), so
+//   |s~ - r*| + |r_c - r*| <= sqrt(3) u |d| P + u |d| |p| + (1 + 1 + 1 + 1 + 1.5 + 2) u |d~| |e~| + 2^-50 |e| |d| + O(u^2)
+//                          =  sqrt(3) u |d| P + u |d| |p| + 7.5 u |d~| |e~| + ...
+// |e~|_1 >= |e~| bounds the length without a second root.  Underflow: an inner product or fma result below 2^-126 carries an absolute
+// error <= eta (even with denormals flushed), which moves c by < 4 eta; a subnormal difference e~_k is exact (flushed: off by < eta,
+// c moves by < 2 eta); the three squares and two fmas of q~ put at most 4 eta under the root and move it by <= sqrt(4 eta) < 2.2e-19.
+// The exact path's own underflow: the band of pow2_normaliser keeps |c| sc^-1 above 2^-511 or its square's error below 3 * 2^-1074,
+// which moves r sc by < 1e-80.  The coefficients, each with room for evaluating E itself in f32 (four roundings, < 5 u relative), for
+// writing |d~|, |e~| for |d|, |e^| (factors 1 + O(u)) and for the O(u^2) terms:
+//   E = e1 P + e0 + e2 l~      e1 = 2 u D                   >= 1.15 * sqrt(3) u |d|              D = 1.001 |d| (f64, rounded up)
+//                              e0 = 2 u D |p| 1.001 + 1e-18 >= 2 * u |d| |p|, + 4 * 2.2e-19
+//                              e2 = 8 u D                   >= 1.06 * (7.5 + 2^-26) u |d~|
+//   reject  <=>  m := s~ - E > T'' = Ts (1 + 2^-6).  m is rounded once and monotonically, which is paid from the margin of the threshold
+//   as in the round family: r_c > Ts (1 + 2^-7), and the computed r_c^2, which the exact path compares, exceeds Ts^2 = T2 sc^2 - the
+//   exact path's arithmetic on d / sc is that on d scaled by a power of two.  The root form is kept: the squared form (q~ against
+//   (T'' + E)^2) would be correct only because the 1e-18 floor keeps the square a normal f32, a coupling this budget should not hide.
+// Group test on the 3-D ball (stored centre g, radius rho, Pmax) of 64 Morton-consecutive points (sp_line_bounds_kernel<SPAN, 3>, the
+// rows planes and spheres get): r* is |d|-Lipschitz in x, so every member has r* >= r*(g) - |d| rho, and its |e|_1 is at most
+// |e_g|_1 + sqrt(3) rho, which bounds the error terms of the member's own exact evaluation (g is an f32 value: no input rounding, the
+// e1 Pmax term is kept all the same):
+//   reject the group  <=>  s~_g - E(Pmax, l~_g + 1.74 rho) - 1.001 D rho > 1.001 T''.
+// Switch-off, E = inf and the exact path decides: a set with coordinates beyond 1e17 or |p| beyond 1e17 (q~ must stay below the f32
+// overflow: |c~| <= sqrt(3) * 3.5e17), a threshold Ts outside the ordinary f32 range, a direction outside pow2_normaliser's band -
+// d = 0, whose residuals are all 0 on the exact path, and Inf entries among them: inf - inf is NaN, and a NaN comparison is false.
+// A NaN entry culls the hypothesis outright (all six enter every residual).  The exact path is 17 FP64 operations without a division or
+// a root, so as for planes the per-pair filter buys little and the cull buys almost everything: a line's inliers are a tube of
+// radius T, which few 64-point balls touch (DESIGN.md 4.8 has the measurement).
+template <> struct Filter32<kLine3D> {
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    struct Lane { float p[3]; float d[3]; float e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
+    // reject() reads p, d, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject)
+    static constexpr int kStagedVals = 10;
+    static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, e1) == 6 * sizeof(float) &&
+                  offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
+                  sizeof(Lane) == 12 * sizeof(float), "p, d, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        const double d0[3] = {m[3], m[4], m[5]};
+        bool off;
+        const double sc = pow2_normaliser<3>(d0, &off);
+        bool nan = false;
+        double d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k] = d0[k] * sc;
+            ln.p[k] = (float)m[k];
+            ln.d[k] = (float)d[k];
+            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
+        }
+        ln.nanh = nan ? 1.0f : 0.0f;
+        const double Ts = sqrt(T2) * sc;   // the threshold in the scaled direction's units: must be an ordinary f32 as well
+        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
+        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
+        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
+        const double u = 5.9604644775390625e-8;
+        ln.e1 = f32_up(2.0 * u * dn);
+        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * dn * pn + 1e-18);   // inf: nothing is rejected
+        ln.e2 = f32_up(8.0 * u * dn);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        ln.nrm = f32_up(dn);
+        return ln;
+    }
+    // s~ and l~ of a point or a centre
+    static __device__ __forceinline__ float dist(const float* p, const Lane& ln, float* l1) {
+        const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];
+        const float* d = ln.d;
+        const float c0 = __builtin_fmaf(e1, d[2], -(e2 * d[1]));
+        const float c1 = __builtin_fmaf(e2, d[0], -(e0 * d[2]));
+        const float c2 = __builtin_fmaf(e0, d[1], -(e1 * d[0]));
+        *l1 = (fabsf(e0) + fabsf(e1)) + fabsf(e2);
+        return sqrtf(__builtin_fmaf(c0, c0, __builtin_fmaf(c1, c1, c2 * c2)));
+    }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        float l1;
+        const float s = dist(p, ln, &l1);
+        const float m = s - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (centre[3], rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
+        float l1;
+        const float s = dist(g, ln, &l1);
+        const float m = s - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
 }  // namespace pgx

@@ -28,7 +28,9 @@
 //   singular systems (det == 0), non-finite values and radii outside the context's pgx_set_radius_range give NaN
 //     3-D sphere through four points    findSpheres' minimal solver: Cramer's rule on cross products (det == 0: coplanar points)
 //     2-D circle through three points   findCircles' minimal solver: Cramer's rule on the 2x2 system (det == 0: collinear points)
-// The five solvers with one model per sample (line, vanishing point, plane, sphere, circle) share one kernel shell, solve_kernel<MT>;
+//   3-D line through two points         findLines3D's minimal solver (no reference counterpart): d = (b - a) / |b - a|, p = a;
+//                                       coincident points and a length that is not finite give NaN
+// The six solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line) share one kernel shell, solve_kernel<MT>;
 // the 7-point, 4-point and P3P solvers run one lane per sample in kernels of their own.
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
@@ -152,6 +154,26 @@ __device__ __forceinline__ void solve_minimal(Type<kCircle2D>, const double* con
     const double r = sqrt(e0 * e0 + e1 * e1);
     const double c[2] = {p0[0] + e0, p0[1] + e1};
     accept_round<2>(det, c, r, rmin, rmax, m);
+}
+
+// 2-point 3-D line -> (p, d), a point on the line and a unit direction.  Operation order (the contract; Line3DEstimator.minimal
+// restates it):
+//   v = b - a (componentwise), ln = sqrt((v0 v0 + v1 v1) + v2 v2), d = v / ln, p = a.
+// ln == 0 (coincident points; also false on NaN) gives a NaN model, and so does a non-finite ln, unlike the plane solver: v / inf
+// would be a zero direction, and every point is an inlier of that.
+__device__ __forceinline__ void solve_minimal(Type<kLine3D>, const double* const* p, double, double, double* m)
+{
+    const double *a = p[0], *b = p[1];
+    const double v0 = b[0] - a[0], v1 = b[1] - a[1], v2 = b[2] - a[2];
+    const double ln = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
+    if (ln > 0.0 && isfinite(ln)) {
+        m[0] = a[0];
+        m[1] = a[1];
+        m[2] = a[2];
+        m[3] = v0 / ln;
+        m[4] = v1 / ln;
+        m[5] = v2 / ln;
+    }
 }
 
 // The shell: samples[S][sample] -> S x P models, one lane per padded model.  An index outside 0 .. n-1 gives a NaN model.
@@ -612,7 +634,7 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     const int mt = ctx->model_type;
     ModelInfo mi;
     if (!model_info(mt, &mi) || mi.slots == 0)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 4-point homography, 7-point fundamental matrix, P3P)", mt);
     // isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1 for these model types, so the solvers take
     // fscale, which pgx_set_points computes from the caller-visible data: umax is not kept either)
     const bool scaled = mt == kFundamental || mt == kHomography;

@@ -221,6 +221,61 @@ class PlaneEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 3-D line (findLines3D; no reference counterpart): the plane's scatter matrix read from the other end of its spectrum
+# ---------------------------------------------------------------------------------------------------------------------
+class Line3DEstimator(Estimator):
+    model_type = _lib.LINE3D
+    sample_size = 2
+    nonminimal_sample_size = 2
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
+    cols = 6
+
+    def minimal(self, pts, samples):
+        """samples [S, 2] -> lines (p, d), a point and a unit direction, bitwise csrc/solve.hip's solve_minimal for 3-D lines:
+        v = b - a, ln = sqrt((v0 v0 + v1 v1) + v2 v2), d = v / ln, p = a.  Coincident samples (ln == 0) and a length that is not
+        finite (NaN or Inf coordinates, an overflowing square) give no model."""
+        a, b = pts[samples[:, 0]], pts[samples[:, 1]]
+        with np.errstate(all="ignore"):
+            v = b - a
+            ln = np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+            ok = (ln > 0) & np.isfinite(ln)
+            d = v / np.where(ok, ln, 1.0)[:, None]
+        models = np.column_stack([a, d])
+        return models[ok], np.nonzero(ok)[0]
+
+    def _direction(self, scatter):
+        """largest eigenvectors of the 3x3 scatter matrices [B, 3, 3] (all finite) -> [B, 3]; the smallest of -scatter under
+        "jacobi", so the device eigen-solver serves unchanged"""
+        if self.refit_solver == "jacobi":
+            return self._smallest(-scatter)
+        return np.linalg.eigh(scatter)[1][:, :, -1]
+
+    def _fit_many(self, gram, B, inits):
+        """Total least squares: one Gram request (sum w [1,x,y,z][1,x,y,z]^T), the weighted mean is the point and the eigenvector of
+        the largest eigenvalue of the scatter about it the direction, signed so that its largest-magnitude component (the first of
+        equals) is positive - which makes the two eigen-solvers agree.  A non-finite Gram matrix or scatter gives no model."""
+        out = [[] for _ in range(B)]
+        G, cnt, _ = gram(_lib.GRAM_AFFINE, None, True, 1, np.arange(B))
+        W = G[:, 0, 0]
+        idx = np.nonzero((np.asarray(cnt) >= 2) & (W > 0) & np.isfinite(G).all(axis=(1, 2)))[0]
+        if idx.size == 0:
+            return out
+        Wk = W[idx]
+        mean = G[idx, 0, 1:] / Wk[:, None]
+        scatter = G[idx][:, 1:, 1:] - Wk[:, None, None] * (mean[:, :, None] * mean[:, None, :])
+        ok = np.isfinite(scatter).all(axis=(1, 2))
+        if not ok.any():
+            return out
+        dirs = self._direction(scatter[ok])
+        for k, b in enumerate(idx[ok]):
+            d = dirs[k]
+            if d[int(np.argmax(np.abs(d)))] < 0:
+                d = -d
+            out[b] = [np.concatenate([mean[ok][k], d])]
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The round family (no reference counterpart): 3-D sphere (findSpheres, 4-point minimal solver) and 2-D circle (findCircles, 3-point),
 # one algebraic refit on normalised coordinates
 # ---------------------------------------------------------------------------------------------------------------------
@@ -971,6 +1026,7 @@ ESTIMATORS = {
     "plane": PlaneEstimator,
     "sphere": SphereEstimator,
     "circle": CircleEstimator,
+    "line3d": Line3DEstimator,
     "vanishing_point": VanishingPointEstimator,
     "homography": HomographyEstimator,
     "homography_sym": SymmetricHomographyEstimator,

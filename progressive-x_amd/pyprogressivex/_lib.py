@@ -19,11 +19,12 @@ LIB_PATH = os.environ.get("PGX_LIBPGX") or os.path.join(_HERE, "libpgx.so")   # 
 LINE2D, HOMOGRAPHY, FUNDAMENTAL, PNP, VANISHING_POINT, HOMOGRAPHY_SYM, PLANE3D = range(7)
 SPHERE3D = 8                   # (7 is not assigned: include/pgx.h)
 CIRCLE2D = 10                  # (9 is not assigned either)
+LINE3D = 12                    # (nor is 11)
 # per model type: (doubles per point, doubles per model, minimal sample size, hypotheses per sample of the device solver);
 # sample size 0 = no device solver (pgx_solve_minimal fails).  The numbers of csrc/residuals.hip.h; tests/test_abi.py compares.
 MODEL_TABLE = {LINE2D: (2, 3, 2, 1), HOMOGRAPHY: (4, 9, 4, 1), FUNDAMENTAL: (4, 9, 7, 3), PNP: (5, 12, 3, 4),
                VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1),
-               CIRCLE2D: (2, 3, 3, 1)}
+               CIRCLE2D: (2, 3, 3, 1), LINE3D: (3, 6, 2, 1)}
 POINT_DIM = {t: row[0] for t, row in MODEL_TABLE.items()}
 PARAM_DIM = {t: row[1] for t, row in MODEL_TABLE.items()}
 FIXED_ONE = float(1 << 32)
@@ -507,7 +508,7 @@ class Context:
         return off, idx[:arcs], mult[:arcs]
 
     def solve_minimal(self, samples, fetch=True):
-        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, ...), generated from the
+        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, ...), generated from the
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)

@@ -83,6 +83,31 @@ def make_planes(n_per_plane=8000, n_planes=6, n_outliers=48000, sigma=0.01, size
     return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(models)
 
 
+def make_lines3d(n_per_line=2000, n_lines=6, n_outliers=12000, sigma=0.01, size=10.0, length=(4.0, 10.0), seed=0):
+    """findLines3D's workload: K segments with uniformly random unit directions and lengths uniform in `length`, each lying wholly
+    inside the box [0, size]^3 (the midpoint is drawn where both ends fit); the inliers of line k are uniform along its segment with
+    isotropic Gaussian noise of `sigma` per coordinate (their distance to the axis is Rayleigh, mean sigma sqrt(pi / 2)); the outliers
+    are uniform in the box.  Returns (points [n, 3], labels [n] (k + 1 = line k, 0 = outlier), gt_lines [K, 6] = (midpoint, unit
+    direction)).  A pure function of the seed."""
+    rng = np.random.default_rng(seed)
+    if not 0.0 < length[0] <= length[1] <= size:
+        raise ValueError("length should satisfy 0 < min <= max <= size")
+    pts, labels, models = [], [], []
+    for k in range(n_lines):
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        ln = rng.uniform(length[0], length[1])
+        half = 0.5 * ln * np.abs(d)
+        mid = rng.uniform(half, size - half)
+        t = rng.uniform(-0.5 * ln, 0.5 * ln, n_per_line)
+        pts.append(mid + t[:, None] * d + rng.normal(0, sigma, (n_per_line, 3)))
+        labels.append(np.full(n_per_line, k + 1))
+        models.append(np.concatenate([mid, d]))
+    pts.append(rng.uniform(0, size, (n_outliers, 3)))
+    labels.append(np.zeros(n_outliers, dtype=int))
+    return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(models).reshape(-1, 6)
+
+
 def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.5), coverage=1.0, seed=0):
     """findSpheres' workload: K non-overlapping spheres with radii uniform in `radius` and centres inside the box [0, size]^3 (each
     sphere lies wholly inside it); the inliers of sphere k are uniform on its surface - or, with coverage < 1, on the cap of that
@@ -366,4 +391,5 @@ def misclassification_models(preferences, annotation, K_annot):
 
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
-                   vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D)
+                   vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D,
+                   line3d=_lib.LINE3D)
