@@ -43,9 +43,12 @@ enum pgx_model_type {
     PGX_PLANE3D = 6,          /* point (x,y,z);          model (a,b,c,d), (a,b,c) unit normal findPlanes           */
     PGX_SPHERE3D = 8,         /* point (x,y,z);          model (cx,cy,cz,r)                   findSpheres          */
     PGX_CIRCLE2D = 10,        /* point (x,y);            model (cx,cy,r)                      findCircles          */
-    PGX_LINE3D = 12           /* point (x,y,z);          model (px,py,pz,dx,dy,dz), a point on the line and a direction
+    PGX_LINE3D = 12,          /* point (x,y,z);          model (px,py,pz,dx,dy,dz), a point on the line and a direction
                                                          (unit from the solver and the refit)  findLines3D          */
-    /* 7, 9 and 11 are not assigned: pgx_model_dims(7, 9 or 11) and pgx_set_points(7, 9 or 11, ...) fail with PGX_ERR_INVALID */
+    PGX_CYLINDER3D = 14       /* point (x,y,z);          model (px,py,pz,dx,dy,dz,r), a point on the axis, a direction (unit from
+                                                         the solver and the refit) and a radius; the minimal solver also reads the
+                                                         resident normals (pgx_set_normals)     findCylinders        */
+    /* 7, 9, 11 and 13 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -93,16 +96,24 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * [U-4] (samples[S][2], S x 3 models), the 3-point plane solver (samples[S][3], S x 4, findPlanes), the 4-point sphere solver
  * (samples[S][4], S x 4, findSpheres; radii outside pgx_set_radius_range give NaN), the 3-point circle solver
  * (samples[S][3], S x 3, findCircles; the same radius range), the 2-point 3-D line solver (samples[S][2], S x 6, findLines3D:
- * a point and a unit direction; coincident points or a length that is not finite give NaN), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
+ * a point and a unit direction; coincident points or a length that is not finite give NaN), the 2-point cylinder solver
+ * (samples[S][2], S x 7, findCylinders: it reads the two samples' resident normals and fails with PGX_ERR_INVALID when
+ * pgx_set_normals has not been called for the resident points; parallel normals, non-finite values and radii outside
+ * pgx_set_radius_range give NaN), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
  * FOUR slots per sample: 4S x 12 [R|t], DefaultPnPEstimator progressivex_python.cpp:119, absent upstream); a degenerate sample
  * or an absent root yields a NaN model (never an inlier).  Other model types: PGX_ERR_INVALID.  `samples` is consumed before the
  * call returns; with models_out == NULL the call does not wait for the solver (the batch stays on the device). */
 int pgx_solve_minimal(pgx_ctx *ctx, const int32_t *samples, int S, double *models_out);
-/* The radii the sphere and the circle solver accept (context state, [0, +inf] at pgx_create; those two solvers read it): a sample whose
- * sphere or circle has r outside [rmin, rmax] yields a NaN model.  NaN, rmin < 0 or rmax < rmin: PGX_ERR_INVALID.  rmax = +inf is allowed. */
+/* The radii the sphere, the circle and the cylinder solver accept (context state, [0, +inf] at pgx_create; those three solvers read it):
+ * a sample whose sphere, circle or cylinder has r outside [rmin, rmax] yields a NaN model.  NaN, rmin < 0 or rmax < rmin:
+ * PGX_ERR_INVALID.  rmax = +inf is allowed. */
 int pgx_set_radius_range(pgx_ctx *ctx, double rmin, double rmax);
+/* Per-point surface normals, n x 3 doubles in the points' order, RESIDENT like the weights of pgx_set_weights and under the same
+ * rules: len == n is checked (PGX_ERR_INVALID), (NULL, 0) clears them, pgx_set_points invalidates them.  They need not be unit
+ * length nor consistently oriented.  Only the cylinder's minimal solver reads them; the point rows stay n x 3. */
+int pgx_set_normals(pgx_ctx *ctx, const double *normals, int64_t len);
 /* The same with the samples DRAWN ON THE DEVICE by the in-repo counter-based generator (csrc/rng.hip.h: Philox4x32-10; sample s
  * of batch `batch` under `key` is a pure function of (key, batch, s); m = the resident model type's minimal sample size).
  * sampler 0: gcransac::sampler::UniformSampler - m distinct indices of range(n) (progressivex_python.cpp:121, 215-245);
@@ -290,9 +301,13 @@ int pgx_one_workgroup_launches(pgx_ctx *ctx, int64_t out[2]);
  *   PGX_GRAM_PNP_GN   Gauss-Newton rows (J_u, r_u), (J_v, r_v) at the pose params = [R|t] 3x4  q = 7
  *   PGX_GRAM_SPHERE   (1, u, v, w, (u u + v v) + w w), (u, v, w) = (p - o) / s, params = (ox,oy,oz,s), 3-D points    q = 5
  *   PGX_GRAM_CIRCLE   (1, u, v, u u + v v), (u, v) = (p - o) / s, params = (ox,oy,s), 2-D points                          q = 4
+ *   PGX_GRAM_CYL_GN   the Gauss-Newton row (gu, gv, t gu, t gv, -1, s - r) of a cylinder at params = (p[3], d[3], r, u[3]), d unit,
+ *                     u unit and orthogonal to d, v = d x u: e = x - p, c = e x d, s = |c|, t = e . d, gu = (c . v) / s,
+ *                     gv = -(c . u) / s; 3-D points                                                                            q = 6
  * Selection: PGX_SEL_INDEX (index[m], host) or PGX_SEL_LABEL (label == `label` on the resident labelling).
- * count = selected points, bad = points skipped because the row is undefined (PnP: depth ~ 0). */
-enum { PGX_GRAM_AFFINE = 0, PGX_GRAM_DLT_H = 1, PGX_GRAM_EPI_F = 2, PGX_GRAM_VP = 3, PGX_GRAM_PNP_GN = 4, PGX_GRAM_SPHERE = 5, PGX_GRAM_CIRCLE = 6 };
+ * count = selected points, bad = points skipped because the row is undefined (PnP: depth ~ 0; cylinder: a point on the axis). */
+enum { PGX_GRAM_AFFINE = 0, PGX_GRAM_DLT_H = 1, PGX_GRAM_EPI_F = 2, PGX_GRAM_VP = 3, PGX_GRAM_PNP_GN = 4, PGX_GRAM_SPHERE = 5, PGX_GRAM_CIRCLE = 6,
+       PGX_GRAM_CYL_GN = 7 };
 enum { PGX_SEL_INDEX = 0, PGX_SEL_LABEL = 1 };
 int pgx_set_weights(pgx_ctx *ctx, const double *weights, int64_t len);
 int pgx_gram(pgx_ctx *ctx, int kind, const double *params, int nparams, int sel, const int32_t *index, int64_t m,

@@ -215,7 +215,7 @@ void pgx_destroy(pgx_ctx* ctx)
                       &ctx->red_partials, &ctx->red_out, &ctx->dq, &ctx->kmodels, &ctx->labels, &ctx->goff,
                       &ctx->gidx, &ctx->gmult, &ctx->grev, &ctx->scratch, &ctx->fit_scratch, &ctx->pts_s, &ctx->pts32_s,
                       &ctx->pmax_s, &ctx->comp_s, &ctx->pperm, &ctx->gbounds, &ctx->masks_s, &ctx->cull_lists, &ctx->cull_counts, &ctx->score_wl, &ctx->gc, &ctx->gc_sel,
-                      &ctx->weights, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops};
+                      &ctx->weights, &ctx->normals, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops};
     for (DevBuf* b : bufs) release(*b);
     for (DevBuf& b : ctx->slots) release(b);
     release(ctx->h_res);
@@ -357,6 +357,7 @@ int pgx_set_points(pgx_ctx* ctx, int model_type, const double* points, int64_t n
     ctx->batch.points_changed();   // (before the fallible work: the old points are gone whether or not the new ones arrive)
     ctx->dq_n = 0; ctx->L = 0; ctx->labels_n = 0;
     ctx->weights_n = 0;  // weights belong to a point set
+    ctx->normals_n = 0;  // and so do normals
     ctx->score_global_n = 0;   // the fixed-point scale of a sharded job belongs to that job's point set
     expansion_points_changed(ctx);
     // upload + every derived copy on the device (setpoints.hip): filter scales, f32 rows, Morton order, group bounds
@@ -916,6 +917,21 @@ int pgx_set_weights(pgx_ctx* ctx, const double* weights, int64_t len)
     PGX_HIP(ctx, hipMemcpyAsync(ctx->weights.p, weights, (size_t)len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->weights_n = len;
+    return PGX_OK;
+}
+
+int pgx_set_normals(pgx_ctx* ctx, const double* normals, int64_t len)
+{
+    CTX_GUARD(ctx);
+    if (!normals || len == 0) { ctx->normals_n = 0; return PGX_OK; }  // clears
+    if (ctx->n <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_set_normals: points not set");
+    if (len != ctx->n)
+        return fail(ctx, PGX_ERR_INVALID, "pgx_set_normals: %lld normals for %lld points", (long long)len, (long long)ctx->n);
+    ctx->normals_n = 0;   // (a failed upload leaves none)
+    PGX_TRY(ensure(ctx, ctx->normals, (size_t)len * 3 * sizeof(double)));
+    PGX_HIP(ctx, hipMemcpyAsync(ctx->normals.p, normals, (size_t)len * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->normals_n = len;
     return PGX_OK;
 }
 

@@ -68,6 +68,7 @@ struct GenDltH { static constexpr int Q = 9, D = 4; };
 struct GenEpiF { static constexpr int Q = 9, D = 4; };
 struct GenVp { static constexpr int Q = 3, D = 4; };
 struct GenPnpGn { static constexpr int Q = 7, D = 5; };
+struct GenCylGn { static constexpr int Q = 6, D = 3; };
 
 // the affine row (1, p[0], .., p[DIM - 1]) of a DIM-D point: lines (2), planes (3) and the 4- and 5-D rows
 template <int DIM> struct GenAffine {
@@ -151,6 +152,32 @@ __device__ __forceinline__ void emit<GenPnpGn>(const double* pt, const FitParams
     const double jv[7] = {a * (-rz) + c * ry, c * (-rx), a * rx, 0.0, a, c, dv};
     acc.add(ju, w);
     acc.add(jv, w);
+}
+// The cylinder's Gauss-Newton row.  prm = (p[3], d[3], r, u[3]): a point on the axis, the unit direction, the radius and a unit vector
+// orthogonal to d; v = d x u (cross3's component order) completes the frame here.  With e = x - p, c = e x d and s = |c| exactly as
+// Residual<kLine3D> computes them (so |a[5]| is Residual<kCylinder3D>::plain bit for bit), t = (e0 d0 + e1 d1) + e2 d2,
+// cv = (c0 v0 + c1 v1) + c2 v2 and cu = (c0 u0 + c1 u1) + c2 u2:
+//   gu = cv / s,  gv = -(cu / s),  a = (gu, gv, t gu, t gv, -1, s - r)
+// the derivatives of f = s - r by (alpha, beta, gamma, eta, rho) at 0 in p + alpha u + beta v, normalise(d + gamma u + eta v),
+// r + rho, followed by f: d s / d p = -(d x c) / s and d x c = e - t d is the radial vector, whose u and v components are -cv and cu;
+// a tilt of d by gamma u moves the axis at height t by t gamma u.  A point on the axis (!(s > 0)) or a non-finite s has no row.
+template <>
+__device__ __forceinline__ void emit<GenCylGn>(const double* pt, const FitParams& prm, Acc<6>& acc, double w, int& bad)
+{
+    const double* m = prm.v;
+    const double* u = prm.v + 7;
+    const double v0 = m[4] * u[2] - m[5] * u[1], v1 = -(m[3] * u[2] - m[5] * u[0]), v2 = m[3] * u[1] - m[4] * u[0];
+    const double e0 = pt[0] - m[0], e1 = pt[1] - m[1], e2 = pt[2] - m[2];
+    const double c0 = e1 * m[5] - e2 * m[4];
+    const double c1 = -(e0 * m[5] - e2 * m[3]);
+    const double c2 = e0 * m[4] - e1 * m[3];
+    const double s = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+    if (!(s > 0.0) || !isfinite(s)) { bad = 1; return; }
+    const double t = (e0 * m[3] + e1 * m[4]) + e2 * m[5];
+    const double gu = ((c0 * v0 + c1 * v1) + c2 * v2) / s;
+    const double gv = -(((c0 * u[0] + c1 * u[1]) + c2 * u[2]) / s);
+    const double a[6] = {gu, gv, t * gu, t * gv, -1.0, s - m[6]};
+    acc.add(a, w);
 }
 
 // ---- the reduction passes, each written once ---------------------------------------------------------------------------------
@@ -484,6 +511,7 @@ static int gram_row_length(pgx_ctx* ctx, const char* who, int kind, int nparams,
     case PGX_GRAM_PNP_GN: *q = 7; if (D != 5 || nparams != 12) return fail(ctx, PGX_ERR_INVALID, "%s: needs 5-D 2D-3D rows and a 3x4 pose", who); break;
     case PGX_GRAM_SPHERE: *q = 5; if (D != 3 || nparams != 4) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 4 parameters (ox, oy, oz, s)", who); break;
     case PGX_GRAM_CIRCLE: *q = 4; if (D != 2 || nparams != 3) return fail(ctx, PGX_ERR_INVALID, "%s: needs 2-D points and 3 parameters (ox, oy, s)", who); break;
+    case PGX_GRAM_CYL_GN: *q = 6; if (D != 3 || nparams != 10) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 10 parameters (p, d, r, u)", who); break;
     default: return fail(ctx, PGX_ERR_INVALID, "%s: unknown row kind %d", who, kind);
     }
     return PGX_OK;
@@ -505,6 +533,7 @@ static void with_gram_generator(int kind, int D, F&& f)
     case PGX_GRAM_VP: f(GenVp{}); break;
     case PGX_GRAM_SPHERE: f(GenRound<3>{}); break;
     case PGX_GRAM_CIRCLE: f(GenRound<2>{}); break;
+    case PGX_GRAM_CYL_GN: f(GenCylGn{}); break;
     default: f(GenPnpGn{}); break;
     }
 }

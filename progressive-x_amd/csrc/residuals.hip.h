@@ -1,6 +1,6 @@
 // residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the geometric primitives: the two
 // families flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension, and the 3-D line
-// (distance to an axis).  gfx950 device code.
+// (distance to an axis) and the cylinder (that distance less a radius).  gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -20,8 +20,8 @@ namespace pgx {
 
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
-    kSphere3D = 8, kCircle2D = 10, kLine3D = 12,
-    kNumModelTypes = 13   // 7, 9 and 11 are not assigned (pgx_model_dims(7), (9) and (11) are errors)
+    kSphere3D = 8, kCircle2D = 10, kLine3D = 12, kCylinder3D = 14,
+    kNumModelTypes = 15   // 7, 9, 11 and 13 are not assigned (pgx_model_dims(7), (9), (11) and (13) are errors)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -107,6 +107,26 @@ template <> struct Residual<kLine3D> : NoProjectiveMap {
     }
     template <class PT, class MD>
     static __device__ __forceinline__ double plain(const PT& p, const MD& m) { return sqrt(squared(p, m)); }
+};
+
+// Cylinder (findCylinders; no reference counterpart): model (p[3], d[3], r), a point on the axis, a direction and a radius.  The 3-D
+// line's distance followed by the round family's last step:
+//   q = Residual<kLine3D>::squared(x, m)  (the same expressions: the code is shared),  plain = |sqrt(q) - r|,  squared = plain * plain.
+// The direction is taken as given, as for kLine3D (unit from the solver and the refit; otherwise the axis distance comes times |d|).
+// Every entry of (p, d) enters q and r enters the subtraction: a NaN in any of the seven entries makes every residual NaN.  d = 0 makes
+// q = 0 and every residual |r|.  r = 0 gives the 3-D line's residual, r < 0 the axis distance plus |r|.  This operation order is the
+// contract of every cylinder check (tests restate it in numpy).
+template <> struct Residual<kCylinder3D> : NoProjectiveMap {
+    static constexpr int D = 3, P = 7, sample = 2, slots = 1, bound = kBoundBall;
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        return fabs(sqrt(Residual<kLine3D>::squared(p, m)) - m[6]);
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double r = plain(p, m);
+        return r * r;
+    }
 };
 
 // DefaultHomographyEstimator (progressivex_python.cpp:252) [U-1]: one-way forward transfer error,
@@ -216,6 +236,7 @@ template <class F> inline bool with_model_type(int mt, F&& f) {
     case kSphere3D: f(std::integral_constant<int, kSphere3D>{}); return true;
     case kCircle2D: f(std::integral_constant<int, kCircle2D>{}); return true;
     case kLine3D: f(std::integral_constant<int, kLine3D>{}); return true;
+    case kCylinder3D: f(std::integral_constant<int, kCylinder3D>{}); return true;
     default: return false;
     }
 }

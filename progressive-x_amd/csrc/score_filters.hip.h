@@ -748,8 +748,8 @@ template <> struct Filter32<kLine3D> {
         ln.nrm = f32_up(dn);
         return ln;
     }
-    // s~ and l~ of a point or a centre
-    static __device__ __forceinline__ float dist(const float* p, const Lane& ln, float* l1) {
+    // s~ and l~ of a point or a centre (any lane with p[3] and d[3]: the cylinder's filter calls this too)
+    template <class L> static __device__ __forceinline__ float dist(const float* p, const L& ln, float* l1) {
         const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];
         const float* d = ln.d;
         const float c0 = __builtin_fmaf(e1, d[2], -(e2 * d[1]));
@@ -771,6 +771,98 @@ template <> struct Filter32<kLine3D> {
         float l1;
         const float s = dist(g, ln, &l1);
         const float m = s - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
+// ---- cylinders: r = | |(x - p) x d| - cr | (Residual<kCylinder3D>), inlier iff r^2 < T2 ----------------------------------------------
+// The 3-D line's distance followed by the round family's last step, and so is the test.  Homogeneous in the direction only: with the
+// 3-D line's sc = pow2_normaliser<3>(d), s* = |(x - p) x (d sc)| and the radius in the same units, R = cr sc (exact in f64: a power of
+// two), the residual times sc is |s* - R|, tested against Ts = T sc.  Scaling by sc commutes with the exact path, root included: the
+// exact path's c on d sc is its c on d times sc, its sum of squares is q sc^2, and sc^2 is an EVEN power of two, so the correctly
+// rounded sqrt(q sc^2) is sc sqrt(q) bit for bit; the subtraction of cr sc and the square scale along.  The exact path's decision on
+// (d, cr, T2) is the one its arithmetic would take on (d sc, R, T2 sc^2).  Per point, in f32 - this operation order is the contract
+// of the f32 test (tests restate it with fma as one rounding):
+//   s~, l~ = Filter32<kLine3D>::dist(x~, p~, d~)  (the same code),   r~ = (float)(cr sc),   n~ = s~ - r~
+// With u = 2^-24 and the 3-D line's terms as derived above (inputs, e~, c~_k, q~, sqrtf: sqrt(3) u |d| P + u |d| |p| + 7.5 u |d~| |e~|
+// and the underflow floor) the cylinder adds:
+//   input r~   |r~ - R| <= u |R|, and n is 1-Lipschitz in R: u |R|
+//   exact path its extra root is one more relative 2^-53 on s_c <= |e| |d|: the 3-D line's 4 + 2 become 4 + 2 + 1 = 7 units of 2^-53
+//              |e| |d|, still < 2^-50 |e| |d| = u 2^-26 |e| |d|, which the 3-D line's e2 already carries; the subtraction s_c - cr is
+//              rounded once, relatively, 2^-53 |s_c - cr|, which is part of the T'' margin below (as in the round family)
+//   n~         the subtraction s~ - r~ is rounded once, relatively: n~ = (s~ - r~)(1 + t), |t| <= u.  Charged to the T'' margin and not
+//              to E, as the round family charges it: m > T'' gives |s~ - r~| >= (T'' + E)(1 - u), Ts (1 + 2^-6)(1 - u) > Ts (1 + 2^-7),
+//              and E (1 - u) covers the terms as soon as E carries a relative margin of u over them (it carries > 6 %)
+// so |(s~ - r~) - (s_c sc - R)| <= sqrt(3) u |d| P + u (|d| |p| + |R|) + (7.5 + 2^-26) u |d~| |e~| + O(u^2), and with the 3-D line's D:
+//   E = e1 P + e0 + e2 l~      e1 = 2 u D                              >= 1.15 * sqrt(3) u |d|          D = 1.001 |d| (f64, rounded up)
+//                              e0 = 2 u (D |p| 1.001 + |R|) + 1e-18    >= 2 * u (|d| |p| + |R|), + 4 * 2.2e-19
+//                              e2 = 8 u D                              >= 1.06 * (7.5 + 2^-26) u |d~|
+//   reject  <=>  m := |n~| - E > T'' = Ts (1 + 2^-6):  m is rounded once and monotonically, so |s_c sc - R| > Ts (1 + 2^-7), and the
+//   computed residual's square, which the exact path compares, exceeds Ts^2 = T2 sc^2.
+// Group test on the 3-D ball rows (stored centre g, radius rho, Pmax) that planes, spheres and lines get: s* is |d|-Lipschitz in x, so
+// every member's s* lies in [s*_g - |d| rho, s*_g + |d| rho] and its residual is at least |s*_g - R| - |d| rho, less the errors above
+// with P = Pmax and |e|_1 <= |e_g|_1 + sqrt(3) rho:
+//   reject the group  <=>  |s~_g - r~| - E(Pmax, l~_g + 1.74 rho) - 1.001 D rho > 1.001 T''.
+// One rule for points outside the cylinder, inside it, for cr = 0 (the 3-D line) and cr < 0 (every residual is s + |cr|).
+// Switch-off, E = inf and the exact path decides: the 3-D line's cases - coordinates beyond 1e17 or |p| beyond 1e17, Ts outside the
+// ordinary f32 range, a direction outside pow2_normaliser's band (d = 0, whose residuals are all |cr| on the exact path, and Inf
+// entries among them) - and a radius beyond 1e17 in the filter's units (|R| > 1e17; Inf included: r~ must stay an ordinary f32, or
+// s~ - inf would reject everything.  inf - inf is NaN, and a NaN comparison is false).  A NaN entry culls the hypothesis outright (all
+// seven enter every residual).  The exact path is the 3-D line's 17 FP64 operations plus a root, a subtraction and a square.
+template <> struct Filter32<kCylinder3D> {
+    using Line = Filter32<kLine3D>;
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    struct Lane { float p[3]; float d[3]; float r, e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
+    // reject() reads p, d, r, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject)
+    static constexpr int kStagedVals = 11;
+    static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, r) == 6 * sizeof(float) && offsetof(Lane, e1) == 7 * sizeof(float) &&
+                  offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
+                  sizeof(Lane) == 13 * sizeof(float), "p, d, r, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        const double d0[3] = {m[3], m[4], m[5]};
+        bool off;
+        const double sc = pow2_normaliser<3>(d0, &off);
+        bool nan = !(m[6] == m[6]);
+        double d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k] = d0[k] * sc;
+            ln.p[k] = (float)m[k];
+            ln.d[k] = (float)d[k];
+            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
+        }
+        ln.nanh = nan ? 1.0f : 0.0f;
+        const double R = m[6] * sc;        // the radius in the scaled direction's units
+        ln.r = (float)R;
+        const double Ts = sqrt(T2) * sc;   // the threshold in the same units: must be an ordinary f32 as well
+        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
+        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
+        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(fabs(R) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
+        const double u = 5.9604644775390625e-8;
+        ln.e1 = f32_up(2.0 * u * dn);
+        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * (dn * pn + fabs(R)) + 1e-18);   // inf: nothing is rejected
+        ln.e2 = f32_up(8.0 * u * dn);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        ln.nrm = f32_up(dn);
+        return ln;
+    }
+    // s~ and l~ of a point or a centre: the 3-D line's code on this lane's p and d
+    static __device__ __forceinline__ float dist(const float* p, const Lane& ln, float* l1) { return Line::dist(p, ln, l1); }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        float l1;
+        const float s = dist(p, ln, &l1);
+        const float m = fabsf(s - ln.r) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (centre[3], rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
+        float l1;
+        const float s = dist(g, ln, &l1);
+        const float m = fabsf(s - ln.r) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
         return m > ln.tpp * 1.001f;
     }
 };

@@ -30,7 +30,11 @@
 //     2-D circle through three points   findCircles' minimal solver: Cramer's rule on the 2x2 system (det == 0: collinear points)
 //   3-D line through two points         findLines3D's minimal solver (no reference counterpart): d = (b - a) / |b - a|, p = a;
 //                                       coincident points and a length that is not finite give NaN
-// The six solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line) share one kernel shell, solve_kernel<MT>;
+//   cylinder through two oriented points findCylinders' minimal solver (no reference counterpart): the axis along na x nb through the
+//                                       point where a + s na and b + t nb cross seen along it, r = |s| |na|; the normals are the
+//                                       resident side array of pgx_set_normals; parallel normals, non-finite values and radii
+//                                       outside pgx_set_radius_range give NaN
+// The seven solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line, cylinder) share one kernel shell, solve_kernel<MT>;
 // the 7-point, 4-point and P3P solvers run one lane per sample in kernels of their own.
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
@@ -58,12 +62,14 @@ __device__ __forceinline__ void cross3(double a1, double b1, double c1, double a
 }
 
 // ---- the lane-per-model solvers: one __device__ function per type, one kernel shell ---------------------------------------------
-// solve_minimal(type, p, rmin, rmax, m): p = the sample's Residual<MT>::sample point rows (all inside the point set), m = the model,
-// preset to NaN - a degenerate sample leaves it so.  rmin, rmax: the context's pgx_set_radius_range (the round family reads them).
+// solve_minimal(type, p, nq, rmin, rmax, m): p = the sample's Residual<MT>::sample point rows (all inside the point set), nq = the same
+// points' rows of the resident normals (pgx_set_normals; only the cylinder reads them, and the launch refuses it without them), m = the
+// model, preset to NaN - a degenerate sample leaves it so.  rmin, rmax: the context's pgx_set_radius_range (the round family and the
+// cylinder read them).
 template <int MT> using Type = std::integral_constant<int, MT>;
 
 // 2-point line [U-4]: unit normal (-dy, dx) / |d|, offset c = -(n . a); coincident points (ln == 0; also false on NaN) give NaN.
-__device__ __forceinline__ void solve_minimal(Type<kLine2D>, const double* const* p, double, double, double* m)
+__device__ __forceinline__ void solve_minimal(Type<kLine2D>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double ax = p[0][0], ay = p[0][1];
     const double dx = p[1][0] - ax, dy = p[1][1] - ay;
@@ -76,7 +82,7 @@ __device__ __forceinline__ void solve_minimal(Type<kLine2D>, const double* const
 }
 
 // vanishing point of two segments (solver_vanishing_point_two_lines.h:174-182); parallel or identical lines give NaN.
-__device__ __forceinline__ void solve_minimal(Type<kVanishingPoint>, const double* const* p, double, double, double* m)
+__device__ __forceinline__ void solve_minimal(Type<kVanishingPoint>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double *a = p[0], *b = p[1];
     double l0[3], l1[3], v[3];
@@ -91,7 +97,7 @@ __device__ __forceinline__ void solve_minimal(Type<kVanishingPoint>, const doubl
 //   u = p1 - p0, v = p2 - p0 (componentwise), n = cross3(u, v), ln = sqrt((n0 n0 + n1 n1) + n2 n2),
 //   a = n0 / ln, b = n1 / ln, c = n2 / ln, d = -((a x0 + b y0) + c z0).
 // ln == 0 (coincident or collinear points; also false on NaN) gives a NaN model.
-__device__ __forceinline__ void solve_minimal(Type<kPlane3D>, const double* const* p, double, double, double* m)
+__device__ __forceinline__ void solve_minimal(Type<kPlane3D>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double *p0 = p[0], *p1 = p[1], *p2 = p[2];
     double nv[3];
@@ -121,7 +127,7 @@ __device__ __forceinline__ void accept_round(double det, const double* c, double
 //   a_i = p_i - p0 (componentwise, i = 1..3), h_i = 0.5 ((a_i0 a_i0 + a_i1 a_i1) + a_i2 a_i2),
 //   n1 = cross3(a2, a3), n2 = cross3(a3, a1), n3 = cross3(a1, a2), det = (a1_0 n1_0 + a1_1 n1_1) + a1_2 n1_2,
 //   e_k = ((h1 n1_k + h2 n2_k) + h3 n3_k) / det, r = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2), c = p0 + e.
-__device__ __forceinline__ void solve_minimal(Type<kSphere3D>, const double* const* p, double rmin, double rmax, double* m)
+__device__ __forceinline__ void solve_minimal(Type<kSphere3D>, const double* const* p, const double* const*, double rmin, double rmax, double* m)
 {
     const double* p0 = p[0];
     double a[3][3], h[3];
@@ -144,7 +150,7 @@ __device__ __forceinline__ void solve_minimal(Type<kSphere3D>, const double* con
 // 3-point circle -> (cx, cy, r).  Operation order (the contract; CircleEstimator.minimal restates it):
 //   a_i = p_i - p0 (componentwise, i = 1, 2), h_i = 0.5 (a_i0 a_i0 + a_i1 a_i1), det = a_10 a_21 - a_11 a_20,
 //   e_0 = (h_1 a_21 - h_2 a_11) / det, e_1 = (a_10 h_2 - a_20 h_1) / det, r = sqrt(e_0 e_0 + e_1 e_1), c = p0 + e.
-__device__ __forceinline__ void solve_minimal(Type<kCircle2D>, const double* const* p, double rmin, double rmax, double* m)
+__device__ __forceinline__ void solve_minimal(Type<kCircle2D>, const double* const* p, const double* const*, double rmin, double rmax, double* m)
 {
     const double *p0 = p[0], *p1 = p[1], *p2 = p[2];
     const double a10 = p1[0] - p0[0], a11 = p1[1] - p0[1], a20 = p2[0] - p0[0], a21 = p2[1] - p0[1];
@@ -161,7 +167,7 @@ __device__ __forceinline__ void solve_minimal(Type<kCircle2D>, const double* con
 //   v = b - a (componentwise), ln = sqrt((v0 v0 + v1 v1) + v2 v2), d = v / ln, p = a.
 // ln == 0 (coincident points; also false on NaN) gives a NaN model, and so does a non-finite ln, unlike the plane solver: v / inf
 // would be a zero direction, and every point is an inlier of that.
-__device__ __forceinline__ void solve_minimal(Type<kLine3D>, const double* const* p, double, double, double* m)
+__device__ __forceinline__ void solve_minimal(Type<kLine3D>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double *a = p[0], *b = p[1];
     const double v0 = b[0] - a[0], v1 = b[1] - a[1], v2 = b[2] - a[2];
@@ -176,11 +182,45 @@ __device__ __forceinline__ void solve_minimal(Type<kLine3D>, const double* const
     }
 }
 
-// The shell: samples[S][sample] -> S x P models, one lane per padded model.  An index outside 0 .. n-1 gives a NaN model.
+// 2-point cylinder from oriented points -> (c, d, r), a point on the axis, a unit direction and a radius (findCylinders; no reference
+// counterpart).  Both normals are orthogonal to the axis and both points lie r from it, so with samples (a, b) and their normals
+// (na, nb), which need be neither unit nor consistently signed: the axis runs along na x nb, and it meets the line a + s na where
+// that line, seen along the axis, crosses the line b + t nb.  Operation order (the contract; CylinderEstimator.minimal restates it):
+//   D = cross3(na, nb), dd = (D0 D0 + D1 D1) + D2 D2, ln = sqrt(dd), d = D / ln,
+//   v = b - a (componentwise), k = (v0 d0 + v1 d1) + v2 d2, w = v - k d (componentwise: w_j = v_j - k d_j),
+//   x = cross3(w, nb), s = ((x0 D0 + x1 D1) + x2 D2) / dd,
+//   c = a + s na (c_j = a_j + s na_j), r = |s| sqrt((na0 na0 + na1 na1) + na2 na2).
+// (w + t nb = s na crossed with nb and dotted with D gives s |D|^2 = (w x nb) . D.)  Flipping or rescaling a normal changes D and s
+// together and leaves c, r and the axis - d up to its sign - the same up to rounding.  The model stays NaN unless ln > 0 and ln is
+// finite (parallel normals, a zero normal, coincident samples with one normal, the same index twice, non-finite input or an
+// overflowing square), every entry of c and r are finite, and rmin <= r <= rmax.  Coincident points with different normals give r = 0.
+__device__ __forceinline__ void solve_minimal(Type<kCylinder3D>, const double* const* p, const double* const* nq, double rmin, double rmax, double* m)
+{
+    const double *a = p[0], *b = p[1], *na = nq[0], *nb = nq[1];
+    double D[3], x[3];
+    cross3(na[0], na[1], na[2], nb[0], nb[1], nb[2], D);
+    const double dd = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2];
+    const double ln = sqrt(dd);
+    if (!(ln > 0.0) || !isfinite(ln)) return;
+    const double d0 = D[0] / ln, d1 = D[1] / ln, d2 = D[2] / ln;
+    const double v0 = b[0] - a[0], v1 = b[1] - a[1], v2 = b[2] - a[2];
+    const double k = (v0 * d0 + v1 * d1) + v2 * d2;
+    cross3(v0 - k * d0, v1 - k * d1, v2 - k * d2, nb[0], nb[1], nb[2], x);
+    const double s = ((x[0] * D[0] + x[1] * D[1]) + x[2] * D[2]) / dd;
+    const double c0 = a[0] + s * na[0], c1 = a[1] + s * na[1], c2 = a[2] + s * na[2];
+    const double r = fabs(s) * sqrt((na[0] * na[0] + na[1] * na[1]) + na[2] * na[2]);
+    if (!(isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(r) && r >= rmin && r <= rmax)) return;
+    m[0] = c0; m[1] = c1; m[2] = c2;
+    m[3] = d0; m[4] = d1; m[5] = d2;
+    m[6] = r;
+}
+
+// The shell: samples[S][sample] -> S x P models, one lane per padded model.  An index outside 0 .. n-1 gives a NaN model.  normals
+// may be null for every type whose solver does not read them.
 template <int MT>
-__global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ samples,
-                                                            int S, double rmin, double rmax, double* __restrict__ models,
-                                                            int* __restrict__ perm, int Mpad)
+__global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __restrict__ pts, const double* __restrict__ normals, int64_t n,
+                                                            const int* __restrict__ samples, int S, double rmin, double rmax,
+                                                            double* __restrict__ models, int* __restrict__ perm, int Mpad)
 {
     using R = Residual<MT>;
     const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
@@ -195,9 +235,12 @@ __global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __rest
     double m[R::P];
     for (int k = 0; k < R::P; ++k) m[k] = __builtin_nan("");
     if (inb) {
-        const double* p[R::sample];
-        for (int k = 0; k < R::sample; ++k) p[k] = pts + (int64_t)ix[k] * R::D;
-        solve_minimal(Type<MT>{}, p, rmin, rmax, m);
+        const double *p[R::sample], *nq[R::sample];
+        for (int k = 0; k < R::sample; ++k) {
+            p[k] = pts + (int64_t)ix[k] * R::D;
+            nq[k] = normals ? normals + (int64_t)ix[k] * 3 : nullptr;
+        }
+        solve_minimal(Type<MT>{}, p, nq, rmin, rmax, m);
     }
     for (int k = 0; k < R::P; ++k) models[(int64_t)s * R::P + k] = m[k];
 }
@@ -634,7 +677,9 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     const int mt = ctx->model_type;
     ModelInfo mi;
     if (!model_info(mt, &mi) || mi.slots == 0)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+    if (mt == kCylinder3D && ctx->normals_n != ctx->n)
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: the cylinder solver needs the resident points' normals (pgx_set_normals after pgx_set_points)");
     // isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1 for these model types, so the solvers take
     // fscale, which pgx_set_points computes from the caller-visible data: umax is not kept either)
     const bool scaled = mt == kFundamental || mt == kHomography;
@@ -645,6 +690,7 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     PGX_TRY(ensure(ctx, ctx->perm, (size_t)Mpad * sizeof(int)));
     if (!resident) PGX_TRY(upload_samples(ctx, samples, (size_t)S * mi.sample * sizeof(int32_t)));
     const double* pts = ctx->pts.as<double>();
+    const double* normals = ctx->normals_n == ctx->n ? ctx->normals.as<double>() : nullptr;
     const int* smp = ctx->scratch.as<int>();
     double* models = ctx->models.as<double>();
     int* perm = ctx->perm.as<int>();
@@ -657,7 +703,7 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
         with_model_type(mt, [&](auto t) {
             constexpr int MT = decltype(t)::value;
             if constexpr (Residual<MT>::slots > 0 && MT != kFundamental && MT != kHomography && MT != kPnP)
-                hipLaunchKernelGGL((solve_kernel<MT>), gm, bm, 0, ctx->stream, pts, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
+                hipLaunchKernelGGL((solve_kernel<MT>), gm, bm, 0, ctx->stream, pts, normals, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
         });
     PGX_HIP(ctx, hipGetLastError());
     if (models_out) {

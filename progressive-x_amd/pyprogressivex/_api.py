@@ -1,4 +1,4 @@
-"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -79,8 +79,8 @@ def _run(estimator, pts, graph_points, radius, sampler_factory, *, threshold, co
          do_logging=False, weights=None, seed=None, max_outer_iterations=10, neighborhood="flann_like",
          local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack",
          setup=None):
-    """setup(ctx), when given, runs on the context before anything else touches it (per-call context state such as findSpheres'
-    radius range)."""
+    """setup(ctx), when given, runs on the context right after the run has made the points resident (per-call context state such as
+    findSpheres' radius range and findCylinders' normals, which belong to a point set)."""
     n = pts.shape[0]
     if sampler_rng not in ("numpy", "philox"):
         raise ValueError("sampler_rng should be 'numpy' or 'philox'")
@@ -92,8 +92,6 @@ def _run(estimator, pts, graph_points, radius, sampler_factory, *, threshold, co
         _unknown_sampler(sampler_factory.sampler_id)
         return [], np.zeros(n, dtype=np.int32), None
     ctx = _context()
-    if setup is not None:
-        setup(ctx)
     # multi-GPU, OPT-IN (distributed=True or PGX_MULTI_GPU=1, one process per GPU, WORLD_SIZE > 1): the proposal batches are
     # sharded over the ranks and the score triples all-gathered over RCCL (parallel.py); everything else runs replicated, so
     # every rank returns the same result.  Every rank must make this call with the same data (checked) and draw the same
@@ -158,7 +156,7 @@ def _run(estimator, pts, graph_points, radius, sampler_factory, *, threshold, co
                          neighborhood=str(neighborhood), sample_size=int(estimator.sample_size),
                          nonminimal_sample_size=int(estimator.nonminimal_sample_size), settings=s))
     px = _engine.ProgressiveX(ctx, estimator, pts, graph, sampler, s, scoring_exponent=scoring_exponent,
-                              do_logging=do_logging, graph_resident=resident, exchange=exchange, trace=trace)
+                              do_logging=do_logging, graph_resident=resident, exchange=exchange, trace=trace, setup=setup)
     models, stats = px.run()
     labeling = np.asarray(stats.labeling, dtype=np.int64).astype(np.int32)     # bindings.cpp:152-156
     return models, labeling, stats
@@ -326,7 +324,7 @@ def _point_cloud(points, weights, n_min, dim=3):
 
 
 def _radius_range(radius_range):
-    """radius_range=None or (rmin, rmax) of findSpheres / findCircles -> (rmin, rmax), checked"""
+    """radius_range=None or (rmin, rmax) of findSpheres / findCircles / findCylinders -> (rmin, rmax), checked"""
     if radius_range is None:
         return 0.0, np.inf
     try:
@@ -365,20 +363,19 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
 
 
 def _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
-    """findPlanes / findSpheres / findCircles / findLines3D behind their signatures: the estimator says the point dimension (its model type's), the
-    sample size (= the fewest points accepted) and the columns of a model.  Only an estimator with a radius takes radius_range: it goes
-    to the estimator and, per call, to the context."""
+    """findPlanes / findSpheres / findCircles / findLines3D / findCylinders behind their signatures: the estimator says the point dimension (its
+    model type's), the sample size (= the fewest points accepted) and the columns of a model.  Only an estimator with a radius takes
+    radius_range (its takes_radius_range says so): it goes to the estimator, and the estimator's context_setup puts its per-call state on
+    the context."""
     points, w, grid_pts, ext = _point_cloud(points, weights, est.sample_size, dim=_lib.POINT_DIM[est.model_type])
-    setup = None
-    if isinstance(est, _estimators.RoundEstimator):
-        rmin, rmax = est.radius_range = _radius_range(radius_range)
-        setup = lambda ctx: ctx.set_radius_range(rmin, rmax)   # noqa: E731
+    if est.takes_radius_range:
+        est.radius_range = _radius_range(radius_range)
     if do_logging and sampler_id == 1:
         print("Note: PROSAC sampler requires the points to be order by quality, e.g., SNN ratio.")
     models, labels, _ = _run(est, points, points, radius,
                              _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac", 3: "pnapsac"}, grid_pts, ext,
                                               est.sample_size),
-                             do_logging=bool(do_logging), weights=w, setup=setup, **run_kw)
+                             do_logging=bool(do_logging), weights=w, setup=est.context_setup, **run_kw)
     return _stack(est, models, est.cols), labels
 
 
@@ -449,6 +446,44 @@ def findLines3D(points, weights=None, threshold=0.05, conf=0.5, spatial_coherenc
     or spurious lines through the outliers or between two lines are accepted.  It also has an upper side: the run stops when fewer
     inliers than that are predicted as still unseen, and in the same measurement no sampler returned all six lines with n / 40."""
     return _find_primitive(_estimators.Line3DEstimator(), points, weights, None, sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+
+
+def findCylinders(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
+                  neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
+                  minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
+                  do_logging=False, *, radius_range=None, seed=None, max_outer_iterations=10, neighborhood="flann_like",
+                  local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+    """Multi-cylinder fitting of an oriented 3-D point cloud: pipes, columns, trunks, tanks (no reference counterpart: findSpheres'
+    pipeline with a 2-point solver on points with normals and a Gauss-Newton refit of the geometric distance).  points [n, 3], normals
+    [n, 3] (required): one surface normal per point, as a normal estimator gives them - they may be unsigned (either orientation) and
+    need not be unit length; only the minimal solver reads them, and a sample whose normals are parallel, zero or not finite gives no
+    hypothesis.  Returns (cylinders[K, 7] float64 (px, py, pz, dx, dy, dz, r): a point on the axis - the foot of its points' mean -,
+    a unit direction and a radius; labels[n] int32) in findPlanes' labelling convention.  The axis is a line: the model says nothing
+    about where the cylinder ends.  threshold bounds the distance from the point to the cylinder's surface, abs(|(x - p) x d| - r), in
+    the cloud's units.  radius_range=(rmin, rmax) (keyword-only; default: any radius) drops hypotheses and refits whose radius lies
+    outside it.  `weights` [n], when given, weight the least-squares refits.  Sampler ids as findSpheres': 0 uniform, 1 PROSAC, 2 NAPSAC
+    on the neighbourhood graph, 3 (the default, following findSpheres) Progressive NAPSAC on a grid over the bounding box; any other id
+    prints to stderr and returns zero models.  Samplers 3 and 1 take the points as ordered by quality (every proposal starts from the
+    first points): shuffle a cloud that comes in scan order.  Measured on make_cylinders scenes (six cylinders, half outliers, 10^4 to
+    10^6 points, radius_range=(0.1, 2)), nothing recovers all six reliably: with minimum_point_number = n / 40 every
+    sampler returned three to five cylinders, all but one of them true ones; with n / 150 the default found five, six and five of six
+    and uniform sampling six at 10^4 and 10^6, but 8 of those 12 runs also returned up to three cylinders that match no true one.  No
+    sampler stood out (NAPSAC, the fastest for 3-D lines, was the slowest at 10^6).  minimum_point_number has to exceed the outliers a
+    shell of width 3 x threshold about the largest admitted cylinder holds, and what a cylinder through the crossing of two true ones
+    collects, or spurious cylinders are accepted - an rmax keeps that shell small; it also has the upper side findLines3D describes:
+    the run stops when fewer inliers than that are predicted as still unseen."""
+    est = _estimators.CylinderEstimator()
+    points, nrm = _as_f64(points), _as_f64(normals)
+    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
+        raise ValueError("normals should be an array with dims [n,3], one row per point")
+    est.normals = nrm
+    return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
                            threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
                            maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
                            minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,

@@ -40,6 +40,12 @@ class Estimator:
             return ctx.eigh_smallest_batch(A)[0]
         return np.linalg.eigh(A)[1][:, :, 0]
 
+    takes_radius_range = False   # True: the estimator has a `radius_range` that the radius_range= keyword of its entry point sets
+
+    def context_setup(self, ctx):
+        """Per-call context state this estimator's device solver reads besides the points (the radius range, the cylinder's normals);
+        the run calls it once the points are resident, since some of that state belongs to a point set.  Default: none."""
+
     def minimal(self, pts, samples):
         """samples [S, m] -> (models [H, P], sample_of_model [H]); several or zero solutions per sample allowed."""
         raise NotImplementedError
@@ -290,6 +296,10 @@ class RoundEstimator(Estimator):
     device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
     gram_kind = None           # GRAM_CIRCLE / GRAM_SPHERE: the rows (1, q, |q|^2) of the refit
     radius_range = (0.0, np.inf)   # the radii a model may have (findSpheres / findCircles set it; the device solver reads pgx_set_radius_range)
+    takes_radius_range = True
+
+    def context_setup(self, ctx):
+        ctx.set_radius_range(*self.radius_range)
 
     def _in_range(self, r):
         return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
@@ -361,6 +371,131 @@ class SphereEstimator(RoundEstimator):
             models = np.column_stack([p0[:, 0] + e[0], p0[:, 1] + e[1], p0[:, 2] + e[2], r])
             ok = (det != 0) & np.isfinite(models).all(axis=1) & self._in_range(r)
         return models[ok], np.nonzero(ok)[0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Cylinder (findCylinders; no reference counterpart): 2-point solver on oriented points, Gauss-Newton refit on five parameters
+# ---------------------------------------------------------------------------------------------------------------------
+def _cylinder_frame(d):
+    """The one rule for the chart's u, [B, 3] unit directions d -> [B, 3]: the coordinate axis of d's smallest-magnitude component (the
+    first of equals) crossed with d, normalised.  That axis is the one farthest from d, so |axis x d| >= sqrt(2 / 3)."""
+    axis = np.zeros_like(d)
+    axis[np.arange(len(d)), np.argmin(np.abs(d), axis=1)] = 1.0
+    u = np.cross(axis, d)
+    return u / np.linalg.norm(u, axis=1)[:, None]
+
+
+class CylinderEstimator(Estimator):
+    """Model (p[3], d[3], r): a point on the axis, a unit direction, a radius.  `normals` [n, 3] (per point, neither unit nor
+    consistently signed) are read by the minimal solver alone; `radius_range` bounds the radii of hypotheses and refits.
+
+    nonminimal_sample_size is 5, the number of parameters of the chart (a line in space has four, the radius is the fifth): with fewer
+    points the 5x5 normal matrix is singular for every configuration, with five it is regular for points in general position.  It is
+    not raised above that: the refit always starts from a model that was scored (`init`), the local optimisation draws 14 points, and a
+    refit of a small, noisy selection that comes out worse than its start loses to it when both are scored."""
+    model_type = _lib.CYLINDER3D
+    sample_size = 2
+    nonminimal_sample_size = 5
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
+    cols = 7
+    takes_radius_range = True
+    radius_range = (0.0, np.inf)
+    normals = None             # [n, 3] float64, in the points' order (findCylinders sets it)
+
+    def context_setup(self, ctx):
+        ctx.set_radius_range(*self.radius_range)
+        ctx.set_normals(self.normals)
+
+    def _in_range(self, r):
+        return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
+
+    def minimal(self, pts, samples):
+        """samples [S, 2] -> cylinders (c, d, r), bitwise csrc/solve.hip's solve_minimal for cylinders, with (a, b) the samples and
+        (na, nb) their normals: D = cross3(na, nb), dd = (D0 D0 + D1 D1) + D2 D2, ln = sqrt(dd), d = D / ln, v = b - a,
+        k = (v0 d0 + v1 d1) + v2 d2, w = v - k d, x = cross3(w, nb), s = ((x0 D0 + x1 D1) + x2 D2) / dd, c = a + s na,
+        r = |s| sqrt((na0 na0 + na1 na1) + na2 na2).  No model unless ln > 0 and finite (parallel or zero normals, the same point
+        twice, non-finite input), c and r are finite and r lies in radius_range."""
+        a, b = pts[samples[:, 0]], pts[samples[:, 1]]
+        nrm = np.asarray(self.normals, dtype=np.float64)
+        na, nb = nrm[samples[:, 0]], nrm[samples[:, 1]]
+        with np.errstate(all="ignore"):
+            D = _cross3(na, nb)
+            dd = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]
+            ln = np.sqrt(dd)
+            d = [D[j] / ln for j in range(3)]
+            v = b - a
+            k = (v[:, 0] * d[0] + v[:, 1] * d[1]) + v[:, 2] * d[2]
+            w = np.column_stack([v[:, j] - k * d[j] for j in range(3)])
+            x = _cross3(w, nb)
+            s = ((x[0] * D[0] + x[1] * D[1]) + x[2] * D[2]) / dd
+            r = np.abs(s) * np.sqrt((na[:, 0] * na[:, 0] + na[:, 1] * na[:, 1]) + na[:, 2] * na[:, 2])
+            models = np.column_stack([a[:, 0] + s * na[:, 0], a[:, 1] + s * na[:, 1], a[:, 2] + s * na[:, 2], d[0], d[1], d[2], r])
+            ok = (ln > 0) & np.isfinite(ln) & np.isfinite(models[:, [0, 1, 2, 6]]).all(axis=1) & self._in_range(r)
+        return models[ok], np.nonzero(ok)[0]
+
+    def _fit_many(self, gram, B, inits, iterations=10):
+        """Geometric least squares, sum w (|(x - p) x d| - r)^2, by Gauss-Newton from `inits` in the shape of PnPEstimator._fit_many:
+        at most 10 iterations on [B, ...] stacks, each ONE Gram request (GRAM_CYL_GN, weight power 1) at params (p, d, r, u) with
+        u = _cylinder_frame(d) and v = d x u.  The rows are (J, f) with J = df / d(alpha, beta, gamma, eta, rho) in the chart
+        p + alpha u + beta v, normalise(d + gamma u + eta v), r + rho (csrc/fit.hip GenCylGn), so delta = pinv(J^T J)(-J^T f) with the
+        cut-off 6 eps, then that update; an item stops at |delta| < 1e-12.  An item fails without an init, with fewer than 5 points,
+        with a point on its axis (bad) or with non-finite sums.  Afterwards the model is made canonical: p slides along d to the foot
+        of the selection's weighted mean (one GRAM_AFFINE request), d is signed like Line3DEstimator's (its largest-magnitude
+        component, the first of equals, positive); a model that is not finite or whose radius is outside radius_range is dropped."""
+        out = [[] for _ in range(B)]
+        have = np.array([ini is not None for ini in inits], dtype=bool)
+        if not have.any():
+            return out
+        m = np.zeros((B, 7))
+        m[:, 5] = 1.0
+        for b in np.nonzero(have)[0]:
+            m[b] = np.asarray(inits[b], dtype=np.float64).reshape(7)
+        with np.errstate(all="ignore"):
+            m[:, 3:6] /= np.linalg.norm(m[:, 3:6], axis=1)[:, None]
+        failed = ~have | ~np.isfinite(m).all(axis=1)
+        running = ~failed
+        for _ in range(iterations):
+            act = np.nonzero(running)[0]
+            if act.size == 0:
+                break
+            u = _cylinder_frame(m[act, 3:6])
+            G, cnt, bad = gram(_lib.GRAM_CYL_GN, np.column_stack([m[act], u]), True, 1, act)
+            A, rhs = G[:, :5, :5], -G[:, :5, 5]
+            ok = (np.asarray(bad) == 0) & (np.asarray(cnt) >= 5) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(rhs).all(axis=1)
+            failed[act[~ok]] = True
+            running[act[~ok]] = False
+            if not ok.any():
+                break
+            act, A, rhs, u = act[ok], A[ok], rhs[ok], u[ok]
+            d = m[act, 3:6]
+            v = np.cross(d, u)
+            delta = np.einsum("bij,bj->bi", np.linalg.pinv(A, rcond=6 * np.finfo(np.float64).eps), rhs)
+            m[act, 0:3] += delta[:, 0:1] * u + delta[:, 1:2] * v
+            d = d + delta[:, 2:3] * u + delta[:, 3:4] * v
+            m[act, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
+            m[act, 6] += delta[:, 4]
+            fin = np.isfinite(m[act]).all(axis=1)
+            failed[act[~fin]] = True
+            running[act[~fin]] = False
+            running[act[np.linalg.norm(delta, axis=1) < 1e-12]] = False
+        rows = np.nonzero(~failed)[0]
+        if rows.size == 0:
+            return out
+        G, _, _ = gram(_lib.GRAM_AFFINE, None, True, 1, rows)
+        W = G[:, 0, 0]
+        with np.errstate(all="ignore"):
+            mean = G[:, 0, 1:] / W[:, None]
+        for k, b in enumerate(rows):
+            p, d, r = m[b, 0:3], m[b, 3:6], m[b, 6]
+            if not (W[k] > 0 and np.isfinite(mean[k]).all()):
+                continue
+            p = p + ((mean[k] - p) @ d) * d
+            if d[int(np.argmax(np.abs(d)))] < 0:
+                d = -d
+            model = np.array([*p.tolist(), *d.tolist(), r])
+            if np.isfinite(model).all() and self._in_range(r):
+                out[b] = [model]
+        return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1027,6 +1162,7 @@ ESTIMATORS = {
     "sphere": SphereEstimator,
     "circle": CircleEstimator,
     "line3d": Line3DEstimator,
+    "cylinder": CylinderEstimator,
     "vanishing_point": VanishingPointEstimator,
     "homography": HomographyEstimator,
     "homography_sym": SymmetricHomographyEstimator,

@@ -108,6 +108,52 @@ def make_lines3d(n_per_line=2000, n_lines=6, n_outliers=12000, sigma=0.01, size=
     return np.ascontiguousarray(np.vstack(pts)), np.concatenate(labels).astype(np.int32), np.array(models).reshape(-1, 6)
 
 
+def make_cylinders(n_per_cylinder=8000, n_cylinders=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.0), length=(3.0, 6.0),
+                   coverage=1.0, normal_noise_deg=5.0, seed=0):
+    """findCylinders' workload: K cylinders with uniformly random unit axis directions, radii uniform in `radius` and lengths uniform in
+    `length`, each lying wholly inside the box [0, size]^3 (the midpoint is drawn where both end discs fit; cylinders may cross); the
+    inliers of cylinder k are uniform on its lateral surface - or, with coverage < 1, on the arc of that fraction of the circumference
+    around a random direction (what one scan sees of a pipe) - with Gaussian noise of `sigma` along the radius; their normals are the
+    radial unit vectors tilted by an angle uniform in [0, normal_noise_deg] about a random axis orthogonal to them, each with a random
+    sign.  The outliers are uniform in the box with uniformly random unit normals.  Returns (points [n, 3], normals [n, 3] (unit),
+    labels [n] (k + 1 = cylinder k, 0 = outlier), gt_cylinders [K, 7] = (midpoint of the axis segment, unit direction, radius)).
+    A pure function of the seed."""
+    rng = np.random.default_rng(seed)
+    if not 0.0 < coverage <= 1.0:
+        raise ValueError("coverage should lie in (0, 1]")
+    if not (0.0 < length[0] <= length[1] and 0.0 < radius[0] <= radius[1] and length[1] + 2.0 * radius[1] <= size):
+        raise ValueError("length and radius should satisfy 0 < min <= max and max length + 2 max radius <= size")
+    pts, nrm, labels, models = [], [], [], []
+    for k in range(n_cylinders):
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        r = rng.uniform(radius[0], radius[1])
+        ln = rng.uniform(length[0], length[1])
+        half = 0.5 * ln * np.abs(d) + r
+        mid = rng.uniform(half, size - half)
+        e1 = np.cross(d, rng.normal(size=3))
+        e1 /= np.linalg.norm(e1)
+        e2 = np.cross(d, e1)
+        t = rng.uniform(-0.5 * ln, 0.5 * ln, n_per_cylinder)
+        phi = rng.uniform(-np.pi * coverage, np.pi * coverage, n_per_cylinder)
+        rad = np.cos(phi)[:, None] * e1 + np.sin(phi)[:, None] * e2
+        pts.append(mid + t[:, None] * d + rad * (r + rng.normal(0, sigma, n_per_cylinder))[:, None])
+        # tilt: rotate rad by `ang` towards a random unit vector orthogonal to it (psi picks it in the tangent plane spanned by d, d x rad)
+        ang = np.deg2rad(rng.uniform(0.0, normal_noise_deg, n_per_cylinder))
+        psi = rng.uniform(0.0, 2.0 * np.pi, n_per_cylinder)
+        tang = np.cos(psi)[:, None] * d + np.sin(psi)[:, None] * np.cross(d, rad)
+        nk = np.cos(ang)[:, None] * rad + np.sin(ang)[:, None] * tang
+        nrm.append(nk * rng.choice([-1.0, 1.0], n_per_cylinder)[:, None])
+        labels.append(np.full(n_per_cylinder, k + 1))
+        models.append(np.concatenate([mid, d, [r]]))
+    pts.append(rng.uniform(0, size, (n_outliers, 3)))
+    no = rng.normal(size=(n_outliers, 3))
+    nrm.append(no / np.linalg.norm(no, axis=1)[:, None])
+    labels.append(np.zeros(n_outliers, dtype=int))
+    return (np.ascontiguousarray(np.vstack(pts)), np.ascontiguousarray(np.vstack(nrm)), np.concatenate(labels).astype(np.int32),
+            np.array(models).reshape(-1, 7))
+
+
 def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.5), coverage=1.0, seed=0):
     """findSpheres' workload: K non-overlapping spheres with radii uniform in `radius` and centres inside the box [0, size]^3 (each
     sphere lies wholly inside it); the inliers of sphere k are uniform on its surface - or, with coverage < 1, on the cap of that
@@ -392,4 +438,4 @@ def misclassification_models(preferences, annotation, K_annot):
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
                    vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D,
-                   line3d=_lib.LINE3D)
+                   line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D)
