@@ -181,12 +181,21 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
 //   64  the filter runs in every lane and the tail group's lanes beyond n are taken out of the ballot by one mask computed once:
 //       no exec region around the filter in every step, no bool between the comparison and the ballot, and a lane's candidate flag
 //       is its bit of the surviving mask as it stands
+// Four of the cull kernel, all on (docs/lab-notebook.md, "Cull kernel: keep words per tile, one generation, a shorter way in"):
+//   128 a wave keeps the tile's keep words in registers - lane i holds the word of group t0 + i - and they are stored once per tile
+//       instead of once per bound test (and once more per culled super-group); an item's weight is the popcount of its four words
+//   256 the pose instances are held to 64 registers, 8 waves per SIMD: all 2 048 workgroups of the metric launch resident at once
+//   512 the first tile's bound rows are requested together with the model and staged before the FP64 preparation (one barrier
+//       instead of two dependent round trips), and a workgroup whose segment lies behind the last group leaves after its zeroing
+//   1024 a bound row is read from LDS as a whole before its test begins: one LDS round trip per test instead of two dependent ones
 #ifndef PGX_SCORE_TRIM
-#define PGX_SCORE_TRIM 71
+#define PGX_SCORE_TRIM 1991
 #endif
 constexpr bool kTrimRows = (PGX_SCORE_TRIM & 1) != 0, kTrimDrain = (PGX_SCORE_TRIM & 2) != 0, kTrimDirect = (PGX_SCORE_TRIM & 4) != 0;
 constexpr bool kTrimLocate = (PGX_SCORE_TRIM & 8) != 0, kTrimArgs = (PGX_SCORE_TRIM & 16) != 0, kTrimItem = (PGX_SCORE_TRIM & 32) != 0,
                kTrimTail = (PGX_SCORE_TRIM & 64) != 0;
+constexpr bool kTrimKeepTile = (PGX_SCORE_TRIM & 128) != 0, kTrimResident = (PGX_SCORE_TRIM & 256) != 0, kTrimEarly = (PGX_SCORE_TRIM & 512) != 0,
+               kTrimRowFirst = (PGX_SCORE_TRIM & 1024) != 0;
 
 // A hypothesis' f32 constants as the cull kernel stores them (hyp32) and the group kernel stages them (LDS): the first kVals
 // floats of Filter32<MT>::Lane in float4 chunks.  Rows of hyp32 are kStride floats apart - 16-byte aligned, 64 bytes for the pose
@@ -253,10 +262,14 @@ constexpr int kCullTile = 64;   // group bounds staged in LDS per step
 
 // The group bounds of a segment are staged in LDS by the whole workgroup (coalesced vector loads, one round trip per 64
 // groups) and read back as broadcasts: with scalar loads a wave paid one ~1 us scalar-cache miss per four groups, and the
-// kernel — a single generation of waves — took as long as that latency chain (43 us for 27 VALU instructions per test).
+// kernel took as long as that latency chain (43 us for 27 VALU instructions per test).
 // (waves per SIMD: the budget the kernel had before it weighed items - 72 registers for the two 12-parameter filters, 64 for the rest;
-// the compiler meets it without scratch, and left alone it gives a wave away on four of the nine types)
-template <int MT> constexpr int kCullWavesPerSimd = (MT == kPnP || MT == kHomographySym) ? 7 : 8;
+// the compiler meets it without scratch, and left alone it gives a wave away on four of the nine types.  At 7 waves per SIMD a CU
+// holds 7 workgroups and the chip 1 792: the metric launch - 2 048 workgroups, 1 960 of them with a tile - is NOT one generation of
+// waves, its last 168 working workgroups start as others retire.  Bit 256 asks 8 of the pose instances.)
+template <int MT> constexpr int kCullWavesPerSimd = ((MT == kPnP && !kTrimResident) || MT == kHomographySym) ? 7 : 8;
+static_assert(kCullWaves == kWlItemWords && kCullTile * kGroupRow == 3 * 64 * kCullWaves && kCullTile / kSuper * kGroupRow <= 64 * kCullWaves,
+              "an item is a workgroup's words; a tile's rows are three loads per thread, its super-group rows less than one");
 // LISTS: also weigh the tile's (group, 4-word) items and append the non-empty ones to the work lists (without: the kernel as it was)
 template <int MT, bool LISTS>
 __global__ __launch_bounds__(64 * kCullWaves) __attribute__((amdgpu_waves_per_eu(kCullWavesPerSimd<MT>))) void score_cull_kernel(
@@ -270,67 +283,154 @@ __global__ __launch_bounds__(64 * kCullWaves) __attribute__((amdgpu_waves_per_eu
     using R = Residual<MT>;
     using F32 = Filter32<MT>;
     __shared__ __attribute__((aligned(16))) float s_gb[kCullTile + kCullTile / kSuper][kGroupRow];  // groups | their super-groups
-    __shared__ unsigned s_wt[kCullWaves][kCullTile];   // work lists: surviving steps per (word of this workgroup, group of the tile)
+    // work lists: surviving steps per (word of this workgroup, group of the tile) - with bit 128 the keep words themselves, [group][word]
+    __shared__ unsigned s_wt[(LISTS && !kTrimKeepTile) ? kCullWaves : 1][kCullTile];
+    __shared__ __attribute__((aligned(16))) unsigned long long s_kw[(LISTS && kTrimKeepTile) ? kCullTile : 1][kCullWaves];
     {
         const int64_t nthreads = (int64_t)gridDim.x * gridDim.y * (64 * kCullWaves);
         for (int64_t i = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (64 * kCullWaves) + threadIdx.x; i < zero_words; i += nthreads) zero[i] = 0ull;
     }
     const int lane = (int)(threadIdx.x & 63);
     const int w = (int)blockIdx.x * kCullWaves + (int)(threadIdx.x >> 6), seg = (int)blockIdx.y;
+    const int g0 = seg * gps, g1 = g0 + gps < groups ? g0 + gps : groups;
+    // a segment behind the last group (the metric launch has 11 of 256) has no tile, and only segment 0 stores the hypotheses' rows
+    if (kTrimEarly && seg != 0 && g0 >= groups) return;
     const int m = w * 64 + lane;
     const bool live = w < W && m < M;
-    double mdl[R::P];
+    // T'' of the group test depends on the launch alone.  Bit 256: computed before anything is loaded and handed to the scalar unit,
+    // so that its FP64 root is not in flight among the preparation's and it takes no vector register in the tile loop.
+    float Tup32 = 0.0f;
+    if constexpr (kTrimResident) Tup32 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(f32_up(sqrt(T2) * (1.0 + 1.0 / 64.0)))));
+    // Bit 512: a tile's rows as straight-line code - every thread requests its three floats of the group rows and its float of the
+    // super-group rows under a clamped index instead of a loop bound (request), and writes them to LDS (commit); what a thread behind
+    // the tile's rows writes is a copy of the last float, into a row no test reads.
+    float rv[3], sv;
+    auto request = [&](int t0, int cnt, int scnt) {
+        const int last = cnt > 0 ? cnt * kGroupRow - 1 : 0, slast = scnt > 0 ? scnt * kGroupRow - 1 : 0;
+        const float* __restrict__ rows = gbounds + (int64_t)t0 * kGroupRow;
+        const float* __restrict__ srows = gbounds + ((int64_t)groups + t0 / kSuper) * kGroupRow;
 #pragma unroll
-    for (int k = 0; k < R::P; ++k) mdl[k] = live ? models[(int64_t)m * R::P + k] : __builtin_nan("");
+        for (int k = 0; k < 3; ++k) {
+            const int e = (int)threadIdx.x + k * 64 * kCullWaves;
+            rv[k] = rows[e < last ? e : last];
+        }
+        sv = srows[(int)threadIdx.x < slast ? (int)threadIdx.x : slast];
+    };
+    auto commit = [&]() {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) (&s_gb[0][0])[(int)threadIdx.x + k * 64 * kCullWaves] = rv[k];
+        if (threadIdx.x < kCullTile / kSuper * kGroupRow) (&s_gb[kCullTile][0])[threadIdx.x] = sv;
+    };
+    // Bit 1024: the whole row is in registers before the test begins.  Left alone the compiler turns the test's three comparisons
+    // into nested exec regions and sinks the reads of the row's second half into the second one: two dependent LDS round trips per
+    // test, on the one chain the longest wave of the kernel is made of.  (Code motion only: the operations and their order stay.)
+    auto row_first = [](float* row) {
+        if constexpr (kTrimRowFirst) {
+#pragma unroll
+            for (int k = 0; k < F32::kGroupVals; ++k) asm volatile("" : "+v"(row[k]));
+        }
+    };
+    double mdl[R::P];
+    if constexpr (kTrimEarly) {
+        // The first tile's rows do not depend on the model: requested together with it, they are in LDS before the FP64 preparation,
+        // and one barrier behind it replaces two dependent round trips.  The model's loads are unconditional too (row 0 for a lane
+        // behind M, which then takes its NaNs), so that nothing stands between the two requests.
+        const double* __restrict__ row = models + (int64_t)(live ? m : 0) * R::P;
+#pragma unroll
+        for (int k = 0; k < R::P; ++k) mdl[k] = row[k];
+        const int cnt = g1 - g0 < kCullTile ? g1 - g0 : kCullTile;
+        request(g0, cnt, (cnt + kSuper - 1) / kSuper);
+#pragma unroll
+        for (int k = 0; k < R::P; ++k) mdl[k] = live ? mdl[k] : __builtin_nan("");
+        if (seg == 0 && w < W) {
+#pragma unroll
+            for (int k = 0; k < R::P; ++k) models_t[(int64_t)k * W * 64 + m] = mdl[k];
+        }
+        commit();
+    } else {
+#pragma unroll
+        for (int k = 0; k < R::P; ++k) mdl[k] = live ? models[(int64_t)m * R::P + k] : __builtin_nan("");
+    }
     const typename F32::Lane flane32 = F32::prep(mdl, guard32, T2);
     if (seg == 0 && w < W) {
         HypRow<MT>::store(flane32, hyp32 + (int64_t)m * HypRow<MT>::kStride);
+        if constexpr (!kTrimEarly) {
 #pragma unroll
-        for (int k = 0; k < R::P; ++k) models_t[(int64_t)k * W * 64 + m] = mdl[k];
+            for (int k = 0; k < R::P; ++k) models_t[(int64_t)k * W * 64 + m] = mdl[k];
+        }
     }
-    const float Tup32 = f32_up(sqrt(T2) * (1.0 + 1.0 / 64.0));
-    const int g0 = seg * gps, g1 = g0 + gps < groups ? g0 + gps : groups;
+    if constexpr (!kTrimResident) Tup32 = f32_up(sqrt(T2) * (1.0 + 1.0 / 64.0));
     for (int t0 = g0; t0 < g1; t0 += kCullTile) {
         const int cnt = g1 - t0 < kCullTile ? g1 - t0 : kCullTile;
-        __syncthreads();  // the previous tile has been read
         const int scnt = (cnt + kSuper - 1) / kSuper;  // t0 is a multiple of kSuper (gps is)
-        for (int e = (int)threadIdx.x; e < cnt * kGroupRow; e += 64 * kCullWaves)
-            (&s_gb[0][0])[e] = gbounds[(int64_t)t0 * kGroupRow + e];
-        for (int e = (int)threadIdx.x; e < scnt * kGroupRow; e += 64 * kCullWaves)
-            (&s_gb[kCullTile][0])[e] = gbounds[((int64_t)groups + t0 / kSuper) * kGroupRow + e];
+        if constexpr (kTrimEarly) {
+            if (t0 != g0) {
+                __syncthreads();  // the previous tile has been read
+                request(t0, cnt, scnt);
+                commit();
+            }
+        } else {
+            __syncthreads();  // the previous tile has been read
+            for (int e = (int)threadIdx.x; e < cnt * kGroupRow; e += 64 * kCullWaves)
+                (&s_gb[0][0])[e] = gbounds[(int64_t)t0 * kGroupRow + e];
+            for (int e = (int)threadIdx.x; e < scnt * kGroupRow; e += 64 * kCullWaves)
+                (&s_gb[kCullTile][0])[e] = gbounds[((int64_t)groups + t0 / kSuper) * kGroupRow + e];
+        }
         __syncthreads();
         unsigned steps = 0;   // work lists: lane i holds the surviving steps of (this wave's word, group t0 + i)
+        unsigned long long kw = 0;       // bit 128: lane i holds the keep word of (group t0 + i, this wave's word); 0 where nothing was tested
         if (w < W)
             for (int sgi = 0; sgi < scnt; ++sgi) {
                 const int i0 = sgi * kSuper, i1 = i0 + kSuper < cnt ? i0 + kSuper : cnt;
                 float sr[kGroupRow];
 #pragma unroll
                 for (int k = 0; k < F32::kGroupVals; ++k) sr[k] = s_gb[kCullTile + sgi][k];  // same address in every lane: LDS broadcast
+                row_first(sr);
                 if (__ballot(live && !F32::group_reject(sr, flane32, Tup32)) == 0) {  // no hypothesis of the word reaches these 512 points
-                    if (lane < i1 - i0) keep[(int64_t)(t0 + i0 + lane) * W + w] = 0;
+                    if (!kTrimKeepTile && lane < i1 - i0) keep[(int64_t)(t0 + i0 + lane) * W + w] = 0;
                     continue;
                 }
                 for (int i = i0; i < i1; ++i) {
                     float gr[kGroupRow];
 #pragma unroll
                     for (int k = 0; k < F32::kGroupVals; ++k) gr[k] = s_gb[i][k];
+                    row_first(gr);
                     const unsigned long long bm = __ballot(live && !F32::group_reject(gr, flane32, Tup32));
-                    if (lane == 0) keep[(int64_t)(t0 + i) * W + w] = bm;
-                    if (LISTS) steps = lane == i ? (unsigned)__popcll(bm) : steps;
+                    if constexpr (kTrimKeepTile) {
+                        kw = lane == i ? bm : kw;
+                    } else {
+                        if (lane == 0) keep[(int64_t)(t0 + i) * W + w] = bm;
+                        if (LISTS) steps = lane == i ? (unsigned)__popcll(bm) : steps;
+                    }
                 }
             }
+        if constexpr (kTrimKeepTile && !LISTS) {
+            if (w < W && lane < cnt) keep[(int64_t)(t0 + lane) * W + w] = kw;   // one store per wave and tile, from registers
+        }
         if (!LISTS) continue;
         // ---- the tile's items (group t0 + i, this workgroup's words) onto the work lists: lane i of the first wave weighs item i -
         // the surviving steps of its live words - and the non-empty ones are appended to list [g & 7][class of the weight].  One
         // returning atomic per (XCD, class) pair that occurs in the tile: lanes with equal lane & 7 have equal g & 7, so the pair's
         // lanes are the class' ballot under one byte-lane mask; positions inside the pair's block follow from the lanes below.
-        s_wt[threadIdx.x >> 6][lane] = steps;
-        __syncthreads();
-        if (threadIdx.x >= 64) continue;
-        const int nlive = W - (int)blockIdx.x * kCullWaves < kCullWaves ? W - (int)blockIdx.x * kCullWaves : kCullWaves;
         unsigned wt = 0;
-        if (lane < cnt)
-            for (int v = 0; v < nlive; ++v) wt += s_wt[v][lane];
+        if constexpr (kTrimKeepTile) {
+            // the four waves' words meet in LDS; behind the barrier every thread stores one word of the tile (four neighbouring lanes
+            // an item's 32 bytes), and an item's weight is the popcount of its words - zero for a wave past W or a lane past cnt
+            s_kw[lane][threadIdx.x >> 6] = kw;
+            __syncthreads();
+            const int64_t at = wl_tile_store_index((int)threadIdx.x, t0, cnt, (int)blockIdx.x, W);
+            if (at >= 0) keep[at] = s_kw[threadIdx.x / kCullWaves][threadIdx.x % kCullWaves];
+            if (threadIdx.x >= 64) continue;
+#pragma unroll
+            for (int v = 0; v < kCullWaves; ++v) wt += (unsigned)__popcll(s_kw[lane][v]);
+        } else {
+            s_wt[threadIdx.x >> 6][lane] = steps;
+            __syncthreads();
+            if (threadIdx.x >= 64) continue;
+            const int nlive = W - (int)blockIdx.x * kCullWaves < kCullWaves ? W - (int)blockIdx.x * kCullWaves : kCullWaves;
+            if (lane < cnt)
+                for (int v = 0; v < nlive; ++v) wt += s_wt[v][lane];
+        }
         const int cls = wt != 0 ? wl_class(wt, wl_t1, wl_t2, wl_t3) : -1;
         unsigned long long mine = 0;   // the lanes of this lane's (XCD, class) pair
 #pragma unroll

@@ -84,4 +84,14 @@ PGX_WL_FN void wl_words_shift(uint64_t v0, uint64_t v1, uint64_t v2, uint64_t v3
     out[3] = d == 0 ? v3 : 0;
 }
 
+// ---- the cull kernel's tile store: the 64 * kWlItemWords threads of workgroup x (item column x) write the keep words of a tile of
+// cnt <= 64 groups beginning at group t0.  Thread t takes group t0 + t / 4 and word 4 x + t % 4, so four neighbouring lanes write the
+// 32 contiguous bytes of one item.  The word's index in keep[groups][W], or -1: nothing to store (a group behind the tile's last,
+// a word at or past W).
+PGX_WL_FN int64_t wl_tile_store_index(int t, int t0, int cnt, int x, int W)
+{
+    const int gi = t / kWlItemWords, w = x * kWlItemWords + t % kWlItemWords;
+    return (gi < cnt && w < W) ? (int64_t)(t0 + gi) * W + w : -1;
+}
+
 }  // namespace pgx
