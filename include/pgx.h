@@ -352,6 +352,31 @@ int pgx_pnp_refine_batch(pgx_ctx *ctx, const double *inits, const int32_t *index
  * when refit_solver="jacobi" (default "lapack": unchanged results). */
 int pgx_eigh_smallest_batch(pgx_ctx *ctx, const double *A, int q, int64_t B, double *vec, double *val);
 
+/* Per-point surface normals of a 3-D point cloud from the neighbourhood graph resident NOW (no reference counterpart: what
+ * pgx_set_normals wants and a scan does not carry).  points: n x 3 doubles (host), the way pgx_graph_build takes them; the call neither
+ * reads nor alters the resident problem (points, normals, weights, hypothesis batch).  viewpoint: 3 doubles or NULL; normals_out
+ * [n][3], curvature_out [n] (may be NULL), *undefined (may be NULL) = number of undefined points.  PGX_ERR_INVALID: no graph resident
+ * ("needs a neighbourhood graph of the points"), a graph of other than n sites ("<n> points for a graph of <gn> sites"), points or
+ * normals_out NULL ("NULL argument"), a viewpoint that is not finite ("non-finite viewpoint"); n == 0 is PGX_OK and writes nothing but
+ * *undefined = 0.  The definition, all of it FP64 without contraction, IEEE division and square root:
+ *   1. the neighbourhood of i is i itself followed by row i of the symmetric CSR in the row's (ascending index) order, every stored
+ *      neighbour once whatever its multiplicity; m = 1 + row length;
+ *   2. offsets from the point itself, e_j = x_j - x_i per component (e = 0 for i);
+ *   3. pass 1: s_a = sum of e_ja, sequentially in that order from 0; mu_a = s_a / m;
+ *   4. pass 2: c_ab (a <= b) = sum of (e_ja - mu_a) (e_jb - mu_b), sequentially in that order, the self term (0 - mu_a)(0 - mu_b)
+ *      first; mirrored into both triangles;
+ *   5. the normal is the eigenvector of the smallest eigenvalue lambda_0 of c by cyclic Jacobi in pgx_eigh_smallest_batch's operation
+ *      order at q = 3, including its choice of the first smallest diagonal entry; not renormalised: the bits of pgxo_eigh_smallest;
+ *   6. sign: negated if its entry of largest magnitude (lowest index on ties) is negative; then, with a viewpoint v, negated again if
+ *      t = ((v_0 - x_i0) n_0 + (v_1 - x_i1) n_1) + (v_2 - x_i2) n_2 < 0;
+ *   7. curvature = lambda_0 / ((c_00 + c_11) + c_22), the surface variation, the trace taken before the rotations (0 / 0 = NaN);
+ *   8. undefined - the three normal entries and the curvature NaN, counted in *undefined - when m < 3, when a coordinate of the
+ *      neighbourhood is not finite, or when an entry of c is not finite.  (NaN normals are "no hypothesis" to the cylinder's solver.)
+ * One lane per point; the lanes follow the Morton order of the graph's coordinates when pgx_graph_build left it, the caller's order
+ * after pgx_set_graph: the results do not depend on it. */
+int pgx_estimate_normals(pgx_ctx *ctx, const double *points, int64_t n, const double *viewpoint, double *normals_out,
+                         double *curvature_out, int64_t *undefined);
+
 /* ---- the inlier/outlier graph cut of GC-RANSAC's local optimisation.
  * Replaces gcransac::GCRANSAC::labeling as reached from proposal_engine->run (progressive_x.h:294-299; settings
  * spatial_coherence_weight / threshold at :541-545).  The graph-cut-ransac sources are absent from the snapshot, so the

@@ -1117,6 +1117,13 @@ int pgx_eigh_smallest_batch(pgx_ctx* ctx, const double* A, int q, int64_t B, dou
     return eigh_smallest_launch(ctx, A, q, B, vec, val);
 }
 
+int pgx_estimate_normals(pgx_ctx* ctx, const double* points, int64_t n, const double* viewpoint, double* normals_out, double* curvature_out,
+                         int64_t* undefined)
+{
+    CTX_GUARD(ctx);
+    return estimate_normals_launch(ctx, points, n, viewpoint, normals_out, curvature_out, undefined);
+}
+
 int pgx_gc_labeling(pgx_ctx* ctx, const double* model, double T2, double lambda, int32_t* flags, int64_t* count)
 {
     CTX_GUARD(ctx);

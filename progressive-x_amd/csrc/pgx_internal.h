@@ -260,6 +260,8 @@ int run_move(pgx_ctx* ctx, MoveRequest& rq);              // lambda > 0, any tab
 void maxflow_free(pgx_ctx* ctx);
 int maxflow_schedule_stats(pgx_ctx* ctx, int64_t out[8]);   // maxflow.hip
 int eigh_smallest_launch(pgx_ctx* ctx, const double* A, int q, int64_t B, double* vec, double* val);   // fit.hip
+int estimate_normals_launch(pgx_ctx* ctx, const double* points, int64_t n, const double* viewpoint, double* normals_out,
+                            double* curvature_out, int64_t* undefined);   // normals.hip
 int expand_alpha_tile(pgx_ctx* ctx, MoveRequest& rq);   // maxflow_tile.hip: the whole graph in one workgroup, one launch
 void tile_free(pgx_ctx* ctx);
 struct MfView;

@@ -5,8 +5,8 @@ The five entry points keep the reference's names, argument order, defaults, retu
 findPlanes, findSpheres, findLines3D and findCylinders (3-D point clouds) and findCircles (2-D point sets) are the same pipeline on model
 types the reference does not have.
 """
-from ._api import (find6DPoses, findCircles, findCylinders, findFundamentalMatrices, findHomographies, findLines, findLines3D, findPlanes,
-                   findSpheres, findTwoViewMotions, findVanishingPoints)
+from ._api import (estimateNormals, find6DPoses, findCircles, findCylinders, findFundamentalMatrices, findHomographies, findLines,
+                   findLines3D, findPlanes, findSpheres, findTwoViewMotions, findVanishingPoints)
 
 __all__ = ["find6DPoses", "findHomographies", "findTwoViewMotions", "findFundamentalMatrices", "findLines",
-           "findVanishingPoints", "findPlanes", "findSpheres", "findCircles", "findLines3D", "findCylinders"]
+           "findVanishingPoints", "findPlanes", "findSpheres", "findCircles", "findLines3D", "findCylinders", "estimateNormals"]

@@ -454,6 +454,46 @@ def findLines3D(points, weights=None, threshold=0.05, conf=0.5, spatial_coherenc
                            distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
 
 
+def estimateNormals(points, k=16, radius=None, viewpoint=None, return_curvature=False):
+    """Per-point surface normals of a 3-D point cloud, on the GPU: the eigenvector of the smallest eigenvalue of the covariance of each
+    point's neighbourhood in the neighbourhood graph (include/pgx.h pgx_estimate_normals states the arithmetic).  points [n, 3], n >= 3,
+    finite; returns normals [n, 3] float64 (unit to rounding) - and, with return_curvature=True, (normals, curvature [n]): the surface
+    variation lambda_0 / trace, 0 on a plane, at most 1/3.  The graph: k given and radius None - the k nearest neighbours (the default,
+    k = 16; the graph build takes k <= 16); k and radius given - the k nearest inside the ball; k=None and radius given - every point
+    inside the ball.  The neighbourhood is the point's row of the SYMMETRIC graph - j is a neighbour of i when either lists the other -
+    so a point can have more than k neighbours.  The normals are unsigned (the entry of largest magnitude is made positive) unless a
+    viewpoint (3 finite numbers) is given: then each normal points to the half-space of the viewpoint as seen from its point.
+    findCylinders accepts either.  Consistent orientation by propagation over the graph is not done.  NaN rows mark undefined normals:
+    a point with fewer than two neighbours (a ball that holds none), or a neighbourhood whose covariance is not finite."""
+    points = _as_f64(points)
+    if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 3:
+        raise ValueError("points should be an array with dims [n,3], n>=3")
+    if k is None and radius is None:
+        raise ValueError("k or radius should be given")
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2:
+            raise ValueError("k should be an integer >= 2 (or None with a radius)")
+    if radius is not None:
+        try:
+            radius = float(radius)
+        except (TypeError, ValueError):
+            raise ValueError("radius should be None or a number > 0") from None
+        if not (radius > 0.0 and np.isfinite(radius)):
+            raise ValueError("radius should be None or a number > 0")
+    if viewpoint is not None:
+        try:
+            viewpoint = np.asarray(viewpoint, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError("viewpoint should be None or 3 finite numbers") from None
+        if viewpoint.shape[0] != 3 or not np.isfinite(viewpoint).all():
+            raise ValueError("viewpoint should be None or 3 finite numbers")
+    kind = _lib.GRAPH_BALL if k is None else _lib.GRAPH_KNN if radius is None else _lib.GRAPH_KNN_IN_BALL
+    ctx = _context()
+    ctx.graph_build(points, kind, radius=0.0 if radius is None else radius, k=1 if k is None else int(k), fetch=False)
+    normals, curvature, _ = ctx.estimate_normals(points, viewpoint=viewpoint, want_curvature=bool(return_curvature))
+    return (normals, curvature) if return_curvature else normals
+
+
 def findCylinders(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
                   neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
                   minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
@@ -461,7 +501,8 @@ def findCylinders(points, normals, weights=None, threshold=0.05, conf=0.5, spati
                   local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
     """Multi-cylinder fitting of an oriented 3-D point cloud: pipes, columns, trunks, tanks (no reference counterpart: findSpheres'
     pipeline with a 2-point solver on points with normals and a Gauss-Newton refit of the geometric distance).  points [n, 3], normals
-    [n, 3] (required): one surface normal per point, as a normal estimator gives them - they may be unsigned (either orientation) and
+    [n, 3] (required): one surface normal per point, as a normal estimator gives them (estimateNormals(points) computes them from the
+    cloud itself) - they may be unsigned (either orientation) and
     need not be unit length; only the minimal solver reads them, and a sample whose normals are parallel, zero or not finite gives no
     hypothesis.  Returns (cylinders[K, 7] float64 (px, py, pz, dx, dy, dz, r): a point on the axis - the foot of its points' mean -,
     a unit direction and a radius; labels[n] int32) in findPlanes' labelling convention.  The axis is a line: the model says nothing

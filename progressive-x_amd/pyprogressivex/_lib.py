@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "pgx_score", "pgx_score_upload", "pgx_score_launch", "pgx_score_fetch", "pgx_score_algorithmic_bytes", "pgx_score_stats", "pgx_score_profile", "pgx_score_kernel_times", "pgx_score_debug_fetch", "pgx_score_debug_geometry",
     "pgx_preference", "pgx_get_preference", "pgx_compound_update",
     "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_normals",
-    "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch",
+    "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals",
     "pgx_bucket", "pgx_residual_sum", "pgx_gc_labeling", "pgx_gc_inliers", "pgx_epipolar_support", "pgx_gram_batch", "pgx_gram_labels", "pgx_residual_sums", "pgx_pnp_refine_batch",
     "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_barrier", "pgx_comm_allreduce_max_f64",
     "pgx_score_allgather", "pgx_score_fetch_all", "pgx_score_allgather_begin", "pgx_score_allgather_end", "pgx_compound_allreduce_max",
@@ -708,6 +708,24 @@ class Context:
         self._ck(self._lib.pgx_eigh_smallest_batch(self._h, _ptr(A, C.c_double), C.c_int(q), C.c_int64(B), _ptr(vec, C.c_double),
                                                    _ptr(val, C.c_double)), "pgx_eigh_smallest_batch")
         return vec, val
+
+    def estimate_normals(self, points, viewpoint=None, want_curvature=False):
+        """pgx_estimate_normals: (normals [n, 3], curvature [n] or None, undefined) of the points [n, 3] from the graph resident now
+        (graph_build / set_graph on the same n points).  NaN rows mark undefined normals (fewer than two neighbours, a non-finite
+        coordinate or covariance entry); `undefined` counts them.  The resident problem is neither read nor changed."""
+        pts = _f64(points)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("points must be [n,3]")
+        n = pts.shape[0]
+        vp = None if viewpoint is None else _f64(viewpoint).reshape(-1)
+        if vp is not None and vp.shape[0] != 3:
+            raise ValueError("viewpoint must hold 3 numbers")
+        nrm = np.empty((n, 3), dtype=np.float64)
+        curv = np.empty(n, dtype=np.float64) if want_curvature else None
+        undefined = C.c_int64()
+        self._ck(self._lib.pgx_estimate_normals(self._h, _ptr(pts, C.c_double), C.c_int64(n), _ptr(vp, C.c_double), _ptr(nrm, C.c_double),
+                                                _ptr(curv, C.c_double), C.byref(undefined)), "pgx_estimate_normals")
+        return nrm, curv, int(undefined.value)
 
     def expansion_schedule(self):
         """How the level-synchronous min-cut spent its dependent steps (include/pgx.h pgx_expansion_schedule)."""

@@ -109,7 +109,7 @@ def make_lines3d(n_per_line=2000, n_lines=6, n_outliers=12000, sigma=0.01, size=
 
 
 def make_cylinders(n_per_cylinder=8000, n_cylinders=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.0), length=(3.0, 6.0),
-                   coverage=1.0, normal_noise_deg=5.0, seed=0):
+                   coverage=1.0, normal_noise_deg=5.0, seed=0, normals="synthetic"):
     """findCylinders' workload: K cylinders with uniformly random unit axis directions, radii uniform in `radius` and lengths uniform in
     `length`, each lying wholly inside the box [0, size]^3 (the midpoint is drawn where both end discs fit; cylinders may cross); the
     inliers of cylinder k are uniform on its lateral surface - or, with coverage < 1, on the arc of that fraction of the circumference
@@ -117,7 +117,10 @@ def make_cylinders(n_per_cylinder=8000, n_cylinders=6, n_outliers=48000, sigma=0
     radial unit vectors tilted by an angle uniform in [0, normal_noise_deg] about a random axis orthogonal to them, each with a random
     sign.  The outliers are uniform in the box with uniformly random unit normals.  Returns (points [n, 3], normals [n, 3] (unit),
     labels [n] (k + 1 = cylinder k, 0 = outlier), gt_cylinders [K, 7] = (midpoint of the axis segment, unit direction, radius)).
-    A pure function of the seed."""
+    A pure function of the seed.  normals="estimated" returns, in place of those synthetic normals, what estimateNormals(points) computes
+    from the same points (k = 16 nearest neighbours, unsigned; needs the GPU): the normals a scan of the scene would come with."""
+    if normals not in ("synthetic", "estimated"):
+        raise ValueError('normals should be "synthetic" or "estimated"')
     rng = np.random.default_rng(seed)
     if not 0.0 < coverage <= 1.0:
         raise ValueError("coverage should lie in (0, 1]")
@@ -150,8 +153,11 @@ def make_cylinders(n_per_cylinder=8000, n_cylinders=6, n_outliers=48000, sigma=0
     no = rng.normal(size=(n_outliers, 3))
     nrm.append(no / np.linalg.norm(no, axis=1)[:, None])
     labels.append(np.zeros(n_outliers, dtype=int))
-    return (np.ascontiguousarray(np.vstack(pts)), np.ascontiguousarray(np.vstack(nrm)), np.concatenate(labels).astype(np.int32),
-            np.array(models).reshape(-1, 7))
+    pts, nrm = np.ascontiguousarray(np.vstack(pts)), np.ascontiguousarray(np.vstack(nrm))
+    if normals == "estimated":
+        from ._api import estimateNormals
+        nrm = estimateNormals(pts)
+    return pts, nrm, np.concatenate(labels).astype(np.int32), np.array(models).reshape(-1, 7)
 
 
 def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.5), coverage=1.0, seed=0):

@@ -7,7 +7,11 @@ noise along the radius, normals within 5 degrees of radial with random sign, poi
 wall time.  Writes one JSON record (default profiles/cylinders_bench.json) and prints it; the numbers go to DESIGN.md.  There is no
 target for them.
 
-usage: bench_cylinders.py [--steps 20] [--sizes 10000,100000,1000000] [--samplers 3,2,1,0] [--mpn-divisors 40,150] [--out FILE]"""
+--normals estimated runs the findCylinders table alone, with estimateNormals(points, k=--normals-k) - or, with --normals-radius R, the
+ball graph estimateNormals(points, k=None, radius=R) - in place of the scene's synthetic normals (the time of that call is recorded per size), and writes profiles/cylinders_estimated_normals_bench.json: DESIGN.md 4.10.
+
+usage: bench_cylinders.py [--steps 20] [--sizes 10000,100000,1000000] [--samplers 3,2,1,0] [--mpn-divisors 40,150] [--out FILE]
+                          [--normals synthetic|estimated] [--normals-k 16] [--normals-radius R]"""
 import argparse
 import json
 import os
@@ -52,10 +56,18 @@ def main():
     ap.add_argument("--sizes", default="10000,100000,1000000")
     ap.add_argument("--samplers", default="3,2,1,0")
     ap.add_argument("--mpn-divisors", default="40,150")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cylinders_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--normals", default="synthetic", choices=("synthetic", "estimated"))
+    ap.add_argument("--normals-k", type=int, default=16)
+    ap.add_argument("--normals-radius", type=float, default=None)
     args = ap.parse_args()
+    estimated = args.normals == "estimated"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "cylinders_estimated_normals_bench.json" if estimated else "cylinders_bench.json")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     T2 = 2.25 * THR * THR
+    if estimated:
+        return recovery(args, dict(workload="cylinders", normals="estimated", normals_k=args.normals_k, normals_radius=args.normals_radius, threshold=THR, radius_range=[0.1, 2.0]))
     pts, nrm, _, _ = scene(1_000_000)
     n = pts.shape[0]
     out = dict(workload="cylinders", n_score=n, threshold=THR, radius_range=[0.1, 2.0])
@@ -89,12 +101,31 @@ def main():
         out[name].update(dense_score_ms=ms_d, cull_speedup=ms_d / out[name]["score_ms"],
                          dense_counts_identical=bool(np.array_equal(fast[name], counts_d)))
     dense.close()
+    recovery(args, out)
 
+
+def recovery(args, out):
+    """findCylinders per size, minimum_point_number and sampler: cylinders found / returned and wall time"""
+    estimated = args.normals == "estimated"
+    graph = dict(k=args.normals_k) if args.normals_radius is None else dict(k=None, radius=args.normals_radius)
     calls = {}
     for size in [int(s) for s in args.sizes.split(",") if s]:
         p, nr, gen, gt = scene(size, seed=2)
         order = np.random.default_rng(0).permutation(len(p))
-        p, nr = np.ascontiguousarray(p[order]), np.ascontiguousarray(nr[order])
+        p, nr, gen = np.ascontiguousarray(p[order]), np.ascontiguousarray(nr[order]), gen[order]
+        if estimated:
+            px.estimateNormals(p[: min(size, 20000)], **graph)                                     # warm-up
+            t0 = time.perf_counter()
+            nr = px.estimateNormals(p, **graph)
+            dt = time.perf_counter() - t0
+            inl = (gen > 0) & ~np.isnan(nr).any(axis=1)
+            g = gt[gen[inl] - 1]
+            radial = p[inl] - g[:, :3]
+            radial -= (radial * g[:, 3:6]).sum(1)[:, None] * g[:, 3:6]
+            radial /= np.linalg.norm(radial, axis=1)[:, None]
+            err = np.degrees(np.arccos(np.clip(np.abs((radial * nr[inl]).sum(1)), 0.0, 1.0)))
+            out.setdefault("estimateNormals", {})[str(size)] = dict(seconds=dt, median_error_deg=float(np.median(err)),
+                                                                    p95_error_deg=float(np.percentile(err, 95)), undefined=int(np.isnan(nr).any(axis=1).sum()))
         # minimum_point_number = n / divisor.  A cylinder has n / 12 inliers; a shell of width 3 thr about a cylinder of radius 1 and
         # length 6 holds 2 pi x 6 x 0.15 / 1000 = 0.6 % of the outliers, n / 350
         for div in [int(s) for s in args.mpn_divisors.split(",") if s]:
