@@ -45,10 +45,14 @@ enum pgx_model_type {
     PGX_CIRCLE2D = 10,        /* point (x,y);            model (cx,cy,r)                      findCircles          */
     PGX_LINE3D = 12,          /* point (x,y,z);          model (px,py,pz,dx,dy,dz), a point on the line and a direction
                                                          (unit from the solver and the refit)  findLines3D          */
-    PGX_CYLINDER3D = 14       /* point (x,y,z);          model (px,py,pz,dx,dy,dz,r), a point on the axis, a direction (unit from
+    PGX_CYLINDER3D = 14,      /* point (x,y,z);          model (px,py,pz,dx,dy,dz,r), a point on the axis, a direction (unit from
                                                          the solver and the refit) and a radius; the minimal solver also reads the
                                                          resident normals (pgx_set_normals)     findCylinders        */
-    /* 7, 9, 11 and 13 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
+    PGX_CONE3D = 16           /* point (x,y,z);          model (ax,ay,az,dx,dy,dz,c,s), the apex, an axis direction pointing into the
+                                                         nappe (unit from the solver and the refit) and the cosine and sine of the
+                                                         half-angle; the minimal solver also reads the resident normals
+                                                         (pgx_set_normals)                      findCones            */
+    /* 7, 9, 11, 13 and 15 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -99,7 +103,10 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * a point and a unit direction; coincident points or a length that is not finite give NaN), the 2-point cylinder solver
  * (samples[S][2], S x 7, findCylinders: it reads the two samples' resident normals and fails with PGX_ERR_INVALID when
  * pgx_set_normals has not been called for the resident points; parallel normals, non-finite values and radii outside
- * pgx_set_radius_range give NaN), the 4-point homography solver (samples[S][4], S x 9, h33 = 1,
+ * pgx_set_radius_range give NaN), the 3-point cone solver (samples[S][3], S x 8, findCones: it reads the three samples' resident
+ * normals and fails with PGX_ERR_INVALID without them; tangent planes without a common point, a sample at the apex, non-finite
+ * values, a half-angle of 90 degrees or more and sin(half-angle) outside pgx_set_radius_range give NaN), the 4-point homography
+ * solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
  * FOUR slots per sample: 4S x 12 [R|t], DefaultPnPEstimator progressivex_python.cpp:119, absent upstream); a degenerate sample
@@ -108,11 +115,12 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
 int pgx_solve_minimal(pgx_ctx *ctx, const int32_t *samples, int S, double *models_out);
 /* The radii the sphere, the circle and the cylinder solver accept (context state, [0, +inf] at pgx_create; those three solvers read it):
  * a sample whose sphere, circle or cylinder has r outside [rmin, rmax] yields a NaN model.  NaN, rmin < 0 or rmax < rmin:
- * PGX_ERR_INVALID.  rmax = +inf is allowed. */
+ * PGX_ERR_INVALID.  rmax = +inf is allowed.  For PGX_CONE3D the same range bounds s = sin(half-angle) of the cone solver's models:
+ * a cone has no radius, and (sin(theta_min), sin(theta_max)) is its angle range. */
 int pgx_set_radius_range(pgx_ctx *ctx, double rmin, double rmax);
 /* Per-point surface normals, n x 3 doubles in the points' order, RESIDENT like the weights of pgx_set_weights and under the same
  * rules: len == n is checked (PGX_ERR_INVALID), (NULL, 0) clears them, pgx_set_points invalidates them.  They need not be unit
- * length nor consistently oriented.  Only the cylinder's minimal solver reads them; the point rows stay n x 3. */
+ * length nor consistently oriented.  Only the cylinder's and the cone's minimal solvers read them; the point rows stay n x 3. */
 int pgx_set_normals(pgx_ctx *ctx, const double *normals, int64_t len);
 /* The same with the samples DRAWN ON THE DEVICE by the in-repo counter-based generator (csrc/rng.hip.h: Philox4x32-10; sample s
  * of batch `batch` under `key` is a pure function of (key, batch, s); m = the resident model type's minimal sample size).
@@ -304,10 +312,13 @@ int pgx_one_workgroup_launches(pgx_ctx *ctx, int64_t out[2]);
  *   PGX_GRAM_CYL_GN   the Gauss-Newton row (gu, gv, t gu, t gv, -1, s - r) of a cylinder at params = (p[3], d[3], r, u[3]), d unit,
  *                     u unit and orthogonal to d, v = d x u: e = x - p, c = e x d, s = |c|, t = e . d, gu = (c . v) / s,
  *                     gv = -(c . u) / s; 3-D points                                                                            q = 6
+ *   PGX_GRAM_CONE_GN  the Gauss-Newton row (-g.u, -g.v, -g.d, -(e.u) k, -(e.v) k, -(rho s + h c), f) of a cone at params = (a[3], d[3],
+ *                     c, s, u[3]), d unit, u unit and orthogonal to d, v = d x u: e = x - a, h = e . d, rho = |e x d|,
+ *                     rhohat = (e - h d) / rho, f = c rho - s h, g = c rhohat - s d, k = c h / rho + s; 3-D points             q = 7
  * Selection: PGX_SEL_INDEX (index[m], host) or PGX_SEL_LABEL (label == `label` on the resident labelling).
- * count = selected points, bad = points skipped because the row is undefined (PnP: depth ~ 0; cylinder: a point on the axis). */
+ * count = selected points, bad = points skipped because the row is undefined (PnP: depth ~ 0; cylinder and cone: a point on the axis). */
 enum { PGX_GRAM_AFFINE = 0, PGX_GRAM_DLT_H = 1, PGX_GRAM_EPI_F = 2, PGX_GRAM_VP = 3, PGX_GRAM_PNP_GN = 4, PGX_GRAM_SPHERE = 5, PGX_GRAM_CIRCLE = 6,
-       PGX_GRAM_CYL_GN = 7 };
+       PGX_GRAM_CYL_GN = 7, PGX_GRAM_CONE_GN = 8 };
 enum { PGX_SEL_INDEX = 0, PGX_SEL_LABEL = 1 };
 int pgx_set_weights(pgx_ctx *ctx, const double *weights, int64_t len);
 int pgx_gram(pgx_ctx *ctx, int kind, const double *params, int nparams, int sel, const int32_t *index, int64_t m,

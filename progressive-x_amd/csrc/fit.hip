@@ -69,6 +69,7 @@ struct GenEpiF { static constexpr int Q = 9, D = 4; };
 struct GenVp { static constexpr int Q = 3, D = 4; };
 struct GenPnpGn { static constexpr int Q = 7, D = 5; };
 struct GenCylGn { static constexpr int Q = 6, D = 3; };
+struct GenConeGn { static constexpr int Q = 7, D = 3; };
 
 // the affine row (1, p[0], .., p[DIM - 1]) of a DIM-D point: lines (2), planes (3) and the 4- and 5-D rows
 template <int DIM> struct GenAffine {
@@ -177,6 +178,43 @@ __device__ __forceinline__ void emit<GenCylGn>(const double* pt, const FitParams
     const double gu = ((c0 * v0 + c1 * v1) + c2 * v2) / s;
     const double gv = -(((c0 * u[0] + c1 * u[1]) + c2 * u[2]) / s);
     const double a[6] = {gu, gv, t * gu, t * gv, -1.0, s - m[6]};
+    acc.add(a, w);
+}
+// The cone's Gauss-Newton row.  prm = (a[3], d[3], c, s, u[3]): the apex, the unit direction, the cosine and sine of the half-angle and
+// a unit vector orthogonal to d; v = d x u (cross3's component order) completes the frame here.  With e = x - a, cr = e x d and
+// rho = |cr| exactly as Residual<kLine3D> computes them and h = (e0 d0 + e1 d1) + e2 d2 (so the last entry is Residual<kCone3D>'s
+// c rho - s h before its fabs, bit for bit):
+//   rh_k = (e_k - h d_k) / rho,  g_k = c rh_k - s d_k,  gu = (g0 u0 + g1 u1) + g2 u2, gv and gd likewise with v and d,
+//   eu = (e0 u0 + e1 u1) + e2 u2, ev likewise,  k = (c h) / rho + s,
+//   row = (-gu, -gv, -gd, -(eu k), -(ev k), -(rho s + h c), c rho - s h)
+// the derivatives of f = c rho - s h by (alpha, beta, gamma, delta, eta, tau) at 0 in a + alpha u + beta v + gamma d,
+// normalise(d + delta u + eta v), (c, s) <- normalise(c - tau s, s + tau c), followed by f: g = c rhohat - s d is the gradient of f in x,
+// so moving the apex by t moves f by -g . t; a tilt of d by delta u changes h by delta (e . u) and rho by -delta h (e . u) / rho; a
+// turn of the half-angle by tau changes (c, s) by tau (-s, c).  A point on the axis (!(rho > 0)) or a non-finite rho has no row.
+template <>
+__device__ __forceinline__ void emit<GenConeGn>(const double* pt, const FitParams& prm, Acc<7>& acc, double w, int& bad)
+{
+    const double* m = prm.v;
+    const double* u = prm.v + 8;
+    const double c = m[6], s = m[7];
+    const double v0 = m[4] * u[2] - m[5] * u[1], v1 = -(m[3] * u[2] - m[5] * u[0]), v2 = m[3] * u[1] - m[4] * u[0];
+    const double e0 = pt[0] - m[0], e1 = pt[1] - m[1], e2 = pt[2] - m[2];
+    const double c0 = e1 * m[5] - e2 * m[4];
+    const double c1 = -(e0 * m[5] - e2 * m[3]);
+    const double c2 = e0 * m[4] - e1 * m[3];
+    const double rho = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+    if (!(rho > 0.0) || !isfinite(rho)) { bad = 1; return; }
+    const double h = (e0 * m[3] + e1 * m[4]) + e2 * m[5];
+    const double g0 = c * ((e0 - h * m[3]) / rho) - s * m[3];
+    const double g1 = c * ((e1 - h * m[4]) / rho) - s * m[4];
+    const double g2 = c * ((e2 - h * m[5]) / rho) - s * m[5];
+    const double gu = (g0 * u[0] + g1 * u[1]) + g2 * u[2];
+    const double gv = (g0 * v0 + g1 * v1) + g2 * v2;
+    const double gd = (g0 * m[3] + g1 * m[4]) + g2 * m[5];
+    const double eu = (e0 * u[0] + e1 * u[1]) + e2 * u[2];
+    const double ev = (e0 * v0 + e1 * v1) + e2 * v2;
+    const double k = (c * h) / rho + s;
+    const double a[7] = {-gu, -gv, -gd, -(eu * k), -(ev * k), -(rho * s + h * c), c * rho - s * h};
     acc.add(a, w);
 }
 
@@ -512,6 +550,7 @@ static int gram_row_length(pgx_ctx* ctx, const char* who, int kind, int nparams,
     case PGX_GRAM_SPHERE: *q = 5; if (D != 3 || nparams != 4) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 4 parameters (ox, oy, oz, s)", who); break;
     case PGX_GRAM_CIRCLE: *q = 4; if (D != 2 || nparams != 3) return fail(ctx, PGX_ERR_INVALID, "%s: needs 2-D points and 3 parameters (ox, oy, s)", who); break;
     case PGX_GRAM_CYL_GN: *q = 6; if (D != 3 || nparams != 10) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 10 parameters (p, d, r, u)", who); break;
+    case PGX_GRAM_CONE_GN: *q = 7; if (D != 3 || nparams != 11) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 11 parameters (a, d, c, s, u)", who); break;
     default: return fail(ctx, PGX_ERR_INVALID, "%s: unknown row kind %d", who, kind);
     }
     return PGX_OK;
@@ -534,6 +573,7 @@ static void with_gram_generator(int kind, int D, F&& f)
     case PGX_GRAM_SPHERE: f(GenRound<3>{}); break;
     case PGX_GRAM_CIRCLE: f(GenRound<2>{}); break;
     case PGX_GRAM_CYL_GN: f(GenCylGn{}); break;
+    case PGX_GRAM_CONE_GN: f(GenConeGn{}); break;
     default: f(GenPnpGn{}); break;
     }
 }

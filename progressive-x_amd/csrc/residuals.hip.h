@@ -1,6 +1,6 @@
 // residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the geometric primitives: the two
 // families flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension, and the 3-D line
-// (distance to an axis) and the cylinder (that distance less a radius).  gfx950 device code.
+// (distance to an axis), the cylinder (that distance less a radius) and the cone (the distance to a generatrix).  gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -20,8 +20,8 @@ namespace pgx {
 
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
-    kSphere3D = 8, kCircle2D = 10, kLine3D = 12, kCylinder3D = 14,
-    kNumModelTypes = 15   // 7, 9, 11 and 13 are not assigned (pgx_model_dims(7), (9), (11) and (13) are errors)
+    kSphere3D = 8, kCircle2D = 10, kLine3D = 12, kCylinder3D = 14, kCone3D = 16,
+    kNumModelTypes = 17   // 7, 9, 11, 13 and 15 are not assigned (pgx_model_dims(7), (9), (11), (13) and (15) are errors)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -36,7 +36,11 @@ __device__ __forceinline__ double cv_min(double a, double b) { return a > b ? b 
 //   obs0            first of the two observed image coordinates (-1: none; then no scales either)
 //   in0 .. in1      coordinates whose magnitude, at least 1, scales the point filter (in1 < in0: none)
 //   in0 .. box1     coordinates the projective map multiplies (the box / ball part of a kBoundBox row)
+//   normals_solver  only where the minimal solver reads the resident normals (pgx_set_normals): its name in the refusal without them
 template <int MT> struct Residual;
+
+template <class R, class = void> struct NormalsSolver { static constexpr const char* name = nullptr; };
+template <class R> struct NormalsSolver<R, std::void_t<decltype(R::normals_solver)>> { static constexpr const char* name = R::normals_solver; };
 
 struct NoProjectiveMap { static constexpr int obs0 = -1, in0 = 0, in1 = -1, box1 = -1; };
 
@@ -118,9 +122,41 @@ template <> struct Residual<kLine3D> : NoProjectiveMap {
 // contract of every cylinder check (tests restate it in numpy).
 template <> struct Residual<kCylinder3D> : NoProjectiveMap {
     static constexpr int D = 3, P = 7, sample = 2, slots = 1, bound = kBoundBall;
+    static constexpr const char* normals_solver = "cylinder";
     template <class PT, class MD>
     static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
         return fabs(sqrt(Residual<kLine3D>::squared(p, m)) - m[6]);
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double r = plain(p, m);
+        return r * r;
+    }
+};
+
+// Cone (findCones; no reference counterpart): model (a[3], d[3], c, s), the apex, an axis direction pointing into the nappe and the
+// cosine and sine of the half-angle.  The angle is stored as (c, s) so that the exact path has only + - x and sqrt in it: no sin or cos
+// runs on the device.  With e = x - a componentwise:
+//   q = Residual<kLine3D>::squared(x, (a, d))  (the same expressions: the code is shared),  rho = sqrt(q),  h = (e0 d0 + e1 d1) + e2 d2,
+//   plain = |c rho - s h|,  squared = plain * plain.
+// What plain measures: in the half-plane (h, rho) of a point - height along the axis, distance from it - the nappe is the ray from the
+// origin along (c, s), and plain is the distance to the LINE that carries this ray (the generatrix).  For h c + rho s >= 0 the foot
+// lies on the ray and plain is the distance to the surface; near the apex on the far side (h c + rho s < 0) the nearest surface point
+// is the apex itself and plain is smaller than the true distance sqrt(h^2 + rho^2).  The other nappe (the line continued) is not part
+// of the model: a double-cone residual is a different one.
+// Scaling: d, c and s are taken as given (unit d and c^2 + s^2 = 1 from the solver and the refit).  rho and h are homogeneous of degree
+// 1 in d, and plain is homogeneous of degree 1 in d and in (c, s): d or (c, s) times k gives |k| times the residual, there is no division.
+// Every entry of (a, d) enters q, and c and s each enter a product: a NaN in any of the eight entries makes every residual NaN.  d = 0
+// makes every residual 0.  This operation order is the contract of every cone check (tests restate it in numpy).
+template <> struct Residual<kCone3D> : NoProjectiveMap {
+    static constexpr int D = 3, P = 8, sample = 3, slots = 1, bound = kBoundBall;
+    static constexpr const char* normals_solver = "cone";
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        const double e0 = p[0] - m[0], e1 = p[1] - m[1], e2 = p[2] - m[2];
+        const double rho = sqrt(Residual<kLine3D>::squared(p, m));
+        const double h = (e0 * m[3] + e1 * m[4]) + e2 * m[5];
+        return fabs(m[6] * rho - m[7] * h);
     }
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
@@ -237,17 +273,18 @@ template <class F> inline bool with_model_type(int mt, F&& f) {
     case kCircle2D: f(std::integral_constant<int, kCircle2D>{}); return true;
     case kLine3D: f(std::integral_constant<int, kLine3D>{}); return true;
     case kCylinder3D: f(std::integral_constant<int, kCylinder3D>{}); return true;
+    case kCone3D: f(std::integral_constant<int, kCone3D>{}); return true;
     default: return false;
     }
 }
 
 // The constants of Residual<mt> for host code that holds the type as a number.
-struct ModelInfo { int D, P, sample, slots, bound, obs0, in0, in1, box1; };
+struct ModelInfo { int D, P, sample, slots, bound, obs0, in0, in1, box1; const char* normals_solver; };
 
 inline bool model_info(int mt, ModelInfo* out) {
     return with_model_type(mt, [&](auto t) {
         using R = Residual<decltype(t)::value>;
-        *out = {R::D, R::P, R::sample, R::slots, R::bound, R::obs0, R::in0, R::in1, R::box1};
+        *out = {R::D, R::P, R::sample, R::slots, R::bound, R::obs0, R::in0, R::in1, R::box1, NormalsSolver<R>::name};
     });
 }
 

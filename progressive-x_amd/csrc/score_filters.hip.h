@@ -867,4 +867,110 @@ template <> struct Filter32<kCylinder3D> {
     }
 };
 
+// ---- cones: r = |c rho - s h|, rho = |(x - a) x d|, h = (x - a) . d (Residual<kCone3D>), inlier iff r^2 < T2 -------------------------
+// The 3-D line's distance and a dot product with the same direction, combined by the half-angle's (c, s).  Homogeneous in d and in
+// (c, s).  d gets the 3-D line's sc = pow2_normaliser<3>(d): rho and h on d sc are rho sc and h sc (sc^2 is an even power of two, so
+// the root scales bit for bit, as for cylinders; the three products and two sums of h scale exactly), the two products with c and s and
+// their difference scale along, and the exact path's decision on (d, T2) is the one its arithmetic would take on (d sc, T2 sc^2):
+// the test is against Ts = T sc.  (c, s) is NOT rescaled: it is rounded to f32 as it is, every term below is relative to
+// K1 = |c| + |s|, and outside the band 2^-10 <= K1 <= 2^10 the filter is off.  Below d is the scaled direction, rho* = |(x - a) x d|,
+// h* = (x - a) . d and n* = c rho* - s h* in exact arithmetic on the f64 inputs.  Per point, in f32 - this operation order is the
+// contract of the f32 test (tests restate it with fma as one rounding):
+//   s~, l~ = Filter32<kLine3D>::dist(x~, a~, d~)  (the same code; e~_k = x~_k - a~_k),   h~ = fma(e~_2, d~_2, fma(e~_1, d~_1, e~_0 d~_0)),
+//   c~ = (float)c,  s_~ = (float)s,   n~ = fma(s~, c~, -(h~ s_~))
+// With u = 2^-24 and the 3-D line's terms as derived above, B = sqrt(3) u |d| P + u |d| |a| for the inputs x~ and a~ and t = u |d~| |e~|:
+//   rho        |s~ - rho*| + |rho_c - rho*| <= B + (7.5 + 2^-26) t and the underflow floor: the 3-D line's budget, its exact path included
+//   h~         h is |d|-Lipschitz in e and |e|-Lipschitz in d, so the inputs x~, a~ move it by at most B and d~ by t; e~ is rounded once
+//              per component, t; the innermost product is rounded three times (as a product and by both fmas), the middle one twice, the
+//              outer fma once: at most 3 u (|e~_0 d~_0| + |e~_1 d~_1| + |e~_2 d~_2|) <= 3 t by Cauchy-Schwarz.  |h~ - h*| <= B + 5 t
+//   exact h    three differences, three products, two sums in f64: < 2^-50 |e| |d| = 2^-26 t, inside the slack of e2 below
+//   c~, s_~    |c~ - c| <= u |c|, |s_~ - s| <= u |s|: n moves by u (|c| rho + |s| |h|) <= u K1 |e| |d| = K1 t  (rho, |h| <= |e| |d|)
+//   carried    the errors of s~ and h~ enter n~ times |c~| and |s_~|: (|c| + |s|)(B + 7.5 t) = K1 (B + 7.5 t), the larger of the two for both
+//   n~         the product h~ s_~ is rounded once, u |h~| |s_~| <= K1 t; the fma's own rounding is relative to n~ and is charged to
+//              the T'' margin and not to E, as the cylinder's subtraction is
+//   exact n    two products and a difference in f64: the products' 2^-53 (|c| rho + |s| |h|) is inside the same slack, the
+//              difference's rounding is relative and part of the T'' margin
+// so |n~ / (1 + t') - n*| + |n_c - n*| <= K1 (sqrt(3) u |d| P + u |d| |a| + (9.5 + 2^-25) u |d~| |e~|) + O(u^2), |t'| <= u, and with the
+// 3-D line's D = 1.001 |d| and K = 1.001 (|c| + |s|) (f64, rounded up):
+//   E = e1 P + e0 + e2 l~      e1 = 2 u D K                            >= 1.15 * sqrt(3) u |d| K1
+//                              e0 = 2 u D K |a| 1.001 + 1e-18 (K + 1)  >= 2 * u |d| |a| K1; the floor: the 3-D line's 4 * 2.2e-19 on s~
+//                                                                      times |c~| <= K, and 4 eta for h~ and the product h~ s_~
+//                              e2 = 10.5 u D K                         >= 1.1 * (9.5 + 2^-25) u |d~| K1
+//   reject  <=>  m := |n~| - E > T'' = Ts (1 + 2^-6):  m is rounded once and monotonically, so |n_c| > Ts (1 + 2^-7), and the computed
+//   residual's square, which the exact path compares, exceeds Ts^2 = T2 sc^2.
+// Group test on the 3-D ball rows (stored centre g, radius rho_g, Pmax) that planes, spheres, lines and cylinders get, nothing new in
+// setpoints.hip: x -> (h, rho) drops the angle about the axis and is |d|-Lipschitz, so the signed residual c rho - s h is L-Lipschitz in
+// x with L = |d| sqrt(c^2 + s^2) (its gradient is c rhohat - s d, of unit length for a unit d and a unit (c, s)).  Every member's
+// |n*| is at least |n*_g| - L rho_g, less the errors above with P = Pmax and |e|_1 <= |e_g|_1 + sqrt(3) rho_g:
+//   reject the group  <=>  |n~_g| - E(Pmax, l~_g + 1.74 rho_g) - 1.001 L rho_g > 1.001 T'',   L stored as nrm (times 1.001, rounded up).
+// Switch-off, E = inf and the exact path decides: the 3-D line's cases - coordinates beyond 1e17 or |a| beyond 1e17, Ts outside the
+// ordinary f32 range, a direction outside pow2_normaliser's band (d = 0, whose residuals are all 0 on the exact path, and Inf entries
+// among them) - and |c| + |s| outside [2^-10, 2^10], which a non-finite c or s is too (n~ stays below 2^10 * 6.1e17 * 2, an ordinary
+// f32, and an Inf entry would make inf - inf = NaN at best).  A NaN entry culls the hypothesis outright (all eight enter every
+// residual).  The exact path is the 3-D line's 17 FP64 operations plus a root, five for h, two products, a difference and a square.
+template <> struct Filter32<kCone3D> {
+    using Line = Filter32<kLine3D>;
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    struct Lane { float p[3]; float d[3]; float c, s, e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
+    // reject() reads p, d, c, s, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject): three float4 chunks
+    static constexpr int kStagedVals = 12;
+    static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, c) == 6 * sizeof(float) && offsetof(Lane, e1) == 8 * sizeof(float) &&
+                  offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
+                  sizeof(Lane) == 14 * sizeof(float), "p, d, c, s, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        const double d0[3] = {m[3], m[4], m[5]};
+        bool off;
+        const double sc = pow2_normaliser<3>(d0, &off);
+        bool nan = !(m[6] == m[6]) || !(m[7] == m[7]);
+        double d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k] = d0[k] * sc;
+            ln.p[k] = (float)m[k];
+            ln.d[k] = (float)d[k];
+            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
+        }
+        ln.nanh = nan ? 1.0f : 0.0f;
+        ln.c = (float)m[6];
+        ln.s = (float)m[7];
+        const double Ts = sqrt(T2) * sc;   // the threshold in the scaled direction's units: must be an ordinary f32 as well
+        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
+        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
+        const double k1 = fabs(m[6]) + fabs(m[7]);
+        const double K = k1 * 1.001;
+        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off || !(k1 >= 0.0009765625) || !(k1 <= 1024.0);
+        const double u = 5.9604644775390625e-8;
+        ln.e1 = f32_up(2.0 * u * dn * K);
+        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * dn * K * pn + 1e-18 * (K + 1.0));   // inf: nothing is rejected
+        ln.e2 = f32_up(10.5 * u * dn * K);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        ln.nrm = f32_up(dn * sqrt(m[6] * m[6] + m[7] * m[7]));
+        return ln;
+    }
+    // n~ and l~ of a point or a centre: the 3-D line's s~ and l~ on this lane's p and d, then h~ and the final fma
+    static __device__ __forceinline__ float signed_dist(const float* p, const Lane& ln, float* l1) {
+        const float s = Line::dist(p, ln, l1);
+        const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];   // dist's own e~ (the same subtractions)
+        const float h = __builtin_fmaf(e2, ln.d[2], __builtin_fmaf(e1, ln.d[1], e0 * ln.d[0]));
+        return __builtin_fmaf(s, ln.c, -(h * ln.s));
+    }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        float l1;
+        const float n = signed_dist(p, ln, &l1);
+        const float m = fabsf(n) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (centre[3], rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
+        float l1;
+        const float n = signed_dist(g, ln, &l1);
+        const float m = fabsf(n) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
 }  // namespace pgx

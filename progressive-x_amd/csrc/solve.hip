@@ -34,7 +34,11 @@
 //                                       point where a + s na and b + t nb cross seen along it, r = |s| |na|; the normals are the
 //                                       resident side array of pgx_set_normals; parallel normals, non-finite values and radii
 //                                       outside pgx_set_radius_range give NaN
-// The seven solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line, cylinder) share one kernel shell, solve_kernel<MT>;
+//   cone through three oriented points  findCones' minimal solver (no reference counterpart): the apex is the common point of the
+//                                       three tangent planes, the axis is orthogonal to the differences of the three unit vectors
+//                                       from the apex to the samples; tangent planes without a common point, a sample at the apex,
+//                                       non-finite values, cos <= 0 and a sine outside pgx_set_radius_range give NaN
+// The eight solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line, cylinder, cone) share one kernel shell, solve_kernel<MT>;
 // the 7-point, 4-point and P3P solvers run one lane per sample in kernels of their own.
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
@@ -63,9 +67,9 @@ __device__ __forceinline__ void cross3(double a1, double b1, double c1, double a
 
 // ---- the lane-per-model solvers: one __device__ function per type, one kernel shell ---------------------------------------------
 // solve_minimal(type, p, nq, rmin, rmax, m): p = the sample's Residual<MT>::sample point rows (all inside the point set), nq = the same
-// points' rows of the resident normals (pgx_set_normals; only the cylinder reads them, and the launch refuses it without them), m = the
-// model, preset to NaN - a degenerate sample leaves it so.  rmin, rmax: the context's pgx_set_radius_range (the round family and the
-// cylinder read them).
+// points' rows of the resident normals (pgx_set_normals; only the types with Residual<MT>::normals_solver read them, and the launch
+// refuses those without them), m = the model, preset to NaN - a degenerate sample leaves it so.  rmin, rmax: the context's
+// pgx_set_radius_range (the round family and the cylinder read them as radii, the cone as the range of its sine).
 template <int MT> using Type = std::integral_constant<int, MT>;
 
 // 2-point line [U-4]: unit normal (-dy, dx) / |d|, offset c = -(n . a); coincident points (ln == 0; also false on NaN) give NaN.
@@ -213,6 +217,57 @@ __device__ __forceinline__ void solve_minimal(Type<kCylinder3D>, const double* c
     m[0] = c0; m[1] = c1; m[2] = c2;
     m[3] = d0; m[4] = d1; m[5] = d2;
     m[6] = r;
+}
+
+// 3-point cone from oriented points -> (a, d, c, s), the apex, a unit axis direction pointing into the nappe and the cosine and sine of
+// the half-angle (findCones; no reference counterpart).  Every tangent plane of a cone passes through its apex, and the unit vectors
+// from the apex to points of one nappe all make the half-angle with the axis.  With samples p_i and their normals n_i (i = 0, 1, 2),
+// which need be neither unit nor consistently signed.  Operation order (the contract; ConeEstimator.minimal restates it):
+//   X0 = cross3(n1, n2), X1 = cross3(n2, n0), X2 = cross3(n0, n1), det = (n0_0 X0_0 + n0_1 X0_1) + n0_2 X0_2,
+//   b_i = (n_i0 p_i0 + n_i1 p_i1) + n_i2 p_i2,  a_k = ((b0 X0_k + b1 X1_k) + b2 X2_k) / det       (Cramer's rule on n_i . a = b_i),
+//   w_i = p_i - a (componentwise), l_i = sqrt((w_i0 w_i0 + w_i1 w_i1) + w_i2 w_i2), g_i = w_i / l_i,
+//   D = cross3(g1 - g0, g2 - g0), ln = sqrt((D0 D0 + D1 D1) + D2 D2), d = D / ln,
+//   t_i = (d0 g_i0 + d1 g_i1) + d2 g_i2; if (t0 + t1) + t2 < 0 then d = -d (each component);
+//   c = (d0 g_00 + d1 g_01) + d2 g_02 (with the final d),  s = sqrt(Residual<kLine3D>::squared(g0, (0, 0, 0, d))).
+// Flipping or rescaling a normal scales its b_i, two of the X_j and det together and leaves a, and everything after it, the same up to
+// rounding.  The model stays NaN unless det != 0, every l_i > 0, ln > 0, all eight entries are finite, c > 0 (a half-angle below 90
+// degrees: the three samples then lie on the nappe d points into) and rmin <= s <= rmax: the context's radius range bounds the sine
+// of the half-angle here.  A zero normal makes det 0 exactly, the same point twice makes g1 - g0 or g2 - g0 (and so D) 0 exactly, a sample
+// at the apex has l_i = 0.  Coplanar normals make det 0 only up to rounding: where it comes out as a tiny number the apex lies far
+// away and the model, if finite, collects no inliers.
+__device__ __forceinline__ void solve_minimal(Type<kCone3D>, const double* const* p, const double* const* nq, double rmin, double rmax, double* m)
+{
+    const double *n0 = nq[0], *n1 = nq[1], *n2 = nq[2];
+    double X[3][3], b[3], a[3], g[3][3], D[3];
+    cross3(n1[0], n1[1], n1[2], n2[0], n2[1], n2[2], X[0]);
+    cross3(n2[0], n2[1], n2[2], n0[0], n0[1], n0[2], X[1]);
+    cross3(n0[0], n0[1], n0[2], n1[0], n1[1], n1[2], X[2]);
+    const double det = (n0[0] * X[0][0] + n0[1] * X[0][1]) + n0[2] * X[0][2];
+    if (det == 0.0) return;
+    for (int i = 0; i < 3; ++i) b[i] = (nq[i][0] * p[i][0] + nq[i][1] * p[i][1]) + nq[i][2] * p[i][2];
+    for (int k = 0; k < 3; ++k) a[k] = ((b[0] * X[0][k] + b[1] * X[1][k]) + b[2] * X[2][k]) / det;
+    for (int i = 0; i < 3; ++i) {
+        const double w0 = p[i][0] - a[0], w1 = p[i][1] - a[1], w2 = p[i][2] - a[2];
+        const double l = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
+        if (!(l > 0.0)) return;
+        g[i][0] = w0 / l; g[i][1] = w1 / l; g[i][2] = w2 / l;
+    }
+    cross3(g[1][0] - g[0][0], g[1][1] - g[0][1], g[1][2] - g[0][2], g[2][0] - g[0][0], g[2][1] - g[0][1], g[2][2] - g[0][2], D);
+    const double ln = sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
+    if (!(ln > 0.0)) return;
+    double d[3] = {D[0] / ln, D[1] / ln, D[2] / ln};
+    double t[3];
+    for (int i = 0; i < 3; ++i) t[i] = (d[0] * g[i][0] + d[1] * g[i][1]) + d[2] * g[i][2];
+    if ((t[0] + t[1]) + t[2] < 0.0) { d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2]; }
+    const double c = (d[0] * g[0][0] + d[1] * g[0][1]) + d[2] * g[0][2];
+    const double axis[6] = {0.0, 0.0, 0.0, d[0], d[1], d[2]};
+    const double s = sqrt(Residual<kLine3D>::squared(g[0], axis));
+    if (!(isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]) && isfinite(c) &&
+          isfinite(s) && c > 0.0 && s >= rmin && s <= rmax))
+        return;
+    m[0] = a[0]; m[1] = a[1]; m[2] = a[2];
+    m[3] = d[0]; m[4] = d[1]; m[5] = d[2];
+    m[6] = c; m[7] = s;
 }
 
 // The shell: samples[S][sample] -> S x P models, one lane per padded model.  An index outside 0 .. n-1 gives a NaN model.  normals
@@ -677,9 +732,9 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     const int mt = ctx->model_type;
     ModelInfo mi;
     if (!model_info(mt, &mi) || mi.slots == 0)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 4-point homography, 7-point fundamental matrix, P3P)", mt);
-    if (mt == kCylinder3D && ctx->normals_n != ctx->n)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: the cylinder solver needs the resident points' normals (pgx_set_normals after pgx_set_points)");
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+    if (mi.normals_solver && ctx->normals_n != ctx->n)
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: the %s solver needs the resident points' normals (pgx_set_normals after pgx_set_points)", mi.normals_solver);
     // isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1 for these model types, so the solvers take
     // fscale, which pgx_set_points computes from the caller-visible data: umax is not kept either)
     const bool scaled = mt == kFundamental || mt == kHomography;

@@ -2,11 +2,12 @@
 (/root/reference/src/pyprogressivex/src/bindings.cpp:394-494) on top of libpgx.so (HIP, gfx950).
 
 The five entry points keep the reference's names, argument order, defaults, return layout and error messages;
-findPlanes, findSpheres, findLines3D and findCylinders (3-D point clouds) and findCircles (2-D point sets) are the same pipeline on model
+findPlanes, findSpheres, findLines3D, findCylinders and findCones (3-D point clouds) and findCircles (2-D point sets) are the same pipeline on model
 types the reference does not have.
 """
-from ._api import (estimateNormals, find6DPoses, findCircles, findCylinders, findFundamentalMatrices, findHomographies, findLines,
+from ._api import (estimateNormals, find6DPoses, findCircles, findCones, findCylinders, findFundamentalMatrices, findHomographies, findLines,
                    findLines3D, findPlanes, findSpheres, findTwoViewMotions, findVanishingPoints)
 
 __all__ = ["find6DPoses", "findHomographies", "findTwoViewMotions", "findFundamentalMatrices", "findLines",
-           "findVanishingPoints", "findPlanes", "findSpheres", "findCircles", "findLines3D", "findCylinders", "estimateNormals"]
+           "findVanishingPoints", "findPlanes", "findSpheres", "findCircles", "findLines3D", "findCylinders", "estimateNormals",
+           "findCones"]

@@ -1,4 +1,4 @@
-"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCones / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -363,7 +363,7 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
 
 
 def _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
-    """findPlanes / findSpheres / findCircles / findLines3D / findCylinders behind their signatures: the estimator says the point dimension (its
+    """findPlanes / findSpheres / findCircles / findLines3D / findCylinders / findCones behind their signatures: the estimator says the point dimension (its
     model type's), the sample size (= the fewest points accepted) and the columns of a model.  Only an estimator with a radius takes
     radius_range (its takes_radius_range says so): it goes to the estimator, and the estimator's context_setup puts its per-call state on
     the context."""
@@ -525,6 +525,49 @@ def findCylinders(points, normals, weights=None, threshold=0.05, conf=0.5, spati
         raise ValueError("normals should be an array with dims [n,3], one row per point")
     est.normals = nrm
     return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+
+
+def _angle_range(angle_range):
+    """angle_range=(amin, amax) of findCones, half-angles in degrees -> (sin amin, sin amax), checked like radius_range"""
+    try:
+        amin, amax = (float(v) for v in angle_range)
+    except (TypeError, ValueError):
+        raise ValueError("angle_range should be a pair (amin, amax) of half-angles in degrees") from None
+    if not (amin > 0.0 and amax >= amin and amax < 90.0):
+        raise ValueError("angle_range should satisfy 0 < amin <= amax < 90 (degrees, no NaN)")
+    return float(np.sin(np.deg2rad(amin))), float(np.sin(np.deg2rad(amax)))
+
+
+def findCones(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
+              neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
+              minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
+              do_logging=False, *, angle_range=(1.0, 89.0), seed=None, max_outer_iterations=10, neighborhood="flann_like",
+              local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+    """Multi-cone fitting of an oriented 3-D point cloud: funnels, reducers, hoppers, tapered columns (no reference counterpart:
+    findCylinders' pipeline with a 3-point solver on points with normals and a Gauss-Newton refit on six parameters).  points [n, 3],
+    normals [n, 3] (required): one surface normal per point, as a normal estimator gives them (estimateNormals(points) computes them
+    from the cloud itself) - they may be unsigned and need not be unit length; only the minimal solver reads them, and a sample whose
+    three tangent planes have no single common point gives no hypothesis.  Returns (cones[K, 8] float64 (ax, ay, az, dx, dy, dz, c, s):
+    the apex, a unit axis direction pointing into the nappe, and the cosine and sine of the half-angle, both positive; labels[n]
+    int32) in findPlanes' labelling convention.  The model is one nappe without ends: it says nothing about where the cone is cut.
+    threshold bounds abs(c rho - s h) in the cloud's units, with h = (x - a) . d the height over the apex and rho = |(x - a) x d| the
+    distance from the axis: the distance to the generatrix line, which is the distance to the surface except behind the apex
+    (h c + rho s < 0), where it is smaller than the distance to the apex.  angle_range=(amin, amax) (keyword-only, half-angles in
+    degrees, 0 < amin <= amax < 90) drops hypotheses and refits whose half-angle lies outside it.  `weights` [n], when given, weight
+    the least-squares refits.  Sampler ids, the remaining arguments and their caveats are findCylinders'; recovery on make_cones
+    scenes is reported, not tuned, in DESIGN.md 4.12."""
+    est = _estimators.ConeEstimator()
+    points, nrm = _as_f64(points), _as_f64(normals)
+    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
+        raise ValueError("normals should be an array with dims [n,3], one row per point")
+    est.normals = nrm
+    return _find_primitive(est, points, weights, _angle_range(angle_range), sampler_id, do_logging, neighborhood_ball_radius,
                            threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
                            maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
                            minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,

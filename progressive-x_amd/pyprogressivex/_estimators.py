@@ -499,6 +499,145 @@ class CylinderEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Cone (findCones; no reference counterpart): 3-point solver on oriented points, Gauss-Newton refit on six parameters
+# ---------------------------------------------------------------------------------------------------------------------
+class ConeEstimator(Estimator):
+    """Model (a[3], d[3], c, s): the apex, a unit axis direction pointing into the nappe, the cosine and sine of the half-angle.
+    `normals` [n, 3] (per point, neither unit nor consistently signed) are read by the minimal solver alone.  `radius_range` is the
+    range of s = sin(half-angle) of hypotheses and refits, (sin theta_min, sin theta_max): a cone has no radius, and the context's radius
+    range carries its angle range (include/pgx.h).
+
+    nonminimal_sample_size is 6, the number of parameters of the chart (apex 3, direction 2, angle 1): with fewer points the 6x6 normal
+    matrix is singular for every configuration.  As for cylinders it is not raised above that: the refit always starts from a model
+    that was scored."""
+    model_type = _lib.CONE3D
+    sample_size = 3
+    nonminimal_sample_size = 6
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
+    cols = 8
+    takes_radius_range = True
+    radius_range = (0.0, 1.0)
+    normals = None             # [n, 3] float64, in the points' order (findCones sets it)
+
+    def context_setup(self, ctx):
+        ctx.set_radius_range(*self.radius_range)
+        ctx.set_normals(self.normals)
+
+    def _in_range(self, s):
+        return (s >= self.radius_range[0]) & (s <= self.radius_range[1])
+
+    def minimal(self, pts, samples):
+        """samples [S, 3] -> cones (a, d, c, s), bitwise csrc/solve.hip's solve_minimal for cones, with p_i the samples and n_i their
+        normals: X0 = cross3(n1, n2), X1 = cross3(n2, n0), X2 = cross3(n0, n1), det = (n0_0 X0_0 + n0_1 X0_1) + n0_2 X0_2,
+        b_i = (n_i0 p_i0 + n_i1 p_i1) + n_i2 p_i2, a_k = ((b0 X0_k + b1 X1_k) + b2 X2_k) / det, w_i = p_i - a, l_i = |w_i|, g_i = w_i / l_i,
+        D = cross3(g1 - g0, g2 - g0), ln = |D|, d = D / ln, negated when ((d . g0) + (d . g1)) + (d . g2) < 0, c = d . g0,
+        s = sqrt of the 3-D line's squared residual of g0 about (0, d).  No model unless det != 0, every l_i > 0, ln > 0, everything is
+        finite, c > 0 and s lies in radius_range."""
+        p = [pts[samples[:, i]] for i in range(3)]
+        nrm = np.asarray(self.normals, dtype=np.float64)
+        n = [nrm[samples[:, i]] for i in range(3)]
+        dot = lambda x, y: (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]   # noqa: E731  (on component lists)
+        comp = lambda x: [x[:, 0], x[:, 1], x[:, 2]]                   # noqa: E731
+        with np.errstate(all="ignore"):
+            X = [_cross3(n[1], n[2]), _cross3(n[2], n[0]), _cross3(n[0], n[1])]
+            det = dot(comp(n[0]), X[0])
+            b = [dot(comp(n[i]), comp(p[i])) for i in range(3)]
+            a = [((b[0] * X[0][k] + b[1] * X[1][k]) + b[2] * X[2][k]) / det for k in range(3)]
+            g, lpos = [], np.ones(len(samples), dtype=bool)
+            for i in range(3):
+                w = [p[i][:, k] - a[k] for k in range(3)]
+                ln_i = np.sqrt(dot(w, w))
+                lpos &= ln_i > 0
+                g.append([w[k] / ln_i for k in range(3)])
+            r1 = np.column_stack([g[1][k] - g[0][k] for k in range(3)])
+            r2 = np.column_stack([g[2][k] - g[0][k] for k in range(3)])
+            D = _cross3(r1, r2)
+            ln = np.sqrt(dot(D, D))
+            d = [D[k] / ln for k in range(3)]
+            t = [dot(d, g[i]) for i in range(3)]
+            flip = (t[0] + t[1]) + t[2] < 0
+            d = [np.where(flip, -d[k], d[k]) for k in range(3)]
+            c = dot(d, g[0])
+            e = [g[0][k] - 0.0 for k in range(3)]
+            c0 = e[1] * d[2] - e[2] * d[1]
+            c1 = -(e[0] * d[2] - e[2] * d[0])
+            c2 = e[0] * d[1] - e[1] * d[0]
+            s = np.sqrt((c0 * c0 + c1 * c1) + c2 * c2)
+            models = np.column_stack([a[0], a[1], a[2], d[0], d[1], d[2], c, s])
+            ok = (det != 0) & lpos & (ln > 0) & np.isfinite(models).all(axis=1) & (c > 0) & self._in_range(s)
+        return models[ok], np.nonzero(ok)[0]
+
+    @staticmethod
+    def canonical(m):
+        """[B, 8] -> the same cones (every residual keeps its value) with s >= 0 and c >= 0: (c, s) -> (-c, -s) negates c rho - s h, and
+        so does (d, c) -> (-d, -c).  Afterwards d points into the nappe: that is its sign, there is no other convention."""
+        m = np.array(m, dtype=np.float64, copy=True)
+        neg = m[:, 7] < 0
+        m[neg, 6:8] = -m[neg, 6:8]
+        neg = m[:, 6] < 0
+        m[neg, 3:7] = -m[neg, 3:7]
+        return m
+
+    def _fit_many(self, gram, B, inits, iterations=10):
+        """Geometric least squares, sum w (c rho - s h)^2 with rho = |(x - a) x d| and h = (x - a) . d, by Gauss-Newton from `inits` in
+        the shape of CylinderEstimator._fit_many: at most 10 iterations on [B, ...] stacks, each ONE Gram request (GRAM_CONE_GN, weight
+        power 1) at params (a, d, c, s, u) with u = _cylinder_frame(d) and v = d x u.  The rows are (J, f) with
+        J = df / d(alpha, beta, gamma, delta, eta, tau) in the chart a + alpha u + beta v + gamma d, normalise(d + delta u + eta v),
+        (c, s) <- normalise(c - tau s, s + tau c) (csrc/fit.hip GenConeGn), so step = pinv(J^T J)(-J^T f) with the cut-off 6 eps, then
+        that update; an item stops at |step| < 1e-12.  An item fails without an init, with fewer than 6 points, with a point on its axis
+        (bad) or with non-finite sums.  Afterwards the model is made canonical (canonical(): d unit and pointing into the nappe, (c, s)
+        unit with both entries positive); a model that is not finite, has c <= 0 or s <= 0, or whose s is outside radius_range is
+        dropped."""
+        out = [[] for _ in range(B)]
+        have = np.array([ini is not None for ini in inits], dtype=bool)
+        if not have.any():
+            return out
+        m = np.zeros((B, 8))
+        m[:, 5] = m[:, 6] = 1.0
+        for b in np.nonzero(have)[0]:
+            m[b] = np.asarray(inits[b], dtype=np.float64).reshape(8)
+        with np.errstate(all="ignore"):
+            m[:, 3:6] /= np.linalg.norm(m[:, 3:6], axis=1)[:, None]
+            m[:, 6:8] /= np.linalg.norm(m[:, 6:8], axis=1)[:, None]
+        failed = ~have | ~np.isfinite(m).all(axis=1)
+        running = ~failed
+        for _ in range(iterations):
+            act = np.nonzero(running)[0]
+            if act.size == 0:
+                break
+            u = _cylinder_frame(m[act, 3:6])
+            G, cnt, bad = gram(_lib.GRAM_CONE_GN, np.column_stack([m[act], u]), True, 1, act)
+            A, rhs = G[:, :6, :6], -G[:, :6, 6]
+            ok = (np.asarray(bad) == 0) & (np.asarray(cnt) >= 6) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(rhs).all(axis=1)
+            failed[act[~ok]] = True
+            running[act[~ok]] = False
+            if not ok.any():
+                break
+            act, A, rhs, u = act[ok], A[ok], rhs[ok], u[ok]
+            d = m[act, 3:6]
+            v = np.cross(d, u)
+            step = np.einsum("bij,bj->bi", np.linalg.pinv(A, rcond=6 * np.finfo(np.float64).eps), rhs)
+            m[act, 0:3] += step[:, 0:1] * u + step[:, 1:2] * v + step[:, 2:3] * d
+            d = d + step[:, 3:4] * u + step[:, 4:5] * v
+            m[act, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
+            cs = np.column_stack([m[act, 6] - step[:, 5] * m[act, 7], m[act, 7] + step[:, 5] * m[act, 6]])
+            m[act, 6:8] = cs / np.linalg.norm(cs, axis=1)[:, None]
+            fin = np.isfinite(m[act]).all(axis=1)
+            failed[act[~fin]] = True
+            running[act[~fin]] = False
+            running[act[np.linalg.norm(step, axis=1) < 1e-12]] = False
+        rows = np.nonzero(~failed)[0]
+        if rows.size == 0:
+            return out
+        mc = self.canonical(m[rows])
+        for k, b in enumerate(rows):
+            model = mc[k]
+            if np.isfinite(model).all() and model[6] > 0 and model[7] > 0 and self._in_range(model[7]):
+                out[b] = [model]
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D circle: the round family's other member
 # ---------------------------------------------------------------------------------------------------------------------
 class CircleEstimator(RoundEstimator):
@@ -1163,6 +1302,7 @@ ESTIMATORS = {
     "circle": CircleEstimator,
     "line3d": Line3DEstimator,
     "cylinder": CylinderEstimator,
+    "cone": ConeEstimator,
     "vanishing_point": VanishingPointEstimator,
     "homography": HomographyEstimator,
     "homography_sym": SymmetricHomographyEstimator,

@@ -21,11 +21,12 @@ SPHERE3D = 8                   # (7 is not assigned: include/pgx.h)
 CIRCLE2D = 10                  # (9 is not assigned either)
 LINE3D = 12                    # (nor is 11)
 CYLINDER3D = 14                # (nor 13)
+CONE3D = 16                    # (nor 15)
 # per model type: (doubles per point, doubles per model, minimal sample size, hypotheses per sample of the device solver);
 # sample size 0 = no device solver (pgx_solve_minimal fails).  The numbers of csrc/residuals.hip.h; tests/test_abi.py compares.
 MODEL_TABLE = {LINE2D: (2, 3, 2, 1), HOMOGRAPHY: (4, 9, 4, 1), FUNDAMENTAL: (4, 9, 7, 3), PNP: (5, 12, 3, 4),
                VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1),
-               CIRCLE2D: (2, 3, 3, 1), LINE3D: (3, 6, 2, 1), CYLINDER3D: (3, 7, 2, 1)}
+               CIRCLE2D: (2, 3, 3, 1), LINE3D: (3, 6, 2, 1), CYLINDER3D: (3, 7, 2, 1), CONE3D: (3, 8, 3, 1)}
 POINT_DIM = {t: row[0] for t, row in MODEL_TABLE.items()}
 PARAM_DIM = {t: row[1] for t, row in MODEL_TABLE.items()}
 FIXED_ONE = float(1 << 32)
@@ -49,8 +50,8 @@ ABI_SYMBOLS = [
 
 
 GRAPH_KNN_IN_BALL, GRAPH_BALL, GRAPH_KNN = 0, 1, 2
-GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE, GRAM_CYL_GN = 0, 1, 2, 3, 4, 5, 6, 7
-GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5, GRAM_CIRCLE: 4, GRAM_CYL_GN: 6}   # GRAM_AFFINE: point dimension + 1
+GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE, GRAM_CYL_GN, GRAM_CONE_GN = 0, 1, 2, 3, 4, 5, 6, 7, 8
+GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5, GRAM_CIRCLE: 4, GRAM_CYL_GN: 6, GRAM_CONE_GN: 7}   # GRAM_AFFINE: point dimension + 1
 
 
 _TRIU = {}
@@ -279,12 +280,12 @@ class Context:
         self._w_obj = weights
 
     def set_radius_range(self, rmin=0.0, rmax=float("inf")):
-        """pgx_set_radius_range: the radii the 4-point sphere, the 3-point circle and the 2-point cylinder solver accept (context state; [0, inf] at creation)"""
+        """pgx_set_radius_range: the radii the 4-point sphere, the 3-point circle and the 2-point cylinder solver accept, and the range of sin(half-angle) the 3-point cone solver accepts (context state; [0, inf] at creation)"""
         self._ck(self._lib.pgx_set_radius_range(self._h, C.c_double(float(rmin)), C.c_double(float(rmax))), "pgx_set_radius_range")
 
     def set_normals(self, normals):
         """pgx_set_normals: per-point normals [n, 3] of the resident points, uploaded once and checked against n (None clears).  Only
-        the cylinder's minimal solver reads them; they need be neither unit nor consistently oriented.  set_points invalidates them."""
+        the cylinder's and the cone's minimal solvers read them; they need be neither unit nor consistently oriented.  set_points invalidates them."""
         if normals is None or len(normals) == 0:
             self._ck(self._lib.pgx_set_normals(self._h, None, C.c_int64(0)), "pgx_set_normals")
             return
@@ -520,7 +521,7 @@ class Context:
         return off, idx[:arcs], mult[:arcs]
 
     def solve_minimal(self, samples, fetch=True):
-        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder from the resident normals, ...), generated from the
+        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder and 3-point cone from the resident normals, ...), generated from the
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)

@@ -160,6 +160,64 @@ def make_cylinders(n_per_cylinder=8000, n_cylinders=6, n_outliers=48000, sigma=0
     return pts, nrm, np.concatenate(labels).astype(np.int32), np.array(models).reshape(-1, 7)
 
 
+def make_cones(n_per_cone=8000, n_cones=6, n_outliers=48000, sigma=0.01, size=10.0, half_angle_deg=(15.0, 40.0), extent=(1.0, 4.0),
+               normal_noise_deg=5.0, seed=0, normals="synthetic"):
+    """findCones' workload: K cones with uniformly random unit axis directions and half-angles uniform in `half_angle_deg` (degrees),
+    each cut to the axial extent [hmin, hmax] = `extent` measured from the apex along the axis and lying wholly inside the box
+    [0, size]^3 (the apex is drawn where the piece up to hmax fits; cones may cross); the inliers of cone k are uniform on that piece
+    of its lateral surface (the height is the root of a uniform draw between hmin^2 and hmax^2: the circumference grows with the
+    height) with Gaussian noise of `sigma` along the surface normal cos(theta) rhohat - sin(theta) d; their normals are those unit
+    surface normals tilted by an angle uniform in [0, normal_noise_deg] about a random axis orthogonal to them, each with a random
+    sign.  The outliers are uniform in the box with uniformly random unit normals.  Returns (points [n, 3], normals [n, 3] (unit),
+    labels [n] (k + 1 = cone k, 0 = outlier), gt_cones [K, 8] = (apex, unit direction into the nappe, cos(theta), sin(theta))).
+    A pure function of the seed.  normals="estimated" returns, in place of those synthetic normals, what estimateNormals(points) computes
+    from the same points (k = 16 nearest neighbours, unsigned; needs the GPU)."""
+    if normals not in ("synthetic", "estimated"):
+        raise ValueError('normals should be "synthetic" or "estimated"')
+    rng = np.random.default_rng(seed)
+    amin, amax = (float(v) for v in half_angle_deg)
+    hmin, hmax = (float(v) for v in extent)
+    if not (0.0 < amin <= amax < 90.0 and 0.0 <= hmin < hmax):
+        raise ValueError("half_angle_deg and extent should satisfy 0 < min <= max < 90 and 0 <= hmin < hmax")
+    tmax = np.deg2rad(amax)
+    if not max(hmax / np.cos(tmax), 2.0 * hmax * np.tan(tmax)) <= size:
+        raise ValueError("the largest cone, hmax / cos(max angle) long and 2 hmax tan(max angle) wide, should fit the box")
+    pts, nrm, labels, models = [], [], [], []
+    for k in range(n_cones):
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        theta = np.deg2rad(rng.uniform(amin, amax))
+        c, s = np.cos(theta), np.sin(theta)
+        side = hmax * np.tan(theta) * np.sqrt(np.maximum(0.0, 1.0 - d * d))
+        lo, hi = np.minimum(0.0, hmax * d - side), np.maximum(0.0, hmax * d + side)
+        apex = rng.uniform(-lo, size - hi)
+        e1 = np.cross(d, rng.normal(size=3))
+        e1 /= np.linalg.norm(e1)
+        e2 = np.cross(d, e1)
+        h = np.sqrt(rng.uniform(hmin * hmin, hmax * hmax, n_per_cone))
+        phi = rng.uniform(-np.pi, np.pi, n_per_cone)
+        rad = np.cos(phi)[:, None] * e1 + np.sin(phi)[:, None] * e2
+        nk0 = c * rad - s * d
+        pts.append(apex + h[:, None] * d + (h * (s / c))[:, None] * rad + nk0 * rng.normal(0, sigma, n_per_cone)[:, None])
+        # tilt: rotate the normal by `ang` towards a random unit vector of its tangent plane, spanned by the generatrix and d x rad
+        ang = np.deg2rad(rng.uniform(0.0, normal_noise_deg, n_per_cone))
+        psi = rng.uniform(0.0, 2.0 * np.pi, n_per_cone)
+        tang = np.cos(psi)[:, None] * (c * d + s * rad) + np.sin(psi)[:, None] * np.cross(d, rad)
+        nk = np.cos(ang)[:, None] * nk0 + np.sin(ang)[:, None] * tang
+        nrm.append(nk * rng.choice([-1.0, 1.0], n_per_cone)[:, None])
+        labels.append(np.full(n_per_cone, k + 1))
+        models.append(np.concatenate([apex, d, [c, s]]))
+    pts.append(rng.uniform(0, size, (n_outliers, 3)))
+    no = rng.normal(size=(n_outliers, 3))
+    nrm.append(no / np.linalg.norm(no, axis=1)[:, None])
+    labels.append(np.zeros(n_outliers, dtype=int))
+    pts, nrm = np.ascontiguousarray(np.vstack(pts)), np.ascontiguousarray(np.vstack(nrm))
+    if normals == "estimated":
+        from ._api import estimateNormals
+        nrm = estimateNormals(pts)
+    return pts, nrm, np.concatenate(labels).astype(np.int32), np.array(models).reshape(-1, 8)
+
+
 def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.5), coverage=1.0, seed=0):
     """findSpheres' workload: K non-overlapping spheres with radii uniform in `radius` and centres inside the box [0, size]^3 (each
     sphere lies wholly inside it); the inliers of sphere k are uniform on its surface - or, with coverage < 1, on the cap of that
@@ -444,4 +502,4 @@ def misclassification_models(preferences, annotation, K_annot):
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
                    vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D,
-                   line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D)
+                   line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D, cone=_lib.CONE3D)
