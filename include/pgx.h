@@ -48,11 +48,18 @@ enum pgx_model_type {
     PGX_CYLINDER3D = 14,      /* point (x,y,z);          model (px,py,pz,dx,dy,dz,r), a point on the axis, a direction (unit from
                                                          the solver and the refit) and a radius; the minimal solver also reads the
                                                          resident normals (pgx_set_normals)     findCylinders        */
-    PGX_CONE3D = 16           /* point (x,y,z);          model (ax,ay,az,dx,dy,dz,c,s), the apex, an axis direction pointing into the
+    PGX_CONE3D = 16,          /* point (x,y,z);          model (ax,ay,az,dx,dy,dz,c,s), the apex, an axis direction pointing into the
                                                          nappe (unit from the solver and the refit) and the cosine and sine of the
                                                          half-angle; the minimal solver also reads the resident normals
                                                          (pgx_set_normals)                      findCones            */
-    /* 7, 9, 11, 13 and 15 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
+    PGX_PRIMITIVE3D = 18      /* point (x,y,z);          model (class, q0 .. q7): a tagged union of the four surface types.  class is
+                                                         the constituent's type number as a double (6 plane, 8 sphere, 14 cylinder,
+                                                         16 cone), q its model row padded with zeros; the residual is the
+                                                         constituent's on q, bit for bit, and any other class (NaN included) gives
+                                                         NaN residuals.  The minimal solver makes four hypotheses per sample of four
+                                                         oriented points, one per class (pgx_set_primitive_classes), and reads the
+                                                         resident normals (pgx_set_normals)     findPrimitives       */
+    /* 7, 9, 11, 13, 15 and 17 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -105,7 +112,12 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * pgx_set_normals has not been called for the resident points; parallel normals, non-finite values and radii outside
  * pgx_set_radius_range give NaN), the 3-point cone solver (samples[S][3], S x 8, findCones: it reads the three samples' resident
  * normals and fails with PGX_ERR_INVALID without them; tangent planes without a common point, a sample at the apex, non-finite
- * values, a half-angle of 90 degrees or more and sin(half-angle) outside pgx_set_radius_range give NaN), the 4-point homography
+ * values, a half-angle of 90 degrees or more and sin(half-angle) outside pgx_set_radius_range give NaN), the 4-point mixed-primitive
+ * solver (samples[S][4], FOUR slots per sample: 4S x 9 rows (class, q), slot 0 the plane of samples 0 1 2, slot 1 the sphere of all
+ * four, slot 2 the cylinder of samples 0 1 and slot 3 the cone of samples 0 1 2 with their normals, each the constituent solver's
+ * model behind its class number; it fails with PGX_ERR_INVALID without the resident normals; a slot without a model, of a class
+ * that pgx_set_primitive_classes has switched off, or with an index outside the points among those its own solver reads is an
+ * all-NaN row, class included), the 4-point homography
  * solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
@@ -118,9 +130,17 @@ int pgx_solve_minimal(pgx_ctx *ctx, const int32_t *samples, int S, double *model
  * PGX_ERR_INVALID.  rmax = +inf is allowed.  For PGX_CONE3D the same range bounds s = sin(half-angle) of the cone solver's models:
  * a cone has no radius, and (sin(theta_min), sin(theta_max)) is its angle range. */
 int pgx_set_radius_range(pgx_ctx *ctx, double rmin, double rmax);
+/* What the mixed-primitive solver (PGX_PRIMITIVE3D) makes (context state; at pgx_create all four classes and [0, 1]).  class_mask:
+ * bit 0 plane, bit 1 sphere, bit 2 cylinder, bit 3 cone, in slot order; a class that is off leaves its slot an all-NaN row.
+ * (smin, smax) is the range of s = sin(half-angle) of that solver's cones.  Its spheres and cylinders read pgx_set_radius_range as
+ * radii, as under their own types: one pair cannot be a range of radii and a range of sines at once, which is why this call exists.
+ * No other model type reads this state.  A mask of 0, a mask with bits above the four, NaN or !(0 <= smin <= smax <= 1):
+ * PGX_ERR_INVALID, and the state stays as it was. */
+int pgx_set_primitive_classes(pgx_ctx *ctx, int class_mask, double smin, double smax);
 /* Per-point surface normals, n x 3 doubles in the points' order, RESIDENT like the weights of pgx_set_weights and under the same
  * rules: len == n is checked (PGX_ERR_INVALID), (NULL, 0) clears them, pgx_set_points invalidates them.  They need not be unit
- * length nor consistently oriented.  Only the cylinder's and the cone's minimal solvers read them; the point rows stay n x 3. */
+ * length nor consistently oriented.  Only the cylinder's, the cone's and the mixed-primitive minimal solvers read them; the point rows
+ * stay n x 3. */
 int pgx_set_normals(pgx_ctx *ctx, const double *normals, int64_t len);
 /* The same with the samples DRAWN ON THE DEVICE by the in-repo counter-based generator (csrc/rng.hip.h: Philox4x32-10; sample s
  * of batch `batch` under `key` is a pure function of (key, batch, s); m = the resident model type's minimal sample size).

@@ -945,6 +945,19 @@ int pgx_set_radius_range(pgx_ctx* ctx, double rmin, double rmax)
     return PGX_OK;
 }
 
+int pgx_set_primitive_classes(pgx_ctx* ctx, int class_mask, double smin, double smax)
+{
+    CTX_GUARD(ctx);
+    if (class_mask <= 0 || class_mask > 15)
+        return fail(ctx, PGX_ERR_INVALID, "pgx_set_primitive_classes: class_mask %d (bits 0 .. 3: plane, sphere, cylinder, cone; at least one)", class_mask);
+    if (!(smin >= 0.0) || !(smax >= smin) || !(smax <= 1.0))   // also NaN
+        return fail(ctx, PGX_ERR_INVALID, "pgx_set_primitive_classes: need 0 <= smin <= smax <= 1 (got %g, %g)", smin, smax);
+    ctx->prim_mask = class_mask;
+    ctx->prim_smin = smin;
+    ctx->prim_smax = smax;
+    return PGX_OK;
+}
+
 int pgx_gram(pgx_ctx* ctx, int kind, const double* params, int nparams, int sel, const int32_t* index, int64_t m, int label,
              int use_weights, int weight_power, double* out, int64_t* count, int64_t* bad)
 {

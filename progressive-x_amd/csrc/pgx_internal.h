@@ -59,6 +59,8 @@ struct pgx_ctx {
     double umax = 0.0;       // max |observed image coordinate| over all points
     double fscale = 0.0;     // max(1, max |coordinate|) over all points: isotropic pre-scaling of the minimal solvers
     double rmin = 0.0, rmax = __builtin_inf();   // pgx_set_radius_range: the radii the sphere, the circle and the cylinder solver accept, the sines of the cone's (context state)
+    int prim_mask = 15;                          // pgx_set_primitive_classes: the classes the mixed-primitive solver makes (bit j = slot j) and the
+    double prim_smin = 0.0, prim_smax = 1.0;     // sines its cones may have (context state; its spheres and cylinders read rmin, rmax)
     pgx::ScoreSwitches score_sw;   // PGX_NO_FILTER, PGX_SCORE_NO_CULL, PGX_SCORE_MIRROR, PGX_VERIFY and pgx_score_debug_geometry: what plan_score reads (score_plan.h)
     pgx::DevBuf stats_buf;         // work counters of a pgx_score_stats launch
     // spatially sorted copies for the score kernel (group-level rejection); aliases of the originals
@@ -154,7 +156,7 @@ struct pgx_ctx {
     pgx::DevBuf weights;      // resident per-point weights of the weighted refits (pgx_set_weights), weights_n == n when valid
     int64_t weights_n = 0;
     pgx::DevBuf normals;      // resident per-point normals n x 3, caller's order (pgx_set_normals), normals_n == n when valid: only the
-    int64_t normals_n = 0;    // cylinder's and the cone's minimal solvers read them
+    int64_t normals_n = 0;    // cylinder's, the cone's and the mixed-primitive minimal solvers read them
 
     pgx::CommState* comm = nullptr;
 };

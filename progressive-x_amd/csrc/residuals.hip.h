@@ -1,6 +1,7 @@
 // residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the geometric primitives: the two
 // families flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension, and the 3-D line
-// (distance to an axis), the cylinder (that distance less a radius) and the cone (the distance to a generatrix).  gfx950 device code.
+// (distance to an axis), the cylinder (that distance less a radius), the cone (the distance to a generatrix) and the union of plane,
+// sphere, cylinder and cone whose model row carries its class.  gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -20,8 +21,8 @@ namespace pgx {
 
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
-    kSphere3D = 8, kCircle2D = 10, kLine3D = 12, kCylinder3D = 14, kCone3D = 16,
-    kNumModelTypes = 17   // 7, 9, 11, 13 and 15 are not assigned (pgx_model_dims(7), (9), (11), (13) and (15) are errors)
+    kSphere3D = 8, kCircle2D = 10, kLine3D = 12, kCylinder3D = 14, kCone3D = 16, kPrimitive3D = 18,
+    kNumModelTypes = 19   // 7, 9, 11, 13, 15 and 17 are not assigned (pgx_model_dims(7), (9), (11), (13), (15) and (17) are errors)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -165,6 +166,37 @@ template <> struct Residual<kCone3D> : NoProjectiveMap {
     }
 };
 
+// Mixed primitives (findPrimitives; no reference counterpart): a tagged union of the four surface types.  Model (class, q[8]): class is
+// the constituent's type number as a double - 6 plane, 8 sphere, 14 cylinder, 16 cone - and q is that type's model row, padded with
+// zeros.  The residual is the constituent's on q: the same functions, so the same bits as the model scored under its own type.  Any
+// other class value (NaN and values that are no whole number included: the comparisons are on the double itself) gives a NaN residual,
+// which is never an inlier.  The padding is never read.  The four types share D = 3 and the ball bound, so the resident point rows,
+// their Morton order and the group rows are the same whichever of the five types is resident.  Instances never change class.
+template <> struct Residual<kPrimitive3D> : NoProjectiveMap {
+    static constexpr int D = 3, P = 9, sample = 4, slots = 4, bound = kBoundBall;
+    static constexpr const char* normals_solver = "primitive";
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        const double cls = m[0];
+        const double q[8] = {m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]};
+        if (cls == (double)kPlane3D) return Residual<kPlane3D>::plain(p, q);
+        if (cls == (double)kSphere3D) return Residual<kSphere3D>::plain(p, q);
+        if (cls == (double)kCylinder3D) return Residual<kCylinder3D>::plain(p, q);
+        if (cls == (double)kCone3D) return Residual<kCone3D>::plain(p, q);
+        return __builtin_nan("");
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double cls = m[0];
+        const double q[8] = {m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]};
+        if (cls == (double)kPlane3D) return Residual<kPlane3D>::squared(p, q);
+        if (cls == (double)kSphere3D) return Residual<kSphere3D>::squared(p, q);
+        if (cls == (double)kCylinder3D) return Residual<kCylinder3D>::squared(p, q);
+        if (cls == (double)kCone3D) return Residual<kCone3D>::squared(p, q);
+        return __builtin_nan("");
+    }
+};
+
 // DefaultHomographyEstimator (progressivex_python.cpp:252) [U-1]: one-way forward transfer error,
 // H row-major 3x3 (progressivex_python.cpp:292-300).
 template <> struct Residual<kHomography> {
@@ -274,6 +306,7 @@ template <class F> inline bool with_model_type(int mt, F&& f) {
     case kLine3D: f(std::integral_constant<int, kLine3D>{}); return true;
     case kCylinder3D: f(std::integral_constant<int, kCylinder3D>{}); return true;
     case kCone3D: f(std::integral_constant<int, kCone3D>{}); return true;
+    case kPrimitive3D: f(std::integral_constant<int, kPrimitive3D>{}); return true;
     default: return false;
     }
 }

@@ -973,4 +973,78 @@ template <> struct Filter32<kCone3D> {
     }
 };
 
+// ---- mixed primitives: the constituent's filter behind the class (Residual<kPrimitive3D>) -------------------------------------------
+// Nothing is derived here.  A lane is the class followed by the constituent's own lane, float for float as its prep() made it from the
+// constituent's model row q = m + 1; reject() and group_reject() hand that lane to the constituent's functions, so every f32 operation,
+// every constant and every decision is the constituent's, and so are its budget and its switch-off cases (tests hold the union's
+// surviving (hypothesis, group) pairs and masks to the constituents').  The point rows and the group rows are the four types' common
+// ones: kRowVals = 6, kGroupVals = 5.  The widest staged form is the cone's 12 floats, so 13 are staged: the plane's and the sphere's
+// nine (their whole lanes), the cylinder's 11 and the cone's 12 all lie inside them, and what lies behind (nrm, nanh of the cylinder and
+// the cone) only group_reject() reads, in the cull kernel, from registers.
+// An unknown class never rejects a pair or a group: its lane holds class 0 and zeros, and the exact path produces the NaN residual.  The
+// one exception is a NaN class in group_reject(): it culls, as a NaN entry does in every constituent (the class enters every residual,
+// and the solver's empty slots are all-NaN rows: without the cull each of them would be evaluated against every point).
+// The class is compared, never used as an index: a lane copy is a fixed sequence of register moves, and a divergent word of the cull
+// kernel or of the hypothesis-per-lane kernel runs the paths of the classes it holds one after the other under their lane masks.  In
+// the group-major and the pointwise kernels a hypothesis is uniform over the wave and exactly one path runs.
+template <> struct Filter32<kPrimitive3D> {
+    using Plane = Filter32<kPlane3D>;
+    using Sphere = Filter32<kSphere3D>;
+    using Cylinder = Filter32<kCylinder3D>;
+    using Cone = Filter32<kCone3D>;
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    static constexpr int kSubVals = 14;   // the widest constituent lane (the cone's)
+    struct Lane { float cls; float v[kSubVals]; };   // a row of floats in this order (score.hip HypRow)
+    static constexpr int kStagedVals = 1 + StagedVals<Cone>::value;
+    static_assert(Plane::kRowVals == 6 && Sphere::kRowVals == 6 && Cylinder::kRowVals == 6 && Cone::kRowVals == 6 && Plane::kGroupVals == 5 &&
+                  Sphere::kGroupVals == 5 && Cylinder::kGroupVals == 5 && Cone::kGroupVals == 5, "the four constituents read the same rows");
+    static_assert(sizeof(Plane::Lane) <= kSubVals * sizeof(float) && sizeof(Sphere::Lane) <= kSubVals * sizeof(float) &&
+                  sizeof(Cylinder::Lane) <= kSubVals * sizeof(float) && sizeof(Cone::Lane) == kSubVals * sizeof(float) &&
+                  StagedVals<Plane>::value < kStagedVals && StagedVals<Sphere>::value < kStagedVals && StagedVals<Cylinder>::value < kStagedVals &&
+                  offsetof(Lane, v) == sizeof(float) && sizeof(Lane) == (1 + kSubVals) * sizeof(float), "class, then the constituent's lane");
+    // the constituent's lane into v, zeros behind it / out of v again: constant indices only
+    template <class L> static __device__ __forceinline__ void put(Lane& ln, const L& sub) {
+        const float* src = reinterpret_cast<const float*>(&sub);
+#pragma unroll
+        for (int k = 0; k < kSubVals; ++k) ln.v[k] = k < (int)(sizeof(L) / sizeof(float)) ? src[k] : 0.0f;
+    }
+    template <class L> static __device__ __forceinline__ L sub(const Lane& ln) {
+        L out;
+        float* dst = reinterpret_cast<float*>(&out);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(L) / sizeof(float)); ++k) dst[k] = ln.v[k];
+        return out;
+    }
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        const double cls = m[0];
+        const double q[8] = {m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]};
+        ln.cls = cls == cls ? 0.0f : __builtin_nanf("");
+#pragma unroll
+        for (int k = 0; k < kSubVals; ++k) ln.v[k] = 0.0f;
+        if (cls == (double)kPlane3D) { ln.cls = (float)kPlane3D; put(ln, Plane::prep(q, pscale, T2)); }
+        else if (cls == (double)kSphere3D) { ln.cls = (float)kSphere3D; put(ln, Sphere::prep(q, pscale, T2)); }
+        else if (cls == (double)kCylinder3D) { ln.cls = (float)kCylinder3D; put(ln, Cylinder::prep(q, pscale, T2)); }
+        else if (cls == (double)kCone3D) { ln.cls = (float)kCone3D; put(ln, Cone::prep(q, pscale, T2)); }
+        return ln;
+    }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float T2d) {
+        if (ln.cls == (float)kPlane3D) return Plane::reject(p, sub<Plane::Lane>(ln), T2d);
+        if (ln.cls == (float)kSphere3D) return Sphere::reject(p, sub<Sphere::Lane>(ln), T2d);
+        if (ln.cls == (float)kCylinder3D) return Cylinder::reject(p, sub<Cylinder::Lane>(ln), T2d);
+        if (ln.cls == (float)kCone3D) return Cone::reject(p, sub<Cone::Lane>(ln), T2d);
+        return false;
+    }
+    // g = (centre[3], rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float Tup) {
+        if (ln.cls == (float)kPlane3D) return Plane::group_reject(g, sub<Plane::Lane>(ln), Tup);
+        if (ln.cls == (float)kSphere3D) return Sphere::group_reject(g, sub<Sphere::Lane>(ln), Tup);
+        if (ln.cls == (float)kCylinder3D) return Cylinder::group_reject(g, sub<Cylinder::Lane>(ln), Tup);
+        if (ln.cls == (float)kCone3D) return Cone::group_reject(g, sub<Cone::Lane>(ln), Tup);
+        return ln.cls != ln.cls;   // a NaN class: every residual is NaN, never an inlier; any other unknown class is kept
+    }
+};
+
 }  // namespace pgx

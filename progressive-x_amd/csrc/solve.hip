@@ -39,7 +39,8 @@
 //                                       from the apex to the samples; tangent planes without a common point, a sample at the apex,
 //                                       non-finite values, cos <= 0 and a sine outside pgx_set_radius_range give NaN
 // The eight solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line, cylinder, cone) share one kernel shell, solve_kernel<MT>;
-// the 7-point, 4-point and P3P solvers run one lane per sample in kernels of their own.
+// the 7-point, 4-point and P3P solvers and the mixed-primitive solver (four slots of four classes per sample) run one lane per sample in
+// kernels of their own.
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
 // A degenerate sample (coincident points / parallel or identical lines) yields a NaN model, which can never have an
 // inlier; the caller drops it (the reference's solvers return "no model").
@@ -298,6 +299,53 @@ __global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __rest
         solve_minimal(Type<MT>{}, p, nq, rmin, rmax, m);
     }
     for (int k = 0; k < R::P; ++k) models[(int64_t)s * R::P + k] = m[k];
+}
+
+// ---- mixed primitives: four hypotheses of four classes per sample ---------------------------------------------------------------------
+// One lane per sample of four oriented points (i0, i1, i2, i3); its four slots are rows 4 s + j of the batch, each (class, q[8]):
+//   slot 0  class 6   the plane of points 0, 1, 2                          solve_minimal(Type<kPlane3D>)
+//   slot 1  class 8   the sphere of points 0 .. 3                          solve_minimal(Type<kSphere3D>), radii in [rmin, rmax]
+//   slot 2  class 14  the cylinder of points 0, 1 and their normals        solve_minimal(Type<kCylinder3D>), radii in [rmin, rmax]
+//   slot 3  class 16  the cone of points 0, 1, 2 and their normals         solve_minimal(Type<kCone3D>), sines in [smin, smax]
+// Each slot is the constituent's own device function on the sample's prefix - the same code, so the same bits as that type's solver on
+// the same indices - written behind its class number, the rest of the row zeros.  A slot whose solver leaves its model all NaN, whose
+// class is switched off (bit j of `mask`, pgx_set_primitive_classes) or whose PREFIX - the indices its solver reads - has an index
+// outside 0 .. n-1 is an all-NaN row, class included: an index behind a slot's prefix does not concern that slot, as under its own type.
+__global__ __launch_bounds__(64) void solve_primitive_kernel(const double* __restrict__ pts, const double* __restrict__ normals, int64_t n,
+                                                             const int* __restrict__ samples, int S, int mask, double rmin, double rmax,
+                                                             double smin, double smax, double* __restrict__ models, int* __restrict__ perm,
+                                                             int Mpad)
+{
+    using R = Residual<kPrimitive3D>;
+    const int s = (int)(blockIdx.x * 64 + threadIdx.x);
+    for (int t = s; t < Mpad; t += (int)(gridDim.x * 64)) perm[t] = t < 4 * S ? t : 0;
+    if (s >= S) return;
+    const double nan = __builtin_nan("");
+    const double *p[4], *nq[4];
+    int inb = 0;   // the leading indices that are inside the point set
+    for (int k = 0; k < 4; ++k) {
+        const int i = samples[4 * s + k];
+        const bool in = i >= 0 && i < n;
+        if (in && inb == k) inb = k + 1;
+        p[k] = pts + (int64_t)(in ? i : 0) * 3;
+        nq[k] = normals + (int64_t)(in ? i : 0) * 3;
+    }
+    double* out = models + (int64_t)s * 4 * R::P;
+    auto slot = [&](int j, auto type) {
+        constexpr int MT = decltype(type)::value;
+        double q[Residual<MT>::P];
+        for (int k = 0; k < Residual<MT>::P; ++k) q[k] = nan;
+        if (inb >= Residual<MT>::sample && ((mask >> j) & 1)) solve_minimal(type, p, nq, MT == kCone3D ? smin : rmin, MT == kCone3D ? smax : rmax, q);
+        bool have = false;   // any entry set: the row is the constituent's as it stands (a plane of overflowing points may hold a NaN)
+        for (int k = 0; k < Residual<MT>::P; ++k) have = have || q[k] == q[k];
+        double* row = out + j * R::P;
+        row[0] = have ? (double)MT : nan;
+        for (int k = 0; k < R::P - 1; ++k) row[1 + k] = !have ? nan : k < Residual<MT>::P ? q[k] : 0.0;
+    };
+    slot(0, Type<kPlane3D>{});
+    slot(1, Type<kSphere3D>{});
+    slot(2, Type<kCylinder3D>{});
+    slot(3, Type<kCone3D>{});
 }
 
 // ---- P3P -------------------------------------------------------------------------------------------------------------
@@ -732,7 +780,7 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     const int mt = ctx->model_type;
     ModelInfo mi;
     if (!model_info(mt, &mi) || mi.slots == 0)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone, 4-point mixed primitives, 4-point homography, 7-point fundamental matrix, P3P)", mt);
     if (mi.normals_solver && ctx->normals_n != ctx->n)
         return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: the %s solver needs the resident points' normals (pgx_set_normals after pgx_set_points)", mi.normals_solver);
     // isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1 for these model types, so the solvers take
@@ -754,10 +802,13 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     if (mt == kFundamental) hipLaunchKernelGGL(solve_f7_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
     else if (mt == kHomography) hipLaunchKernelGGL(solve_h4_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
     else if (mt == kPnP) hipLaunchKernelGGL(solve_p3p_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
+    else if (mt == kPrimitive3D)
+        hipLaunchKernelGGL(solve_primitive_kernel, gs, bs, 0, ctx->stream, pts, normals, ctx->n, smp, S, ctx->prim_mask, ctx->rmin, ctx->rmax, ctx->prim_smin,
+                           ctx->prim_smax, models, perm, Mpad);
     else   // the lane-per-model solvers: whatever else declares slots has a solve_minimal, or this does not compile
         with_model_type(mt, [&](auto t) {
             constexpr int MT = decltype(t)::value;
-            if constexpr (Residual<MT>::slots > 0 && MT != kFundamental && MT != kHomography && MT != kPnP)
+            if constexpr (Residual<MT>::slots > 0 && MT != kFundamental && MT != kHomography && MT != kPnP && MT != kPrimitive3D)
                 hipLaunchKernelGGL((solve_kernel<MT>), gm, bm, 0, ctx->stream, pts, normals, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
         });
     PGX_HIP(ctx, hipGetLastError());

@@ -1,4 +1,4 @@
-"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCones / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCones / findPrimitives / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -363,7 +363,7 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
 
 
 def _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
-    """findPlanes / findSpheres / findCircles / findLines3D / findCylinders / findCones behind their signatures: the estimator says the point dimension (its
+    """findPlanes / findSpheres / findCircles / findLines3D / findCylinders / findCones / findPrimitives behind their signatures: the estimator says the point dimension (its
     model type's), the sample size (= the fewest points accepted) and the columns of a model.  Only an estimator with a radius takes
     radius_range (its takes_radius_range says so): it goes to the estimator, and the estimator's context_setup puts its per-call state on
     the context."""
@@ -568,6 +568,48 @@ def findCones(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_c
         raise ValueError("normals should be an array with dims [n,3], one row per point")
     est.normals = nrm
     return _find_primitive(est, points, weights, _angle_range(angle_range), sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+
+
+PRIMITIVE_CLASSES = dict(_estimators.PRIMITIVE_CLASSES)   # name -> class number (column 0 of findPrimitives' models)
+
+
+def findPrimitives(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
+                   neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
+                   minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
+                   do_logging=False, *, classes=("plane", "sphere", "cylinder", "cone"), radius_range=None, angle_range=(1.0, 89.0), seed=None,
+                   max_outer_iterations=10, neighborhood="flann_like", local_optimization="auto", labeling_l0="greedy", distributed=None,
+                   sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+    """Planes, spheres, cylinders and cones of an oriented 3-D point cloud in ONE fit: walls, tanks, pipes and reducers of the same scan
+    compete for its points under one compound score, one Tanimoto validation and one labelling (no reference counterpart: findCones'
+    pipeline on a model type whose instances carry their class).  points [n, 3], normals [n, 3].  The normals are REQUIRED whatever the
+    classes - also for classes=("plane",), whose solver does not read them: a sample is four oriented points, and the call does not
+    change its inputs with its options.  They may be unsigned and need not be unit length; only the minimal solvers of cylinders and
+    cones read them.  estimateNormals(points, radius=...) computes them from the cloud itself: choose its radius against the noise, a
+    few times sigma at least (16 nearest neighbours of a dense scan see only its noise).
+    Returns (models[K, 9] float64, labels[n] int32) in findPlanes' labelling convention.  Column 0 of a model is its class number
+    (PRIMITIVE_CLASSES: plane 6, sphere 8, cylinder 14, cone 16), columns 1 .. 8 that class's model row as findPlanes (a, b, c, d),
+    findSpheres (cx, cy, cz, r), findCylinders (px, py, pz, dx, dy, dz, r) and findCones (ax, ay, az, dx, dy, dz, c, s) return it, padded
+    with zeros.  threshold bounds the class's own residual, in the cloud's units.  Every sample of four points gives up to four
+    hypotheses: the plane of its first three points, the sphere of all four, the cylinder of the first two and the cone of the first
+    three with their normals.  An instance never changes class: refits keep the class of the hypothesis they start from.
+    classes (keyword-only) selects the classes that are proposed, by name; radius_range=(rmin, rmax) bounds the radii of spheres and
+    cylinders (default: any), angle_range=(amin, amax) the half-angles of cones in degrees, 0 < amin <= amax < 90.  PEARL refits no
+    instance with fewer points than the largest refit among the selected classes needs (6 with cones).  `weights`, the sampler ids and
+    the remaining arguments are findCones'.  What the call recovers on make_primitives scenes, and what the four single-class calls
+    find on the same scenes, is reported, not tuned, in DESIGN.md 4.13."""
+    est = _estimators.PrimitiveEstimator(classes)
+    points, nrm = _as_f64(points), _as_f64(normals)
+    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
+        raise ValueError("normals should be an array with dims [n,3], one row per point")
+    est.normals = nrm
+    est.sine_range = _angle_range(angle_range)
+    return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
                            threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
                            maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
                            minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,

@@ -638,6 +638,139 @@ class ConeEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Mixed primitives (findPrimitives; no reference counterpart): planes, spheres, cylinders and cones in one fit
+# ---------------------------------------------------------------------------------------------------------------------
+# name -> class number, in the slot order of the device solver (and the bit order of pgx_set_primitive_classes)
+PRIMITIVE_CLASSES = {"plane": _lib.PLANE3D, "sphere": _lib.SPHERE3D, "cylinder": _lib.CYLINDER3D, "cone": _lib.CONE3D}
+
+
+class PrimitiveEstimator(Estimator):
+    """Model (class, q0 .. q7): the class number of a constituent type (6 plane, 8 sphere, 14 cylinder, 16 cone) and that type's model
+    row padded with zeros.  The estimator owns one constituent estimator per enabled class (`parts`, class number -> estimator) and
+    adds nothing of its own to their arithmetic: minimal() is their minimal() on the sample prefixes, a refit is their refit on the
+    items of their class.  An instance never changes class: a refit reads the class from its init and puts it back in front.
+
+    `radius_range` bounds the radii of spheres and cylinders, `sine_range` the sine of the cones' half-angle (the device solver reads
+    the first from pgx_set_radius_range and the second from pgx_set_primitive_classes); `normals` [n, 3] go to the cylinder's and the
+    cone's solvers.  nonminimal_sample_size is the largest among the enabled classes: PEARL refits no instance with fewer points,
+    whatever its class."""
+    model_type = _lib.PRIMITIVE3D
+    sample_size = 4
+    nonminimal_sample_size = 6
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU, four slots per sample (same operation order as minimal())
+    device_slots = 4
+    cols = 9
+    takes_radius_range = True
+    # per class, in slot order: (class number, constituent, points of the sample it reads)
+    _SLOTS = ((_lib.PLANE3D, PlaneEstimator, 3), (_lib.SPHERE3D, SphereEstimator, 4), (_lib.CYLINDER3D, CylinderEstimator, 2),
+              (_lib.CONE3D, ConeEstimator, 3))
+
+    def __init__(self, classes=tuple(PRIMITIVE_CLASSES)):
+        try:
+            classes = list(classes)
+        except TypeError:
+            classes = []
+        unknown = [c for c in classes if c not in PRIMITIVE_CLASSES]
+        if unknown or not classes or len(set(classes)) != len(classes):
+            raise ValueError("classes should be a non-empty selection of distinct names among " + ", ".join(PRIMITIVE_CLASSES))
+        on = {PRIMITIVE_CLASSES[c] for c in classes}
+        self.parts = {cls: make() for cls, make, _ in self._SLOTS if cls in on}
+        self.class_mask = sum(1 << j for j, (cls, _, _) in enumerate(self._SLOTS) if cls in on)
+        self.nonminimal_sample_size = max(p.nonminimal_sample_size for p in self.parts.values())
+        self._radius_range = (0.0, np.inf)
+        self._sine_range = (0.0, 1.0)
+        self._normals = None
+        self.radius_range, self.sine_range = self._radius_range, self._sine_range
+
+    @property
+    def radius_range(self):
+        return self._radius_range
+
+    @radius_range.setter
+    def radius_range(self, rng):
+        self._radius_range = (float(rng[0]), float(rng[1]))
+        for cls in (_lib.SPHERE3D, _lib.CYLINDER3D):
+            if cls in self.parts:
+                self.parts[cls].radius_range = self._radius_range
+
+    @property
+    def sine_range(self):
+        return self._sine_range
+
+    @sine_range.setter
+    def sine_range(self, rng):
+        self._sine_range = (float(rng[0]), float(rng[1]))
+        if _lib.CONE3D in self.parts:
+            self.parts[_lib.CONE3D].radius_range = self._sine_range     # the cone estimator's range is that of its sine
+
+    @property
+    def normals(self):
+        return self._normals
+
+    @normals.setter
+    def normals(self, nrm):
+        self._normals = nrm
+        for cls in (_lib.CYLINDER3D, _lib.CONE3D):
+            if cls in self.parts:
+                self.parts[cls].normals = nrm
+
+    def context_setup(self, ctx):
+        ctx.set_normals(self._normals)
+        ctx.set_radius_range(*self._radius_range)
+        ctx.set_primitive_classes(self.class_mask, *self._sine_range)
+
+    def _row(self, cls, q):
+        """(class, q padded with zeros) for one model row or a stack of them"""
+        q = np.asarray(q, dtype=np.float64)
+        out = np.zeros(q.shape[:-1] + (self.cols,))
+        out[..., 0] = cls
+        out[..., 1:1 + q.shape[-1]] = q
+        return out
+
+    def minimal(self, pts, samples):
+        """samples [S, 4] -> the rows csrc/solve.hip's solve_primitive_kernel fills, bit for bit, without its all-NaN rows: slot j of sample
+        s (row 4 s + j there) is the j-th constituent's minimal() on the sample's first 3 (plane), 4 (sphere), 2 (cylinder) or 3 (cone)
+        indices, behind its class number.  Returned in that order, sample by sample; a class that is off has no slot."""
+        samples = np.asarray(samples)
+        rows, src, slot = [], [], []
+        for j, (cls, _, m) in enumerate(self._SLOTS):
+            if cls not in self.parts:
+                continue
+            models, of = self.parts[cls].minimal(pts, samples[:, :m])
+            rows.append(self._row(cls, models).reshape(-1, self.cols))
+            src.append(np.asarray(of, dtype=np.int64))
+            slot.append(np.full(len(of), j, dtype=np.int64))
+        rows, src, slot = np.concatenate(rows), np.concatenate(src), np.concatenate(slot)
+        order = np.lexsort((slot, src))
+        return rows[order], src[order]
+
+    def _fit_many(self, gram, B, inits):
+        """The items are grouped by the class of their init, and each group goes to its constituent's _fit_many with the inits' model
+        rows and a Gram provider restricted to the group's items: a request of the constituent for its items `rows` is the request of
+        this provider for items group[rows], so no request mixes kinds, and the constituent sees exactly its rows and parameter rows.
+        The results come back in place with the class in front.  An item without an init, with a class that is unknown or not
+        enabled, gets no model.  The class of a result is the class of its init."""
+        out = [[] for _ in range(B)]
+        cls_of = np.full(B, np.nan)
+        for b, ini in enumerate(inits):
+            if ini is not None:
+                cls_of[b] = np.asarray(ini, dtype=np.float64).reshape(-1)[0]
+        for cls, part in self.parts.items():
+            group = np.nonzero(cls_of == float(cls))[0]
+            if group.size == 0:
+                continue
+            part.refit_solver, part._eig_ctx = self.refit_solver, self._eig_ctx
+
+            def sub(kind, prm, use_w, wpow, rows, group=group):
+                return gram(kind, prm, use_w, wpow, group[np.asarray(rows, dtype=np.int64)])
+            P = part.cols
+            fits = part._fit_many(sub, len(group), [np.asarray(inits[b], dtype=np.float64).reshape(-1)[1:1 + P] for b in group])
+            for b, models in zip(group, fits):
+                out[b] = [self._row(cls, m) for m in models]
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D circle: the round family's other member
 # ---------------------------------------------------------------------------------------------------------------------
 class CircleEstimator(RoundEstimator):
@@ -1303,6 +1436,7 @@ ESTIMATORS = {
     "line3d": Line3DEstimator,
     "cylinder": CylinderEstimator,
     "cone": ConeEstimator,
+    "primitive": PrimitiveEstimator,
     "vanishing_point": VanishingPointEstimator,
     "homography": HomographyEstimator,
     "homography_sym": SymmetricHomographyEstimator,

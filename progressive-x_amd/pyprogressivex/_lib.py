@@ -22,11 +22,13 @@ CIRCLE2D = 10                  # (9 is not assigned either)
 LINE3D = 12                    # (nor is 11)
 CYLINDER3D = 14                # (nor 13)
 CONE3D = 16                    # (nor 15)
+PRIMITIVE3D = 18               # (nor 17): the union of PLANE3D, SPHERE3D, CYLINDER3D and CONE3D, model (class, q0 .. q7)
 # per model type: (doubles per point, doubles per model, minimal sample size, hypotheses per sample of the device solver);
 # sample size 0 = no device solver (pgx_solve_minimal fails).  The numbers of csrc/residuals.hip.h; tests/test_abi.py compares.
 MODEL_TABLE = {LINE2D: (2, 3, 2, 1), HOMOGRAPHY: (4, 9, 4, 1), FUNDAMENTAL: (4, 9, 7, 3), PNP: (5, 12, 3, 4),
                VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1),
-               CIRCLE2D: (2, 3, 3, 1), LINE3D: (3, 6, 2, 1), CYLINDER3D: (3, 7, 2, 1), CONE3D: (3, 8, 3, 1)}
+               CIRCLE2D: (2, 3, 3, 1), LINE3D: (3, 6, 2, 1), CYLINDER3D: (3, 7, 2, 1), CONE3D: (3, 8, 3, 1),
+               PRIMITIVE3D: (3, 9, 4, 4)}
 POINT_DIM = {t: row[0] for t, row in MODEL_TABLE.items()}
 PARAM_DIM = {t: row[1] for t, row in MODEL_TABLE.items()}
 FIXED_ONE = float(1 << 32)
@@ -39,7 +41,7 @@ ABI_SYMBOLS = [
     "pgx_set_points", "pgx_set_compound", "pgx_get_compound",
     "pgx_score", "pgx_score_upload", "pgx_score_launch", "pgx_score_fetch", "pgx_score_algorithmic_bytes", "pgx_score_stats", "pgx_score_profile", "pgx_score_kernel_times", "pgx_score_debug_fetch", "pgx_score_debug_geometry",
     "pgx_preference", "pgx_get_preference", "pgx_compound_update",
-    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_normals",
+    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_primitive_classes", "pgx_set_normals",
     "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals",
     "pgx_bucket", "pgx_residual_sum", "pgx_gc_labeling", "pgx_gc_inliers", "pgx_epipolar_support", "pgx_gram_batch", "pgx_gram_labels", "pgx_residual_sums", "pgx_pnp_refine_batch",
     "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_barrier", "pgx_comm_allreduce_max_f64",
@@ -283,9 +285,17 @@ class Context:
         """pgx_set_radius_range: the radii the 4-point sphere, the 3-point circle and the 2-point cylinder solver accept, and the range of sin(half-angle) the 3-point cone solver accepts (context state; [0, inf] at creation)"""
         self._ck(self._lib.pgx_set_radius_range(self._h, C.c_double(float(rmin)), C.c_double(float(rmax))), "pgx_set_radius_range")
 
+    def set_primitive_classes(self, class_mask=15, smin=0.0, smax=1.0):
+        """pgx_set_primitive_classes: the classes the mixed-primitive solver (PRIMITIVE3D) makes - bit 0 plane, 1 sphere, 2 cylinder, 3 cone, in
+        slot order - and the range of sin(half-angle) of its cones (context state; all four and [0, 1] at creation).  Its spheres and
+        cylinders read set_radius_range as radii."""
+        self._ck(self._lib.pgx_set_primitive_classes(self._h, C.c_int(int(class_mask)), C.c_double(float(smin)), C.c_double(float(smax))),
+                 "pgx_set_primitive_classes")
+
     def set_normals(self, normals):
         """pgx_set_normals: per-point normals [n, 3] of the resident points, uploaded once and checked against n (None clears).  Only
-        the cylinder's and the cone's minimal solvers read them; they need be neither unit nor consistently oriented.  set_points invalidates them."""
+        the cylinder's, the cone's and the mixed-primitive minimal solvers read them; they need be neither unit nor consistently oriented.
+        set_points invalidates them."""
         if normals is None or len(normals) == 0:
             self._ck(self._lib.pgx_set_normals(self._h, None, C.c_int64(0)), "pgx_set_normals")
             return
@@ -521,7 +531,7 @@ class Context:
         return off, idx[:arcs], mult[:arcs]
 
     def solve_minimal(self, samples, fetch=True):
-        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder and 3-point cone from the resident normals, ...), generated from the
+        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone and the four slots of the mixed primitives from the resident normals, ...), generated from the
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)

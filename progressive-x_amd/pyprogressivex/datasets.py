@@ -218,6 +218,62 @@ def make_cones(n_per_cone=8000, n_cones=6, n_outliers=48000, sigma=0.01, size=10
     return pts, nrm, np.concatenate(labels).astype(np.int32), np.array(models).reshape(-1, 8)
 
 
+def make_primitives(n_per=8000, n_outliers=32000, seed=0, n_each=1, sigma=0.01, size=10.0, normal_noise_deg=5.0, normals="synthetic"):
+    """findPrimitives' workload: `n_each` planes, spheres, cylinders and cones in one box [0, size]^3, `n_per` points on each, and
+    `n_outliers` uniform points.  The instances and their inliers are those of make_planes, make_spheres, make_cylinders and make_cones
+    with their default shapes, each called for its class alone (no outliers) under its own seed derived from `seed`, so every class keeps
+    its generator's conventions and its noise of `sigma` along the surface normal; instances of different classes may cross.  The
+    normals: the cylinders' and cones' are their generators' tilted ones; the planes' and spheres' are the true unit normals (the plane's
+    normal, the sphere's radial direction) tilted the same way - by an angle uniform in [0, normal_noise_deg] towards a random unit
+    vector orthogonal to them, each with a random sign; the outliers' are uniformly random unit vectors.  Returns (points [n, 3],
+    normals [n, 3] (unit), gt_class [n] (the class number 6 / 8 / 14 / 16 of the point's instance, 0 = outlier), gt_instance [n]
+    (k + 1 = row k of gt_models, 0 = outlier), gt_models [4 n_each, 9] = (class, the generator's model row padded with zeros), planes
+    first, then spheres, cylinders, cones).  A pure function of the seed.  normals="estimated" returns, in place of the synthetic
+    normals, what estimateNormals(points) computes from the same points (k = 16 nearest neighbours, unsigned; needs the GPU)."""
+    if normals not in ("synthetic", "estimated"):
+        raise ValueError('normals should be "synthetic" or "estimated"')
+    if n_each < 1 or n_per < 1 or n_outliers < 0:
+        raise ValueError("n_each and n_per should be at least 1, n_outliers at least 0")
+    seeds = [int(v) for v in np.random.SeedSequence(int(seed)).generate_state(5)]
+    rng = np.random.default_rng(seeds[4])
+
+    def tilted(nk0):
+        t = np.cross(nk0, rng.normal(size=nk0.shape))
+        t /= np.linalg.norm(t, axis=1)[:, None]
+        ang = np.deg2rad(rng.uniform(0.0, normal_noise_deg, len(nk0)))
+        nk = np.cos(ang)[:, None] * nk0 + np.sin(ang)[:, None] * t
+        return nk * rng.choice([-1.0, 1.0], len(nk0))[:, None]
+
+    p_pl, l_pl, g_pl = make_planes(n_per_plane=n_per, n_planes=n_each, n_outliers=0, sigma=sigma, size=size, seed=seeds[0])
+    p_sp, l_sp, g_sp = make_spheres(n_per_sphere=n_per, n_spheres=n_each, n_outliers=0, sigma=sigma, size=size, seed=seeds[1])
+    p_cy, n_cy, l_cy, g_cy = make_cylinders(n_per_cylinder=n_per, n_cylinders=n_each, n_outliers=0, sigma=sigma, size=size,
+                                            normal_noise_deg=normal_noise_deg, seed=seeds[2])
+    p_co, n_co, l_co, g_co = make_cones(n_per_cone=n_per, n_cones=n_each, n_outliers=0, sigma=sigma, size=size,
+                                        normal_noise_deg=normal_noise_deg, seed=seeds[3])
+    n_pl = tilted(g_pl[l_pl - 1, :3])
+    radial = p_sp - g_sp[l_sp - 1, :3]
+    n_sp = tilted(radial / np.linalg.norm(radial, axis=1)[:, None])
+    out_p = rng.uniform(0, size, (n_outliers, 3))
+    out_n = rng.normal(size=(n_outliers, 3))
+    out_n /= np.linalg.norm(out_n, axis=1)[:, None]
+    pts = np.ascontiguousarray(np.vstack([p_pl, p_sp, p_cy, p_co, out_p]))
+    nrm = np.ascontiguousarray(np.vstack([n_pl, n_sp, n_cy, n_co, out_n]))
+    parts = ((_lib.PLANE3D, l_pl, g_pl), (_lib.SPHERE3D, l_sp, g_sp), (_lib.CYLINDER3D, l_cy, g_cy), (_lib.CONE3D, l_co, g_co))
+    gt = np.zeros((4 * n_each, 9))
+    cls, inst = [], []
+    for j, (c, lab, g) in enumerate(parts):
+        gt[j * n_each:(j + 1) * n_each, 0] = c
+        gt[j * n_each:(j + 1) * n_each, 1:1 + g.shape[1]] = g
+        cls.append(np.full(len(lab), c))
+        inst.append(lab + j * n_each)
+    cls.append(np.zeros(n_outliers, dtype=int))
+    inst.append(np.zeros(n_outliers, dtype=int))
+    if normals == "estimated":
+        from ._api import estimateNormals
+        nrm = estimateNormals(pts)
+    return pts, nrm, np.concatenate(cls).astype(np.int32), np.concatenate(inst).astype(np.int32), gt
+
+
 def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.5), coverage=1.0, seed=0):
     """findSpheres' workload: K non-overlapping spheres with radii uniform in `radius` and centres inside the box [0, size]^3 (each
     sphere lies wholly inside it); the inliers of sphere k are uniform on its surface - or, with coverage < 1, on the cap of that
@@ -502,4 +558,4 @@ def misclassification_models(preferences, annotation, K_annot):
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
                    vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D,
-                   line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D, cone=_lib.CONE3D)
+                   line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D, cone=_lib.CONE3D, primitive=_lib.PRIMITIVE3D)
