@@ -52,14 +52,33 @@ enum pgx_model_type {
                                                          nappe (unit from the solver and the refit) and the cosine and sine of the
                                                          half-angle; the minimal solver also reads the resident normals
                                                          (pgx_set_normals)                      findCones            */
-    PGX_PRIMITIVE3D = 18      /* point (x,y,z);          model (class, q0 .. q7): a tagged union of the four surface types.  class is
+    PGX_PRIMITIVE3D = 18,     /* point (x,y,z);          model (class, q0 .. q7): a tagged union of the four surface types.  class is
                                                          the constituent's type number as a double (6 plane, 8 sphere, 14 cylinder,
                                                          16 cone), q its model row padded with zeros; the residual is the
                                                          constituent's on q, bit for bit, and any other class (NaN included) gives
                                                          NaN residuals.  The minimal solver makes four hypotheses per sample of four
                                                          oriented points, one per class (pgx_set_primitive_classes), and reads the
                                                          resident normals (pgx_set_normals)     findPrimitives       */
-    /* 7, 9, 11, 13, 15 and 17 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
+    PGX_ORIENTED_PRIMITIVE3D = 20 /* point (x,y,z);      model (class, q0 .. q7) exactly as PGX_PRIMITIVE3D, and its distance; but a point
+                                                         supports a model only if its resident normal n (pgx_set_normals) also agrees with
+                                                         the model's surface normal at the point (Schnabel et al., Efficient RANSAC, 4.3).
+                                                         g, the unnormalised direction of that normal: plane (a,b,c); sphere x - c;
+                                                         cylinder e - t d with e = x - p, t = e.d; cone c w - (s rho) d with e = x - a,
+                                                         h = e.d, w = e - h d, rho the root the cone's residual computes.  Every dot
+                                                         product is a left fold, (u0 v0 + u1 v1) + u2 v2; with nn = n.n, gg = g.g,
+                                                         ng = n.g and w = nn gg the point is COMPATIBLE iff ng ng >= kappa w and w > 0,
+                                                         kappa = cos^2(tolerance) (pgx_set_normal_tolerance): FP64, no contraction, no
+                                                         division; blind to the sign and the length of n; any NaN, a zero normal and g = 0
+                                                         (a point on the axis, at the apex or the centre) are incompatible.  The squared
+                                                         residual - scores, masks, preference vectors, unary costs, the inlier / outlier
+                                                         cut - is type 18's where the point is compatible and +inf where it is not (a class
+                                                         that is no class: NaN); the unsquared residual of pgx_residual_sum(s) is type
+                                                         18's distance whatever the normal, the quantity the refits minimise.  Every call
+                                                         that evaluates the squared residual fails with PGX_ERR_INVALID without the
+                                                         resident normals.  The minimal solver is type 18's, and a slot whose model is not
+                                                         compatible with every point of its own prefix is an all-NaN row
+                                                                                                findOrientedPrimitives */
+    /* 7, 9, 11, 13, 15, 17 and 19 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -117,7 +136,8 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * four, slot 2 the cylinder of samples 0 1 and slot 3 the cone of samples 0 1 2 with their normals, each the constituent solver's
  * model behind its class number; it fails with PGX_ERR_INVALID without the resident normals; a slot without a model, of a class
  * that pgx_set_primitive_classes has switched off, or with an index outside the points among those its own solver reads is an
- * all-NaN row, class included), the 4-point homography
+ * all-NaN row, class included; under PGX_ORIENTED_PRIMITIVE3D the same four slots, and a slot whose model is not compatible with every
+ * point of its own prefix at the resident normal tolerance is an all-NaN row as well), the 4-point homography
  * solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
@@ -140,8 +160,13 @@ int pgx_set_primitive_classes(pgx_ctx *ctx, int class_mask, double smin, double 
 /* Per-point surface normals, n x 3 doubles in the points' order, RESIDENT like the weights of pgx_set_weights and under the same
  * rules: len == n is checked (PGX_ERR_INVALID), (NULL, 0) clears them, pgx_set_points invalidates them.  They need not be unit
  * length nor consistently oriented.  Only the cylinder's, the cone's and the mixed-primitive minimal solvers read them; the point rows
- * stay n x 3. */
+ * stay n x 3.  Under PGX_ORIENTED_PRIMITIVE3D the squared residual reads them as well: the call also places them in the order of every
+ * copy of the rows that the kernels read, and a second call with other normals makes every later result follow the new ones. */
 int pgx_set_normals(pgx_ctx *ctx, const double *normals, int64_t len);
+/* kappa = cos^2 of the angle by which a point's normal may deviate from a model's surface normal under PGX_ORIENTED_PRIMITIVE3D (context
+ * state like pgx_set_radius_range; 0 at pgx_create: every finite non-zero normal agrees with every non-zero surface normal).  No other
+ * model type reads it.  !(0 <= cos2 <= 1), NaN included: PGX_ERR_INVALID, and the state stays as it was. */
+int pgx_set_normal_tolerance(pgx_ctx *ctx, double cos2);
 /* The same with the samples DRAWN ON THE DEVICE by the in-repo counter-based generator (csrc/rng.hip.h: Philox4x32-10; sample s
  * of batch `batch` under `key` is a pure function of (key, batch, s); m = the resident model type's minimal sample size).
  * sampler 0: gcransac::sampler::UniformSampler - m distinct indices of range(n) (progressivex_python.cpp:121, 215-245);

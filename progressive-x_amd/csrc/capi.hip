@@ -48,6 +48,61 @@ void release(DevBuf& b)
     b.cap = 0;
 }
 
+// ---- an oriented type's normals where its kernels read them (residuals.hip.h: behind the rows, in the rows' order) ---------------------
+// One thread per element of the group-blocked copy (padded: groups * 64 points): point j of the Morton order is point pperm[j] of the
+// caller's; the lanes at or past n of the last group take point n - 1 of the Morton order, the copy their row is.  Without sorted copies
+// (pperm == nullptr) only the caller's order is written.
+__global__ __launch_bounds__(256) void oriented_normals_kernel(const double* __restrict__ normals, const int* __restrict__ pperm, int64_t n,
+                                                               int64_t padded, double* __restrict__ behind_pts, double* __restrict__ behind_pts_s,
+                                                               double* __restrict__ behind_pts_g)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= padded) return;
+    if (j < n) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) behind_pts[j * 3 + k] = normals[j * 3 + k];
+    }
+    if (pperm == nullptr) return;
+    const int64_t i = pperm[j < n ? j : n - 1];
+    const int64_t g = j >> 6, l = j & 63;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double v = normals[i * 3 + k];
+        if (j < n) behind_pts_s[j * 3 + k] = v;
+        behind_pts_g[(g * 3 + k) * 64 + l] = v;
+    }
+}
+
+// kappa behind the normals of every copy (one double each)
+static int place_oriented_kappa(pgx_ctx* ctx)
+{
+    const int64_t n = ctx->n, padded = (n + 63) / 64 * 64, w = ctx->D + 3;
+    double* at[3] = {ctx->pts.as<double>() + n * w, ctx->point_sort ? ctx->pts_s.as<double>() + n * w : nullptr,
+                     ctx->point_sort ? ctx->pts_g.as<double>() + padded * w : nullptr};
+    for (double* q : at)
+        if (q) PGX_HIP(ctx, hipMemcpyAsync(q, &ctx->normal_cos2, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the source is a field of the context)
+    return PGX_OK;
+}
+
+static int place_oriented_normals(pgx_ctx* ctx)
+{
+    const int64_t n = ctx->n, padded = (n + 63) / 64 * 64, d = ctx->D;
+    hipLaunchKernelGGL(oriented_normals_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, ctx->stream, ctx->normals.as<double>(),
+                       ctx->point_sort ? ctx->pperm.as<int>() : (const int*)nullptr, n, padded, ctx->pts.as<double>() + n * d,
+                       ctx->point_sort ? ctx->pts_s.as<double>() + n * d : (double*)nullptr,
+                       ctx->point_sort ? ctx->pts_g.as<double>() + padded * d : (double*)nullptr);
+    PGX_HIP(ctx, hipGetLastError());
+    return place_oriented_kappa(ctx);
+}
+
+int need_oriented_normals(pgx_ctx* ctx, const char* who)
+{
+    if (ctx->oriented && ctx->normals_n != ctx->n)
+        return fail(ctx, PGX_ERR_INVALID, "%s: the oriented residual needs the resident points' normals (pgx_set_normals after pgx_set_points)", who);
+    return PGX_OK;
+}
+
 // (both sides of kStageMax, per entry point: tests/test_gpu_switches.py test_*_either_side_of_the_ring; its docstring says why no entry
 //  point can fill kStageRing, and test_graph_fetch_either_side_of_the_ring holds the three staged copies that come closest)
 constexpr size_t kStageRing = 256 << 10, kStageMax = 32 << 10;
@@ -354,16 +409,24 @@ int pgx_set_points(pgx_ctx* ctx, int model_type, const double* points, int64_t n
     if (!points || n <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: empty input");
     if (n >= ((int64_t)1 << 31)) return fail(ctx, PGX_ERR_INVALID, "pgx_set_points: n must be < 2^31");
     ctx->model_type = model_type; ctx->D = mi.D; ctx->P = mi.P; ctx->n = n;
+    ctx->oriented = mi.oriented ? 1 : 0;
     ctx->batch.points_changed();   // (before the fallible work: the old points are gone whether or not the new ones arrive)
     ctx->dq_n = 0; ctx->L = 0; ctx->labels_n = 0;
     ctx->weights_n = 0;  // weights belong to a point set
     ctx->normals_n = 0;  // and so do normals
     ctx->score_global_n = 0;   // the fixed-point scale of a sharded job belongs to that job's point set
     expansion_points_changed(ctx);
+    int rc = PGX_OK;
+    if (mi.oriented) {   // room behind the rows of the three copies the kernels read for the normals and kappa (residuals.hip.h); ensure() only grows
+        const size_t padded = (size_t)((n + 63) / 64) * 64;
+        rc = ensure(ctx, ctx->pts, ((size_t)n * (mi.D + 3) + 1) * sizeof(double));
+        if (rc == PGX_OK) rc = ensure(ctx, ctx->pts_s, ((size_t)n * (mi.D + 3) + 1) * sizeof(double));
+        if (rc == PGX_OK) rc = ensure(ctx, ctx->pts_g, (padded * (mi.D + 3) + 1) * sizeof(double));
+    }
     // upload + every derived copy on the device (setpoints.hip): filter scales, f32 rows, Morton order, group bounds
-    const int rc = !ctx->setpoints_host ? set_points_device(ctx, mi, points, n) : set_points_host(ctx, mi, points, n);
+    if (rc == PGX_OK) rc = !ctx->setpoints_host ? set_points_device(ctx, mi, points, n) : set_points_host(ctx, mi, points, n);
     if (rc != PGX_OK) {   // half-built copies (an allocation failed midway): no resident problem, every later call fails cleanly
-        ctx->n = 0; ctx->model_type = -1; ctx->D = 0; ctx->P = 0; ctx->point_sort = 0;
+        ctx->n = 0; ctx->model_type = -1; ctx->D = 0; ctx->P = 0; ctx->point_sort = 0; ctx->oriented = 0;
         return rc;
     }
     for (DevBuf& b : ctx->slots) release(b);
@@ -799,8 +862,10 @@ int pgx_pearl_unary(pgx_ctx* ctx, const double* models, int K, double threshold,
     PGX_TRY(unary_launch(ctx, K, threshold, lambda));
     {   // what each column was computed from, byte for byte (the first-cycle memo of pgx_expansion compares these)
         std::vector<std::string> ident((size_t)L);
-        char head[64];
-        const int hl = std::snprintf(head, sizeof head, "%d|%lld|%a|%a|", ctx->model_type, (long long)ctx->expansion.points_version, threshold, lambda);
+        char head[96];
+        int hl = std::snprintf(head, sizeof head, "%d|%lld|%a|%a|", ctx->model_type, (long long)ctx->expansion.points_version, threshold, lambda);
+        // (an oriented type's columns also depend on the normals and on kappa)
+        if (ctx->oriented && hl > 0 && hl < 64) hl += std::snprintf(head + hl, sizeof head - (size_t)hl, "%lld|", (long long)ctx->oriented_version);
         for (int l = 0; l < K; ++l)
             ident[(size_t)l] = std::string(head, (size_t)hl) + std::string((const char*)(models + (size_t)l * ctx->P), (size_t)ctx->P * sizeof(double));
         ident[(size_t)K] = std::string(head, (size_t)hl) + "outlier";
@@ -931,7 +996,24 @@ int pgx_set_normals(pgx_ctx* ctx, const double* normals, int64_t len)
     PGX_TRY(ensure(ctx, ctx->normals, (size_t)len * 3 * sizeof(double)));
     PGX_HIP(ctx, hipMemcpyAsync(ctx->normals.p, normals, (size_t)len * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->oriented) {   // the residual reads them too: into the rows' orders, and whatever was computed from the old ones is no longer the table's
+        PGX_TRY(place_oriented_normals(ctx));
+        ctx->oriented_version += 1;
+    }
     ctx->normals_n = len;
+    return PGX_OK;
+}
+
+int pgx_set_normal_tolerance(pgx_ctx* ctx, double cos2)
+{
+    CTX_GUARD(ctx);
+    if (!(cos2 >= 0.0) || !(cos2 <= 1.0))   // also NaN
+        return fail(ctx, PGX_ERR_INVALID, "pgx_set_normal_tolerance: need 0 <= cos2 <= 1 (got %g)", cos2);
+    ctx->normal_cos2 = cos2;
+    if (ctx->oriented && ctx->n > 0) {
+        PGX_TRY(place_oriented_kappa(ctx));
+        ctx->oriented_version += 1;
+    }
     return PGX_OK;
 }
 

@@ -156,7 +156,10 @@ struct pgx_ctx {
     pgx::DevBuf weights;      // resident per-point weights of the weighted refits (pgx_set_weights), weights_n == n when valid
     int64_t weights_n = 0;
     pgx::DevBuf normals;      // resident per-point normals n x 3, caller's order (pgx_set_normals), normals_n == n when valid: only the
-    int64_t normals_n = 0;    // cylinder's, the cone's and the mixed-primitive minimal solvers read them
+    int64_t normals_n = 0;    // cylinder's, the cone's and the mixed-primitive minimal solvers read them - and an ORIENTED type's residual:
+    int oriented = 0;         // the resident type is one (Residual<MT>::oriented).  Its normals and kappa also lie behind the rows of pts, pts_s
+    double normal_cos2 = 0.0; // and pts_g (residuals.hip.h; place_oriented_normals).  kappa = cos^2(tolerance), pgx_set_normal_tolerance (context state)
+    int64_t oriented_version = 0;   // bumped when an oriented type's normals or kappa change: part of a unary column's identity
 
     pgx::CommState* comm = nullptr;
 };
@@ -165,6 +168,9 @@ namespace pgx {
 
 int fail(pgx_ctx* ctx, int code, const char* fmt, ...);
 int ensure(pgx_ctx* ctx, DevBuf& b, size_t bytes);
+// An oriented type's squared residual reads the resident normals: every entry point that evaluates it refuses without them (PGX_OK for
+// every other type).
+int need_oriented_normals(pgx_ctx* ctx, const char* who);
 // Small read-backs go through pinned memory: a copy into a pageable target is a BLOCKING command (14 us against 4 for one into pinned
 // memory, scripts/micro/small_copy_bench.hip), and an entry point that returns three small arrays paid it three times.  d2h() enqueues the
 // copy into a slice of a pinned ring and remembers where the bytes belong; sync_deliver() synchronises the stream once and hands them

@@ -81,6 +81,8 @@ __global__ __launch_bounds__(kPwBlock) void final_sum_kernel(const double* __res
         for (int k = 0; k < NV; ++k) out[(int64_t)blockIdx.x * NV + k] = acc[k];
 }
 
+// (an oriented type's kernels also take the point's normal and kappa from behind the rows: load_normal, oriented_kappa, squared_at of
+// residuals.hip.h; for every other type those are nothing and R::squared(pt, mdl))
 template <int MT>
 __device__ __forceinline__ void load_point(const double* __restrict__ pts, int64_t i, double (&pt)[Residual<MT>::D])
 {
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(kPwBlock) void preference_kernel(const double* __re
     if (i < n) {
         double pt[R::D];
         load_point<MT>(pts, i, pt);
-        const double sq = R::squared(pt, mdl.v);
+        const double sq = squared_at<MT>(pt, load_normal<MT>(pts, n, i), mdl.v, T2, oriented_kappa<MT>(pts, n));
         const double v = 1.0 - sq / T2;
         const double p = cv_max(0.0, v);  // progx_model.h:85  MAX(0, ...)
         pref[i] = p;
@@ -122,6 +124,7 @@ __global__ __launch_bounds__(kPwBlock) void preference_kernel(const double* __re
 int preference_launch(pgx_ctx* ctx, const double* model, double T2, double* d_pref, double out3[3])
 {
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_preference: points not set");
+    PGX_TRY(need_oriented_normals(ctx, "pgx_preference"));
     const ModelArg mdl = model_arg(ctx, model);
     const int blocks = (int)((ctx->n + kPwBlock - 1) / kPwBlock);
     PGX_TRY(ensure(ctx, ctx->red_partials, (size_t)blocks * 3 * sizeof(double)));
@@ -188,12 +191,14 @@ __global__ __launch_bounds__(kPwBlock) void unary_kernel(const double* __restric
     if (i >= n) return;
     double pt[R::D];
     load_point<MT>(pts, i, pt);
+    const Normal<MT> nrm = load_normal<MT>(pts, n, i);
+    const double kappa = oriented_kappa<MT>(pts, n);
     const double far = 2.0 * oml;
     for (int k = 0; k < K; ++k) {
         double mdl[R::P];
 #pragma unroll
         for (int j = 0; j < R::P; ++j) mdl[j] = models[k * R::P + j];
-        const double sq = R::squared(pt, mdl);
+        const double sq = squared_at<MT>(pt, nrm, mdl, T2, kappa);
         double c;
         if (sq > T2) c = far;            // PEARL.h:123-124
         else c = oml * sq / T2;          // PEARL.h:126-127
@@ -206,6 +211,7 @@ __global__ __launch_bounds__(kPwBlock) void unary_kernel(const double* __restric
 int unary_launch(pgx_ctx* ctx, int K, double threshold, double lambda)
 {
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_pearl_unary: points not set");
+    PGX_TRY(need_oriented_normals(ctx, "pgx_pearl_unary"));
     const double T2 = 9.0 / 4.0 * threshold * threshold;  // PEARL.h:51
     const double oml = 1.0 - lambda;                       // PEARL.h:48
     const int blocks = (int)((ctx->n + kPwBlock - 1) / kPwBlock);
@@ -239,7 +245,7 @@ __global__ __launch_bounds__(kPwBlock) void gc_energy_kernel(const double* __res
     if (i >= n) return;
     double pt[R::D];
     load_point<MT>(pts, i, pt);
-    const double sq = R::squared(pt, mdl.v);
+    const double sq = squared_at<MT>(pt, load_normal<MT>(pts, n, i), mdl.v, T2, oriented_kappa<MT>(pts, n));
     // negative = beyond the threshold (or NaN): e = 1; the sign carries the branch of the unary term
     e[i] = (sq <= T2) ? cv_max(0.0, sq / T2) : -1.0;
 }
@@ -321,6 +327,7 @@ int gc_labeling_launch(pgx_ctx* ctx, const double* model, double T2, double lamb
 {
     const int64_t n = ctx->n;
     if (n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_gc_labeling: points not set");
+    PGX_TRY(need_oriented_normals(ctx, "pgx_gc_labeling"));
     if (ctx->gn != n) return fail(ctx, PGX_ERR_INVALID, "pgx_gc_labeling: needs a neighbourhood graph over the %lld points", (long long)n);
     if (!(lambda > 0.0) || !(lambda < 1.0)) return fail(ctx, PGX_ERR_INVALID, "pgx_gc_labeling: lambda must lie in (0, 1)");
     if (!(T2 > 0.0)) return fail(ctx, PGX_ERR_INVALID, "pgx_gc_labeling: threshold must be positive");

@@ -1,7 +1,7 @@
 // residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the geometric primitives: the two
 // families flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension, and the 3-D line
-// (distance to an axis), the cylinder (that distance less a radius), the cone (the distance to a generatrix) and the union of plane,
-// sphere, cylinder and cone whose model row carries its class.  gfx950 device code.
+// (distance to an axis), the cylinder (that distance less a radius), the cone (the distance to a generatrix), the union of plane,
+// sphere, cylinder and cone whose model row carries its class, and that union with a test of the point's normal.  gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -22,7 +22,8 @@ namespace pgx {
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
     kSphere3D = 8, kCircle2D = 10, kLine3D = 12, kCylinder3D = 14, kCone3D = 16, kPrimitive3D = 18,
-    kNumModelTypes = 19   // 7, 9, 11, 13, 15 and 17 are not assigned (pgx_model_dims(7), (9), (11), (13), (15) and (17) are errors)
+    kOrientedPrimitive3D = 20,
+    kNumModelTypes = 21   // 7, 9, 11, 13, 15, 17 and 19 are not assigned (pgx_model_dims(7), (9), (11), (13), (15), (17) and (19) are errors)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -38,6 +39,7 @@ __device__ __forceinline__ double cv_min(double a, double b) { return a > b ? b 
 //   in0 .. in1      coordinates whose magnitude, at least 1, scales the point filter (in1 < in0: none)
 //   in0 .. box1     coordinates the projective map multiplies (the box / ball part of a kBoundBox row)
 //   normals_solver  only where the minimal solver reads the resident normals (pgx_set_normals): its name in the refusal without them
+//   oriented        only where squared() reads the point's resident normal as well (squared_at() below is how the kernels call it)
 template <int MT> struct Residual;
 
 template <class R, class = void> struct NormalsSolver { static constexpr const char* name = nullptr; };
@@ -197,6 +199,91 @@ template <> struct Residual<kPrimitive3D> : NoProjectiveMap {
     }
 };
 
+// Oriented mixed primitives (findOrientedPrimitives; no reference counterpart): type 18's model row (class, q[8]) and type 18's distance,
+// but a point supports a model only if its resident normal n (pgx_set_normals) also agrees with the surface normal of the model at the
+// point - the compatibility test of Schnabel, Wahl and Klein, "Efficient RANSAC for Point-Cloud Shape Detection", section 4.3.  With g the
+// UNNORMALISED direction of the model's normal at the point x,
+//   plane    (a, b, c, d)     g = (a, b, c)
+//   sphere   (c, r)           g = x - c                            componentwise
+//   cylinder (p, d, r)        e = x - p,  t = (e0 d0 + e1 d1) + e2 d2,  g_k = e_k - t d_k
+//   cone     (a, d, c, s)     e = x - a,  h = (e0 d0 + e1 d1) + e2 d2,  w_k = e_k - h d_k,  rho = sqrt(Residual<kLine3D>::squared(x, (a, d)))
+//                             (the root the cone's residual computes),  g_k = c w_k - (s rho) d_k
+// (d and (c, s) taken as given, as in the residuals: unit from the solver and the refit), every dot product a left fold,
+//   nn = (n0 n0 + n1 n1) + n2 n2,   gg = (g0 g0 + g1 g1) + g2 g2,   ng = (n0 g0 + n1 g1) + n2 g2,   w = nn gg,
+// the point is COMPATIBLE iff  ng ng >= kappa w  and  w > 0,  kappa = cos^2(tolerance) (pgx_set_normal_tolerance).  FP64, no contraction, no
+// division, no root besides the cone's own.  The squares make the test blind to the sign and the length of n: normals may stay unsigned
+// and unnormalised.  Every comparison is false on NaN, so a NaN anywhere, a zero normal and a point on the axis, at the apex or at the
+// centre (g = 0) are incompatible.  This operation order is the contract of every oriented check (tests restate it in numpy).
+//   squared  type 18's squared where the point is compatible, +inf where it is not; a class that is no class still gives NaN
+//   plain    type 18's plain, WITHOUT the test: it is the quantity the refits minimise and pgx_residual_sum(s) adds up over a label's
+//            points, and PEARL's coherence term may hand a model a point whose normal disagrees - the sum must not become infinite
+//            because of it (a refit's own inlier lists come from squared and hold compatible points only)
+// squared_within(.., T2, ..) is what the kernels evaluate: the distance first, the test only where the value is at most T2 (or NaN) - it
+// equals squared wherever squared <= T2 and lies above T2 wherever squared does, which is all that any caller decides by (sq < T2,
+// sq <= T2, sq > T2, max(0, 1 - sq / T2)).  Filter32 and the group bound are type 18's: they reject by distance alone and the normal test
+// only removes inliers, so every rejection stays conservative.
+template <> struct Residual<kOrientedPrimitive3D> : NoProjectiveMap {
+    using Base = Residual<kPrimitive3D>;
+    static constexpr int D = 3, P = 9, sample = 4, slots = 4, bound = kBoundBall;
+    static constexpr const char* normals_solver = "oriented-primitive";
+    static constexpr bool oriented = true;
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) { return Base::plain(p, m); }
+    // g of the table above; false for a class that is no class
+    template <class PT, class MD>
+    static __device__ __forceinline__ bool surface_normal(const PT& p, const MD& m, double (&g)[3]) {
+        const double cls = m[0];
+        if (cls == (double)kPlane3D) {
+            g[0] = m[1]; g[1] = m[2]; g[2] = m[3];
+            return true;
+        }
+        if (cls == (double)kSphere3D) {
+            g[0] = p[0] - m[1]; g[1] = p[1] - m[2]; g[2] = p[2] - m[3];
+            return true;
+        }
+        if (cls == (double)kCylinder3D) {
+            const double e0 = p[0] - m[1], e1 = p[1] - m[2], e2 = p[2] - m[3];
+            const double t = (e0 * m[4] + e1 * m[5]) + e2 * m[6];
+            g[0] = e0 - t * m[4]; g[1] = e1 - t * m[5]; g[2] = e2 - t * m[6];
+            return true;
+        }
+        if (cls == (double)kCone3D) {
+            const double q[6] = {m[1], m[2], m[3], m[4], m[5], m[6]};
+            const double e0 = p[0] - m[1], e1 = p[1] - m[2], e2 = p[2] - m[3];
+            const double h = (e0 * m[4] + e1 * m[5]) + e2 * m[6];
+            const double rho = sqrt(Residual<kLine3D>::squared(p, q));
+            const double sr = m[8] * rho;
+            g[0] = m[7] * (e0 - h * m[4]) - sr * m[4];
+            g[1] = m[7] * (e1 - h * m[5]) - sr * m[5];
+            g[2] = m[7] * (e2 - h * m[6]) - sr * m[6];
+            return true;
+        }
+        return false;
+    }
+    template <class NT>
+    static __device__ __forceinline__ bool agrees(const NT& n, const double (&g)[3], double kappa) {
+        const double nn = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+        const double gg = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+        const double ng = (n[0] * g[0] + n[1] * g[1]) + n[2] * g[2];
+        const double w = nn * gg;
+        return ng * ng >= kappa * w && w > 0.0;
+    }
+    template <class PT, class NT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const NT& n, const MD& m, double kappa) {
+        const double sq = Base::squared(p, m);
+        double g[3];
+        if (!surface_normal(p, m, g)) return sq;   // no class: NaN
+        return agrees(n, g, kappa) ? sq : __builtin_inf();
+    }
+    template <class PT, class NT, class MD>
+    static __device__ __forceinline__ double squared_within(const PT& p, const NT& n, const MD& m, double T2, double kappa) {
+        const double sq = Base::squared(p, m);
+        if (!(sq <= T2)) return sq;   // beyond T2 either way, or NaN: never an inlier, priced as beyond the threshold
+        double g[3];
+        return surface_normal(p, m, g) && agrees(n, g, kappa) ? sq : __builtin_inf();
+    }
+};
+
 // DefaultHomographyEstimator (progressivex_python.cpp:252) [U-1]: one-way forward transfer error,
 // H row-major 3x3 (progressivex_python.cpp:292-300).
 template <> struct Residual<kHomography> {
@@ -307,17 +394,69 @@ template <class F> inline bool with_model_type(int mt, F&& f) {
     case kCylinder3D: f(std::integral_constant<int, kCylinder3D>{}); return true;
     case kCone3D: f(std::integral_constant<int, kCone3D>{}); return true;
     case kPrimitive3D: f(std::integral_constant<int, kPrimitive3D>{}); return true;
+    case kOrientedPrimitive3D: f(std::integral_constant<int, kOrientedPrimitive3D>{}); return true;
     default: return false;
     }
 }
 
+// ---- oriented types: how the kernels reach a point's normal --------------------------------------------------------------------------
+// An oriented type's row buffers carry the normals and kappa BEHIND the rows, in the rows' own order, so that no kernel takes another
+// argument and the instances of the other types stay what they were:
+//   rows [count][D]  |  normals [count][3]  |  kappa                     the caller's order (pts) and the Morton order (pts_s), count = n
+//   rows [groups][D][64]  |  normals [groups][3][64]  |  kappa           the group-blocked copy (pts_g), the tail group padded with its
+//                                                                        last point's normal, as its rows are
+// pgx_set_points reserves the room, pgx_set_normals and pgx_set_normal_tolerance fill it (capi.hip).  Normal<MT> is what a kernel
+// carries per point: three doubles for an oriented type, nothing for the others - whose code is then R::squared(pt, mdl) as before.
+template <class R, class = void> struct IsOriented : std::false_type {};
+template <class R> struct IsOriented<R, std::enable_if_t<R::oriented>> : std::true_type {};
+template <int MT> constexpr bool kOriented = IsOriented<Residual<MT>>::value;
+
+template <int MT, bool = kOriented<MT>> struct Normal {};
+template <int MT> struct Normal<MT, true> { double v[3]; };
+
+template <int MT> __device__ __forceinline__ double oriented_kappa(const double* __restrict__ rows, int64_t count /* n, or groups * 64 */)
+{
+    if constexpr (kOriented<MT>) return rows[count * (Residual<MT>::D + 3)];
+    else return 0.0;
+}
+// normal of row i of an array-of-rows buffer of n rows
+template <int MT> __device__ __forceinline__ Normal<MT> load_normal(const double* __restrict__ rows, int64_t n, int64_t i)
+{
+    Normal<MT> nr;
+    if constexpr (kOriented<MT>) {
+        const double* __restrict__ q = rows + n * Residual<MT>::D + i * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nr.v[k] = q[k];
+    }
+    return nr;
+}
+// normal of lane `lane` of group g of the group-blocked copy
+template <int MT> __device__ __forceinline__ Normal<MT> load_normal_blocked(const double* __restrict__ rows_g, int groups, int g, int lane)
+{
+    Normal<MT> nr;
+    if constexpr (kOriented<MT>) {
+        const double* __restrict__ q = rows_g + ((int64_t)groups * Residual<MT>::D + (int64_t)g * 3) * 64 + lane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) nr.v[k] = q[k * 64];
+    }
+    return nr;
+}
+// The one way the scoring and the pointwise kernels evaluate a squared residual: R::squared(pt, mdl) for every type but the oriented
+// ones, whose value also depends on the point's normal and is only needed up to T2 (Residual<kOrientedPrimitive3D>::squared_within).
+template <int MT, class PT, class MD>
+__device__ __forceinline__ double squared_at(const PT& p, const Normal<MT>& nr, const MD& m, double T2, double kappa)
+{
+    if constexpr (kOriented<MT>) return Residual<MT>::squared_within(p, nr.v, m, T2, kappa);
+    else return Residual<MT>::squared(p, m);
+}
+
 // The constants of Residual<mt> for host code that holds the type as a number.
-struct ModelInfo { int D, P, sample, slots, bound, obs0, in0, in1, box1; const char* normals_solver; };
+struct ModelInfo { int D, P, sample, slots, bound, obs0, in0, in1, box1; const char* normals_solver; bool oriented; };
 
 inline bool model_info(int mt, ModelInfo* out) {
     return with_model_type(mt, [&](auto t) {
         using R = Residual<decltype(t)::value>;
-        *out = {R::D, R::P, R::sample, R::slots, R::bound, R::obs0, R::in0, R::in1, R::box1, NormalsSolver<R>::name};
+        *out = {R::D, R::P, R::sample, R::slots, R::bound, R::obs0, R::in0, R::in1, R::box1, NormalsSolver<R>::name, IsOriented<R>::value};
     });
 }
 

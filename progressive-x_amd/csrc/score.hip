@@ -69,17 +69,18 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
     unsigned cnt = 0;
     double val = 0.0, sh = 0.0;
     unsigned long long word = 0;
+    const double kappa = oriented_kappa<MT>(pts, n);   // (an oriented type's normals and kappa lie behind its rows: residuals.hip.h)
 
     // One point per step; the body is written once and instantiated for a group of kUnroll points whose scalar loads
     // are all issued before the first use, so one s_waitcnt covers kUnroll points (SMEM returns out of order: the
     // only usable wait is lgkmcnt(0), which makes per-point prefetching impossible).
-    auto step = [&](int64_t i, const double (&pt)[R::D], double pm, const float* p32) {
+    auto step = [&](int64_t i, const double (&pt)[R::D], const Normal<MT>& nr, double pm, const float* p32) {
         bool inl = false;
         bool rejected = false;
         if (FILT == 1 && F::enabled) rejected = F::reject(pt, mdl, flane, pm, T2d);
         if (FILT == 2 && F32::enabled) rejected = F32::reject(p32, flane32, T2d32);
         if (live && !rejected) {  // exact path: oracle operation order, no contraction
-            const double sq = R::squared(pt, mdl);
+            const double sq = squared_at<MT>(pt, nr, mdl, T2, kappa);
             inl = sq < T2;  // strict, scoring_function_with_compound_model.h:85
             if (inl) {
                 ++cnt;                                        // :91
@@ -116,12 +117,14 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
         for (; i + kUnroll <= gend; i += kUnroll) {
             const double* __restrict__ prow = pts + i * R::D;  // wave-uniform address -> scalar loads
             double pt[kUnroll][R::D];
+            Normal<MT> nr[kUnroll];
             double pm[kUnroll];
             float p32[kUnroll][8];
 #pragma unroll
             for (int u = 0; u < kUnroll; ++u) {
 #pragma unroll
                 for (int k = 0; k < R::D; ++k) pt[u][k] = prow[u * R::D + k];
+                nr[u] = load_normal<MT>(pts, n, i + u);   // wave-uniform as well
                 pm[u] = (FILT == 1 && F::enabled) ? pmax[i + u] : 1.0;
                 if (FILT == 2 && F32::enabled) {
 #pragma unroll
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
                 }
             }
 #pragma unroll
-            for (int u = 0; u < kUnroll; ++u) step(i + u, pt[u], pm[u], p32[u]);
+            for (int u = 0; u < kUnroll; ++u) step(i + u, pt[u], nr[u], pm[u], p32[u]);
         }
         for (; i < gend; ++i) {
             const double* __restrict__ prow = pts + i * R::D;
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
 #pragma unroll
                 for (int k = 0; k < 8; ++k) p32[k] = pts32[i * 8 + k];
             }
-            step(i, pt, (FILT == 1 && F::enabled) ? pmax[i] : 1.0, p32);
+            step(i, pt, load_normal<MT>(pts, n, i), (FILT == 1 && F::enabled) ? pmax[i] : 1.0, p32);
         }
     }
     const int64_t o = (int64_t)gy * Mpad + m;
@@ -194,6 +197,13 @@ __global__ __launch_bounds__(kScoreBlock) void score_kernel(
 constexpr bool kTrimRows = (PGX_SCORE_TRIM & 1) != 0, kTrimDrain = (PGX_SCORE_TRIM & 2) != 0, kTrimDirect = (PGX_SCORE_TRIM & 4) != 0;
 constexpr bool kTrimLocate = (PGX_SCORE_TRIM & 8) != 0, kTrimArgs = (PGX_SCORE_TRIM & 16) != 0, kTrimItem = (PGX_SCORE_TRIM & 32) != 0,
                kTrimTail = (PGX_SCORE_TRIM & 64) != 0;
+// An oriented type's normal in the group-major kernel (score_group_kernel): by default the lane loads it next to its point row and drain()
+// shuffles it; with -DPGX_ORIENTED_GATHER a candidate's normal is gathered from the sorted copy on the exact path only.
+#ifdef PGX_ORIENTED_GATHER
+constexpr bool kOrientedGather = true;
+#else
+constexpr bool kOrientedGather = false;
+#endif
 constexpr bool kTrimKeepTile = (PGX_SCORE_TRIM & 128) != 0, kTrimResident = (PGX_SCORE_TRIM & 256) != 0, kTrimEarly = (PGX_SCORE_TRIM & 512) != 0,
                kTrimRowFirst = (PGX_SCORE_TRIM & 1024) != 0;
 
@@ -590,6 +600,21 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
 #pragma unroll
         for (int q = 0; q < 8; ++q) p32[q] = pts32[jj * 8 + q];
     }
+    // An oriented type (residuals.hip.h): the lane's normal next to its row, from the copy its row came from - the tail group's lanes at
+    // or past n see the last point's normal, as they see its row - and kappa from behind the same copy.  drain() shuffles the normal
+    // with the row.  (The other design, a gather of the candidate's normal from the sorted copy inside drain() and direct():
+    // -DPGX_ORIENTED_GATHER, docs/lab-notebook.md "Oriented primitives: where the group-major kernel takes the normal from".)
+    Normal<MT> nrm;
+    double kappa = 0.0;
+    if constexpr (kOriented<MT>) {
+        if (pts_g != nullptr) {
+            kappa = oriented_kappa<MT>(pts_g, (int64_t)groups * 64);
+            if constexpr (!kOrientedGather) nrm = load_normal_blocked<MT>(pts_g, groups, g, lane);
+        } else {
+            kappa = oriented_kappa<MT>(pts, n);
+            if constexpr (!kOrientedGather) nrm = load_normal<MT>(pts, n, jj);
+        }
+    }
     if (!kTrimItem && has_comp) cmp = comp[jj];
     if (item_words) wl_words_shift(kwv.x, kwv.y, kwv.z, kwv.w, w0 - kwb, kw);   // (first use of the keep words: behind the requests for the rows)
     // nrep replicas of the integer accumulators, chosen by workgroup id: workgroup ids go round-robin over the XCDs, so with
@@ -619,12 +644,18 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
 #pragma unroll
         for (int k = 0; k < R::D; ++k) q_pt[k] = __shfl(pt[k], src, 64);
         const double q_cmp = has_comp ? __shfl(cmp, src, 64) : 0.0;
+        Normal<MT> q_nrm;
+        if constexpr (kOriented<MT> && !kOrientedGather) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) q_nrm.v[k] = __shfl(nrm.v[k], src, 64);
+        }
         long long cnt = 0, val = 0, shq = 0;  // (kTrimDrain: val = run_pack(count, value), cnt is only the lane's own 0 / 1)
         if (act) {  // exact path: oracle operation order, no contraction
             double mdl[R::P];
 #pragma unroll
             for (int k = 0; k < R::P; ++k) mdl[k] = models_t[(int64_t)k * Mpad + m];  // neighbours in m share cache lines
-            const double sq = R::squared(q_pt, mdl);
+            if constexpr (kOriented<MT> && kOrientedGather) q_nrm = load_normal<MT>(pts, n, (int64_t)g * 64 + src);   // (a candidate is a valid lane: < n)
+            const double sq = squared_at<MT>(q_pt, q_nrm, mdl, T2, kappa);
             if (STATS) ++st_exact;
             if (sq < T2) {  // strict, scoring_function_with_compound_model.h:85
                 const double sc = cv_max(0.0, 1.0 - sq / T2);                       // :94
@@ -683,7 +714,8 @@ __global__ __launch_bounds__(64 * kGroupWaves) void score_group_kernel(
             double mdl[R::P];
 #pragma unroll
             for (int k = 0; k < R::P; ++k) mdl[k] = models[(int64_t)m * R::P + k];
-            const double sq = R::squared(pt, mdl);
+            if constexpr (kOriented<MT> && kOrientedGather) nrm = load_normal<MT>(pts, n, jj);
+            const double sq = squared_at<MT>(pt, nrm, mdl, T2, kappa);
             inl = sq < T2;  // strict, scoring_function_with_compound_model.h:85
             if (STATS) { ++st_exact; if (inl) ++st_inl; }
             if (inl) {
@@ -814,6 +846,8 @@ __global__ __launch_bounds__(64) void score_verify_kernel(const double* __restri
     for (int q = 0; q < R::D; ++q) pt[q] = pts[jj * R::D + q];
 #pragma unroll
     for (int q = 0; q < 8; ++q) p32[q] = pts32[jj * 8 + q];
+    const Normal<MT> nrm = load_normal<MT>(pts, n, jj);
+    const double kappa = oriented_kappa<MT>(pts, n);
     const float T2d32 = f32_up(T2 * (1.0 + kFilter32Delta));
     const unsigned long long todo = keep[(int64_t)g * W + w];
     unsigned long long c_cull = 0, c_filt = 0, c_inl = 0;
@@ -823,7 +857,7 @@ __global__ __launch_bounds__(64) void score_verify_kernel(const double* __restri
         double mdl[R::P];
 #pragma unroll
         for (int k = 0; k < R::P; ++k) mdl[k] = models[(int64_t)m * R::P + k];
-        const bool inl = valid && R::squared(pt, mdl) < T2;
+        const bool inl = valid && squared_at<MT>(pt, nrm, mdl, T2, kappa) < T2;
         const bool kept = (todo >> h) & 1ull;
         const LaneT ln = HypRow<MT>::load(hyp32 + (int64_t)m * HypRow<MT>::kStride);
         const bool rej = F32::reject(p32, ln, T2d32);
@@ -1314,6 +1348,7 @@ int score_launch(pgx_ctx* ctx, double T2, int has_compound, int want_masks, bool
 {
     if (ctx->n <= 0 || ctx->model_type < 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score: points not set");
     if (ctx->batch.resident.M <= 0) return fail(ctx, PGX_ERR_INVALID, "pgx_score: no hypotheses uploaded");
+    PGX_TRY(need_oriented_normals(ctx, "pgx_score"));
     int rc = PGX_OK;
     if (!with_model_type(ctx->model_type, [&](auto mt) { rc = score_launch_typed<decltype(mt)::value>(ctx, T2, has_compound, want_masks, want_counters); }))
         return fail(ctx, PGX_ERR_INVALID, "pgx_score: bad model type %d", ctx->model_type);

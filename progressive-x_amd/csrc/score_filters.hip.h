@@ -1047,4 +1047,10 @@ template <> struct Filter32<kPrimitive3D> {
     }
 };
 
+// ---- oriented mixed primitives (Residual<kOrientedPrimitive3D>): type 18's filter and group test as they stand --------------------------
+// Both reject by the distance alone.  An oriented inlier is a type-18 inlier whose normal also agrees: the test of the normal only takes
+// pairs away, so a pair or a group that type 18 may drop holds no oriented inlier either - every rejection stays conservative, with the
+// constituents' budgets unchanged.  A NaN class is culled as under type 18 (the solver's empty and incompatible slots are all-NaN rows).
+template <> struct Filter32<kOrientedPrimitive3D> : Filter32<kPrimitive3D> {};
+
 }  // namespace pgx

@@ -348,6 +348,37 @@ __global__ __launch_bounds__(64) void solve_primitive_kernel(const double* __res
     slot(3, Type<kCone3D>{});
 }
 
+// ---- oriented mixed primitives: Schnabel's candidate test behind the mixed-primitive solver -------------------------------------------
+// Type 20's slots are solve_primitive_kernel's, on the same indices with the same bits.  This pass then takes out every slot whose model
+// does not agree with the normals of its OWN sample: a slot is kept iff each point of its prefix (3 plane, 4 sphere, 2 cylinder, 3 cone)
+// is compatible with it at kappa - Residual<kOrientedPrimitive3D>'s test, the distance left out (the sample lies on its model up to
+// rounding).  Any other slot becomes an all-NaN row, class included: such a hypothesis could never count its own sample, and as a NaN
+// row it dies in the cull.  The plane of three points whose normals lie in it is the typical case.  One lane per slot; a slot that is
+// an all-NaN row already (no model, class off, index outside the points) is left alone, so every index read here is inside the points.
+__global__ __launch_bounds__(64) void oriented_slots_kernel(const double* __restrict__ pts, const double* __restrict__ normals, const int* __restrict__ samples,
+                                                            int S, double kappa, double* __restrict__ models)
+{
+    using R = Residual<kOrientedPrimitive3D>;
+    const int t = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (t >= 4 * S) return;
+    double* row = models + (int64_t)t * R::P;
+    double m[R::P];
+    for (int k = 0; k < R::P; ++k) m[k] = row[k];
+    if (m[0] != m[0]) return;
+    const int j = t & 3;
+    const int prefix = j == 0 ? Residual<kPlane3D>::sample : j == 1 ? Residual<kSphere3D>::sample : j == 2 ? Residual<kCylinder3D>::sample : Residual<kCone3D>::sample;
+    bool ok = true;
+    for (int k = 0; k < prefix; ++k) {
+        const int64_t i = samples[4 * (t >> 2) + k];
+        const double p[3] = {pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]};
+        const double nq[3] = {normals[i * 3], normals[i * 3 + 1], normals[i * 3 + 2]};
+        double g[3];
+        ok = ok && R::surface_normal(p, m, g) && R::agrees(nq, g, kappa);
+    }
+    if (!ok)
+        for (int k = 0; k < R::P; ++k) row[k] = __builtin_nan("");
+}
+
 // ---- P3P -------------------------------------------------------------------------------------------------------------
 /* monic cubic x^3 + a x^2 + b x + c: one real root by 200 bisection steps inside the Cauchy bound, the other two from the
  * quadratic factor (NaN when complex).  Only + - * / sqrt. */
@@ -802,13 +833,16 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     if (mt == kFundamental) hipLaunchKernelGGL(solve_f7_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
     else if (mt == kHomography) hipLaunchKernelGGL(solve_h4_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, ctx->fscale, models, perm, Mpad);
     else if (mt == kPnP) hipLaunchKernelGGL(solve_p3p_kernel, gs, bs, 0, ctx->stream, pts, ctx->n, smp, S, models, perm, Mpad);
-    else if (mt == kPrimitive3D)
+    else if (mt == kPrimitive3D || mt == kOrientedPrimitive3D) {
         hipLaunchKernelGGL(solve_primitive_kernel, gs, bs, 0, ctx->stream, pts, normals, ctx->n, smp, S, ctx->prim_mask, ctx->rmin, ctx->rmax, ctx->prim_smin,
                            ctx->prim_smax, models, perm, Mpad);
+        if (mt == kOrientedPrimitive3D)   // the slots that disagree with their own sample's normals become all-NaN rows
+            hipLaunchKernelGGL(oriented_slots_kernel, dim3((unsigned)((4 * S + 63) / 64)), bs, 0, ctx->stream, pts, normals, smp, S, ctx->normal_cos2, models);
+    }
     else   // the lane-per-model solvers: whatever else declares slots has a solve_minimal, or this does not compile
         with_model_type(mt, [&](auto t) {
             constexpr int MT = decltype(t)::value;
-            if constexpr (Residual<MT>::slots > 0 && MT != kFundamental && MT != kHomography && MT != kPnP && MT != kPrimitive3D)
+            if constexpr (Residual<MT>::slots > 0 && MT != kFundamental && MT != kHomography && MT != kPnP && MT != kPrimitive3D && MT != kOrientedPrimitive3D)
                 hipLaunchKernelGGL((solve_kernel<MT>), gm, bm, 0, ctx->stream, pts, normals, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
         });
     PGX_HIP(ctx, hipGetLastError());

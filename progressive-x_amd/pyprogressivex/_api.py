@@ -1,4 +1,4 @@
-"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCones / findPrimitives / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCones / findPrimitives / findOrientedPrimitives / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -604,6 +604,40 @@ def findPrimitives(points, normals, weights=None, threshold=0.05, conf=0.5, spat
     the remaining arguments are findCones'.  What the call recovers on make_primitives scenes, and what the four single-class calls
     find on the same scenes, is reported, not tuned, in DESIGN.md 4.13."""
     est = _estimators.PrimitiveEstimator(classes)
+    points, nrm = _as_f64(points), _as_f64(normals)
+    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
+        raise ValueError("normals should be an array with dims [n,3], one row per point")
+    est.normals = nrm
+    est.sine_range = _angle_range(angle_range)
+    return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+
+
+def findOrientedPrimitives(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
+                           neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
+                           minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
+                           do_logging=False, *, normal_tolerance=20.0, classes=("plane", "sphere", "cylinder", "cone"), radius_range=None,
+                           angle_range=(1.0, 89.0), seed=None, max_outer_iterations=10, neighborhood="flann_like", local_optimization="auto",
+                           labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None, pearl_abs="double", refit_solver="lapack"):
+    """findPrimitives with the compatibility test of Schnabel, Wahl and Klein ("Efficient RANSAC for Point-Cloud Shape Detection", 4.3): a
+    point supports a plane, sphere, cylinder or cone only if it lies within `threshold` of it AND its normal deviates from the shape's
+    normal at that point by less than `normal_tolerance` degrees.  Under findPrimitives the normals are read by the minimal solvers
+    alone, and a flexible shape collects the points of a wall or of the outlier cloud by distance; here scores, preference vectors,
+    PEARL's data costs, the inlier / outlier cut and the inlier lists of the refits all apply the test (model type 20: DESIGN.md 4.14).
+    A hypothesis that disagrees with the normals of its own sample is never scored.
+    points [n, 3], normals [n, 3]: unsigned and unnormalised normals are fine (the test squares the cosine); a zero or non-finite
+    normal supports nothing.  normal_tolerance (keyword-only, degrees, 0 < tolerance <= 90; else ValueError) defaults to 20, the order
+    of magnitude Schnabel et al. use - a default, NOT a value tuned on this project's scenes; normals estimated from a noisy scan want
+    a tolerance above their own error (DESIGN.md 4.14 reports 10, 20 and 40 degrees as found).  90 degrees accepts every defined
+    normal.  All other parameters, their order and the return value (models[K, 9], labels[n]) are findPrimitives'; the refits are
+    the same least-squares fits on the compatible inliers, and the distance sums PEARL compares before and after a refit ignore the
+    normals (they are the quantity the refits minimise)."""
+    est = _estimators.OrientedPrimitiveEstimator(classes, normal_tolerance)
     points, nrm = _as_f64(points), _as_f64(normals)
     if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
         raise ValueError("normals should be an array with dims [n,3], one row per point")

@@ -771,6 +771,84 @@ class PrimitiveEstimator(Estimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Oriented mixed primitives (findOrientedPrimitives; no reference counterpart): findPrimitives whose inliers agree with the normals
+# ---------------------------------------------------------------------------------------------------------------------
+def surface_normals(pts, row):
+    """g [n, 3], the unnormalised direction of the surface normal of the model row (class, q0 .. q7) at the points pts [n, 3], in the
+    operation order of csrc/residuals.hip.h Residual<kOrientedPrimitive3D>::surface_normal; None for a class that is no class."""
+    pts = np.asarray(pts, dtype=np.float64)
+    row = np.asarray(row, dtype=np.float64).reshape(-1)
+    cls, x = row[0], [pts[:, 0], pts[:, 1], pts[:, 2]]
+    if cls == _lib.PLANE3D:
+        return np.stack([np.full(len(pts), row[1 + k]) for k in range(3)], axis=1)
+    if cls == _lib.SPHERE3D:
+        return np.stack([x[k] - row[1 + k] for k in range(3)], axis=1)
+    if cls not in (_lib.CYLINDER3D, _lib.CONE3D):
+        return None
+    e = [x[k] - row[1 + k] for k in range(3)]
+    d = row[4:7]
+    t = (e[0] * d[0] + e[1] * d[1]) + e[2] * d[2]
+    if cls == _lib.CYLINDER3D:
+        return np.stack([e[k] - t * d[k] for k in range(3)], axis=1)
+    c0 = e[1] * d[2] - e[2] * d[1]                 # the 3-D line's squared distance, as the cone's residual computes it
+    c1 = -(e[0] * d[2] - e[2] * d[0])
+    c2 = e[0] * d[1] - e[1] * d[0]
+    with np.errstate(invalid="ignore"):
+        rho = np.sqrt((c0 * c0 + c1 * c1) + c2 * c2)
+    sr = row[8] * rho
+    return np.stack([row[7] * (e[k] - t * d[k]) - sr * d[k] for k in range(3)], axis=1)
+
+
+def normals_agree(nrm, g, kappa):
+    """bool [n]: (n.g)^2 >= kappa (n.n)(g.g) and (n.n)(g.g) > 0, every dot product a left fold (the device's test, bit for bit)."""
+    nrm = np.asarray(nrm, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        nn = (nrm[:, 0] * nrm[:, 0] + nrm[:, 1] * nrm[:, 1]) + nrm[:, 2] * nrm[:, 2]
+        gg = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
+        ng = (nrm[:, 0] * g[:, 0] + nrm[:, 1] * g[:, 1]) + nrm[:, 2] * g[:, 2]
+        w = nn * gg
+        return (ng * ng >= kappa * w) & (w > 0.0)
+
+
+class OrientedPrimitiveEstimator(PrimitiveEstimator):
+    """PrimitiveEstimator on model type 20: the same model rows, solvers and refits, but a point supports a model only if its normal
+    deviates from the model's surface normal at the point by less than `normal_tolerance` degrees (csrc/residuals.hip.h
+    Residual<kOrientedPrimitive3D>: the device reads kappa = cos^2(tolerance) from pgx_set_normal_tolerance).  A hypothesis that does
+    not agree with the normals of its own sample's prefix is dropped (Schnabel's candidate test; an all-NaN row on the device).  The
+    refits are the constituents' on the inlier lists they are given, which under this type hold compatible points only."""
+    model_type = _lib.ORIENTED_PRIMITIVE3D
+
+    def __init__(self, classes=tuple(PRIMITIVE_CLASSES), normal_tolerance=20.0):
+        super().__init__(classes)
+        tol = float(normal_tolerance)
+        if not (0.0 < tol <= 90.0):
+            raise ValueError("normal_tolerance should be an angle in degrees with 0 < normal_tolerance <= 90")
+        self.normal_tolerance = tol
+        c = np.cos(np.deg2rad(tol)) if tol < 90.0 else 0.0
+        self.kappa = float(c * c)
+
+    def context_setup(self, ctx):
+        super().context_setup(ctx)
+        ctx.set_normal_tolerance(self.kappa)
+
+    def minimal(self, pts, samples):
+        """PrimitiveEstimator.minimal's rows without those that disagree with the normals of their own prefix: what
+        csrc/solve.hip's oriented_slots_kernel leaves, without its all-NaN rows."""
+        rows, src = super().minimal(pts, samples)
+        samples, pts = np.asarray(samples), np.asarray(pts, dtype=np.float64)
+        nrm = np.asarray(self._normals, dtype=np.float64)
+        prefix = {cls: m for cls, _, m in self._SLOTS}
+        keep = np.zeros(len(rows), dtype=bool)
+        for r, (row, s) in enumerate(zip(rows, src)):
+            if not row[0] == row[0]:
+                continue
+            idx = samples[s, :prefix[int(row[0])]]
+            g = surface_normals(pts[idx], row)
+            keep[r] = g is not None and bool(normals_agree(nrm[idx], g, self.kappa).all())
+        return rows[keep], src[keep]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D circle: the round family's other member
 # ---------------------------------------------------------------------------------------------------------------------
 class CircleEstimator(RoundEstimator):
@@ -1437,6 +1515,7 @@ ESTIMATORS = {
     "cylinder": CylinderEstimator,
     "cone": ConeEstimator,
     "primitive": PrimitiveEstimator,
+    "oriented_primitive": OrientedPrimitiveEstimator,
     "vanishing_point": VanishingPointEstimator,
     "homography": HomographyEstimator,
     "homography_sym": SymmetricHomographyEstimator,

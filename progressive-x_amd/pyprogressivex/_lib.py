@@ -23,12 +23,13 @@ LINE3D = 12                    # (nor is 11)
 CYLINDER3D = 14                # (nor 13)
 CONE3D = 16                    # (nor 15)
 PRIMITIVE3D = 18               # (nor 17): the union of PLANE3D, SPHERE3D, CYLINDER3D and CONE3D, model (class, q0 .. q7)
+ORIENTED_PRIMITIVE3D = 20      # (nor 19): PRIMITIVE3D whose inliers must also agree with the resident normals (set_normal_tolerance)
 # per model type: (doubles per point, doubles per model, minimal sample size, hypotheses per sample of the device solver);
 # sample size 0 = no device solver (pgx_solve_minimal fails).  The numbers of csrc/residuals.hip.h; tests/test_abi.py compares.
 MODEL_TABLE = {LINE2D: (2, 3, 2, 1), HOMOGRAPHY: (4, 9, 4, 1), FUNDAMENTAL: (4, 9, 7, 3), PNP: (5, 12, 3, 4),
                VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1),
                CIRCLE2D: (2, 3, 3, 1), LINE3D: (3, 6, 2, 1), CYLINDER3D: (3, 7, 2, 1), CONE3D: (3, 8, 3, 1),
-               PRIMITIVE3D: (3, 9, 4, 4)}
+               PRIMITIVE3D: (3, 9, 4, 4), ORIENTED_PRIMITIVE3D: (3, 9, 4, 4)}
 POINT_DIM = {t: row[0] for t, row in MODEL_TABLE.items()}
 PARAM_DIM = {t: row[1] for t, row in MODEL_TABLE.items()}
 FIXED_ONE = float(1 << 32)
@@ -41,7 +42,7 @@ ABI_SYMBOLS = [
     "pgx_set_points", "pgx_set_compound", "pgx_get_compound",
     "pgx_score", "pgx_score_upload", "pgx_score_launch", "pgx_score_fetch", "pgx_score_algorithmic_bytes", "pgx_score_stats", "pgx_score_profile", "pgx_score_kernel_times", "pgx_score_debug_fetch", "pgx_score_debug_geometry",
     "pgx_preference", "pgx_get_preference", "pgx_compound_update",
-    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_primitive_classes", "pgx_set_normals",
+    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_primitive_classes", "pgx_set_normals", "pgx_set_normal_tolerance",
     "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals",
     "pgx_bucket", "pgx_residual_sum", "pgx_gc_labeling", "pgx_gc_inliers", "pgx_epipolar_support", "pgx_gram_batch", "pgx_gram_labels", "pgx_residual_sums", "pgx_pnp_refine_batch",
     "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_barrier", "pgx_comm_allreduce_max_f64",
@@ -292,10 +293,15 @@ class Context:
         self._ck(self._lib.pgx_set_primitive_classes(self._h, C.c_int(int(class_mask)), C.c_double(float(smin)), C.c_double(float(smax))),
                  "pgx_set_primitive_classes")
 
+    def set_normal_tolerance(self, cos2=0.0):
+        """pgx_set_normal_tolerance: kappa = cos^2 of the angle a point's normal may deviate from a model's surface normal under
+        ORIENTED_PRIMITIVE3D (context state; 0 at creation: every finite non-zero normal agrees).  No other model type reads it."""
+        self._ck(self._lib.pgx_set_normal_tolerance(self._h, C.c_double(float(cos2))), "pgx_set_normal_tolerance")
+
     def set_normals(self, normals):
         """pgx_set_normals: per-point normals [n, 3] of the resident points, uploaded once and checked against n (None clears).  Only
-        the cylinder's, the cone's and the mixed-primitive minimal solvers read them; they need be neither unit nor consistently oriented.
-        set_points invalidates them."""
+        the cylinder's, the cone's and the mixed-primitive minimal solvers read them - and, under ORIENTED_PRIMITIVE3D, every kernel that
+        evaluates the squared residual; they need be neither unit nor consistently oriented.  set_points invalidates them."""
         if normals is None or len(normals) == 0:
             self._ck(self._lib.pgx_set_normals(self._h, None, C.c_int64(0)), "pgx_set_normals")
             return

@@ -558,4 +558,5 @@ def misclassification_models(preferences, annotation, K_annot):
 
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
                    vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D,
-                   line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D, cone=_lib.CONE3D, primitive=_lib.PRIMITIVE3D)
+                   line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D, cone=_lib.CONE3D, primitive=_lib.PRIMITIVE3D,
+                   oriented_primitive=_lib.ORIENTED_PRIMITIVE3D)
