@@ -59,7 +59,7 @@ enum pgx_model_type {
                                                          NaN residuals.  The minimal solver makes four hypotheses per sample of four
                                                          oriented points, one per class (pgx_set_primitive_classes), and reads the
                                                          resident normals (pgx_set_normals)     findPrimitives       */
-    PGX_ORIENTED_PRIMITIVE3D = 20 /* point (x,y,z);      model (class, q0 .. q7) exactly as PGX_PRIMITIVE3D, and its distance; but a point
+    PGX_ORIENTED_PRIMITIVE3D = 20, /* point (x,y,z);     model (class, q0 .. q7) exactly as PGX_PRIMITIVE3D, and its distance; but a point
                                                          supports a model only if its resident normal n (pgx_set_normals) also agrees with
                                                          the model's surface normal at the point (Schnabel et al., Efficient RANSAC, 4.3).
                                                          g, the unnormalised direction of that normal: plane (a,b,c); sphere x - c;
@@ -78,7 +78,14 @@ enum pgx_model_type {
                                                          resident normals.  The minimal solver is type 18's, and a slot whose model is not
                                                          compatible with every point of its own prefix is an all-NaN row
                                                                                                 findOrientedPrimitives */
-    /* 7, 9, 11, 13, 15, 17 and 19 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
+    PGX_TORUS3D = 22          /* point (x,y,z);          model (cx,cy,cz,dx,dy,dz,R,r), the centre, an axis direction (unit from the solver
+                                                         and the refit), the major radius R from the axis to the tube's centre circle and
+                                                         the minor (tube) radius r; a ring torus, R > r > 0, from the solver and the refit.
+                                                         With e = x - c, rho the 3-D line's distance about (c, d) and h = e.d the residual
+                                                         is |sqrt((rho - R)^2 + h^2) - r|.  The minimal solver reads the resident normals
+                                                         (pgx_set_normals) as LINES: the axis is a common transversal of four of them
+                                                                                                findTori             */
+    /* 7, 9, 11, 13, 15, 17, 19 and 21 are not assigned: pgx_model_dims and pgx_set_points on them fail with PGX_ERR_INVALID */
 };
 
 #define PGX_FIXED_SHIFT 32    /* min-cut energies are multiples of 2^-32 */
@@ -137,7 +144,11 @@ int pgx_score_upload(pgx_ctx *ctx, const double *models, int M);
  * model behind its class number; it fails with PGX_ERR_INVALID without the resident normals; a slot without a model, of a class
  * that pgx_set_primitive_classes has switched off, or with an index outside the points among those its own solver reads is an
  * all-NaN row, class included; under PGX_ORIENTED_PRIMITIVE3D the same four slots, and a slot whose model is not compatible with every
- * point of its own prefix at the resident normal tolerance is an all-NaN row as well), the 4-point homography
+ * point of its own prefix at the resident normal tolerance is an all-NaN row as well), the 4-point torus solver (samples[S][4], TWO
+ * slots per sample: 2S x 8, rows 2 s + j, findTori: the axis is the j-th common transversal of the four samples' normal lines, the
+ * tube's circle goes through samples 0 1 2 in the half-plane about it; it fails with PGX_ERR_INVALID without the resident normals;
+ * no real transversal, coplanar or parallel normal lines, a singular circle, non-finite values, R <= r, r outside pgx_set_radius_range
+ * and R outside pgx_set_major_radius_range give NaN), the 4-point homography
  * solver (samples[S][4], S x 9, h33 = 1,
  * DefaultHomographyEstimator progressivex_python.cpp:252, absent upstream), the 7-point fundamental matrix solver (samples[S][7], THREE model slots per
  * sample: 3S x 9, DefaultFundamentalMatrixEstimator progressivex_python.cpp:616, absent upstream), P3P (samples[S][3],
@@ -148,8 +159,12 @@ int pgx_solve_minimal(pgx_ctx *ctx, const int32_t *samples, int S, double *model
 /* The radii the sphere, the circle and the cylinder solver accept (context state, [0, +inf] at pgx_create; those three solvers read it):
  * a sample whose sphere, circle or cylinder has r outside [rmin, rmax] yields a NaN model.  NaN, rmin < 0 or rmax < rmin:
  * PGX_ERR_INVALID.  rmax = +inf is allowed.  For PGX_CONE3D the same range bounds s = sin(half-angle) of the cone solver's models:
- * a cone has no radius, and (sin(theta_min), sin(theta_max)) is its angle range. */
+ * a cone has no radius, and (sin(theta_min), sin(theta_max)) is its angle range.  For PGX_TORUS3D it bounds the minor (tube) radius r. */
 int pgx_set_radius_range(pgx_ctx *ctx, double rmin, double rmax);
+/* The major radii R the torus solver accepts (context state of the same kind, [0, +inf] at pgx_create; only PGX_TORUS3D's solver reads
+ * it): a sample whose torus has R outside [Rmin, Rmax] yields a NaN model.  NaN, Rmin < 0 or Rmax < Rmin: PGX_ERR_INVALID, and the
+ * state stays as it was.  Rmax = +inf is allowed. */
+int pgx_set_major_radius_range(pgx_ctx *ctx, double Rmin, double Rmax);
 /* What the mixed-primitive solver (PGX_PRIMITIVE3D) makes (context state; at pgx_create all four classes and [0, 1]).  class_mask:
  * bit 0 plane, bit 1 sphere, bit 2 cylinder, bit 3 cone, in slot order; a class that is off leaves its slot an all-NaN row.
  * (smin, smax) is the range of s = sin(half-angle) of that solver's cones.  Its spheres and cylinders read pgx_set_radius_range as
@@ -159,7 +174,7 @@ int pgx_set_radius_range(pgx_ctx *ctx, double rmin, double rmax);
 int pgx_set_primitive_classes(pgx_ctx *ctx, int class_mask, double smin, double smax);
 /* Per-point surface normals, n x 3 doubles in the points' order, RESIDENT like the weights of pgx_set_weights and under the same
  * rules: len == n is checked (PGX_ERR_INVALID), (NULL, 0) clears them, pgx_set_points invalidates them.  They need not be unit
- * length nor consistently oriented.  Only the cylinder's, the cone's and the mixed-primitive minimal solvers read them; the point rows
+ * length nor consistently oriented.  Only the cylinder's, the cone's, the torus' and the mixed-primitive minimal solvers read them; the point rows
  * stay n x 3.  Under PGX_ORIENTED_PRIMITIVE3D the squared residual reads them as well: the call also places them in the order of every
  * copy of the rows that the kernels read, and a second call with other normals makes every later result follow the new ones. */
 int pgx_set_normals(pgx_ctx *ctx, const double *normals, int64_t len);
@@ -360,10 +375,15 @@ int pgx_one_workgroup_launches(pgx_ctx *ctx, int64_t out[2]);
  *   PGX_GRAM_CONE_GN  the Gauss-Newton row (-g.u, -g.v, -g.d, -(e.u) k, -(e.v) k, -(rho s + h c), f) of a cone at params = (a[3], d[3],
  *                     c, s, u[3]), d unit, u unit and orthogonal to d, v = d x u: e = x - a, h = e . d, rho = |e x d|,
  *                     rhohat = (e - h d) / rho, f = c rho - s h, g = c rhohat - s d, k = c h / rho + s; 3-D points             q = 7
+ *   PGX_GRAM_TORUS_GN the Gauss-Newton row (-g.u, -g.v, -g.d, (e.u) k, (e.v) k, -t / w, -1, f) of a torus at params = (c[3], d[3], R, r,
+ *                     u[3]), d unit, u unit and orthogonal to d, v = d x u: e = x - c, h = e . d, rho = |e x d|, t = rho - R,
+ *                     w = sqrt(t t + h h), rhohat = (e - h d) / rho, f = w - r, g = (t / w) rhohat + (h / w) d, k = h R / (w rho);
+ *                     3-D points                                                                                               q = 8
  * Selection: PGX_SEL_INDEX (index[m], host) or PGX_SEL_LABEL (label == `label` on the resident labelling).
- * count = selected points, bad = points skipped because the row is undefined (PnP: depth ~ 0; cylinder and cone: a point on the axis). */
+ * count = selected points, bad = points skipped because the row is undefined (PnP: depth ~ 0; cylinder and cone: a point on the axis;
+ * torus: a point on the axis or on the spine, w = 0). */
 enum { PGX_GRAM_AFFINE = 0, PGX_GRAM_DLT_H = 1, PGX_GRAM_EPI_F = 2, PGX_GRAM_VP = 3, PGX_GRAM_PNP_GN = 4, PGX_GRAM_SPHERE = 5, PGX_GRAM_CIRCLE = 6,
-       PGX_GRAM_CYL_GN = 7, PGX_GRAM_CONE_GN = 8 };
+       PGX_GRAM_CYL_GN = 7, PGX_GRAM_CONE_GN = 8, PGX_GRAM_TORUS_GN = 9 };
 enum { PGX_SEL_INDEX = 0, PGX_SEL_LABEL = 1 };
 int pgx_set_weights(pgx_ctx *ctx, const double *weights, int64_t len);
 int pgx_gram(pgx_ctx *ctx, int kind, const double *params, int nparams, int sel, const int32_t *index, int64_t m,

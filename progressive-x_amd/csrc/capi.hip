@@ -1027,6 +1027,16 @@ int pgx_set_radius_range(pgx_ctx* ctx, double rmin, double rmax)
     return PGX_OK;
 }
 
+int pgx_set_major_radius_range(pgx_ctx* ctx, double Rmin, double Rmax)
+{
+    CTX_GUARD(ctx);
+    if (!(Rmin >= 0.0) || !(Rmax >= Rmin))   // also NaN
+        return fail(ctx, PGX_ERR_INVALID, "pgx_set_major_radius_range: need 0 <= Rmin <= Rmax (got %g, %g)", Rmin, Rmax);
+    ctx->major_rmin = Rmin;
+    ctx->major_rmax = Rmax;
+    return PGX_OK;
+}
+
 int pgx_set_primitive_classes(pgx_ctx* ctx, int class_mask, double smin, double smax)
 {
     CTX_GUARD(ctx);

@@ -70,6 +70,7 @@ struct GenVp { static constexpr int Q = 3, D = 4; };
 struct GenPnpGn { static constexpr int Q = 7, D = 5; };
 struct GenCylGn { static constexpr int Q = 6, D = 3; };
 struct GenConeGn { static constexpr int Q = 7, D = 3; };
+struct GenTorusGn { static constexpr int Q = 8, D = 3; };
 
 // the affine row (1, p[0], .., p[DIM - 1]) of a DIM-D point: lines (2), planes (3) and the 4- and 5-D rows
 template <int DIM> struct GenAffine {
@@ -216,6 +217,48 @@ __device__ __forceinline__ void emit<GenConeGn>(const double* pt, const FitParam
     const double k = (c * h) / rho + s;
     const double a[7] = {-gu, -gv, -gd, -(eu * k), -(ev * k), -(rho * s + h * c), c * rho - s * h};
     acc.add(a, w);
+}
+// The torus' Gauss-Newton row.  prm = (c[3], d[3], R, r, u[3]): the centre, the unit direction, the major and minor radius and a unit
+// vector orthogonal to d; v = d x u (cross3's component order) completes the frame here.  With e = x - c, cr = e x d, rho = |cr| and
+// h = (e0 d0 + e1 d1) + e2 d2 exactly as Residual<kTorus3D> computes them, t = rho - R and w = sqrt(t t + h h) (so the last entry is
+// Residual<kTorus3D>'s w - r before its fabs, bit for bit):
+//   tw = t / w,  hw = h / w,  rh_k = (e_k - h d_k) / rho,  g_k = tw rh_k + hw d_k,  gu = (g0 u0 + g1 u1) + g2 u2, gv and gd likewise
+//   with v and d,  eu = (e0 u0 + e1 u1) + e2 u2, ev likewise,  k = (h R) / (w rho),
+//   row = (-gu, -gv, -gd, eu k, ev k, -tw, -1, w - r)
+// the derivatives of f = w - r by (alpha, beta, gamma, delta, eta, dR, dr) at 0 in c + alpha u + beta v + gamma d,
+// normalise(d + delta u + eta v), R + dR, r + dr, followed by f: g = (t / w) rhohat + (h / w) d is the gradient of f in x, so moving
+// the centre by z moves f by -g . z; a tilt of d by delta u changes h by delta (e . u) and rho by -delta h (e . u) / rho, together
+// delta (e . u)(h / w)(1 - t / rho) = delta (e . u) h R / (w rho).  A point on the axis (!(rho > 0)), a point on the spine (!(w > 0)) or
+// a non-finite rho or w has no row.
+template <>
+__device__ __forceinline__ void emit<GenTorusGn>(const double* pt, const FitParams& prm, Acc<8>& acc, double w8, int& bad)
+{
+    const double* m = prm.v;
+    const double* u = prm.v + 8;
+    const double R = m[6], r = m[7];
+    const double v0 = m[4] * u[2] - m[5] * u[1], v1 = -(m[3] * u[2] - m[5] * u[0]), v2 = m[3] * u[1] - m[4] * u[0];
+    const double e0 = pt[0] - m[0], e1 = pt[1] - m[1], e2 = pt[2] - m[2];
+    const double c0 = e1 * m[5] - e2 * m[4];
+    const double c1 = -(e0 * m[5] - e2 * m[3]);
+    const double c2 = e0 * m[4] - e1 * m[3];
+    const double rho = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+    if (!(rho > 0.0) || !isfinite(rho)) { bad = 1; return; }
+    const double h = (e0 * m[3] + e1 * m[4]) + e2 * m[5];
+    const double t = rho - R;
+    const double w = sqrt(t * t + h * h);
+    if (!(w > 0.0) || !isfinite(w)) { bad = 1; return; }
+    const double tw = t / w, hw = h / w;
+    const double g0 = tw * ((e0 - h * m[3]) / rho) + hw * m[3];
+    const double g1 = tw * ((e1 - h * m[4]) / rho) + hw * m[4];
+    const double g2 = tw * ((e2 - h * m[5]) / rho) + hw * m[5];
+    const double gu = (g0 * u[0] + g1 * u[1]) + g2 * u[2];
+    const double gv = (g0 * v0 + g1 * v1) + g2 * v2;
+    const double gd = (g0 * m[3] + g1 * m[4]) + g2 * m[5];
+    const double eu = (e0 * u[0] + e1 * u[1]) + e2 * u[2];
+    const double ev = (e0 * v0 + e1 * v1) + e2 * v2;
+    const double k = (h * R) / (w * rho);
+    const double a[8] = {-gu, -gv, -gd, eu * k, ev * k, -tw, -1.0, w - r};
+    acc.add(a, w8);
 }
 
 // ---- the reduction passes, each written once ---------------------------------------------------------------------------------
@@ -551,6 +594,7 @@ static int gram_row_length(pgx_ctx* ctx, const char* who, int kind, int nparams,
     case PGX_GRAM_CIRCLE: *q = 4; if (D != 2 || nparams != 3) return fail(ctx, PGX_ERR_INVALID, "%s: needs 2-D points and 3 parameters (ox, oy, s)", who); break;
     case PGX_GRAM_CYL_GN: *q = 6; if (D != 3 || nparams != 10) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 10 parameters (p, d, r, u)", who); break;
     case PGX_GRAM_CONE_GN: *q = 7; if (D != 3 || nparams != 11) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 11 parameters (a, d, c, s, u)", who); break;
+    case PGX_GRAM_TORUS_GN: *q = 8; if (D != 3 || nparams != 11) return fail(ctx, PGX_ERR_INVALID, "%s: needs 3-D points and 11 parameters (c, d, R, r, u)", who); break;
     default: return fail(ctx, PGX_ERR_INVALID, "%s: unknown row kind %d", who, kind);
     }
     return PGX_OK;
@@ -574,6 +618,7 @@ static void with_gram_generator(int kind, int D, F&& f)
     case PGX_GRAM_CIRCLE: f(GenRound<2>{}); break;
     case PGX_GRAM_CYL_GN: f(GenCylGn{}); break;
     case PGX_GRAM_CONE_GN: f(GenConeGn{}); break;
+    case PGX_GRAM_TORUS_GN: f(GenTorusGn{}); break;
     default: f(GenPnpGn{}); break;
     }
 }

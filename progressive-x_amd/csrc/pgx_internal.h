@@ -60,6 +60,7 @@ struct pgx_ctx {
     double fscale = 0.0;     // max(1, max |coordinate|) over all points: isotropic pre-scaling of the minimal solvers
     double rmin = 0.0, rmax = __builtin_inf();   // pgx_set_radius_range: the radii the sphere, the circle and the cylinder solver accept, the sines of the cone's (context state)
     int prim_mask = 15;                          // pgx_set_primitive_classes: the classes the mixed-primitive solver makes (bit j = slot j) and the
+    double major_rmin = 0.0, major_rmax = __builtin_inf();   // pgx_set_major_radius_range: the major radii the torus solver accepts (context state; its tube radii read rmin, rmax)
     double prim_smin = 0.0, prim_smax = 1.0;     // sines its cones may have (context state; its spheres and cylinders read rmin, rmax)
     pgx::ScoreSwitches score_sw;   // PGX_NO_FILTER, PGX_SCORE_NO_CULL, PGX_SCORE_MIRROR, PGX_VERIFY and pgx_score_debug_geometry: what plan_score reads (score_plan.h)
     pgx::DevBuf stats_buf;         // work counters of a pgx_score_stats launch

@@ -1,7 +1,8 @@
 // residuals.hip.h — per-(point, model) residuals for the five Progressive-X problem types and the geometric primitives: the two
 // families flat (2-D lines, 3-D planes) and round (2-D circles, 3-D spheres), each written once per dimension, and the 3-D line
-// (distance to an axis), the cylinder (that distance less a radius), the cone (the distance to a generatrix), the union of plane,
-// sphere, cylinder and cone whose model row carries its class, and that union with a test of the point's normal.  gfx950 device code.
+// (distance to an axis), the cylinder (that distance less a radius), the cone (the distance to a generatrix), the torus (the distance
+// to the tube's centre circle less the tube radius), the union of plane, sphere, cylinder and cone whose model row carries its class,
+// and that union with a test of the point's normal.  gfx950 device code.
 //
 // FP64 throughout, compiled with -ffp-contract=off: the reference is built for baseline x86-64 (no FMA,
 // /root/reference/CMakeLists.txt:23) and parity of inlier masks is bit-exact, so every product and sum is
@@ -22,8 +23,8 @@ namespace pgx {
 enum ModelType : int {
     kLine2D = 0, kHomography = 1, kFundamental = 2, kPnP = 3, kVanishingPoint = 4, kHomographySym = 5, kPlane3D = 6,
     kSphere3D = 8, kCircle2D = 10, kLine3D = 12, kCylinder3D = 14, kCone3D = 16, kPrimitive3D = 18,
-    kOrientedPrimitive3D = 20,
-    kNumModelTypes = 21   // 7, 9, 11, 13, 15, 17 and 19 are not assigned (pgx_model_dims(7), (9), (11), (13), (15), (17) and (19) are errors)
+    kOrientedPrimitive3D = 20, kTorus3D = 22,
+    kNumModelTypes = 23   // 7, 9, 11, 13, 15, 17, 19 and 21 are not assigned (pgx_model_dims on each of them is an error)
 };
 
 // OpenCV's MIN/MAX macros (the reference sees them via progx_model.h:36): MAX(a,b) ((a) < (b) ? (b) : (a)).
@@ -160,6 +161,39 @@ template <> struct Residual<kCone3D> : NoProjectiveMap {
         const double rho = sqrt(Residual<kLine3D>::squared(p, m));
         const double h = (e0 * m[3] + e1 * m[4]) + e2 * m[5];
         return fabs(m[6] * rho - m[7] * h);
+    }
+    template <class PT, class MD>
+    static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
+        const double r = plain(p, m);
+        return r * r;
+    }
+};
+
+// Torus (findTori; no reference counterpart): model (c[3], d[3], R, r), the centre, the axis direction, the major radius (from the axis
+// to the tube's centre circle, the spine) and the minor (tube) radius.  With e = x - c componentwise:
+//   q = Residual<kLine3D>::squared(x, (c, d))  (the same expressions: the code is shared),  rho = sqrt(q),  h = (e0 d0 + e1 d1) + e2 d2,
+//   t = rho - R,  w = sqrt(t t + h h),  plain = |w - r|,  squared = plain * plain.
+// Only + - x and sqrt: no division, no contraction.  What plain measures: in the half-plane (h, rho) of a point - height along the axis,
+// distance from it - the tube is the circle of radius r about (0, R), w is the distance to the spine and plain the distance to that
+// circle.  For a ring torus (R > r > 0, what the solver and the refit return) this is the distance to the surface: the mirror circle
+// about (0, -R) of the same meridian plane is farther from every point with rho >= 0.  For R <= r (spindle and horn tori) the inner
+// part of the self-crossing surface still counts as surface; for r < 0 plain is w + |r|.
+// Scaling: d is taken as given, as for lines, cylinders and cones (unit from the solver and the refit).  rho and h are homogeneous of
+// degree 1 in d, R and r are not rescaled with them: with d times k the residual is that of the torus (c, d / |d|, R / |k|, r / |k|)
+// times |k|.  Every entry of (c, d) enters q, R enters t and r the last difference: a NaN in any of the eight entries makes every
+// residual NaN.  d = 0 makes rho = h = 0 and every residual ||R| - r|.  This operation order is the contract of every torus check
+// (tests restate it in numpy).
+template <> struct Residual<kTorus3D> : NoProjectiveMap {
+    static constexpr int D = 3, P = 8, sample = 4, slots = 2, bound = kBoundBall;
+    static constexpr const char* normals_solver = "torus";
+    template <class PT, class MD>
+    static __device__ __forceinline__ double plain(const PT& p, const MD& m) {
+        const double e0 = p[0] - m[0], e1 = p[1] - m[1], e2 = p[2] - m[2];
+        const double rho = sqrt(Residual<kLine3D>::squared(p, m));
+        const double h = (e0 * m[3] + e1 * m[4]) + e2 * m[5];
+        const double t = rho - m[6];
+        const double w = sqrt(t * t + h * h);
+        return fabs(w - m[7]);
     }
     template <class PT, class MD>
     static __device__ __forceinline__ double squared(const PT& p, const MD& m) {
@@ -395,6 +429,7 @@ template <class F> inline bool with_model_type(int mt, F&& f) {
     case kCone3D: f(std::integral_constant<int, kCone3D>{}); return true;
     case kPrimitive3D: f(std::integral_constant<int, kPrimitive3D>{}); return true;
     case kOrientedPrimitive3D: f(std::integral_constant<int, kOrientedPrimitive3D>{}); return true;
+    case kTorus3D: f(std::integral_constant<int, kTorus3D>{}); return true;
     default: return false;
     }
 }

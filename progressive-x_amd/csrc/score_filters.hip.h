@@ -973,6 +973,115 @@ template <> struct Filter32<kCone3D> {
     }
 };
 
+// ---- tori: r = | sqrt((rho - R)^2 + h^2) - cr |, rho = |(x - c) x d|, h = (x - c) . d (Residual<kTorus3D>), inlier iff r^2 < T2 ------
+// The 3-D line's distance and the cone's dot product, then the 2-D circle's last step in the half-plane (h, rho).  Homogeneous in the
+// direction only, as the cylinder is: with the 3-D line's sc = pow2_normaliser<3>(d), rho and h on d sc are rho sc and h sc (the root
+// scales bit for bit, sc^2 being an even power of two; the products and sums of h scale exactly), and with both radii in the same
+// units, R = (major radius) sc and r = cr sc (exact in f64), t = rho - R, t t + h h, its root and the last difference scale along: the
+// exact path's decision on (d, R, cr, T2) is the one its arithmetic would take on (d sc, R sc, cr sc, T2 sc^2), and the test is against
+// Ts = T sc.  Below d, R and r are the scaled ones, and rho*, h*, w* = sqrt((rho* - R)^2 + h*^2), n* = w* - r are exact on the f64
+// inputs.  Per point, in f32 - this operation order is the contract of the f32 test (tests restate it with fma as one rounding):
+//   s~, l~ = Filter32<kLine3D>::dist(x~, c~, d~)  (the same code; e~_k = x~_k - c~_k),   h~ = fma(e~_2, d~_2, fma(e~_1, d~_1, e~_0 d~_0)),
+//   R~ = (float)R,  r~ = (float)r,   t~ = s~ - R~,   w~ = sqrtf(fma(t~, t~, h~ h~)),   n~ = w~ - r~
+// With u = 2^-24, B = sqrt(3) u |d| P + u |d| |c| for the inputs x~ and c~ and t = u |d~| |e~| as in the cone's derivation:
+//   rho        |s~ - rho*| + |rho_c - rho*| <= B + (7.5 + 2^-26) t and the underflow floor: the 3-D line's budget, its exact path included
+//   h~         |h~ - h*| <= B + 5 t: the cone's budget for the same expression; the exact h is inside the slack of e2
+//   R~, t~     |R~ - R| <= u |R|; the subtraction is rounded once, u |t~|
+//   w~         (t, h) -> sqrt(t^2 + h^2) is 1-Lipschitz, so the errors of t~ and h~ move w by at most their sum,
+//              2 B + 12.5 t + u |R|; h~ h~ is rounded as a product and by the fma, t~ t~ by the fma alone: at most 2 u relative under the
+//              root, u w~ after it; v_sqrt_f32's documented 1 ulp = 2 u w~; with t~'s own rounding 4 u w~, and
+//              w~ <= sqrt(rho^2 + h^2) + |R| = |e| |d| + |R|: 4 t + 4 u |R|
+//   r~, n~     |r~ - r| <= u |r|; the last subtraction is rounded once, relatively, and is charged to the T'' margin as the cylinder's is
+//   exact path rho - R, two squares, a sum and a root in f64: < 4 * 2^-53 (|e| |d| + |R|), inside the slack of e2 and of e0's |R| term;
+//              the last difference is relative and part of the T'' margin
+// so |n~ / (1 + t') - n*| + |n_c - n*| <= 2 sqrt(3) u |d| P + 2 u |d| |c| + 5 u |R| + u |r| + (16.5 + 2^-25) u |d~| |e~| + O(u^2), |t'| <= u,
+// and with the 3-D line's D = 1.001 |d| (f64, rounded up):
+//   E = e1 P + e0 + e2 l~      e1 = 4 u D                                         >= 1.15 * 2 sqrt(3) u |d|
+//                              e0 = 2 u (2 D |c| 1.001 + 3 |R| + |r|) + 2e-18     >= 2 u |d| |c| + 5 u |R| + u |r| with a fifth to spare; the
+//                                                                                 floor: the 3-D line's 4 * 2.2e-19 on s~, 4 eta for h~, and
+//                                                                                 two squares below 2^-126 put <= 2 eta under w~'s root,
+//                                                                                 sqrt(2 eta) < 1.6e-19
+//                              e2 = 18 u D                                        >= 1.09 * (16.5 + 2^-25) u |d~|
+//   reject  <=>  m := |n~| - E > T'' = Ts (1 + 2^-6):  m is rounded once and monotonically, so |n_c| > Ts (1 + 2^-7), and the computed
+//   residual's square, which the exact path compares, exceeds Ts^2 = T2 sc^2.
+// Group test on the 3-D ball rows (stored centre g, radius rho_g, Pmax), nothing new in setpoints.hip: x -> (h, rho) drops the angle
+// about the axis and is |d|-Lipschitz, the distance to the spine's point (0, R) of the half-plane and the difference with r are
+// 1-Lipschitz, so the signed residual w - r is |d|-Lipschitz in x.  Every member's |n*| is at least |n*_g| - |d| rho_g, less the errors
+// above with P = Pmax and |e|_1 <= |e_g|_1 + sqrt(3) rho_g:
+//   reject the group  <=>  |n~_g| - E(Pmax, l~_g + 1.74 rho_g) - 1.001 D rho_g > 1.001 T''.
+// One rule for points outside the tube, inside it, in the hole and on the axis (rho = 0 is no special case of w).
+// Switch-off, E = inf and the exact path decides: the 3-D line's cases - coordinates beyond 1e17 or |c| beyond 1e17, Ts outside the
+// ordinary f32 range, a direction outside pow2_normaliser's band (d = 0, whose residuals are all ||R| - cr| on the exact path, and Inf
+// entries among them) - and |R| or |r| beyond 1e17 in the filter's units, which a non-finite radius is too (t~^2 + h~^2 stays below
+// 2 (7e17)^2, an ordinary f32).  A NaN entry culls the hypothesis outright (all eight enter every residual).  The exact path is the
+// 3-D line's 17 FP64 operations plus two roots, five operations for h, four for w, a difference and a square.
+template <> struct Filter32<kTorus3D> {
+    using Line = Filter32<kLine3D>;
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    struct Lane { float p[3]; float d[3]; float R, r, e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
+    // reject() reads p, d, R, r, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject): three float4 chunks,
+    // the cone's count
+    static constexpr int kStagedVals = 12;
+    static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, R) == 6 * sizeof(float) && offsetof(Lane, e1) == 8 * sizeof(float) &&
+                  offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
+                  sizeof(Lane) == 14 * sizeof(float), "p, d, R, r, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        const double d0[3] = {m[3], m[4], m[5]};
+        bool off;
+        const double sc = pow2_normaliser<3>(d0, &off);
+        bool nan = !(m[6] == m[6]) || !(m[7] == m[7]);
+        double d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k] = d0[k] * sc;
+            ln.p[k] = (float)m[k];
+            ln.d[k] = (float)d[k];
+            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
+        }
+        ln.nanh = nan ? 1.0f : 0.0f;
+        const double R = m[6] * sc, r = m[7] * sc;   // both radii in the scaled direction's units
+        ln.R = (float)R;
+        ln.r = (float)r;
+        const double Ts = sqrt(T2) * sc;   // the threshold in the same units: must be an ordinary f32 as well
+        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
+        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
+        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(fabs(R) <= 1e17) || !(fabs(r) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
+        const double u = 5.9604644775390625e-8;
+        ln.e1 = f32_up(4.0 * u * dn);
+        ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * ((2.0 * dn * pn + 3.0 * fabs(R)) + fabs(r)) + 2e-18);   // inf: nothing is rejected
+        ln.e2 = f32_up(18.0 * u * dn);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        ln.nrm = f32_up(dn);
+        return ln;
+    }
+    // n~ and l~ of a point or a centre: the 3-D line's s~ and l~ on this lane's p and d, then h~, t~, w~ and the last difference
+    static __device__ __forceinline__ float signed_dist(const float* p, const Lane& ln, float* l1) {
+        const float s = Line::dist(p, ln, l1);
+        const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];   // dist's own e~ (the same subtractions)
+        const float h = __builtin_fmaf(e2, ln.d[2], __builtin_fmaf(e1, ln.d[1], e0 * ln.d[0]));
+        const float t = s - ln.R;
+        const float w = sqrtf(__builtin_fmaf(t, t, h * h));
+        return w - ln.r;
+    }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        float l1;
+        const float n = signed_dist(p, ln, &l1);
+        const float m = fabsf(n) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (centre[3], rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
+        float l1;
+        const float n = signed_dist(g, ln, &l1);
+        const float m = fabsf(n) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
 // ---- mixed primitives: the constituent's filter behind the class (Residual<kPrimitive3D>) -------------------------------------------
 // Nothing is derived here.  A lane is the class followed by the constituent's own lane, float for float as its prep() made it from the
 // constituent's model row q = m + 1; reject() and group_reject() hand that lane to the constituent's functions, so every f32 operation,

@@ -38,7 +38,12 @@
 //                                       three tangent planes, the axis is orthogonal to the differences of the three unit vectors
 //                                       from the apex to the samples; tangent planes without a common point, a sample at the apex,
 //                                       non-finite values, cos <= 0 and a sine outside pgx_set_radius_range give NaN
-// The eight solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line, cylinder, cone) share one kernel shell, solve_kernel<MT>;
+//   torus through four oriented points  findTori's minimal solver (no reference counterpart), two slots per sample: the axis is a common
+//                                       transversal of the four normal LINES (at most two), the tube's circle goes through three
+//                                       samples in the half-plane about it; no transversal, a singular circle, non-finite values,
+//                                       R <= r and radii outside pgx_set_radius_range / pgx_set_major_radius_range give NaN
+// The eight solvers with one model per sample (line, vanishing point, plane, sphere, circle, 3-D line, cylinder, cone) and the torus'
+// with two share one kernel shell, solve_kernel<MT>, one lane per model row;
 // the 7-point, 4-point and P3P solvers and the mixed-primitive solver (four slots of four classes per sample) run one lane per sample in
 // kernels of their own.
 // Operation order is the contract (bit-exact against the oracle's C restatement, no contraction, IEEE sqrt and divide).
@@ -70,7 +75,9 @@ __device__ __forceinline__ void cross3(double a1, double b1, double c1, double a
 // solve_minimal(type, p, nq, rmin, rmax, m): p = the sample's Residual<MT>::sample point rows (all inside the point set), nq = the same
 // points' rows of the resident normals (pgx_set_normals; only the types with Residual<MT>::normals_solver read them, and the launch
 // refuses those without them), m = the model, preset to NaN - a degenerate sample leaves it so.  rmin, rmax: the context's
-// pgx_set_radius_range (the round family and the cylinder read them as radii, the cone as the range of its sine).
+// pgx_set_radius_range (the round family and the cylinder read them as radii, the cone as the range of its sine, the torus as the
+// range of its tube radius).  A type with more than one slot takes (type, p, nq, rmin, rmax, Rmin, Rmax, slot, m): the torus, with
+// Rmin, Rmax the context's pgx_set_major_radius_range and slot the solution asked for.
 template <int MT> using Type = std::integral_constant<int, MT>;
 
 // 2-point line [U-4]: unit normal (-dy, dx) / |d|, offset c = -(n . a); coincident points (ln == 0; also false on NaN) give NaN.
@@ -271,17 +278,97 @@ __device__ __forceinline__ void solve_minimal(Type<kCone3D>, const double* const
     m[6] = c; m[7] = s;
 }
 
-// The shell: samples[S][sample] -> S x P models, one lane per padded model.  An index outside 0 .. n-1 gives a NaN model.  normals
-// may be null for every type whose solver does not read them.
+// 4-point torus from oriented points -> (c, d, R, r), the centre, a unit axis direction and the major and minor radius (findTori; no
+// reference counterpart), TWO slots per sample.  Every normal of a surface of revolution meets its axis, so the axis is a common
+// transversal of the four normal lines (p_i, n_i), of which there are at most two: slot j takes the j-th.  The normals are read as
+// LINES here, not as tangent planes; they need be neither unit nor consistently signed.  A transversal through a = p0 + s n0 and
+// b = p1 + t n1 meets line i (i = 2, 3) iff det[b - a, n_i, p_i - a] = 0, which is bilinear in (s, t): A_i s t + B_i s + C_i t + D_i = 0
+// (the s^2 term is n0 . (n_i x n0) = 0).  Operation order (the contract; TorusEstimator.minimal restates it), dot(x, y) = (x0 y0 + x1 y1)
+// + x2 y2 throughout:
+//   q = p1 - p0, and for i = 2, 3 (written 1, 2 below):  g = p_i - p0,  X = cross3(n_i, g),  Y = cross3(n_i, n0),
+//   A_i = -dot(n1, Y),  B_i = -(dot(q, Y) + dot(n0, X)),  C_i = dot(n1, X),  D_i = dot(q, X);
+//   t = -(B1 s + D1) / (A1 s + C1) in the second condition leaves qa s^2 + qb s + qc = 0 with
+//   qa = B2 A1 - A2 B1,  qb = ((B2 C1 - A2 D1) - C2 B1) + D2 A1,  qc = D2 C1 - C2 D1,  disc = qb qb - (4 qa) qc,  sq = sqrt(disc),
+//   s = (-qb + sq) / (2 qa) in slot 0 and (-qb - sq) / (2 qa) in slot 1,  den = A1 s + C1,  t = -(B1 s + D1) / den,
+//   a = p0 + s n0,  b = p1 + t n1,  Dv = b - a (componentwise),  ln = sqrt(dot(Dv, Dv)),  d = Dv / ln,
+//   for k = 0, 1, 2:  e = p_k - a,  h_k = dot(e, d),  rho_k = sqrt(Residual<kLine3D>::squared(p_k, (a, d))),
+//   the circle through (h_k, rho_k) by the 3-point circle solver's own arithmetic: a1 = (h_1 - h_0, rho_1 - rho_0), a2 likewise,
+//   g_i = 0.5 (a_i0 a_i0 + a_i1 a_i1), det = a_10 a_21 - a_11 a_20, z_0 = (g_1 a_21 - g_2 a_11) / det, z_1 = (a_10 g_2 - a_20 g_1) / det,
+//   r = sqrt(z_0 z_0 + z_1 z_1),  hc = h_0 + z_0,  R = rho_0 + z_1,  c = a + hc d.
+// The model stays NaN unless disc >= 0, qa != 0, den != 0, ln > 0, det != 0, all eight entries are finite, R > r (a ring torus),
+// rmin <= r <= rmax (pgx_set_radius_range bounds the tube radius here) and Rmin <= R <= Rmax (pgx_set_major_radius_range).  Normal
+// lines that are coplanar or parallel make every coefficient, and so qa, 0 up to rounding: where it comes out as a tiny number the
+// model, if finite, collects no inliers.  The fourth sample enters through the transversal alone.
+__device__ __forceinline__ double dot3(const double* x, const double* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
+__device__ __forceinline__ void solve_minimal(Type<kTorus3D>, const double* const* p, const double* const* nq, double rmin, double rmax, double Rmin,
+                                              double Rmax, int slot, double* m)
+{
+    const double *p0 = p[0], *p1 = p[1], *n0 = nq[0], *n1 = nq[1];
+    const double q[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+    double A[2], B[2], C[2], D[2];
+    for (int i = 0; i < 2; ++i) {
+        const double *pi = p[i + 2], *ni = nq[i + 2];
+        const double g[3] = {pi[0] - p0[0], pi[1] - p0[1], pi[2] - p0[2]};
+        double X[3], Y[3];
+        cross3(ni[0], ni[1], ni[2], g[0], g[1], g[2], X);
+        cross3(ni[0], ni[1], ni[2], n0[0], n0[1], n0[2], Y);
+        A[i] = -dot3(n1, Y);
+        B[i] = -(dot3(q, Y) + dot3(n0, X));
+        C[i] = dot3(n1, X);
+        D[i] = dot3(q, X);
+    }
+    const double qa = B[1] * A[0] - A[1] * B[0];
+    const double qb = ((B[1] * C[0] - A[1] * D[0]) - C[1] * B[0]) + D[1] * A[0];
+    const double qc = D[1] * C[0] - C[1] * D[0];
+    const double disc = qb * qb - (4.0 * qa) * qc;
+    if (!(disc >= 0.0) || qa == 0.0) return;
+    const double sq = sqrt(disc);
+    const double s = slot == 0 ? (-qb + sq) / (2.0 * qa) : (-qb - sq) / (2.0 * qa);
+    const double den = A[0] * s + C[0];
+    if (den == 0.0) return;
+    const double t = -(B[0] * s + D[0]) / den;
+    const double a[3] = {p0[0] + s * n0[0], p0[1] + s * n0[1], p0[2] + s * n0[2]};
+    const double b[3] = {p1[0] + t * n1[0], p1[1] + t * n1[1], p1[2] + t * n1[2]};
+    const double Dv[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    const double ln = sqrt(dot3(Dv, Dv));
+    if (!(ln > 0.0)) return;
+    const double axis[6] = {a[0], a[1], a[2], Dv[0] / ln, Dv[1] / ln, Dv[2] / ln};
+    const double* d = axis + 3;
+    double h[3], rho[3];
+    for (int k = 0; k < 3; ++k) {
+        const double e[3] = {p[k][0] - a[0], p[k][1] - a[1], p[k][2] - a[2]};
+        h[k] = dot3(e, d);
+        rho[k] = sqrt(Residual<kLine3D>::squared(p[k], axis));
+    }
+    const double a10 = h[1] - h[0], a11 = rho[1] - rho[0], a20 = h[2] - h[0], a21 = rho[2] - rho[0];
+    const double g1 = 0.5 * (a10 * a10 + a11 * a11), g2 = 0.5 * (a20 * a20 + a21 * a21);
+    const double det = a10 * a21 - a11 * a20;
+    if (det == 0.0) return;
+    const double z0 = (g1 * a21 - g2 * a11) / det, z1 = (a10 * g2 - a20 * g1) / det;
+    const double r = sqrt(z0 * z0 + z1 * z1);
+    const double hc = h[0] + z0, R = rho[0] + z1;
+    const double c[3] = {a[0] + hc * d[0], a[1] + hc * d[1], a[2] + hc * d[2]};
+    if (!(isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]) && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]) && isfinite(R) && isfinite(r) &&
+          R > r && r >= rmin && r <= rmax && R >= Rmin && R <= Rmax))
+        return;
+    m[0] = c[0]; m[1] = c[1]; m[2] = c[2];
+    m[3] = d[0]; m[4] = d[1]; m[5] = d[2];
+    m[6] = R; m[7] = r;
+}
+
+// The shell: samples[S][sample] -> (slots S) x P models, rows slots * s + j, one lane per padded model.  An index outside 0 .. n-1 gives
+// a NaN model.  normals may be null for every type whose solver does not read them.  A solver with more than one slot takes the slot
+// and the major radius range as well (the torus).
 template <int MT>
 __global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __restrict__ pts, const double* __restrict__ normals, int64_t n,
-                                                            const int* __restrict__ samples, int S, double rmin, double rmax,
+                                                            const int* __restrict__ samples, int S, double rmin, double rmax, double Rmin, double Rmax,
                                                             double* __restrict__ models, int* __restrict__ perm, int Mpad)
 {
     using R = Residual<MT>;
-    const int s = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
-    if (s < Mpad) perm[s] = s < S ? s : 0;  // generated in the caller's order: no locality permutation
-    if (s >= S) return;
+    const int row = (int)(blockIdx.x * kSolveBlock + threadIdx.x);
+    if (row < Mpad) perm[row] = row < R::slots * S ? row : 0;  // generated in the caller's order: no locality permutation
+    if (row >= R::slots * S) return;
+    const int s = row / R::slots;
     int ix[R::sample];
     bool inb = true;
     for (int k = 0; k < R::sample; ++k) {
@@ -296,9 +383,10 @@ __global__ __launch_bounds__(kSolveBlock) void solve_kernel(const double* __rest
             p[k] = pts + (int64_t)ix[k] * R::D;
             nq[k] = normals ? normals + (int64_t)ix[k] * 3 : nullptr;
         }
-        solve_minimal(Type<MT>{}, p, nq, rmin, rmax, m);
+        if constexpr (R::slots == 1) solve_minimal(Type<MT>{}, p, nq, rmin, rmax, m);
+        else solve_minimal(Type<MT>{}, p, nq, rmin, rmax, Rmin, Rmax, row % R::slots, m);
     }
-    for (int k = 0; k < R::P; ++k) models[(int64_t)s * R::P + k] = m[k];
+    for (int k = 0; k < R::P; ++k) models[(int64_t)row * R::P + k] = m[k];
 }
 
 // ---- mixed primitives: four hypotheses of four classes per sample ---------------------------------------------------------------------
@@ -811,7 +899,7 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
     const int mt = ctx->model_type;
     ModelInfo mi;
     if (!model_info(mt, &mi) || mi.slots == 0)
-        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone, 4-point mixed primitives, 4-point homography, 7-point fundamental matrix, P3P)", mt);
+        return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: no device solver for model type %d yet (built: 2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone, 4-point mixed primitives, 4-point torus, 4-point homography, 7-point fundamental matrix, P3P)", mt);
     if (mi.normals_solver && ctx->normals_n != ctx->n)
         return fail(ctx, PGX_ERR_INVALID, "pgx_solve_minimal: the %s solver needs the resident points' normals (pgx_set_normals after pgx_set_points)", mi.normals_solver);
     // isotropic pre-scaling by the largest coordinate magnitude (pmax of set_points is 1 for these model types, so the solvers take
@@ -843,7 +931,8 @@ int solve_minimal_launch(pgx_ctx* ctx, const int32_t* samples, int S, double* mo
         with_model_type(mt, [&](auto t) {
             constexpr int MT = decltype(t)::value;
             if constexpr (Residual<MT>::slots > 0 && MT != kFundamental && MT != kHomography && MT != kPnP && MT != kPrimitive3D && MT != kOrientedPrimitive3D)
-                hipLaunchKernelGGL((solve_kernel<MT>), gm, bm, 0, ctx->stream, pts, normals, ctx->n, smp, S, ctx->rmin, ctx->rmax, models, perm, Mpad);
+                hipLaunchKernelGGL((solve_kernel<MT>), gm, bm, 0, ctx->stream, pts, normals, ctx->n, smp, S, ctx->rmin, ctx->rmax, ctx->major_rmin, ctx->major_rmax, models,
+                                   perm, Mpad);
         });
     PGX_HIP(ctx, hipGetLastError());
     if (models_out) {

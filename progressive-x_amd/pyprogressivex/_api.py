@@ -363,7 +363,7 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
 
 
 def _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
-    """findPlanes / findSpheres / findCircles / findLines3D / findCylinders / findCones / findPrimitives behind their signatures: the estimator says the point dimension (its
+    """findPlanes / findSpheres / findCircles / findLines3D / findCylinders / findCones / findTori / findPrimitives behind their signatures: the estimator says the point dimension (its
     model type's), the sample size (= the fewest points accepted) and the columns of a model.  Only an estimator with a radius takes
     radius_range (its takes_radius_range says so): it goes to the estimator, and the estimator's context_setup puts its per-call state on
     the context."""
@@ -568,6 +568,45 @@ def findCones(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_c
         raise ValueError("normals should be an array with dims [n,3], one row per point")
     est.normals = nrm
     return _find_primitive(est, points, weights, _angle_range(angle_range), sampler_id, do_logging, neighborhood_ball_radius,
+                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
+                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
+                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
+                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
+                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
+                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+
+
+def findTori(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
+             neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
+             minimum_point_number=10, maximum_model_number=-1, sampler_id=3, scoring_exponent=2,
+             do_logging=False, *, radius_range=(0.0, np.inf), major_radius_range=(0.0, np.inf), seed=None, max_outer_iterations=10,
+             neighborhood="flann_like", local_optimization="auto", labeling_l0="greedy", distributed=None, sampler_rng="numpy", trace=None,
+             pearl_abs="double", refit_solver="lapack"):
+    """Multi-torus fitting of an oriented 3-D point cloud: pipe elbows, fillets, rings, handles, tyres (no reference counterpart:
+    findCones' pipeline with a 4-point solver on points with normals, two hypotheses per sample, and a Gauss-Newton refit on seven
+    parameters).  points [n, 3], normals [n, 3] (required): one surface normal per point, as a normal estimator gives them
+    (estimateNormals(points) computes them from the cloud itself) - they may be unsigned and need not be unit length; only the minimal
+    solver reads them, as LINES: the axis of a surface of revolution meets every one of its normals, and a sample whose four normal
+    lines have no common transversal gives no hypothesis.  That makes the solver more sensitive to the normals than the cylinder's and
+    the cone's: with normals tilted by 5 degrees few all-inlier samples give a usable torus.  Returns (tori[K, 8]
+    float64 (cx, cy, cz, dx, dy, dz, R, r): the centre, a unit axis direction (its sign means nothing), the major radius from the axis
+    to the tube's centre circle and the minor (tube) radius; labels[n] int32) in findPlanes' labelling convention.  The model is a
+    whole RING torus, R > r > 0: it says nothing about which arc of an elbow exists, and spindle or horn tori are never returned.
+    threshold bounds abs(sqrt((rho - R)^2 + h^2) - r) in the cloud's units, with h = (x - c) . d the height over the centre plane and
+    rho = |(x - c) x d| the distance from the axis: the distance from the torus' surface.  radius_range=(rmin, rmax) bounds the tube
+    radius r and major_radius_range=(Rmin, Rmax) the major radius R (both keyword-only; default: any) of hypotheses and refits.
+    `weights` [n], when given, weight the least-squares refits.  Sampler ids, the remaining arguments and their caveats are
+    findCylinders'; recovery on make_tori scenes is reported, not tuned, in DESIGN.md 4.15."""
+    est = _estimators.TorusEstimator()
+    points, nrm = _as_f64(points), _as_f64(normals)
+    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
+        raise ValueError("normals should be an array with dims [n,3], one row per point")
+    est.normals = nrm
+    try:
+        est.major_radius_range = _radius_range(major_radius_range)
+    except ValueError as e:
+        raise ValueError(str(e).replace("radius_range", "major_radius_range")) from None
+    return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
                            threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
                            maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
                            minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,

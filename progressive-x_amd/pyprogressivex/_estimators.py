@@ -849,6 +849,158 @@ class OrientedPrimitiveEstimator(PrimitiveEstimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Torus (findTori; no reference counterpart): 4-point solver on oriented points with two slots, Gauss-Newton refit on seven parameters
+# ---------------------------------------------------------------------------------------------------------------------
+class TorusEstimator(Estimator):
+    """Model (c[3], d[3], R, r): the centre, a unit axis direction, the major radius (axis to the tube's centre circle) and the minor
+    (tube) radius of a ring torus, R > r > 0.  `normals` [n, 3] (per point, neither unit nor consistently signed) are read by the
+    minimal solver alone, as lines.  `radius_range` bounds r and `major_radius_range` bounds R, of hypotheses and refits.
+
+    nonminimal_sample_size is 7, the number of parameters of the chart (centre 3, direction 2, two radii): with fewer points the 7x7
+    normal matrix is singular for every configuration.  As for cylinders and cones it is not raised above that: the refit always starts
+    from a model that was scored."""
+    model_type = _lib.TORUS3D
+    sample_size = 4
+    nonminimal_sample_size = 7
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU, two slots per sample (same operation order as minimal())
+    device_slots = 2
+    cols = 8
+    takes_radius_range = True
+    radius_range = (0.0, np.inf)
+    major_radius_range = (0.0, np.inf)
+    normals = None             # [n, 3] float64, in the points' order (findTori sets it)
+
+    def context_setup(self, ctx):
+        ctx.set_radius_range(*self.radius_range)
+        ctx.set_major_radius_range(*self.major_radius_range)
+        ctx.set_normals(self.normals)
+
+    def _in_range(self, R, r):
+        return ((r >= self.radius_range[0]) & (r <= self.radius_range[1]) & (R >= self.major_radius_range[0]) &
+                (R <= self.major_radius_range[1]) & (R > r))
+
+    def minimal_rows(self, pts, samples):
+        """samples [S, 4] -> [2 S, 8], row 2 s + j the torus of slot j or NaN: bitwise csrc/solve.hip's solve_minimal for tori, whose
+        comment states the operation order (the two transversals of the four normal lines by a quadratic in s, the axis through
+        a = p0 + s n0 and b = p1 + t n1, the circle through (h_k, rho_k) of samples 0, 1, 2 by the 3-point circle solver's arithmetic)."""
+        samples = np.asarray(samples)
+        S = len(samples)
+        pts = np.asarray(pts, dtype=np.float64)
+        nrm = np.asarray(self.normals, dtype=np.float64)
+        # every array below is over the 2 S rows: sample s twice, slot 0 then slot 1
+        rows = np.repeat(np.arange(S), 2)
+        slot = np.tile(np.arange(2), S)
+        comp = lambda x: [x[:, 0], x[:, 1], x[:, 2]]                   # noqa: E731
+        dot = lambda x, y: (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]   # noqa: E731  (on component lists)
+        p = [pts[samples[rows, i]] for i in range(4)]
+        n = [nrm[samples[rows, i]] for i in range(4)]
+        with np.errstate(all="ignore"):
+            q = comp(p[1] - p[0])
+            n0, n1 = comp(n[0]), comp(n[1])
+            A, B, C, D = [], [], [], []
+            for i in (2, 3):
+                g = p[i] - p[0]
+                X = _cross3(n[i], g)
+                Y = _cross3(n[i], n[0])
+                A.append(-dot(n1, Y))
+                B.append(-(dot(q, Y) + dot(n0, X)))
+                C.append(dot(n1, X))
+                D.append(dot(q, X))
+            qa = B[1] * A[0] - A[1] * B[0]
+            qb = ((B[1] * C[0] - A[1] * D[0]) - C[1] * B[0]) + D[1] * A[0]
+            qc = D[1] * C[0] - C[1] * D[0]
+            disc = qb * qb - (4.0 * qa) * qc
+            sq = np.sqrt(disc)
+            s = np.where(slot == 0, (-qb + sq) / (2.0 * qa), (-qb - sq) / (2.0 * qa))
+            den = A[0] * s + C[0]
+            t = -(B[0] * s + D[0]) / den
+            a = [p[0][:, k] + s * n0[k] for k in range(3)]
+            b = [p[1][:, k] + t * n1[k] for k in range(3)]
+            Dv = [b[k] - a[k] for k in range(3)]
+            ln = np.sqrt(dot(Dv, Dv))
+            d = [Dv[k] / ln for k in range(3)]
+            h, rho = [], []
+            for k in range(3):
+                e = [p[k][:, j] - a[j] for j in range(3)]
+                h.append(dot(e, d))
+                c0 = e[1] * d[2] - e[2] * d[1]
+                c1 = -(e[0] * d[2] - e[2] * d[0])
+                c2 = e[0] * d[1] - e[1] * d[0]
+                rho.append(np.sqrt((c0 * c0 + c1 * c1) + c2 * c2))
+            a10, a11, a20, a21 = h[1] - h[0], rho[1] - rho[0], h[2] - h[0], rho[2] - rho[0]
+            g1, g2 = 0.5 * (a10 * a10 + a11 * a11), 0.5 * (a20 * a20 + a21 * a21)
+            det = a10 * a21 - a11 * a20
+            z0, z1 = (g1 * a21 - g2 * a11) / det, (a10 * g2 - a20 * g1) / det
+            r = np.sqrt(z0 * z0 + z1 * z1)
+            hc, R = h[0] + z0, rho[0] + z1
+            c = [a[k] + hc * d[k] for k in range(3)]
+            models = np.column_stack([c[0], c[1], c[2], d[0], d[1], d[2], R, r])
+            ok = ((disc >= 0) & (qa != 0) & (den != 0) & (ln > 0) & (det != 0) & np.isfinite(models).all(axis=1) & self._in_range(R, r))
+        models[~ok] = np.nan
+        return models
+
+    def minimal(self, pts, samples):
+        """samples [S, 4] -> (tori [H, 8], sample of each [H]): the rows of minimal_rows that hold a model, in its order"""
+        models = self.minimal_rows(pts, samples)
+        ok = ~np.isnan(models[:, 0])
+        return models[ok], np.nonzero(ok)[0] // 2
+
+    def _fit_many(self, gram, B, inits, iterations=10):
+        """Geometric least squares, sum w (sqrt((rho - R)^2 + h^2) - r)^2 with rho = |(x - c) x d| and h = (x - c) . d, by Gauss-Newton
+        from `inits` in the shape of ConeEstimator._fit_many: at most 10 iterations on [B, ...] stacks, each ONE Gram request
+        (GRAM_TORUS_GN, weight power 1) at params (c, d, R, r, u) with u = _cylinder_frame(d) and v = d x u.  The rows are (J, f) with
+        J = df / d(alpha, beta, gamma, delta, eta, dR, dr) in the chart c + alpha u + beta v + gamma d, normalise(d + delta u + eta v),
+        R + dR, r + dr (csrc/fit.hip GenTorusGn), so step = pinv(J^T J)(-J^T f) with the cut-off 7 eps, then that update; an item stops
+        at |step| < 1e-12.  An item fails without an init, with fewer than 7 points, with a point on its axis or spine (bad) or with
+        non-finite sums.  A model that is not finite, has r <= 0 or R <= r, or whose radii lie outside radius_range /
+        major_radius_range is dropped: Gauss-Newton from a ring torus has no reason to leave r > 0, R > 0, and a model that did is
+        no ring torus (negating r or R is not a symmetry of the residual)."""
+        out = [[] for _ in range(B)]
+        have = np.array([ini is not None for ini in inits], dtype=bool)
+        if not have.any():
+            return out
+        m = np.zeros((B, 8))
+        m[:, 5] = 1.0
+        m[:, 6], m[:, 7] = 2.0, 1.0
+        for b in np.nonzero(have)[0]:
+            m[b] = np.asarray(inits[b], dtype=np.float64).reshape(8)
+        with np.errstate(all="ignore"):
+            m[:, 3:6] /= np.linalg.norm(m[:, 3:6], axis=1)[:, None]
+        failed = ~have | ~np.isfinite(m).all(axis=1)
+        running = ~failed
+        for _ in range(iterations):
+            act = np.nonzero(running)[0]
+            if act.size == 0:
+                break
+            u = _cylinder_frame(m[act, 3:6])
+            G, cnt, bad = gram(_lib.GRAM_TORUS_GN, np.column_stack([m[act], u]), True, 1, act)
+            A, rhs = G[:, :7, :7], -G[:, :7, 7]
+            ok = (np.asarray(bad) == 0) & (np.asarray(cnt) >= 7) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(rhs).all(axis=1)
+            failed[act[~ok]] = True
+            running[act[~ok]] = False
+            if not ok.any():
+                break
+            act, A, rhs, u = act[ok], A[ok], rhs[ok], u[ok]
+            d = m[act, 3:6]
+            v = np.cross(d, u)
+            step = np.einsum("bij,bj->bi", np.linalg.pinv(A, rcond=7 * np.finfo(np.float64).eps), rhs)
+            m[act, 0:3] += step[:, 0:1] * u + step[:, 1:2] * v + step[:, 2:3] * d
+            d = d + step[:, 3:4] * u + step[:, 4:5] * v
+            m[act, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
+            m[act, 6] += step[:, 5]
+            m[act, 7] += step[:, 6]
+            fin = np.isfinite(m[act]).all(axis=1)
+            failed[act[~fin]] = True
+            running[act[~fin]] = False
+            running[act[np.linalg.norm(step, axis=1) < 1e-12]] = False
+        for b in np.nonzero(~failed)[0]:
+            model = m[b]
+            if np.isfinite(model).all() and model[7] > 0 and bool(self._in_range(model[6], model[7])):
+                out[b] = [model.copy()]
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 2-D circle: the round family's other member
 # ---------------------------------------------------------------------------------------------------------------------
 class CircleEstimator(RoundEstimator):
@@ -1514,6 +1666,7 @@ ESTIMATORS = {
     "line3d": Line3DEstimator,
     "cylinder": CylinderEstimator,
     "cone": ConeEstimator,
+    "torus": TorusEstimator,
     "primitive": PrimitiveEstimator,
     "oriented_primitive": OrientedPrimitiveEstimator,
     "vanishing_point": VanishingPointEstimator,

@@ -24,12 +24,13 @@ CYLINDER3D = 14                # (nor 13)
 CONE3D = 16                    # (nor 15)
 PRIMITIVE3D = 18               # (nor 17): the union of PLANE3D, SPHERE3D, CYLINDER3D and CONE3D, model (class, q0 .. q7)
 ORIENTED_PRIMITIVE3D = 20      # (nor 19): PRIMITIVE3D whose inliers must also agree with the resident normals (set_normal_tolerance)
+TORUS3D = 22                   # (nor 21)
 # per model type: (doubles per point, doubles per model, minimal sample size, hypotheses per sample of the device solver);
 # sample size 0 = no device solver (pgx_solve_minimal fails).  The numbers of csrc/residuals.hip.h; tests/test_abi.py compares.
 MODEL_TABLE = {LINE2D: (2, 3, 2, 1), HOMOGRAPHY: (4, 9, 4, 1), FUNDAMENTAL: (4, 9, 7, 3), PNP: (5, 12, 3, 4),
                VANISHING_POINT: (4, 3, 2, 1), HOMOGRAPHY_SYM: (4, 18, 0, 0), PLANE3D: (3, 4, 3, 1), SPHERE3D: (3, 4, 4, 1),
                CIRCLE2D: (2, 3, 3, 1), LINE3D: (3, 6, 2, 1), CYLINDER3D: (3, 7, 2, 1), CONE3D: (3, 8, 3, 1),
-               PRIMITIVE3D: (3, 9, 4, 4), ORIENTED_PRIMITIVE3D: (3, 9, 4, 4)}
+               PRIMITIVE3D: (3, 9, 4, 4), ORIENTED_PRIMITIVE3D: (3, 9, 4, 4), TORUS3D: (3, 8, 4, 2)}
 POINT_DIM = {t: row[0] for t, row in MODEL_TABLE.items()}
 PARAM_DIM = {t: row[1] for t, row in MODEL_TABLE.items()}
 FIXED_ONE = float(1 << 32)
@@ -42,7 +43,7 @@ ABI_SYMBOLS = [
     "pgx_set_points", "pgx_set_compound", "pgx_get_compound",
     "pgx_score", "pgx_score_upload", "pgx_score_launch", "pgx_score_fetch", "pgx_score_algorithmic_bytes", "pgx_score_stats", "pgx_score_profile", "pgx_score_kernel_times", "pgx_score_debug_fetch", "pgx_score_debug_geometry",
     "pgx_preference", "pgx_get_preference", "pgx_compound_update",
-    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_primitive_classes", "pgx_set_normals", "pgx_set_normal_tolerance",
+    "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_major_radius_range", "pgx_set_primitive_classes", "pgx_set_normals", "pgx_set_normal_tolerance",
     "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals",
     "pgx_bucket", "pgx_residual_sum", "pgx_gc_labeling", "pgx_gc_inliers", "pgx_epipolar_support", "pgx_gram_batch", "pgx_gram_labels", "pgx_residual_sums", "pgx_pnp_refine_batch",
     "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_barrier", "pgx_comm_allreduce_max_f64",
@@ -53,8 +54,8 @@ ABI_SYMBOLS = [
 
 
 GRAPH_KNN_IN_BALL, GRAPH_BALL, GRAPH_KNN = 0, 1, 2
-GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE, GRAM_CYL_GN, GRAM_CONE_GN = 0, 1, 2, 3, 4, 5, 6, 7, 8
-GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5, GRAM_CIRCLE: 4, GRAM_CYL_GN: 6, GRAM_CONE_GN: 7}   # GRAM_AFFINE: point dimension + 1
+GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE, GRAM_CYL_GN, GRAM_CONE_GN, GRAM_TORUS_GN = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5, GRAM_CIRCLE: 4, GRAM_CYL_GN: 6, GRAM_CONE_GN: 7, GRAM_TORUS_GN: 8}   # GRAM_AFFINE: point dimension + 1
 
 
 _TRIU = {}
@@ -283,8 +284,12 @@ class Context:
         self._w_obj = weights
 
     def set_radius_range(self, rmin=0.0, rmax=float("inf")):
-        """pgx_set_radius_range: the radii the 4-point sphere, the 3-point circle and the 2-point cylinder solver accept, and the range of sin(half-angle) the 3-point cone solver accepts (context state; [0, inf] at creation)"""
+        """pgx_set_radius_range: the radii the 4-point sphere, the 3-point circle and the 2-point cylinder solver accept, and the range of sin(half-angle) the 3-point cone solver accepts, and the minor (tube) radii of the 4-point torus solver (context state; [0, inf] at creation)"""
         self._ck(self._lib.pgx_set_radius_range(self._h, C.c_double(float(rmin)), C.c_double(float(rmax))), "pgx_set_radius_range")
+
+    def set_major_radius_range(self, Rmin=0.0, Rmax=float("inf")):
+        """pgx_set_major_radius_range: the major radii (axis to the tube's centre circle) the 4-point torus solver accepts (context state; [0, inf] at creation)"""
+        self._ck(self._lib.pgx_set_major_radius_range(self._h, C.c_double(float(Rmin)), C.c_double(float(Rmax))), "pgx_set_major_radius_range")
 
     def set_primitive_classes(self, class_mask=15, smin=0.0, smax=1.0):
         """pgx_set_primitive_classes: the classes the mixed-primitive solver (PRIMITIVE3D) makes - bit 0 plane, 1 sphere, 2 cylinder, 3 cone, in
@@ -300,7 +305,7 @@ class Context:
 
     def set_normals(self, normals):
         """pgx_set_normals: per-point normals [n, 3] of the resident points, uploaded once and checked against n (None clears).  Only
-        the cylinder's, the cone's and the mixed-primitive minimal solvers read them - and, under ORIENTED_PRIMITIVE3D, every kernel that
+        the cylinder's, the cone's, the torus' and the mixed-primitive minimal solvers read them - and, under ORIENTED_PRIMITIVE3D, every kernel that
         evaluates the squared residual; they need be neither unit nor consistently oriented.  set_points invalidates them."""
         if normals is None or len(normals) == 0:
             self._ck(self._lib.pgx_set_normals(self._h, None, C.c_int64(0)), "pgx_set_normals")
@@ -537,7 +542,7 @@ class Context:
         return off, idx[:arcs], mult[:arcs]
 
     def solve_minimal(self, samples, fetch=True):
-        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone and the four slots of the mixed primitives from the resident normals, ...), generated from the
+        """pgx_solve_minimal: hypotheses of the device minimal solvers (2-point line, 2-segment vanishing point, 3-point plane, 4-point sphere, 3-point circle, 2-point 3-D line, 2-point cylinder, 3-point cone, the two slots of the 4-point torus and the four slots of the mixed primitives from the resident normals, ...), generated from the
         resident points straight into the resident hypothesis buffer (score_launch can follow).  NaN rows mark
         degenerate samples."""
         smp = _i32(samples)

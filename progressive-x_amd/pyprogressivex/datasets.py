@@ -274,6 +274,66 @@ def make_primitives(n_per=8000, n_outliers=32000, seed=0, n_each=1, sigma=0.01, 
     return pts, nrm, np.concatenate(cls).astype(np.int32), np.concatenate(inst).astype(np.int32), gt
 
 
+def make_tori(n_per_torus=8000, n_tori=6, n_outliers=48000, sigma=0.01, size=10.0, major_radius=(0.8, 2.0), minor_radius=(0.2, 0.5),
+              normal_noise_deg=5.0, seed=0, normals="synthetic"):
+    """findTori's workload: K ring tori with uniformly random unit axis directions, major radii R uniform in `major_radius` and minor
+    (tube) radii r uniform in `minor_radius` (max r < min R), each lying wholly inside the box [0, size]^3 (tori may cross); the
+    inliers of torus k are uniform on its surface - the angle phi about the axis is uniform and the tube angle theta is drawn with
+    density proportional to R + r cos(theta), the circumference at that angle, by rejection - with Gaussian noise of `sigma` along the
+    surface normal cos(theta) rhohat + sin(theta) d; their normals are those unit surface normals tilted by an angle uniform in
+    [0, normal_noise_deg] about a random axis orthogonal to them, each with a random sign.  The outliers are uniform in the box with
+    uniformly random unit normals.  Returns (points [n, 3], normals [n, 3] (unit), labels [n] (k + 1 = torus k, 0 = outlier),
+    gt_tori [K, 8] = (centre, unit axis direction, R, r)).  A pure function of the seed.  normals="estimated" returns, in place of
+    those synthetic normals, what estimateNormals(points) computes from the same points (k = 16 nearest neighbours, unsigned; needs
+    the GPU)."""
+    if normals not in ("synthetic", "estimated"):
+        raise ValueError('normals should be "synthetic" or "estimated"')
+    rng = np.random.default_rng(seed)
+    Rlo, Rhi = (float(v) for v in major_radius)
+    rlo, rhi = (float(v) for v in minor_radius)
+    if not (0.0 < rlo <= rhi < Rlo <= Rhi):
+        raise ValueError("major_radius and minor_radius should satisfy 0 < rmin <= rmax < Rmin <= Rmax")
+    if not 2.0 * (Rhi + rhi) <= size:
+        raise ValueError("the largest torus, 2 (Rmax + rmax) wide, should fit the box")
+    pts, nrm, labels, models = [], [], [], []
+    for k in range(n_tori):
+        d = rng.normal(size=3)
+        d /= np.linalg.norm(d)
+        R, r = rng.uniform(Rlo, Rhi), rng.uniform(rlo, rhi)
+        half = R * np.sqrt(np.maximum(0.0, 1.0 - d * d)) + r
+        centre = rng.uniform(half, size - half)
+        e1 = np.cross(d, rng.normal(size=3))
+        e1 /= np.linalg.norm(e1)
+        e2 = np.cross(d, e1)
+        theta = np.empty(0)
+        while theta.size < n_per_torus:
+            cand = rng.uniform(-np.pi, np.pi, n_per_torus)
+            theta = np.concatenate([theta, cand[rng.uniform(0.0, R + r, n_per_torus) < R + r * np.cos(cand)]])
+        theta = theta[:n_per_torus]
+        phi = rng.uniform(-np.pi, np.pi, n_per_torus)
+        rad = np.cos(phi)[:, None] * e1 + np.sin(phi)[:, None] * e2
+        ct, st = np.cos(theta)[:, None], np.sin(theta)[:, None]
+        nk0 = ct * rad + st * d
+        pts.append(centre + (R + r * ct) * rad + (r * st) * d + nk0 * rng.normal(0, sigma, n_per_torus)[:, None])
+        # tilt: rotate the normal by `ang` towards a random unit vector of its tangent plane, spanned by the tube's tangent and d x rad
+        ang = np.deg2rad(rng.uniform(0.0, normal_noise_deg, n_per_torus))
+        psi = rng.uniform(0.0, 2.0 * np.pi, n_per_torus)
+        tang = np.cos(psi)[:, None] * (ct * d - st * rad) + np.sin(psi)[:, None] * np.cross(d, rad)
+        nk = np.cos(ang)[:, None] * nk0 + np.sin(ang)[:, None] * tang
+        nrm.append(nk * rng.choice([-1.0, 1.0], n_per_torus)[:, None])
+        labels.append(np.full(n_per_torus, k + 1))
+        models.append(np.concatenate([centre, d, [R, r]]))
+    pts.append(rng.uniform(0, size, (n_outliers, 3)))
+    no = rng.normal(size=(n_outliers, 3))
+    nrm.append(no / np.linalg.norm(no, axis=1)[:, None])
+    labels.append(np.zeros(n_outliers, dtype=int))
+    pts, nrm = np.ascontiguousarray(np.vstack(pts)), np.ascontiguousarray(np.vstack(nrm))
+    if normals == "estimated":
+        from ._api import estimateNormals
+        nrm = estimateNormals(pts)
+    return pts, nrm, np.concatenate(labels).astype(np.int32), np.array(models).reshape(-1, 8)
+
+
 def make_spheres(n_per_sphere=8000, n_spheres=6, n_outliers=48000, sigma=0.01, size=10.0, radius=(0.3, 1.5), coverage=1.0, seed=0):
     """findSpheres' workload: K non-overlapping spheres with radii uniform in `radius` and centres inside the box [0, size]^3 (each
     sphere lies wholly inside it); the inliers of sphere k are uniform on its surface - or, with coverage < 1, on the cap of that
@@ -559,4 +619,4 @@ def misclassification_models(preferences, annotation, K_annot):
 MODEL_TYPES = dict(line=_lib.LINE2D, homography=_lib.HOMOGRAPHY, fundamental=_lib.FUNDAMENTAL, pnp=_lib.PNP,
                    vanishing_point=_lib.VANISHING_POINT, plane=_lib.PLANE3D, sphere=_lib.SPHERE3D, circle=_lib.CIRCLE2D,
                    line3d=_lib.LINE3D, cylinder=_lib.CYLINDER3D, cone=_lib.CONE3D, primitive=_lib.PRIMITIVE3D,
-                   oriented_primitive=_lib.ORIENTED_PRIMITIVE3D)
+                   oriented_primitive=_lib.ORIENTED_PRIMITIVE3D, torus=_lib.TORUS3D)
