@@ -1,4 +1,6 @@
-"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCones / findPrimitives / findOrientedPrimitives / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names / argument order / defaults / return layout /
+"""The five entry points of the reference's pybind11 module (and findPlanes / findSpheres / findLines3D / findCylinders / findCones /
+findPrimitives / findOrientedPrimitives / findCircles, the same pipeline on 3-D point clouds and 2-D point sets), same names /
+argument order / defaults / return layout /
 error messages (/root/reference/src/pyprogressivex/src/bindings.cpp:9-392 wrappers, :410-491 defaults) and the
 parameter plumbing of the problem drivers (/root/reference/src/pyprogressivex/src/progressivex_python.cpp:41-666),
 including their quirks: unknown sampler ids print to stderr and return zero models,
@@ -162,6 +164,17 @@ def _run(estimator, pts, graph_points, radius, sampler_factory, *, threshold, co
     return models, labeling, stats
 
 
+# the options of _run that every entry point takes under the same name
+_RUN_OPTIONS = ("threshold", "conf", "spatial_coherence_weight", "maximum_tanimoto_similarity", "max_iters", "minimum_point_number",
+                "maximum_model_number", "scoring_exponent", "seed", "max_outer_iterations", "neighborhood", "local_optimization",
+                "labeling_l0", "distributed", "sampler_rng", "trace", "pearl_abs", "refit_solver")
+
+
+def _run_options(args, **changed):
+    """_run's keyword options from an entry point's arguments (args = its locals()); `changed` replaces or adds some"""
+    return {**{name: args[name] for name in _RUN_OPTIONS}, **changed}
+
+
 def _stack(estimator, models, cols):
     rows = estimator.rows_per_model
     out = np.zeros((rows * len(models), cols), dtype=np.float64)
@@ -207,11 +220,7 @@ def findHomographies(corrs, w1, h1, w2, h2, threshold=4.0, conf=0.5, spatial_coh
     models, labels, _ = _run(est, corrs, corrs, neighborhood_ball_radius,
                              _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "pnapsac", 3: "napsac"}, corrs,
                                               (w1, h1, w2, h2), est.sample_size),
-                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                             scoring_exponent=scoring_exponent, do_logging=False, seed=seed,
-                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                             **_run_options(locals()))
     return _stack(est, models, 3), labels
 
 
@@ -241,11 +250,7 @@ def findTwoViewMotions(corrs, w1, h1, w2, h2, threshold=4.0, conf=0.5, spatial_c
     models, labels, _ = _run(est, corrs, corrs, neighborhood_ball_radius,
                              _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "pnapsac", 3: "napsac"}, corrs,
                                               (w1, h1, w2, h2), est.sample_size),
-                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                             scoring_exponent=2, do_logging=False, seed=seed,
-                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                             **_run_options(locals(), scoring_exponent=2))
     return _stack(est, models, 3), labels
 
 
@@ -268,12 +273,7 @@ def findVanishingPoints(lines, weights, w, h, threshold=4.0, conf=0.5, spatial_c
     est = _estimators.VanishingPointEstimator()
     models, labels, _ = _run(est, lines, lines, neighborhood_ball_radius,
                              _sampler_factory(sampler_id, {0: "uniform", 1: "prosac"}),
-                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                             scoring_exponent=scoring_exponent, do_logging=bool(do_logging),     # :401
-                             weights=_weights(weights, n), seed=seed, max_outer_iterations=max_outer_iterations,
-                             neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                             **_run_options(locals(), do_logging=bool(do_logging), weights=_weights(weights, n)))     # :401
     return _stack(est, models, 3), labels
 
 
@@ -295,11 +295,7 @@ def findLines(points, weights, w, h, threshold=2.0, conf=0.5, spatial_coherence_
     models, labels, _ = _run(est, points, points, neighborhood_ball_radius,
                              _sampler_factory(sampler_id, {0: "uniform", 1: "prosac", 2: "napsac"},
                                               prosac_sample_size=4),     # the HOMOGRAPHY sample size (quirk, :463)
-                             threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                             scoring_exponent=scoring_exponent, do_logging=False, seed=seed,
-                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                             **_run_options(locals()))
     return _stack(est, models, 3), labels
 
 
@@ -336,6 +332,16 @@ def _radius_range(radius_range):
     return rmin, rmax
 
 
+def _oriented(est, points, normals):
+    """the normals check of the calls on oriented points: normals [n, 3], one row per point, become est.normals; returns the points
+    as float64 (their own checks are _point_cloud's)"""
+    points, nrm = _as_f64(points), _as_f64(normals)
+    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
+        raise ValueError("normals should be an array with dims [n,3], one row per point")
+    est.normals = nrm
+    return points
+
+
 def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
                neighborhood_ball_radius=0.5, maximum_tanimoto_similarity=0.4, max_iters=1000,
                minimum_point_number=10, maximum_model_number=-1, sampler_id=2, scoring_exponent=2,
@@ -354,12 +360,7 @@ def findPlanes(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence
     six, 2 three to five - DESIGN.md 4.5); minimum_point_number has to exceed the outliers a slab of width 3 x threshold
     holds, or spurious planes through the outliers are accepted."""
     return _find_primitive(_estimators.PlaneEstimator(), points, weights, None, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, radius, **run_kw):
@@ -394,12 +395,7 @@ def findSpheres(points, weights=None, threshold=0.05, conf=0.5, spatial_coherenc
 proposal starts from the first points): shuffle a cloud that comes in scan order.  Like findPlanes, minimum_point_number has to exceed the
     outliers a shell of width 3 x threshold holds."""
     return _find_primitive(_estimators.SphereEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def findCircles(points, weights=None, threshold=2.0, conf=0.5, spatial_coherence_weight=0.0,
@@ -418,12 +414,7 @@ def findCircles(points, weights=None, threshold=2.0, conf=0.5, spatial_coherence
     points): shuffle a set that comes in contour order.  minimum_point_number has to exceed the outliers an annulus of width
     3 x threshold holds."""
     return _find_primitive(_estimators.CircleEstimator(), points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def findLines3D(points, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
@@ -446,12 +437,7 @@ def findLines3D(points, weights=None, threshold=0.05, conf=0.5, spatial_coherenc
     or spurious lines through the outliers or between two lines are accepted.  It also has an upper side: the run stops when fewer
     inliers than that are predicted as still unseen, and in the same measurement no sampler returned all six lines with n / 40."""
     return _find_primitive(_estimators.Line3DEstimator(), points, weights, None, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def estimateNormals(points, k=16, radius=None, viewpoint=None, return_curvature=False):
@@ -520,17 +506,9 @@ def findCylinders(points, normals, weights=None, threshold=0.05, conf=0.5, spati
     collects, or spurious cylinders are accepted - an rmax keeps that shell small; it also has the upper side findLines3D describes:
     the run stops when fewer inliers than that are predicted as still unseen."""
     est = _estimators.CylinderEstimator()
-    points, nrm = _as_f64(points), _as_f64(normals)
-    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
-        raise ValueError("normals should be an array with dims [n,3], one row per point")
-    est.normals = nrm
+    points = _oriented(est, points, normals)
     return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def _angle_range(angle_range):
@@ -563,17 +541,9 @@ def findCones(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_c
     the least-squares refits.  Sampler ids, the remaining arguments and their caveats are findCylinders'; recovery on make_cones
     scenes is reported, not tuned, in DESIGN.md 4.12."""
     est = _estimators.ConeEstimator()
-    points, nrm = _as_f64(points), _as_f64(normals)
-    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
-        raise ValueError("normals should be an array with dims [n,3], one row per point")
-    est.normals = nrm
+    points = _oriented(est, points, normals)
     return _find_primitive(est, points, weights, _angle_range(angle_range), sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def findTori(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
@@ -598,21 +568,13 @@ def findTori(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_co
     `weights` [n], when given, weight the least-squares refits.  Sampler ids, the remaining arguments and their caveats are
     findCylinders'; recovery on make_tori scenes is reported, not tuned, in DESIGN.md 4.15."""
     est = _estimators.TorusEstimator()
-    points, nrm = _as_f64(points), _as_f64(normals)
-    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
-        raise ValueError("normals should be an array with dims [n,3], one row per point")
-    est.normals = nrm
+    points = _oriented(est, points, normals)
     try:
         est.major_radius_range = _radius_range(major_radius_range)
     except ValueError as e:
         raise ValueError(str(e).replace("radius_range", "major_radius_range")) from None
     return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 PRIMITIVE_CLASSES = dict(_estimators.PRIMITIVE_CLASSES)   # name -> class number (column 0 of findPrimitives' models)
@@ -643,18 +605,10 @@ def findPrimitives(points, normals, weights=None, threshold=0.05, conf=0.5, spat
     the remaining arguments are findCones'.  What the call recovers on make_primitives scenes, and what the four single-class calls
     find on the same scenes, is reported, not tuned, in DESIGN.md 4.13."""
     est = _estimators.PrimitiveEstimator(classes)
-    points, nrm = _as_f64(points), _as_f64(normals)
-    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
-        raise ValueError("normals should be an array with dims [n,3], one row per point")
-    est.normals = nrm
+    points = _oriented(est, points, normals)
     est.sine_range = _angle_range(angle_range)
     return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def findOrientedPrimitives(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,
@@ -677,18 +631,10 @@ def findOrientedPrimitives(points, normals, weights=None, threshold=0.05, conf=0
     the same least-squares fits on the compatible inliers, and the distance sums PEARL compares before and after a refit ignore the
     normals (they are the quantity the refits minimise)."""
     est = _estimators.OrientedPrimitiveEstimator(classes, normal_tolerance)
-    points, nrm = _as_f64(points), _as_f64(normals)
-    if nrm.ndim != 2 or nrm.shape[1] != 3 or (points.ndim == 2 and nrm.shape[0] != points.shape[0]):
-        raise ValueError("normals should be an array with dims [n,3], one row per point")
-    est.normals = nrm
+    points = _oriented(est, points, normals)
     est.sine_range = _angle_range(angle_range)
     return _find_primitive(est, points, weights, radius_range, sampler_id, do_logging, neighborhood_ball_radius,
-                           threshold=threshold, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                           maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                           minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                           scoring_exponent=scoring_exponent, seed=seed, max_outer_iterations=max_outer_iterations,
-                           neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0,
-                           distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                           **_run_options(locals()))
 
 
 def find6DPoses(x1y1, x2y2z2, K, threshold=4.0, conf=0.90, spatial_coherence_weight=0.1,
@@ -732,9 +678,5 @@ def find6DPoses(x1y1, x2y2z2, K, threshold=4.0, conf=0.90, spatial_coherence_wei
     factory.needs_graph = False
 
     models, labels, _ = _run(est, normalized, raw, neighborhood_ball_radius, factory,
-                             threshold=threshold / f, conf=conf, spatial_coherence_weight=spatial_coherence_weight,
-                             maximum_tanimoto_similarity=maximum_tanimoto_similarity, max_iters=max_iters,
-                             minimum_point_number=minimum_point_number, maximum_model_number=maximum_model_number,
-                             scoring_exponent=int(scoring_exponent), do_logging=False, seed=seed,
-                             max_outer_iterations=max_outer_iterations, neighborhood=neighborhood, local_optimization=local_optimization, labeling_l0=labeling_l0, distributed=distributed, sampler_rng=sampler_rng, trace=trace, pearl_abs=pearl_abs, refit_solver=refit_solver)
+                             **_run_options(locals(), threshold=threshold / f, scoring_exponent=int(scoring_exponent)))
     return _stack(est, models, 4), labels

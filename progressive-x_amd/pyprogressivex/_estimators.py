@@ -374,8 +374,39 @@ class SphereEstimator(RoundEstimator):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Cylinder (findCylinders; no reference counterpart): 2-point solver on oriented points, Gauss-Newton refit on five parameters
+# The iterative refits (cylinder, cone, torus, PnP): the one Gauss-Newton loop, and what the three axial types share besides it
 # ---------------------------------------------------------------------------------------------------------------------
+def _gauss_newton(gram, kind, wpow, npar, min_count, cutoff, failed, params, update, iterations):
+    """The Gauss-Newton loop of the cylinder's, the cone's, the torus' and PnP's `_fit_many`, on B items at once.  `failed` [B] bool
+    marks the items that do not start (it is updated in place and returned); the others run.  Per iteration ONE Gram request for the
+    running items `act`, gram(kind, params(act), True, wpow, act): the rows are (J, f), so the sums hold the normal matrix
+    A = G[:npar, :npar] and the right-hand side -G[:npar, npar].  An item fails with a point that has no row (bad), with fewer than
+    min_count points or with non-finite sums; the others take step = pinv(A) rhs with singular values below cutoff eps s_max dropped,
+    and update(act, step, prm), prm the parameter rows that were sent for them, applies it to the caller's state and returns which
+    of the new iterates are finite.  An item whose iterate is not finite fails at once; one with |step| < 1e-12 stops.  A request
+    holds exactly the items still running, so an item's iterates do not depend on its neighbours."""
+    running = ~failed
+    for _ in range(iterations):
+        act = np.nonzero(running)[0]
+        if act.size == 0:
+            break
+        prm = params(act)
+        G, cnt, bad = gram(kind, prm, True, wpow, act)
+        A, rhs = G[:, :npar, :npar], -G[:, :npar, npar]
+        ok = (np.asarray(bad) == 0) & (np.asarray(cnt) >= min_count) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(rhs).all(axis=1)
+        failed[act[~ok]] = True
+        running[act[~ok]] = False
+        if not ok.any():
+            break
+        act = act[ok]
+        step = np.einsum("bij,bj->bi", np.linalg.pinv(A[ok], rcond=cutoff * np.finfo(np.float64).eps), rhs[ok])
+        fin = update(act, step, prm[ok])
+        failed[act[~fin]] = True
+        running[act[~fin]] = False
+        running[act[np.linalg.norm(step, axis=1) < 1e-12]] = False
+    return failed
+
+
 def _cylinder_frame(d):
     """The one rule for the chart's u, [B, 3] unit directions d -> [B, 3]: the coordinate axis of d's smallest-magnitude component (the
     first of equals) crossed with d, normalised.  That axis is the one farthest from d, so |axis x d| >= sqrt(2 / 3)."""
@@ -385,7 +416,52 @@ def _cylinder_frame(d):
     return u / np.linalg.norm(u, axis=1)[:, None]
 
 
-class CylinderEstimator(Estimator):
+def _axial_start(inits, blank):
+    """The start of a Gauss-Newton refit of models (point[3], d[3], ...): ([B, len(blank)] rows, failed [B]).  An item without an
+    init holds `blank` and fails; d is normalised; the caller fails the rows that are not finite once it has prepared them."""
+    m = np.tile(np.asarray(blank, dtype=np.float64), (len(inits), 1))
+    for b, ini in enumerate(inits):
+        if ini is not None:
+            m[b] = np.asarray(ini, dtype=np.float64).reshape(len(blank))
+    with np.errstate(all="ignore"):
+        m[:, 3:6] /= np.linalg.norm(m[:, 3:6], axis=1)[:, None]
+    return m, np.array([ini is None for ini in inits], dtype=bool)
+
+
+def _axial_params(m, act):
+    """the parameter rows (model, u) of a GRAM_CYL_GN / GRAM_CONE_GN / GRAM_TORUS_GN request, u = _cylinder_frame(d)"""
+    return np.column_stack([m[act], _cylinder_frame(m[act, 3:6])])
+
+
+def _axial_update(m, act, u, across, along, turn):
+    """The chart's step on the axis of the rows m[act], in the frame u, v = d x u: the point moves by across[0] u + across[1] v
+    (+ along d, if given), the direction becomes normalise(d + turn[0] u + turn[1] v).  across, along and turn are [len(act), k]
+    columns of the step."""
+    d = m[act, 3:6]
+    v = np.cross(d, u)
+    shift = across[:, 0:1] * u + across[:, 1:2] * v
+    m[act, 0:3] += shift if along is None else shift + along * d
+    d = d + turn[:, 0:1] * u + turn[:, 1:2] * v
+    m[act, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
+
+
+class OrientedEstimator(Estimator):
+    """What the cylinder, the cone and the torus share besides the refit's loop: a device solver that reads per-point `normals`, and a
+    `radius_range` that bounds hypotheses and refits (the device solver reads it from pgx_set_radius_range)."""
+    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
+    takes_radius_range = True
+    radius_range = (0.0, np.inf)
+    normals = None             # [n, 3] float64, in the points' order (the entry point sets it)
+
+    def context_setup(self, ctx):
+        ctx.set_radius_range(*self.radius_range)
+        ctx.set_normals(self.normals)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Cylinder (findCylinders; no reference counterpart): 2-point solver on oriented points, Gauss-Newton refit on five parameters
+# ---------------------------------------------------------------------------------------------------------------------
+class CylinderEstimator(OrientedEstimator):
     """Model (p[3], d[3], r): a point on the axis, a unit direction, a radius.  `normals` [n, 3] (per point, neither unit nor
     consistently signed) are read by the minimal solver alone; `radius_range` bounds the radii of hypotheses and refits.
 
@@ -396,15 +472,7 @@ class CylinderEstimator(Estimator):
     model_type = _lib.CYLINDER3D
     sample_size = 2
     nonminimal_sample_size = 5
-    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
     cols = 7
-    takes_radius_range = True
-    radius_range = (0.0, np.inf)
-    normals = None             # [n, 3] float64, in the points' order (findCylinders sets it)
-
-    def context_setup(self, ctx):
-        ctx.set_radius_range(*self.radius_range)
-        ctx.set_normals(self.normals)
 
     def _in_range(self, r):
         return (r >= self.radius_range[0]) & (r <= self.radius_range[1])
@@ -434,7 +502,7 @@ class CylinderEstimator(Estimator):
         return models[ok], np.nonzero(ok)[0]
 
     def _fit_many(self, gram, B, inits, iterations=10):
-        """Geometric least squares, sum w (|(x - p) x d| - r)^2, by Gauss-Newton from `inits` in the shape of PnPEstimator._fit_many:
+        """Geometric least squares, sum w (|(x - p) x d| - r)^2, by Gauss-Newton from `inits` (the loop is _gauss_newton's):
         at most 10 iterations on [B, ...] stacks, each ONE Gram request (GRAM_CYL_GN, weight power 1) at params (p, d, r, u) with
         u = _cylinder_frame(d) and v = d x u.  The rows are (J, f) with J = df / d(alpha, beta, gamma, eta, rho) in the chart
         p + alpha u + beta v, normalise(d + gamma u + eta v), r + rho (csrc/fit.hip GenCylGn), so delta = pinv(J^T J)(-J^T f) with the
@@ -443,41 +511,15 @@ class CylinderEstimator(Estimator):
         of the selection's weighted mean (one GRAM_AFFINE request), d is signed like Line3DEstimator's (its largest-magnitude
         component, the first of equals, positive); a model that is not finite or whose radius is outside radius_range is dropped."""
         out = [[] for _ in range(B)]
-        have = np.array([ini is not None for ini in inits], dtype=bool)
-        if not have.any():
-            return out
-        m = np.zeros((B, 7))
-        m[:, 5] = 1.0
-        for b in np.nonzero(have)[0]:
-            m[b] = np.asarray(inits[b], dtype=np.float64).reshape(7)
-        with np.errstate(all="ignore"):
-            m[:, 3:6] /= np.linalg.norm(m[:, 3:6], axis=1)[:, None]
-        failed = ~have | ~np.isfinite(m).all(axis=1)
-        running = ~failed
-        for _ in range(iterations):
-            act = np.nonzero(running)[0]
-            if act.size == 0:
-                break
-            u = _cylinder_frame(m[act, 3:6])
-            G, cnt, bad = gram(_lib.GRAM_CYL_GN, np.column_stack([m[act], u]), True, 1, act)
-            A, rhs = G[:, :5, :5], -G[:, :5, 5]
-            ok = (np.asarray(bad) == 0) & (np.asarray(cnt) >= 5) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(rhs).all(axis=1)
-            failed[act[~ok]] = True
-            running[act[~ok]] = False
-            if not ok.any():
-                break
-            act, A, rhs, u = act[ok], A[ok], rhs[ok], u[ok]
-            d = m[act, 3:6]
-            v = np.cross(d, u)
-            delta = np.einsum("bij,bj->bi", np.linalg.pinv(A, rcond=6 * np.finfo(np.float64).eps), rhs)
-            m[act, 0:3] += delta[:, 0:1] * u + delta[:, 1:2] * v
-            d = d + delta[:, 2:3] * u + delta[:, 3:4] * v
-            m[act, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
+        m, failed = _axial_start(inits, (0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0))
+        failed |= ~np.isfinite(m).all(axis=1)
+
+        def update(act, delta, prm):
+            _axial_update(m, act, prm[:, 7:10], delta[:, 0:2], None, delta[:, 2:4])
             m[act, 6] += delta[:, 4]
-            fin = np.isfinite(m[act]).all(axis=1)
-            failed[act[~fin]] = True
-            running[act[~fin]] = False
-            running[act[np.linalg.norm(delta, axis=1) < 1e-12]] = False
+            return np.isfinite(m[act]).all(axis=1)
+        _gauss_newton(gram, _lib.GRAM_CYL_GN, wpow=1, npar=5, min_count=5, cutoff=6, failed=failed, params=lambda act: _axial_params(m, act),
+                      update=update, iterations=iterations)
         rows = np.nonzero(~failed)[0]
         if rows.size == 0:
             return out
@@ -501,7 +543,7 @@ class CylinderEstimator(Estimator):
 # ---------------------------------------------------------------------------------------------------------------------
 # Cone (findCones; no reference counterpart): 3-point solver on oriented points, Gauss-Newton refit on six parameters
 # ---------------------------------------------------------------------------------------------------------------------
-class ConeEstimator(Estimator):
+class ConeEstimator(OrientedEstimator):
     """Model (a[3], d[3], c, s): the apex, a unit axis direction pointing into the nappe, the cosine and sine of the half-angle.
     `normals` [n, 3] (per point, neither unit nor consistently signed) are read by the minimal solver alone.  `radius_range` is the
     range of s = sin(half-angle) of hypotheses and refits, (sin theta_min, sin theta_max): a cone has no radius, and the context's radius
@@ -513,15 +555,8 @@ class ConeEstimator(Estimator):
     model_type = _lib.CONE3D
     sample_size = 3
     nonminimal_sample_size = 6
-    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU (same operation order as minimal())
     cols = 8
-    takes_radius_range = True
     radius_range = (0.0, 1.0)
-    normals = None             # [n, 3] float64, in the points' order (findCones sets it)
-
-    def context_setup(self, ctx):
-        ctx.set_radius_range(*self.radius_range)
-        ctx.set_normals(self.normals)
 
     def _in_range(self, s):
         return (s >= self.radius_range[0]) & (s <= self.radius_range[1])
@@ -579,8 +614,8 @@ class ConeEstimator(Estimator):
         return m
 
     def _fit_many(self, gram, B, inits, iterations=10):
-        """Geometric least squares, sum w (c rho - s h)^2 with rho = |(x - a) x d| and h = (x - a) . d, by Gauss-Newton from `inits` in
-        the shape of CylinderEstimator._fit_many: at most 10 iterations on [B, ...] stacks, each ONE Gram request (GRAM_CONE_GN, weight
+        """Geometric least squares, sum w (c rho - s h)^2 with rho = |(x - a) x d| and h = (x - a) . d, by Gauss-Newton from `inits`
+        (the loop is _gauss_newton's): at most 10 iterations on [B, ...] stacks, each ONE Gram request (GRAM_CONE_GN, weight
         power 1) at params (a, d, c, s, u) with u = _cylinder_frame(d) and v = d x u.  The rows are (J, f) with
         J = df / d(alpha, beta, gamma, delta, eta, tau) in the chart a + alpha u + beta v + gamma d, normalise(d + delta u + eta v),
         (c, s) <- normalise(c - tau s, s + tau c) (csrc/fit.hip GenConeGn), so step = pinv(J^T J)(-J^T f) with the cut-off 6 eps, then
@@ -589,43 +624,18 @@ class ConeEstimator(Estimator):
         unit with both entries positive); a model that is not finite, has c <= 0 or s <= 0, or whose s is outside radius_range is
         dropped."""
         out = [[] for _ in range(B)]
-        have = np.array([ini is not None for ini in inits], dtype=bool)
-        if not have.any():
-            return out
-        m = np.zeros((B, 8))
-        m[:, 5] = m[:, 6] = 1.0
-        for b in np.nonzero(have)[0]:
-            m[b] = np.asarray(inits[b], dtype=np.float64).reshape(8)
+        m, failed = _axial_start(inits, (0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 1.0, 0.0))
         with np.errstate(all="ignore"):
-            m[:, 3:6] /= np.linalg.norm(m[:, 3:6], axis=1)[:, None]
             m[:, 6:8] /= np.linalg.norm(m[:, 6:8], axis=1)[:, None]
-        failed = ~have | ~np.isfinite(m).all(axis=1)
-        running = ~failed
-        for _ in range(iterations):
-            act = np.nonzero(running)[0]
-            if act.size == 0:
-                break
-            u = _cylinder_frame(m[act, 3:6])
-            G, cnt, bad = gram(_lib.GRAM_CONE_GN, np.column_stack([m[act], u]), True, 1, act)
-            A, rhs = G[:, :6, :6], -G[:, :6, 6]
-            ok = (np.asarray(bad) == 0) & (np.asarray(cnt) >= 6) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(rhs).all(axis=1)
-            failed[act[~ok]] = True
-            running[act[~ok]] = False
-            if not ok.any():
-                break
-            act, A, rhs, u = act[ok], A[ok], rhs[ok], u[ok]
-            d = m[act, 3:6]
-            v = np.cross(d, u)
-            step = np.einsum("bij,bj->bi", np.linalg.pinv(A, rcond=6 * np.finfo(np.float64).eps), rhs)
-            m[act, 0:3] += step[:, 0:1] * u + step[:, 1:2] * v + step[:, 2:3] * d
-            d = d + step[:, 3:4] * u + step[:, 4:5] * v
-            m[act, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
+        failed |= ~np.isfinite(m).all(axis=1)
+
+        def update(act, step, prm):
+            _axial_update(m, act, prm[:, 8:11], step[:, 0:2], step[:, 2:3], step[:, 3:5])
             cs = np.column_stack([m[act, 6] - step[:, 5] * m[act, 7], m[act, 7] + step[:, 5] * m[act, 6]])
             m[act, 6:8] = cs / np.linalg.norm(cs, axis=1)[:, None]
-            fin = np.isfinite(m[act]).all(axis=1)
-            failed[act[~fin]] = True
-            running[act[~fin]] = False
-            running[act[np.linalg.norm(step, axis=1) < 1e-12]] = False
+            return np.isfinite(m[act]).all(axis=1)
+        _gauss_newton(gram, _lib.GRAM_CONE_GN, wpow=1, npar=6, min_count=6, cutoff=6, failed=failed, params=lambda act: _axial_params(m, act),
+                      update=update, iterations=iterations)
         rows = np.nonzero(~failed)[0]
         if rows.size == 0:
             return out
@@ -851,7 +861,7 @@ class OrientedPrimitiveEstimator(PrimitiveEstimator):
 # ---------------------------------------------------------------------------------------------------------------------
 # Torus (findTori; no reference counterpart): 4-point solver on oriented points with two slots, Gauss-Newton refit on seven parameters
 # ---------------------------------------------------------------------------------------------------------------------
-class TorusEstimator(Estimator):
+class TorusEstimator(OrientedEstimator):
     """Model (c[3], d[3], R, r): the centre, a unit axis direction, the major radius (axis to the tube's centre circle) and the minor
     (tube) radius of a ring torus, R > r > 0.  `normals` [n, 3] (per point, neither unit nor consistently signed) are read by the
     minimal solver alone, as lines.  `radius_range` bounds r and `major_radius_range` bounds R, of hypotheses and refits.
@@ -862,18 +872,13 @@ class TorusEstimator(Estimator):
     model_type = _lib.TORUS3D
     sample_size = 4
     nonminimal_sample_size = 7
-    device_minimal = True      # pgx_solve_minimal generates the hypotheses on the GPU, two slots per sample (same operation order as minimal())
-    device_slots = 2
+    device_slots = 2           # two hypotheses per sample
     cols = 8
-    takes_radius_range = True
-    radius_range = (0.0, np.inf)
     major_radius_range = (0.0, np.inf)
-    normals = None             # [n, 3] float64, in the points' order (findTori sets it)
 
     def context_setup(self, ctx):
-        ctx.set_radius_range(*self.radius_range)
+        super().context_setup(ctx)
         ctx.set_major_radius_range(*self.major_radius_range)
-        ctx.set_normals(self.normals)
 
     def _in_range(self, R, r):
         return ((r >= self.radius_range[0]) & (r <= self.radius_range[1]) & (R >= self.major_radius_range[0]) &
@@ -947,7 +952,7 @@ class TorusEstimator(Estimator):
 
     def _fit_many(self, gram, B, inits, iterations=10):
         """Geometric least squares, sum w (sqrt((rho - R)^2 + h^2) - r)^2 with rho = |(x - c) x d| and h = (x - c) . d, by Gauss-Newton
-        from `inits` in the shape of ConeEstimator._fit_many: at most 10 iterations on [B, ...] stacks, each ONE Gram request
+        from `inits` (the loop is _gauss_newton's): at most 10 iterations on [B, ...] stacks, each ONE Gram request
         (GRAM_TORUS_GN, weight power 1) at params (c, d, R, r, u) with u = _cylinder_frame(d) and v = d x u.  The rows are (J, f) with
         J = df / d(alpha, beta, gamma, delta, eta, dR, dr) in the chart c + alpha u + beta v + gamma d, normalise(d + delta u + eta v),
         R + dR, r + dr (csrc/fit.hip GenTorusGn), so step = pinv(J^T J)(-J^T f) with the cut-off 7 eps, then that update; an item stops
@@ -956,43 +961,16 @@ class TorusEstimator(Estimator):
         major_radius_range is dropped: Gauss-Newton from a ring torus has no reason to leave r > 0, R > 0, and a model that did is
         no ring torus (negating r or R is not a symmetry of the residual)."""
         out = [[] for _ in range(B)]
-        have = np.array([ini is not None for ini in inits], dtype=bool)
-        if not have.any():
-            return out
-        m = np.zeros((B, 8))
-        m[:, 5] = 1.0
-        m[:, 6], m[:, 7] = 2.0, 1.0
-        for b in np.nonzero(have)[0]:
-            m[b] = np.asarray(inits[b], dtype=np.float64).reshape(8)
-        with np.errstate(all="ignore"):
-            m[:, 3:6] /= np.linalg.norm(m[:, 3:6], axis=1)[:, None]
-        failed = ~have | ~np.isfinite(m).all(axis=1)
-        running = ~failed
-        for _ in range(iterations):
-            act = np.nonzero(running)[0]
-            if act.size == 0:
-                break
-            u = _cylinder_frame(m[act, 3:6])
-            G, cnt, bad = gram(_lib.GRAM_TORUS_GN, np.column_stack([m[act], u]), True, 1, act)
-            A, rhs = G[:, :7, :7], -G[:, :7, 7]
-            ok = (np.asarray(bad) == 0) & (np.asarray(cnt) >= 7) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(rhs).all(axis=1)
-            failed[act[~ok]] = True
-            running[act[~ok]] = False
-            if not ok.any():
-                break
-            act, A, rhs, u = act[ok], A[ok], rhs[ok], u[ok]
-            d = m[act, 3:6]
-            v = np.cross(d, u)
-            step = np.einsum("bij,bj->bi", np.linalg.pinv(A, rcond=7 * np.finfo(np.float64).eps), rhs)
-            m[act, 0:3] += step[:, 0:1] * u + step[:, 1:2] * v + step[:, 2:3] * d
-            d = d + step[:, 3:4] * u + step[:, 4:5] * v
-            m[act, 3:6] = d / np.linalg.norm(d, axis=1)[:, None]
+        m, failed = _axial_start(inits, (0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 2.0, 1.0))
+        failed |= ~np.isfinite(m).all(axis=1)
+
+        def update(act, step, prm):
+            _axial_update(m, act, prm[:, 8:11], step[:, 0:2], step[:, 2:3], step[:, 3:5])
             m[act, 6] += step[:, 5]
             m[act, 7] += step[:, 6]
-            fin = np.isfinite(m[act]).all(axis=1)
-            failed[act[~fin]] = True
-            running[act[~fin]] = False
-            running[act[np.linalg.norm(step, axis=1) < 1e-12]] = False
+            return np.isfinite(m[act]).all(axis=1)
+        _gauss_newton(gram, _lib.GRAM_TORUS_GN, wpow=1, npar=7, min_count=7, cutoff=7, failed=failed, params=lambda act: _axial_params(m, act),
+                      update=update, iterations=iterations)
         for b in np.nonzero(~failed)[0]:
             model = m[b]
             if np.isfinite(model).all() and model[7] > 0 and bool(self._in_range(model[6], model[7])):
@@ -1611,36 +1589,22 @@ class PnPEstimator(Estimator):
         return [[P[b]] if ok[b] else [] for b in range(B)]
 
     def _fit_many(self, gram, B, inits, iterations=10):
-        """The Gauss-Newton iteration of `nonminimal` for B items at once, with the 6x6 solves, the rotation updates and the
-        convergence tests done on [B, ...] arrays - 50 refits x 10 iterations per graph-cut round were 13 us of lstsq + 15 us
+        """The Gauss-Newton iteration of `nonminimal` for B items at once (the loop is _gauss_newton's), with the 6x6 solves, the rotation
+        updates and the convergence tests done on [B, ...] arrays - 50 refits x 10 iterations per graph-cut round were 13 us of lstsq + 15 us
         of small-array numpy each, a third of C4's proposal time.  The solve is the pseudo-inverse with lstsq's cut-off
         (singular values below eps * 6 * s_max dropped), so an item's iterates are those of `nonminimal` up to rounding."""
-        out = [[] for _ in range(B)]
         have = np.array([ini is not None for ini in inits], dtype=bool)
-        if not have.any():
-            return out
         R = np.zeros((B, 3, 3))
         t = np.zeros((B, 3))
         for b in np.nonzero(have)[0]:
             P0 = np.asarray(inits[b], dtype=np.float64).reshape(3, 4)
             R[b], t[b] = P0[:, :3], P0[:, 3]
-        running = have.copy()                   # still iterating
-        failed = ~have
         eye = np.eye(3)
-        for _ in range(iterations):
-            act = np.nonzero(running)[0]
-            if act.size == 0:
-                break
-            prm = np.concatenate([R[act], t[act][:, :, None]], axis=2).reshape(act.size, 12)
-            G, cnt, bad = gram(_lib.GRAM_PNP_GN, prm, True, 2, act)
-            A, b = G[:, :6, :6], -G[:, :6, 6]
-            ok = (bad == 0) & (cnt >= 4) & np.isfinite(A).all(axis=(1, 2)) & np.isfinite(b).all(axis=1)
-            failed[act[~ok]] = True
-            running[act[~ok]] = False
-            if not ok.any():
-                break
-            act, A, b = act[ok], A[ok], b[ok]
-            delta = np.einsum("bij,bj->bi", np.linalg.pinv(A, rcond=6 * np.finfo(np.float64).eps), b)
+
+        def params(act):
+            return np.concatenate([R[act], t[act][:, :, None]], axis=2).reshape(act.size, 12)
+
+        def update(act, delta, prm):
             om = delta[:, :3]
             ang = np.linalg.norm(om, axis=1)
             k = om / np.where(ang > 0, ang, 1.0)[:, None]
@@ -1650,9 +1614,12 @@ class PnPEstimator(Estimator):
             Kx[:, 2, 0], Kx[:, 2, 1] = -k[:, 1], k[:, 0]
             rot = eye + np.sin(ang)[:, None, None] * Kx + (1 - np.cos(ang))[:, None, None] * (Kx @ Kx)
             rot[ang == 0] = eye                   # R <- exp([omega]_x) R ; t <- t + dt
-            R[act] = rot @ R[act]
-            t[act] = t[act] + delta[:, 3:]
-            running[act[np.linalg.norm(delta, axis=1) < 1e-12]] = False
+            Rn, tn = rot @ R[act], t[act] + delta[:, 3:]
+            R[act], t[act] = Rn, tn
+            return np.isfinite(Rn).all(axis=(1, 2)) & np.isfinite(tn).all(axis=1)
+        # a start that is not finite is sent like any other: its sums fail it
+        failed = _gauss_newton(gram, _lib.GRAM_PNP_GN, wpow=2, npar=6, min_count=4, cutoff=6, failed=~have, params=params, update=update,
+                               iterations=iterations)
         P = np.concatenate([R, t[:, :, None]], axis=2).reshape(B, 12)
         good = ~failed & np.isfinite(P).all(axis=1)
         return [[P[b]] if good[b] else [] for b in range(B)]

@@ -3,13 +3,18 @@ replaced (tests/refit_reference.py), both fed by the same OracleContext: through
 `nonminimal_batch` the models have the count, dtype, shape and bytes of the reference body run once per selection, and the
 context sees the calls it saw before - the same `gram` calls from `nonminimal`, and from the other two one `gram_labels` /
 `gram_batch` call per request for all the items that made that request.  PnP is held by tests/test_host_logic.py (its two
-statements agree to rounding only).  A second test feeds non-finite Gram matrices: no model, no exception, no warning."""
+statements agree to rounding only).  A second test feeds non-finite Gram matrices: no model, no exception, no warning.
+At the end, the one Gauss-Newton loop of the four iterative refits against the four copies of it, byte for byte and request
+for request."""
 import warnings
 
 import numpy as np
 import pytest
 
+import cone_model
+import cylinder_model
 import refit_reference
+import torus_model
 from oracle_ctx import OracleContext
 from pyprogressivex import _estimators, _lib, datasets
 
@@ -289,3 +294,166 @@ def test_the_line_refit_answers_a_non_finite_gram_matrix_as_its_single_item_body
                     _same_models(g, w_, (entry, value))
             else:
                 assert got in want
+
+
+# ---- the Gauss-Newton refits: the one loop (_estimators._gauss_newton) against the four copies of it (tests/refit_reference.py) --------
+GN = {"cylinder": (cylinder_model, 5), "cone": (cone_model, 6), "torus": (torus_model, 7)}     # the model module, the fewest points
+
+
+def _set_provider(sets, log):
+    """A Gram provider over items with their own point sets, sets[r] = (model module, pts, w): every request is written down with
+    its rows, and the module's numpy_gram answers each row on its own.  Returns (provider, what numpy_gram logged per item)."""
+    per_item = [[] for _ in sets]
+
+    def gram(kind, prm, use_w, wpow, rows):
+        log.append((kind, None if prm is None else np.array(prm), use_w, wpow, np.array(rows)))
+        out = [sets[r][0].numpy_gram(sets[r][1], sets[r][2], log=per_item[r])(kind, None if prm is None else prm[k:k + 1], use_w, wpow, [0])
+               for k, r in enumerate(rows)]
+        return np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out]), np.concatenate([o[2] for o in out])
+    return gram, per_item
+
+
+def _same_requests(got, want, where):
+    """two logs of _set_provider: the same requests in the same order - kind, parameter rows (bytes), use_weights, wpow, rows"""
+    assert len(got) == len(want), where
+    for g, r in zip(got, want):
+        assert g[0] == r[0] and g[2] is r[2] and g[3] == r[3] and np.array_equal(g[4], r[4]), where
+        assert (g[1] is None) == (r[1] is None), where
+        if g[1] is not None:
+            assert g[1].dtype == r[1].dtype and g[1].shape == r[1].shape and g[1].tobytes() == r[1].tobytes(), where
+
+
+@pytest.mark.parametrize("name", list(GN))
+def test_the_one_gauss_newton_loop_is_bitwise_the_copy_it_replaced(name):
+    """Five items that leave the loop at different times, on the smallest of the type's refit fixtures: its start (several steps), no
+    init (never starts), a start at the fit itself (stops early), an all-NaN start (never starts) and a selection one point short
+    (fails at its first request).  Product and reference body return the same bytes and make the same requests."""
+    model, n = GN[name]
+    pts, w, gt, start = model.refit_fixture(n, 0.0, False, seed=n)
+    est = _estimators.ESTIMATORS[name]()
+    body = refit_reference.FIT_MANY[type(est)]
+    (fitted,), = body(est, model.numpy_gram(pts, w), 1, [start])
+    sets = [(model, pts, w)] * 4 + [(model, pts[:n - 1], None)]
+    inits = [start, None, fitted, np.full(len(gt), np.nan), start]
+    runs = {}
+    for which, fit in (("product", est._fit_many), ("reference", lambda *a: body(est, *a))):
+        log = []
+        gram, per_item = _set_provider(sets, log)
+        runs[which] = (fit(gram, 5, inits), log, [sum(r[0] != _lib.GRAM_AFFINE for r in item) for item in per_item])
+    got, want = runs["product"], runs["reference"]
+    assert len(got[0]) == len(want[0]) == 5
+    for b in range(5):
+        _same_models(got[0][b], want[0][b], (name, b))
+    _same_requests(got[1], want[1], name)
+    assert [len(m) for m in want[0]] == [1, 0, 1, 0, 0]
+    steps = want[2]                                         # Gauss-Newton requests per item
+    assert steps[1] == steps[3] == 0 and steps[4] == 1 and 1 <= steps[2] < steps[0] <= 10 and got[2] == steps, (name, steps)
+
+
+def test_a_mixed_batch_hands_each_constituent_exactly_its_rows():
+    """two cylinders and two cones interleaved through PrimitiveEstimator._fit_many: the constituents' loops and the reference
+    bodies return the same bytes from the same requests, no request mixes the classes' items, and every item's model is the one
+    its constituent's reference body fits alone"""
+    sets, inits, alone = [], [], []
+    est = _estimators.PrimitiveEstimator(("cylinder", "cone"))
+    for n, weighted in ((0, False), (64, True)):
+        for model, cls in ((cylinder_model, _lib.CYLINDER3D), (cone_model, _lib.CONE3D)):
+            part = est.parts[cls]
+            fewest = part.nonminimal_sample_size
+            pts, w, gt, start = model.refit_fixture(n or fewest, 0.0, weighted, seed=n + fewest)
+            sets.append((model, pts, w))
+            inits.append(est._row(cls, start))
+            (one,), = refit_reference.FIT_MANY[type(part)](part, model.numpy_gram(pts, w), 1, [start])
+            alone.append(est._row(cls, one))
+    ref = _estimators.PrimitiveEstimator(("cylinder", "cone"))
+    for part in ref.parts.values():
+        refit_reference.with_reference_fit_many(part)
+    runs = []
+    for e in (est, ref):
+        log = []
+        runs.append((e._fit_many(_set_provider(sets, log)[0], 4, inits), log))
+    (got, log), (want, ref_log) = runs
+    for b in range(4):
+        _same_models(got[b], want[b], b)
+        _same_models(got[b], [alone[b]], b)
+    _same_requests(log, ref_log, "mixed")
+    kinds = {_lib.GRAM_CYL_GN: {0, 2}, _lib.GRAM_AFFINE: {0, 2}, _lib.GRAM_CONE_GN: {1, 3}}
+    assert {r[0] for r in log} == set(kinds)
+    for kind, _, _, _, rows in log:
+        assert set(rows.tolist()) <= kinds[kind], (kind, rows)
+    assert log[0][4].tolist() == [0, 2] and any(r[4].tolist() == [1, 3] for r in log)        # both items of a class in one request
+
+
+def _pnp_scene():
+    """(ctx with labels 0 .. 4 set, weights, inits per label, selections [5, 8] with a start for them): label 0 = object 1 and
+    label 1 = object 2 from two different finite starts (the test moves label 0's to its fit, so that it stops first), label 2 without an init, label 3 from an all-NaN start, label 4 with three
+    points (a PnP refit needs four); the selections: object 1 twice, one point eight times, object 2, outliers"""
+    x1, x2, K, gt, poses = datasets.make_poses(n_per_object=120, n_objects=2, n_outliers=40, seed=2)
+    pts, _ = datasets.normalize_pnp(x1, x2, K)
+    rng = np.random.default_rng(11)
+    one, two, out = (np.flatnonzero(gt == v) for v in (1, 2, 0))
+    labels = np.full(len(pts), 5, dtype=np.int32)
+    labels[one[:60]], labels[two], labels[one[60:90]], labels[one[90:]], labels[out[:3]] = 0, 1, 2, 3, 4
+    ctx = OracleContext()
+    ctx.set_points(_lib.PNP, pts)
+    ctx.set_labels(labels)
+    far = poses[0].copy()
+    far[[3, 7, 11]] += [1.0, -1.0, 2.0]
+    inits = [poses[0] + 1e-3 * rng.normal(size=12), poses[1] + 1e-2 * rng.normal(size=12), None, np.full(12, np.nan), poses[0], None]
+    index = np.array([np.sort(rng.choice(one, 8, replace=False)), np.sort(rng.choice(one, 8, replace=False)), np.full(8, one[7]),
+                      np.sort(rng.choice(two, 8, replace=False)), np.sort(rng.choice(out, 8, replace=False))])
+    return ctx, rng.uniform(0.5, 2.0, len(pts)), inits, index, far
+
+
+def _same_calls(calls, ref_calls, where):
+    """two logs of Counting: the same context calls in the same order"""
+    assert len(calls) == len(ref_calls), where
+    for c, r in zip(calls, ref_calls):
+        assert c["method"] == r["method"] and c["kind"] == r["kind"] and c["wpow"] == r["wpow"] and c["weights"] is r["weights"], where
+        assert c["params"].dtype == r["params"].dtype and c["params"].shape == r["params"].shape, where
+        assert c["params"].tobytes() == r["params"].tobytes(), where
+        assert np.array_equal(c["what"], r["what"]), where
+
+
+def test_the_pnp_refit_through_the_one_loop_is_bitwise_the_copy_it_replaced():
+    """PnP's stacked refit on the OracleContext, through nonminimal_labels (five labels that leave the loop at different times) and
+    through the base nonminimal_batch (five selections from one start; then no start, then an all-NaN start): the same bytes and
+    the same gram_labels / gram_batch calls as the reference body.  The all-NaN start is SENT (PnP does not look at its start: the
+    sums fail it), which the equal calls hold."""
+    ctx, w, inits, index, far = _pnp_scene()
+    est = _estimators.PnPEstimator()
+    ref = refit_reference.with_reference_fit_many(_estimators.PnPEstimator())
+    with np.errstate(all="ignore"):
+        # -- all labels at once
+        for weights in (w, None):
+            inits[0] = ref.nonminimal_labels(ctx, 6, weights, inits=inits, skip=(1, 2, 3, 4, 5))[0][0]     # label 0 starts at its fit
+            runs = []
+            for e in (est, ref):
+                counting = Counting(ctx)
+                runs.append((e.nonminimal_labels(counting, 6, weights, inits=inits, skip=(5,)), counting.calls))
+            (got, calls), (want, ref_calls) = runs
+            for k in range(6):
+                _same_models(got[k], want[k], ("label", k))
+            _same_calls(calls, ref_calls, "labels")
+            assert [len(m) for m in want] == [1, 1, 0, 0, 0, 0]
+            assert all(c["method"] == "gram_labels" and c["kind"] == _lib.GRAM_PNP_GN and c["wpow"] == 2 for c in calls)
+            sent = [np.flatnonzero(np.any(c["params"] != 0, axis=1)).tolist() for c in calls]    # NaN != 0: label 3 shows
+            assert sent[0] == [0, 1, 3, 4] and all(set(s) <= {0, 1} for s in sent[1:]) and 2 < len(sent) <= 10
+            assert len({sum(k in s for s in sent) for k in (0, 1)}) == 2                        # ... the two fits stop at different times
+        # -- selections of one size from one start
+        base = _estimators.Estimator.nonminimal_batch
+        for init in (far, None, np.full(12, np.nan)):
+            runs = []
+            for e in (est, ref):
+                counting = Counting(ctx)
+                runs.append((base(e, counting, index, w, init), counting.calls))
+            (got, calls), (want, ref_calls) = runs
+            assert len(got) == len(want) == 5
+            for b in range(5):
+                _same_models(got[b], want[b], ("batch row", b))
+            _same_calls(calls, ref_calls, "batch")
+            if init is far:
+                assert 2 < len(calls) <= 10 and len({len(c["what"]) for c in calls}) > 1      # the selections stop at different times
+                assert len(want[0]) == len(want[1]) == 1
+            else:
+                assert want == [[]] * 5 and len(calls) == (0 if init is None else 1)
