@@ -453,6 +453,28 @@ int pgx_eigh_smallest_batch(pgx_ctx *ctx, const double *A, int q, int64_t B, dou
 int pgx_estimate_normals(pgx_ctx *ctx, const double *points, int64_t n, const double *viewpoint, double *normals_out,
                          double *curvature_out, int64_t *undefined);
 
+/* Connected components of a labelling in the neighbourhood graph resident NOW, from pgx_graph_build or pgx_set_graph (no reference
+ * counterpart: a model's label collects every point of its slab, and an instance is a piece of it that hangs together).  labels: n
+ * int32 (host), uploaded into the call's own device buffer; the call neither reads nor alters the resident problem (points, normals,
+ * weights, the labels of pgx_set_labels, unary table, hypothesis batch, expansion memo).  The definition, all of it integers:
+ *   1. site i is LIVE when 0 <= labels[i] < first_ignored;
+ *   2. two live sites are JOINED when the CSR holds an arc between them and their labels are equal; multiplicities are ignored.  The
+ *      resident graph is symmetric and free of self arcs - pgx_graph_build makes it so and pgx_set_graph refuses any other - so "in
+ *      either row" and "in both rows" are the same thing here;
+ *   3. a component is a class of the transitive closure of `joined`; a live site with no same-label neighbour is a component of one;
+ *   4. components are numbered 0 .. C-1 in ascending order of their smallest member.
+ * comp_out [n]: the number of the site's component, -1 for a site that is not live.  first_out [c] = the smallest member of component
+ * c, sizes_out [c] = its size: host buffers of capacity n of which C entries are written, each may be NULL.  *components = C.
+ * n == 0 is PGX_OK with C = 0 and writes nothing else.  PGX_ERR_INVALID: no graph resident ("needs a neighbourhood graph of the
+ * points"), a graph of other than n sites ("<n> labels for a graph of <gn> sites"), labels, comp_out or components NULL ("NULL
+ * argument").  The result is a pure function of (graph, labels, first_ignored): a lock-free union-find whose larger root always goes
+ * below the smaller one, so a tree's root is its smallest member in whatever order the lanes run.  Lane t serves site t's row, in the
+ * Morton order of the graph's coordinates when pgx_graph_build left it; a row of more than PGX_COMPONENTS_LONG_ROW arcs is served by a
+ * whole wave. */
+#define PGX_COMPONENTS_LONG_ROW 64
+int pgx_label_components(pgx_ctx *ctx, const int32_t *labels, int64_t n, int32_t first_ignored, int32_t *comp_out,
+                         int32_t *first_out, int64_t *sizes_out, int64_t *components);
+
 /* ---- the inlier/outlier graph cut of GC-RANSAC's local optimisation.
  * Replaces gcransac::GCRANSAC::labeling as reached from proposal_engine->run (progressive_x.h:294-299; settings
  * spatial_coherence_weight / threshold at :541-545).  The graph-cut-ransac sources are absent from the snapshot, so the

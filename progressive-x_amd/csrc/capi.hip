@@ -270,7 +270,7 @@ void pgx_destroy(pgx_ctx* ctx)
                       &ctx->red_partials, &ctx->red_out, &ctx->dq, &ctx->kmodels, &ctx->labels, &ctx->goff,
                       &ctx->gidx, &ctx->gmult, &ctx->grev, &ctx->scratch, &ctx->fit_scratch, &ctx->pts_s, &ctx->pts32_s,
                       &ctx->pmax_s, &ctx->comp_s, &ctx->pperm, &ctx->gbounds, &ctx->masks_s, &ctx->cull_lists, &ctx->cull_counts, &ctx->score_wl, &ctx->gc, &ctx->gc_sel,
-                      &ctx->weights, &ctx->normals, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops};
+                      &ctx->weights, &ctx->normals, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops, &ctx->cc_buf};
     for (DevBuf* b : bufs) release(*b);
     for (DevBuf& b : ctx->slots) release(b);
     release(ctx->h_res);
@@ -1227,6 +1227,13 @@ int pgx_estimate_normals(pgx_ctx* ctx, const double* points, int64_t n, const do
 {
     CTX_GUARD(ctx);
     return estimate_normals_launch(ctx, points, n, viewpoint, normals_out, curvature_out, undefined);
+}
+
+int pgx_label_components(pgx_ctx* ctx, const int32_t* labels, int64_t n, int32_t first_ignored, int32_t* comp_out, int32_t* first_out,
+                         int64_t* sizes_out, int64_t* components)
+{
+    CTX_GUARD(ctx);
+    return label_components_launch(ctx, labels, n, first_ignored, comp_out, first_out, sizes_out, components);
 }
 
 int pgx_gc_labeling(pgx_ctx* ctx, const double* model, double T2, double lambda, int32_t* flags, int64_t* count)

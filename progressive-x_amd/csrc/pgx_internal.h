@@ -161,6 +161,7 @@ struct pgx_ctx {
     int oriented = 0;         // the resident type is one (Residual<MT>::oriented).  Its normals and kappa also lie behind the rows of pts, pts_s
     double normal_cos2 = 0.0; // and pts_g (residuals.hip.h; place_oriented_normals).  kappa = cos^2(tolerance), pgx_set_normal_tolerance (context state)
     int64_t oriented_version = 0;   // bumped when an oriented type's normals or kappa change: part of a unary column's identity
+    pgx::DevBuf cc_buf;       // pgx_label_components: its labels, parent[], counters, ranks and results (components.hip); nothing resident reads it
 
     pgx::CommState* comm = nullptr;
 };
@@ -271,6 +272,8 @@ int maxflow_schedule_stats(pgx_ctx* ctx, int64_t out[8]);   // maxflow.hip
 int eigh_smallest_launch(pgx_ctx* ctx, const double* A, int q, int64_t B, double* vec, double* val);   // fit.hip
 int estimate_normals_launch(pgx_ctx* ctx, const double* points, int64_t n, const double* viewpoint, double* normals_out,
                             double* curvature_out, int64_t* undefined);   // normals.hip
+int label_components_launch(pgx_ctx* ctx, const int32_t* labels, int64_t n, int32_t first_ignored, int32_t* comp_out, int32_t* first_out,
+                            int64_t* sizes_out, int64_t* components);   // components.hip
 int expand_alpha_tile(pgx_ctx* ctx, MoveRequest& rq);   // maxflow_tile.hip: the whole graph in one workgroup, one launch
 void tile_free(pgx_ctx* ctx);
 struct MfView;

@@ -30,7 +30,7 @@ import sys
 
 import numpy as np
 
-from . import _engine, _estimators, _lib, _proposal
+from . import _components, _engine, _estimators, _lib, _proposal
 
 _ctx = None
 
@@ -440,6 +440,25 @@ def findLines3D(points, weights=None, threshold=0.05, conf=0.5, spatial_coherenc
                            **_run_options(locals()))
 
 
+def _neighbourhood_graph(k, radius):
+    """estimateNormals' and splitComponents' (k, radius), checked -> graph_build's kind, radius and k: k alone the k nearest neighbours,
+    both the k nearest inside the ball, the radius alone every point inside the ball"""
+    if k is None and radius is None:
+        raise ValueError("k or radius should be given")
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2:
+            raise ValueError("k should be an integer >= 2 (or None with a radius)")
+    if radius is not None:
+        try:
+            radius = float(radius)
+        except (TypeError, ValueError):
+            raise ValueError("radius should be None or a number > 0") from None
+        if not (radius > 0.0 and np.isfinite(radius)):
+            raise ValueError("radius should be None or a number > 0")
+    kind = _lib.GRAPH_BALL if k is None else _lib.GRAPH_KNN if radius is None else _lib.GRAPH_KNN_IN_BALL
+    return dict(kind=kind, radius=0.0 if radius is None else radius, k=1 if k is None else int(k))
+
+
 def estimateNormals(points, k=16, radius=None, viewpoint=None, return_curvature=False):
     """Per-point surface normals of a 3-D point cloud, on the GPU: the eigenvector of the smallest eigenvalue of the covariance of each
     point's neighbourhood in the neighbourhood graph (include/pgx.h pgx_estimate_normals states the arithmetic).  points [n, 3], n >= 3,
@@ -454,18 +473,7 @@ def estimateNormals(points, k=16, radius=None, viewpoint=None, return_curvature=
     points = _as_f64(points)
     if points.ndim != 2 or points.shape[1] != 3 or points.shape[0] < 3:
         raise ValueError("points should be an array with dims [n,3], n>=3")
-    if k is None and radius is None:
-        raise ValueError("k or radius should be given")
-    if k is not None:
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2:
-            raise ValueError("k should be an integer >= 2 (or None with a radius)")
-    if radius is not None:
-        try:
-            radius = float(radius)
-        except (TypeError, ValueError):
-            raise ValueError("radius should be None or a number > 0") from None
-        if not (radius > 0.0 and np.isfinite(radius)):
-            raise ValueError("radius should be None or a number > 0")
+    graph = _neighbourhood_graph(k, radius)
     if viewpoint is not None:
         try:
             viewpoint = np.asarray(viewpoint, dtype=np.float64).reshape(-1)
@@ -473,11 +481,53 @@ def estimateNormals(points, k=16, radius=None, viewpoint=None, return_curvature=
             raise ValueError("viewpoint should be None or 3 finite numbers") from None
         if viewpoint.shape[0] != 3 or not np.isfinite(viewpoint).all():
             raise ValueError("viewpoint should be None or 3 finite numbers")
-    kind = _lib.GRAPH_BALL if k is None else _lib.GRAPH_KNN if radius is None else _lib.GRAPH_KNN_IN_BALL
     ctx = _context()
-    ctx.graph_build(points, kind, radius=0.0 if radius is None else radius, k=1 if k is None else int(k), fetch=False)
+    ctx.graph_build(points, fetch=False, **graph)
     normals, curvature, _ = ctx.estimate_normals(points, viewpoint=viewpoint, want_curvature=bool(return_curvature))
     return (normals, curvature) if return_curvature else normals
+
+
+def splitComponents(points, labels, model_number, k=16, radius=None, minimum_point_number=10, keep="all"):
+    """Splits the models of a labelling into instances, on the GPU: a find* call returns models of infinite extent, and a model's label
+    collects every point near it - two table tops that happen to be coplanar, the wall behind them, a stripe of the outliers.  An
+    instance is a connected piece: a connected component of the model's points in the neighbourhood graph of the cloud (include/pgx.h
+    pgx_label_components states the definition).  points [n, d], d = 2 or 3, finite; labels [n] integers in any find* labelling
+    convention: 0 .. model_number-1 are the models, anything else - the outlier label, a negative number - is an outlier.  Returns
+    (new_labels [n] int32, parent [K'] int32): instance j consists of the points with new_labels == j and is a piece of the model
+    parent[j], so the caller writes planes[parent]; K' = len(parent) is the new outlier label.  keep="all": every component of at
+    least minimum_point_number points becomes an instance; keep="largest": only the largest component of each model (ties: the one
+    with the smallest point index), under the same size test.  Instances are ordered by (model ascending, size descending, smallest
+    point index ascending); a model none of whose components passes the size test is absent from parent.
+    The graph is estimateNormals': k given and radius None - the k nearest neighbours (the default, k = 16; the graph build takes
+    k <= 16); k and radius given - the k nearest inside the ball; k=None and radius given - every point inside the ball.  What the
+    neighbourhood means here: two points belong to one surface when a chain of neighbours of the same model joins them, so choose
+    radius as the largest gap that still counts as one surface - a few point spacings.  A k-NN graph without a radius joins stragglers
+    over any distance: every point has k neighbours however far away, and two pieces a metre apart hang together through them.
+    The function is a post-process of a finished labelling: it changes nothing about how the find* calls score, sample or label."""
+    points = _as_f64(points)
+    if points.ndim != 2 or points.shape[1] not in (2, 3):
+        raise ValueError("points should be an array with dims [n,2] or [n,3]")
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.shape[0] != points.shape[0]:
+        raise ValueError("labels should be an array with dims [n], one entry per point")
+    if labels.dtype == np.bool_ or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError("labels should be integers")
+    if isinstance(model_number, bool) or not isinstance(model_number, (int, np.integer)) or not 0 <= model_number < 2 ** 31:
+        raise ValueError("model_number should be an integer >= 0")
+    graph = _neighbourhood_graph(k, radius)
+    if isinstance(minimum_point_number, bool) or not isinstance(minimum_point_number, (int, np.integer)) or minimum_point_number < 1:
+        raise ValueError("minimum_point_number should be an integer >= 1")
+    if keep not in _components.KEEP:
+        raise ValueError('keep should be "all" or "largest"')
+    model_number = int(model_number)
+    if points.shape[0] == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+    live = (labels >= 0) & (labels < model_number)              # before the cast to int32: an int64 outlier label may not fit
+    device_labels = np.where(live, labels, -1).astype(np.int32)
+    ctx = _context()
+    ctx.graph_build(points, fetch=False, **graph)
+    comp, first, sizes = ctx.label_components(device_labels, model_number)
+    return _components.regroup(device_labels, model_number, comp, first, sizes, int(minimum_point_number), keep)
 
 
 def findCylinders(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,

@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "pgx_score", "pgx_score_upload", "pgx_score_launch", "pgx_score_fetch", "pgx_score_algorithmic_bytes", "pgx_score_stats", "pgx_score_profile", "pgx_score_kernel_times", "pgx_score_debug_fetch", "pgx_score_debug_geometry",
     "pgx_preference", "pgx_get_preference", "pgx_compound_update",
     "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_major_radius_range", "pgx_set_primitive_classes", "pgx_set_normals", "pgx_set_normal_tolerance",
-    "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals",
+    "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals", "pgx_label_components",
     "pgx_bucket", "pgx_residual_sum", "pgx_gc_labeling", "pgx_gc_inliers", "pgx_epipolar_support", "pgx_gram_batch", "pgx_gram_labels", "pgx_residual_sums", "pgx_pnp_refine_batch",
     "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_barrier", "pgx_comm_allreduce_max_f64",
     "pgx_score_allgather", "pgx_score_fetch_all", "pgx_score_allgather_begin", "pgx_score_allgather_end", "pgx_compound_allreduce_max",
@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
 
 
 GRAPH_KNN_IN_BALL, GRAPH_BALL, GRAPH_KNN = 0, 1, 2
+COMPONENTS_LONG_ROW = 64       # PGX_COMPONENTS_LONG_ROW (include/pgx.h): pgx_label_components hands a longer row to a whole wave
 GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE, GRAM_CYL_GN, GRAM_CONE_GN, GRAM_TORUS_GN = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5, GRAM_CIRCLE: 4, GRAM_CYL_GN: 6, GRAM_CONE_GN: 7, GRAM_TORUS_GN: 8}   # GRAM_AFFINE: point dimension + 1
 
@@ -748,6 +749,23 @@ class Context:
         self._ck(self._lib.pgx_estimate_normals(self._h, _ptr(pts, C.c_double), C.c_int64(n), _ptr(vp, C.c_double), _ptr(nrm, C.c_double),
                                                 _ptr(curv, C.c_double), C.byref(undefined)), "pgx_estimate_normals")
         return nrm, curv, int(undefined.value)
+
+    def label_components(self, labels, first_ignored):
+        """pgx_label_components: (comp int32 [n], first int32 [C], sizes int64 [C]) - the connected components of the labelling in the graph
+        resident now (graph_build / set_graph): sites with 0 <= label < first_ignored, joined along arcs between equal labels, numbered
+        by their smallest member (first); comp is -1 elsewhere.  The buffers are sized by what is resident NOW (graph_size), and the
+        library checks len(labels) against it.  The resident problem is neither read nor changed."""
+        lab = _i32(labels).reshape(-1)
+        n = max(self.graph_size()[0], 1)
+        comp = np.empty(n, dtype=np.int32)
+        first = np.empty(n, dtype=np.int32)
+        sizes = np.empty(n, dtype=np.int64)
+        count = C.c_int64()
+        self._ck(self._lib.pgx_label_components(self._h, _ptr(lab, C.c_int32), C.c_int64(lab.shape[0]), C.c_int32(int(first_ignored)),
+                                                _ptr(comp, C.c_int32), _ptr(first, C.c_int32), _ptr(sizes, C.c_int64), C.byref(count)),
+                 "pgx_label_components")
+        c = int(count.value)
+        return comp[:lab.shape[0]], first[:c].copy(), sizes[:c].copy()
 
     def expansion_schedule(self):
         """How the level-synchronous min-cut spent its dependent steps (include/pgx.h pgx_expansion_schedule)."""
