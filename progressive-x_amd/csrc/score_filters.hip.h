@@ -662,6 +662,76 @@ template <int DIM> struct RoundFilter32 {
 template <> struct Filter32<kCircle2D> : RoundFilter32<2> {};
 template <> struct Filter32<kSphere3D> : RoundFilter32<3> {};
 
+// ---- the axial family: 3-D lines, cylinders, cones and tori - a residual made of the distance to an axis (p, d) ------------------------
+// What the four filters share is stated here once; what each one derives - its operation order, its error budget E = e1 P + e0 + e2 l~,
+// its switch-off cases - is stated with its shape below (LineShape32, CylinderShape32, ConeShape32, TorusShape32), and every shape's
+// derivation builds on the 3-D line's.  An axial type supplies: its Lane (p[3], d[3], its own fields, then e1, e0, e2, tpp, nrm, nanh)
+// with kStagedVals, kModelVals (the model entries, every one of which enters every residual), budget() - its own lane fields in the
+// filter's units, its own switch-off cases, and e1, e0, e2, nrm - and magnitude(), the non-negative quantity that is compared.
+//
+// s~ and l~ of a point or a centre, for any lane with p[3] and d[3] (the 3-D line's derivation states the operation order)
+template <class L> __device__ __forceinline__ float axial_dist(const float* p, const L& ln, float* l1) {
+    const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];
+    const float* d = ln.d;
+    const float c0 = __builtin_fmaf(e1, d[2], -(e2 * d[1]));
+    const float c1 = __builtin_fmaf(e2, d[0], -(e0 * d[2]));
+    const float c2 = __builtin_fmaf(e0, d[1], -(e1 * d[0]));
+    *l1 = (fabsf(e0) + fabsf(e1)) + fabsf(e2);
+    return sqrtf(__builtin_fmaf(c0, c0, __builtin_fmaf(c1, c1, c2 * c2)));
+}
+// h~ of the same point: axial_dist's own e~ (the same subtractions), then the dot product with d~ (the cone's derivation)
+template <class L> __device__ __forceinline__ float axial_height(const float* p, const L& ln) {
+    const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];
+    return __builtin_fmaf(e2, ln.d[2], __builtin_fmaf(e1, ln.d[1], e0 * ln.d[0]));
+}
+
+template <class Shape> struct AxialFilter32 : Shape {
+    using Lane = typename Shape::Lane;
+    static constexpr bool enabled = true;
+    static constexpr int kRowVals = 6, kGroupVals = 5;
+    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
+        Lane ln;
+        const double d0[3] = {m[3], m[4], m[5]};
+        bool off;
+        const double sc = pow2_normaliser<3>(d0, &off);
+        bool nan = false;
+#pragma unroll
+        for (int k = 6; k < Shape::kModelVals; ++k) nan |= !(m[k] == m[k]);
+        double d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k] = d0[k] * sc;
+            ln.p[k] = (float)m[k];
+            ln.d[k] = (float)d[k];
+            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
+        }
+        ln.nanh = nan ? 1.0f : 0.0f;
+        const double Ts = sqrt(T2) * sc;   // the threshold in the scaled direction's units: must be an ordinary f32 as well
+        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
+        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
+        const bool out = !(pscale <= 1e17) || !(pn <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off;   // the 3-D line's switch-off cases
+        const double u = 5.9604644775390625e-8;
+        Shape::budget(ln, m, sc, dn, pn, u, out);
+        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
+        return ln;
+    }
+    // p = (x, y, z, -, -, P, -, -) in f32
+    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
+        float l1;
+        const float a = Shape::magnitude(p, ln, &l1);
+        const float m = a - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
+        return m > ln.tpp;  // false on NaN / inf - inf
+    }
+    // g = (centre[3], rho, Pmax)
+    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
+        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
+        float l1;
+        const float a = Shape::magnitude(g, ln, &l1);
+        const float m = a - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
+        return m > ln.tpp * 1.001f;
+    }
+};
+
 // ---- 3-D lines: r = |(x - p) x d| (Residual<kLine3D>), inlier iff r^2 < T2 ------------------------------------------------------------
 // Homogeneous in the direction d only (p is a point): the f32 copy of d is made from d after the exact power-of-two scaling
 // sc = pow2_normaliser<3>(d), which leaves its largest entry in [0.5, 1) and |d| in [0.5, sqrt(3)), and is tested against the threshold
@@ -712,68 +782,24 @@ template <> struct Filter32<kSphere3D> : RoundFilter32<3> {};
 // A NaN entry culls the hypothesis outright (all six enter every residual).  The exact path is 17 FP64 operations without a division or
 // a root, so as for planes the per-pair filter buys little and the cull buys almost everything: a line's inliers are a tube of
 // radius T, which few 64-point balls touch (DESIGN.md 4.8 has the measurement).
-template <> struct Filter32<kLine3D> {
-    static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 5;
+struct LineShape32 {
     struct Lane { float p[3]; float d[3]; float e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
     // reject() reads p, d, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject)
     static constexpr int kStagedVals = 10;
+    static constexpr int kModelVals = 6;
     static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, e1) == 6 * sizeof(float) &&
                   offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
                   sizeof(Lane) == 12 * sizeof(float), "p, d, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
-    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
-        Lane ln;
-        const double d0[3] = {m[3], m[4], m[5]};
-        bool off;
-        const double sc = pow2_normaliser<3>(d0, &off);
-        bool nan = false;
-        double d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            d[k] = d0[k] * sc;
-            ln.p[k] = (float)m[k];
-            ln.d[k] = (float)d[k];
-            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
-        }
-        ln.nanh = nan ? 1.0f : 0.0f;
-        const double Ts = sqrt(T2) * sc;   // the threshold in the scaled direction's units: must be an ordinary f32 as well
-        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
-        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
-        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
-        const double u = 5.9604644775390625e-8;
+    template <class MD> static __device__ __forceinline__ void budget(Lane& ln, const MD&, double, double dn, double pn, double u, bool big) {
         ln.e1 = f32_up(2.0 * u * dn);
         ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * dn * pn + 1e-18);   // inf: nothing is rejected
         ln.e2 = f32_up(8.0 * u * dn);
-        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
         ln.nrm = f32_up(dn);
-        return ln;
     }
-    // s~ and l~ of a point or a centre (any lane with p[3] and d[3]: the cylinder's filter calls this too)
-    template <class L> static __device__ __forceinline__ float dist(const float* p, const L& ln, float* l1) {
-        const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];
-        const float* d = ln.d;
-        const float c0 = __builtin_fmaf(e1, d[2], -(e2 * d[1]));
-        const float c1 = __builtin_fmaf(e2, d[0], -(e0 * d[2]));
-        const float c2 = __builtin_fmaf(e0, d[1], -(e1 * d[0]));
-        *l1 = (fabsf(e0) + fabsf(e1)) + fabsf(e2);
-        return sqrtf(__builtin_fmaf(c0, c0, __builtin_fmaf(c1, c1, c2 * c2)));
-    }
-    // p = (x, y, z, -, -, P, -, -) in f32
-    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
-        float l1;
-        const float s = dist(p, ln, &l1);
-        const float m = s - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
-        return m > ln.tpp;  // false on NaN / inf - inf
-    }
-    // g = (centre[3], rho, Pmax)
-    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
-        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
-        float l1;
-        const float s = dist(g, ln, &l1);
-        const float m = s - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
-        return m > ln.tpp * 1.001f;
-    }
+    // s~ itself is compared: a root is never negative, and an absolute value here would be an operation the budget does not have
+    static __device__ __forceinline__ float magnitude(const float* p, const Lane& ln, float* l1) { return axial_dist(p, ln, l1); }
 };
+template <> struct Filter32<kLine3D> : AxialFilter32<LineShape32> {};
 
 // ---- cylinders: r = | |(x - p) x d| - cr | (Residual<kCylinder3D>), inlier iff r^2 < T2 ----------------------------------------------
 // The 3-D line's distance followed by the round family's last step, and so is the test.  Homogeneous in the direction only: with the
@@ -783,7 +809,7 @@ template <> struct Filter32<kLine3D> {
 // rounded sqrt(q sc^2) is sc sqrt(q) bit for bit; the subtraction of cr sc and the square scale along.  The exact path's decision on
 // (d, cr, T2) is the one its arithmetic would take on (d sc, R, T2 sc^2).  Per point, in f32 - this operation order is the contract
 // of the f32 test (tests restate it with fma as one rounding):
-//   s~, l~ = Filter32<kLine3D>::dist(x~, p~, d~)  (the same code),   r~ = (float)(cr sc),   n~ = s~ - r~
+//   s~, l~ = axial_dist(x~, p~, d~)  (the shared code),   r~ = (float)(cr sc),   n~ = s~ - r~
 // With u = 2^-24 and the 3-D line's terms as derived above (inputs, e~, c~_k, q~, sqrtf: sqrt(3) u |d| P + u |d| |p| + 7.5 u |d~| |e~|
 // and the underflow floor) the cylinder adds:
 //   input r~   |r~ - R| <= u |R|, and n is 1-Lipschitz in R: u |R|
@@ -809,63 +835,29 @@ template <> struct Filter32<kLine3D> {
 // entries among them) - and a radius beyond 1e17 in the filter's units (|R| > 1e17; Inf included: r~ must stay an ordinary f32, or
 // s~ - inf would reject everything.  inf - inf is NaN, and a NaN comparison is false).  A NaN entry culls the hypothesis outright (all
 // seven enter every residual).  The exact path is the 3-D line's 17 FP64 operations plus a root, a subtraction and a square.
-template <> struct Filter32<kCylinder3D> {
-    using Line = Filter32<kLine3D>;
-    static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 5;
+struct CylinderShape32 {
     struct Lane { float p[3]; float d[3]; float r, e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
     // reject() reads p, d, r, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject)
     static constexpr int kStagedVals = 11;
+    static constexpr int kModelVals = 7;
     static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, r) == 6 * sizeof(float) && offsetof(Lane, e1) == 7 * sizeof(float) &&
                   offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
                   sizeof(Lane) == 13 * sizeof(float), "p, d, r, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
-    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
-        Lane ln;
-        const double d0[3] = {m[3], m[4], m[5]};
-        bool off;
-        const double sc = pow2_normaliser<3>(d0, &off);
-        bool nan = !(m[6] == m[6]);
-        double d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            d[k] = d0[k] * sc;
-            ln.p[k] = (float)m[k];
-            ln.d[k] = (float)d[k];
-            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
-        }
-        ln.nanh = nan ? 1.0f : 0.0f;
+    template <class MD> static __device__ __forceinline__ void budget(Lane& ln, const MD& m, double sc, double dn, double pn, double u, bool out) {
         const double R = m[6] * sc;        // the radius in the scaled direction's units
         ln.r = (float)R;
-        const double Ts = sqrt(T2) * sc;   // the threshold in the same units: must be an ordinary f32 as well
-        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
-        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
-        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(fabs(R) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
-        const double u = 5.9604644775390625e-8;
+        const bool big = out || !(fabs(R) <= 1e17);
         ln.e1 = f32_up(2.0 * u * dn);
         ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * (dn * pn + fabs(R)) + 1e-18);   // inf: nothing is rejected
         ln.e2 = f32_up(8.0 * u * dn);
-        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
         ln.nrm = f32_up(dn);
-        return ln;
     }
-    // s~ and l~ of a point or a centre: the 3-D line's code on this lane's p and d
-    static __device__ __forceinline__ float dist(const float* p, const Lane& ln, float* l1) { return Line::dist(p, ln, l1); }
-    // p = (x, y, z, -, -, P, -, -) in f32
-    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
-        float l1;
-        const float s = dist(p, ln, &l1);
-        const float m = fabsf(s - ln.r) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
-        return m > ln.tpp;  // false on NaN / inf - inf
-    }
-    // g = (centre[3], rho, Pmax)
-    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
-        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
-        float l1;
-        const float s = dist(g, ln, &l1);
-        const float m = fabsf(s - ln.r) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
-        return m > ln.tpp * 1.001f;
+    static __device__ __forceinline__ float magnitude(const float* p, const Lane& ln, float* l1) {
+        const float s = axial_dist(p, ln, l1);
+        return fabsf(s - ln.r);
     }
 };
+template <> struct Filter32<kCylinder3D> : AxialFilter32<CylinderShape32> {};
 
 // ---- cones: r = |c rho - s h|, rho = |(x - a) x d|, h = (x - a) . d (Residual<kCone3D>), inlier iff r^2 < T2 -------------------------
 // The 3-D line's distance and a dot product with the same direction, combined by the half-angle's (c, s).  Homogeneous in d and in
@@ -876,7 +868,7 @@ template <> struct Filter32<kCylinder3D> {
 // K1 = |c| + |s|, and outside the band 2^-10 <= K1 <= 2^10 the filter is off.  Below d is the scaled direction, rho* = |(x - a) x d|,
 // h* = (x - a) . d and n* = c rho* - s h* in exact arithmetic on the f64 inputs.  Per point, in f32 - this operation order is the
 // contract of the f32 test (tests restate it with fma as one rounding):
-//   s~, l~ = Filter32<kLine3D>::dist(x~, a~, d~)  (the same code; e~_k = x~_k - a~_k),   h~ = fma(e~_2, d~_2, fma(e~_1, d~_1, e~_0 d~_0)),
+//   s~, l~ = axial_dist(x~, a~, d~)  (the shared code; e~_k = x~_k - a~_k),   h~ = axial_height: fma(e~_2, d~_2, fma(e~_1, d~_1, e~_0 d~_0)),
 //   c~ = (float)c,  s_~ = (float)s,   n~ = fma(s~, c~, -(h~ s_~))
 // With u = 2^-24 and the 3-D line's terms as derived above, B = sqrt(3) u |d| P + u |d| |a| for the inputs x~ and a~ and t = u |d~| |e~|:
 //   rho        |s~ - rho*| + |rho_c - rho*| <= B + (7.5 + 2^-26) t and the underflow floor: the 3-D line's budget, its exact path included
@@ -908,70 +900,34 @@ template <> struct Filter32<kCylinder3D> {
 // among them) - and |c| + |s| outside [2^-10, 2^10], which a non-finite c or s is too (n~ stays below 2^10 * 6.1e17 * 2, an ordinary
 // f32, and an Inf entry would make inf - inf = NaN at best).  A NaN entry culls the hypothesis outright (all eight enter every
 // residual).  The exact path is the 3-D line's 17 FP64 operations plus a root, five for h, two products, a difference and a square.
-template <> struct Filter32<kCone3D> {
-    using Line = Filter32<kLine3D>;
-    static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 5;
+struct ConeShape32 {
     struct Lane { float p[3]; float d[3]; float c, s, e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
     // reject() reads p, d, c, s, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject): three float4 chunks
     static constexpr int kStagedVals = 12;
+    static constexpr int kModelVals = 8;
     static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, c) == 6 * sizeof(float) && offsetof(Lane, e1) == 8 * sizeof(float) &&
                   offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
                   sizeof(Lane) == 14 * sizeof(float), "p, d, c, s, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
-    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
-        Lane ln;
-        const double d0[3] = {m[3], m[4], m[5]};
-        bool off;
-        const double sc = pow2_normaliser<3>(d0, &off);
-        bool nan = !(m[6] == m[6]) || !(m[7] == m[7]);
-        double d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            d[k] = d0[k] * sc;
-            ln.p[k] = (float)m[k];
-            ln.d[k] = (float)d[k];
-            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
-        }
-        ln.nanh = nan ? 1.0f : 0.0f;
+    template <class MD> static __device__ __forceinline__ void budget(Lane& ln, const MD& m, double, double dn, double pn, double u, bool out) {
         ln.c = (float)m[6];
         ln.s = (float)m[7];
-        const double Ts = sqrt(T2) * sc;   // the threshold in the scaled direction's units: must be an ordinary f32 as well
-        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
-        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
         const double k1 = fabs(m[6]) + fabs(m[7]);
         const double K = k1 * 1.001;
-        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off || !(k1 >= 0.0009765625) || !(k1 <= 1024.0);
-        const double u = 5.9604644775390625e-8;
+        const bool big = out || !(k1 >= 0.0009765625) || !(k1 <= 1024.0);
         ln.e1 = f32_up(2.0 * u * dn * K);
         ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * dn * K * pn + 1e-18 * (K + 1.0));   // inf: nothing is rejected
         ln.e2 = f32_up(10.5 * u * dn * K);
-        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
         ln.nrm = f32_up(dn * sqrt(m[6] * m[6] + m[7] * m[7]));
-        return ln;
     }
-    // n~ and l~ of a point or a centre: the 3-D line's s~ and l~ on this lane's p and d, then h~ and the final fma
-    static __device__ __forceinline__ float signed_dist(const float* p, const Lane& ln, float* l1) {
-        const float s = Line::dist(p, ln, l1);
-        const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];   // dist's own e~ (the same subtractions)
-        const float h = __builtin_fmaf(e2, ln.d[2], __builtin_fmaf(e1, ln.d[1], e0 * ln.d[0]));
-        return __builtin_fmaf(s, ln.c, -(h * ln.s));
-    }
-    // p = (x, y, z, -, -, P, -, -) in f32
-    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
-        float l1;
-        const float n = signed_dist(p, ln, &l1);
-        const float m = fabsf(n) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
-        return m > ln.tpp;  // false on NaN / inf - inf
-    }
-    // g = (centre[3], rho, Pmax)
-    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
-        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
-        float l1;
-        const float n = signed_dist(g, ln, &l1);
-        const float m = fabsf(n) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
-        return m > ln.tpp * 1.001f;
+    // |n~|: s~ and l~ on this lane's p and d, then h~ and the final fma
+    static __device__ __forceinline__ float magnitude(const float* p, const Lane& ln, float* l1) {
+        const float s = axial_dist(p, ln, l1);
+        const float h = axial_height(p, ln);
+        const float n = __builtin_fmaf(s, ln.c, -(h * ln.s));
+        return fabsf(n);
     }
 };
+template <> struct Filter32<kCone3D> : AxialFilter32<ConeShape32> {};
 
 // ---- tori: r = | sqrt((rho - R)^2 + h^2) - cr |, rho = |(x - c) x d|, h = (x - c) . d (Residual<kTorus3D>), inlier iff r^2 < T2 ------
 // The 3-D line's distance and the cone's dot product, then the 2-D circle's last step in the half-plane (h, rho).  Homogeneous in the
@@ -981,7 +937,7 @@ template <> struct Filter32<kCone3D> {
 // exact path's decision on (d, R, cr, T2) is the one its arithmetic would take on (d sc, R sc, cr sc, T2 sc^2), and the test is against
 // Ts = T sc.  Below d, R and r are the scaled ones, and rho*, h*, w* = sqrt((rho* - R)^2 + h*^2), n* = w* - r are exact on the f64
 // inputs.  Per point, in f32 - this operation order is the contract of the f32 test (tests restate it with fma as one rounding):
-//   s~, l~ = Filter32<kLine3D>::dist(x~, c~, d~)  (the same code; e~_k = x~_k - c~_k),   h~ = fma(e~_2, d~_2, fma(e~_1, d~_1, e~_0 d~_0)),
+//   s~, l~ = axial_dist(x~, c~, d~)  (the shared code; e~_k = x~_k - c~_k),   h~ = axial_height: fma(e~_2, d~_2, fma(e~_1, d~_1, e~_0 d~_0)),
 //   R~ = (float)R,  r~ = (float)r,   t~ = s~ - R~,   w~ = sqrtf(fma(t~, t~, h~ h~)),   n~ = w~ - r~
 // With u = 2^-24, B = sqrt(3) u |d| P + u |d| |c| for the inputs x~ and c~ and t = u |d~| |e~| as in the cone's derivation:
 //   rho        |s~ - rho*| + |rho_c - rho*| <= B + (7.5 + 2^-26) t and the underflow floor: the 3-D line's budget, its exact path included
@@ -1015,72 +971,35 @@ template <> struct Filter32<kCone3D> {
 // entries among them) - and |R| or |r| beyond 1e17 in the filter's units, which a non-finite radius is too (t~^2 + h~^2 stays below
 // 2 (7e17)^2, an ordinary f32).  A NaN entry culls the hypothesis outright (all eight enter every residual).  The exact path is the
 // 3-D line's 17 FP64 operations plus two roots, five operations for h, four for w, a difference and a square.
-template <> struct Filter32<kTorus3D> {
-    using Line = Filter32<kLine3D>;
-    static constexpr bool enabled = true;
-    static constexpr int kRowVals = 6, kGroupVals = 5;
+struct TorusShape32 {
     struct Lane { float p[3]; float d[3]; float R, r, e1, e0, e2, tpp, nrm, nanh; };   // a row of floats in this order (score.hip HypRow)
     // reject() reads p, d, R, r, e1, e0, e2, tpp and nothing behind them (nrm and nanh belong to group_reject): three float4 chunks,
     // the cone's count
     static constexpr int kStagedVals = 12;
+    static constexpr int kModelVals = 8;
     static_assert(offsetof(Lane, d) == 3 * sizeof(float) && offsetof(Lane, R) == 6 * sizeof(float) && offsetof(Lane, e1) == 8 * sizeof(float) &&
                   offsetof(Lane, tpp) == (kStagedVals - 1) * sizeof(float) && offsetof(Lane, nrm) == kStagedVals * sizeof(float) &&
                   sizeof(Lane) == 14 * sizeof(float), "p, d, R, r, e1, e0, e2, tpp lead the lane; nrm, nanh follow");
-    template <class MD> static __device__ __forceinline__ Lane prep(const MD& m, double pscale /* max(|coordinate|, 1) over the set */, double T2) {
-        Lane ln;
-        const double d0[3] = {m[3], m[4], m[5]};
-        bool off;
-        const double sc = pow2_normaliser<3>(d0, &off);
-        bool nan = !(m[6] == m[6]) || !(m[7] == m[7]);
-        double d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            d[k] = d0[k] * sc;
-            ln.p[k] = (float)m[k];
-            ln.d[k] = (float)d[k];
-            nan |= !(m[k] == m[k]) || !(d0[k] == d0[k]);
-        }
-        ln.nanh = nan ? 1.0f : 0.0f;
+    template <class MD> static __device__ __forceinline__ void budget(Lane& ln, const MD& m, double sc, double dn, double pn, double u, bool out) {
         const double R = m[6] * sc, r = m[7] * sc;   // both radii in the scaled direction's units
         ln.R = (float)R;
         ln.r = (float)r;
-        const double Ts = sqrt(T2) * sc;   // the threshold in the same units: must be an ordinary f32 as well
-        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * 1.001;
-        const double pn = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) * 1.001;
-        const bool big = !(pscale <= 1e17) || !(pn <= 1e17) || !(fabs(R) <= 1e17) || !(fabs(r) <= 1e17) || !(Ts > 1e-30) || !(Ts < 1e30) || off;
-        const double u = 5.9604644775390625e-8;
+        const bool big = out || !(fabs(R) <= 1e17) || !(fabs(r) <= 1e17);
         ln.e1 = f32_up(4.0 * u * dn);
         ln.e0 = big ? __builtin_inff() : f32_up(2.0 * u * ((2.0 * dn * pn + 3.0 * fabs(R)) + fabs(r)) + 2e-18);   // inf: nothing is rejected
         ln.e2 = f32_up(18.0 * u * dn);
-        ln.tpp = f32_up(Ts * (1.0 + 1.0 / 64.0));
         ln.nrm = f32_up(dn);
-        return ln;
     }
-    // n~ and l~ of a point or a centre: the 3-D line's s~ and l~ on this lane's p and d, then h~, t~, w~ and the last difference
-    static __device__ __forceinline__ float signed_dist(const float* p, const Lane& ln, float* l1) {
-        const float s = Line::dist(p, ln, l1);
-        const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];   // dist's own e~ (the same subtractions)
-        const float h = __builtin_fmaf(e2, ln.d[2], __builtin_fmaf(e1, ln.d[1], e0 * ln.d[0]));
+    // |n~|: s~ and l~ on this lane's p and d, then h~, t~, w~ and the last difference
+    static __device__ __forceinline__ float magnitude(const float* p, const Lane& ln, float* l1) {
+        const float s = axial_dist(p, ln, l1);
+        const float h = axial_height(p, ln);
         const float t = s - ln.R;
         const float w = sqrtf(__builtin_fmaf(t, t, h * h));
-        return w - ln.r;
-    }
-    // p = (x, y, z, -, -, P, -, -) in f32
-    static __device__ __forceinline__ bool reject(const float* p, const Lane& ln, float) {
-        float l1;
-        const float n = signed_dist(p, ln, &l1);
-        const float m = fabsf(n) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));
-        return m > ln.tpp;  // false on NaN / inf - inf
-    }
-    // g = (centre[3], rho, Pmax)
-    static __device__ __forceinline__ bool group_reject(const float* g, const Lane& ln, float) {
-        if (ln.nanh != 0.0f) return true;  // NaN entry in the hypothesis: every residual is NaN, never an inlier
-        float l1;
-        const float n = signed_dist(g, ln, &l1);
-        const float m = fabsf(n) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;
-        return m > ln.tpp * 1.001f;
+        return fabsf(w - ln.r);
     }
 };
+template <> struct Filter32<kTorus3D> : AxialFilter32<TorusShape32> {};
 
 // ---- mixed primitives: the constituent's filter behind the class (Residual<kPrimitive3D>) -------------------------------------------
 // Nothing is derived here.  A lane is the class followed by the constituent's own lane, float for float as its prep() made it from the

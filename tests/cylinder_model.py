@@ -12,8 +12,6 @@ product.
   literals (header_literals reads them out of the header's text), f32 arithmetic as in line3d_filter_model.py (mpmath at 24 bits, fma
   one rounding).
 """
-import re
-
 import numpy as np
 
 import line3d_filter_model as L3
@@ -224,107 +222,63 @@ def refit_ratios(model, ref, pts):
 
 
 # ---- the f32 filter -------------------------------------------------------------------------------------------------------------------
-MODEL_LITERALS = dict(u=5.9604644775390625e-8, e1=2.0, e0=2.0, floor=1e-18, e2=8.0, dn_inflate=1.001, pn_inflate=1.001, pscale_max=1e17,
-                      pn_max=1e17, r_max=1e17, ts_min=1e-30, ts_max=1e30, margin_inv=64.0, group_l1_rho=1.74, group_rho=1.001,
-                      group_tpp=1.001)
+# the cylinder's shape, CylinderShape32; the shared part (AxialFilter32) is line3d_filter_model's
+MODEL_LITERALS = dict(L3.SHARED_LITERALS, e1=2.0, e0=2.0, floor=1e-18, e2=8.0, r_max=1e17)
 
 _LITERAL_PATTERNS = [
-    (("u",), r"const double u = NUM;"),
     (("e1",), r"ln\.e1 = f32_up\(NUM \* u \* dn\);"),
     (("e0", "floor"), r"ln\.e0 = big \? __builtin_inff\(\) : f32_up\(NUM \* u \* \(dn \* pn \+ fabs\(R\)\) \+ NUM\);"),
     (("e2",), r"ln\.e2 = f32_up\(NUM \* u \* dn\);"),
-    (("dn_inflate",), r"const double dn = sqrt\(\(d\[0\] \* d\[0\] \+ d\[1\] \* d\[1\]\) \+ d\[2\] \* d\[2\]\) \* NUM;"),
-    (("pn_inflate",), r"const double pn = sqrt\(\(m\[0\] \* m\[0\] \+ m\[1\] \* m\[1\]\) \+ m\[2\] \* m\[2\]\) \* NUM;"),
-    (("pscale_max", "pn_max", "r_max", "ts_min", "ts_max"),
-     r"const bool big = !\(pscale <= NUM\) \|\| !\(pn <= NUM\) \|\| !\(fabs\(R\) <= NUM\) \|\| !\(Ts > NUM\) \|\| !\(Ts < NUM\) \|\| off;"),
-    (("margin_inv",), r"ln\.tpp = f32_up\(Ts \* \(1\.0 \+ 1\.0 / NUM\)\);"),
-    (("group_l1_rho",), r"__builtin_fmaf\(NUMf, g\[3\], l1\)"),
-    (("group_rho",), r"- ln\.nrm \* g\[3\] \* NUMf;"),
-    (("group_tpp",), r"return m > ln\.tpp \* NUMf;"),
+    (("r_max",), r"const bool big = out \|\| !\(fabs\(R\) <= NUM\);"),
 ]
 
-# the header's statements of the f32 test's operation order, as prep, reject and group_reject below restate them (dist is the 3-D
-# line's: line3d_filter_model.OPERATION_LINES holds its statements)
-OPERATION_LINES = [
+# the header's statements of the f32 test's operation order, as prep and _magnitude below restate them, behind the shared block's
+OPERATION_LINES = L3.SHARED_OPERATION_LINES + [
     "const double R = m[6] * sc;",
     "ln.r = (float)R;",
-    "const double Ts = sqrt(T2) * sc;",
     "ln.nrm = f32_up(dn);",
-    "static __device__ __forceinline__ float dist(const float* p, const Lane& ln, float* l1) { return Line::dist(p, ln, l1); }",
-    "const float m = fabsf(s - ln.r) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));",
-    "return m > ln.tpp;",
-    "if (ln.nanh != 0.0f) return true;",
-    "const float m = fabsf(s - ln.r) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;",
-    "return m > ln.tpp * 1.001f;",
+    "const float s = axial_dist(p, ln, l1);",
+    "return fabsf(s - ln.r);",
 ]
 
 
 def header_block():
-    """the text of `template <> struct Filter32<kCylinder3D> { ... };` in score_filters.hip.h"""
-    text = open(L3.HEADER).read()
-    start = text.index("template <> struct Filter32<kCylinder3D> {")
-    return text[start:text.index("\n};\n", start)]
+    return L3.axial_header_block("CylinderShape32")
 
 
 def header_literals():
-    block = header_block()
-    out = {}
-    for names, pat in _LITERAL_PATTERNS:
-        found = re.findall(pat.replace("NUM", L3._NUM), block)
-        assert len(found) == 1, (names, found)
-        values = found[0] if isinstance(found[0], tuple) else (found[0],)
-        for k, v in zip(names, values):
-            out[k] = float(v)
-    return out
+    return L3.axial_header_literals("CylinderShape32", _LITERAL_PATTERNS)
 
 
 def prep(m, pscale, T2, plant_zero_budget=False, lit=None):
     """Filter32<kCylinder3D>::prep in float64, the lane's floats as Python floats holding f32 values"""
     L = MODEL_LITERALS if lit is None else lit
-    m = [float(v) for v in m]
-    sc, off = L3.pow2_normaliser(m[3:6])
-    with np.errstate(over="ignore", invalid="ignore"):
-        d = [np.float64(m[3 + k]) * sc for k in range(3)]
-        ln = dict(p=[f32(m[k]) for k in range(3)], d=[f32(d[k]) for k in range(3)])
-        ln["nanh"] = 1.0 if any(v != v for v in m) else 0.0
+
+    def budget(ln, m, sc, dn, pn, u, out):
         R = np.float64(m[6]) * sc
         ln["r"] = f32(R)
-        Ts = np.sqrt(np.float64(T2)) * sc
-        dn = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * L["dn_inflate"]
-        pn = np.sqrt((np.float64(m[0]) * m[0] + np.float64(m[1]) * m[1]) + np.float64(m[2]) * m[2]) * L["pn_inflate"]
-        big = (not (pscale <= L["pscale_max"]) or not (pn <= L["pn_max"]) or not (abs(R) <= L["r_max"]) or not (Ts > L["ts_min"])
-               or not (Ts < L["ts_max"]) or off)
-        u = L["u"]
+        big = out or not (abs(R) <= L["r_max"])
         ln["e1"] = f32_up(L["e1"] * u * dn)
         ln["e0"] = float("inf") if big else f32_up(L["e0"] * u * (dn * pn + abs(R)) + L["floor"])
         ln["e2"] = f32_up(L["e2"] * u * dn)
-        ln["tpp"] = f32_up(Ts * (1.0 + 1.0 / L["margin_inv"]))
         ln["nrm"] = f32_up(dn)
-        ln["lit"] = L
-    if plant_zero_budget:
-        ln["e1"] = ln["e0"] = ln["e2"] = 0.0
-    return ln
+    return L3.axial_prep(m, pscale, T2, L, budget, plant_zero_budget)
+
+
+def _magnitude(row, ln):
+    """CylinderShape32::magnitude: (|s~ - r~|, l~)"""
+    s, l1 = L3._dist(row, ln)
+    return abs(s - L3._mp24().mpf(ln["r"])), l1
 
 
 def reject(row, ln):
     """row = (x~, y~, z~, P): Filter32<kCylinder3D>::reject"""
-    c = L3._mp24()
-    s, l1 = L3._dist(row, ln)
-    m = abs(s - c.mpf(ln["r"])) - L3._fma(c, c.mpf(ln["e2"]), l1, L3._fma(c, c.mpf(ln["e1"]), c.mpf(row[3]), c.mpf(ln["e0"])))
-    return bool(m > c.mpf(ln["tpp"]))
+    return L3.axial_reject(_magnitude, row, ln)
 
 
 def group_reject(g, ln):
     """g = (centre[3], rho, Pmax): Filter32<kCylinder3D>::group_reject"""
-    if ln["nanh"] != 0.0:
-        return True
-    c = L3._mp24()
-    s, l1 = L3._dist(g, ln)
-    rho, L = c.mpf(g[3]), ln["lit"]
-    E = L3._fma(c, c.mpf(ln["e2"]), L3._fma(c, c.mpf(f32(L["group_l1_rho"])), rho, l1),
-                L3._fma(c, c.mpf(ln["e1"]), c.mpf(g[4]), c.mpf(ln["e0"])))
-    m = abs(s - c.mpf(ln["r"])) - E - c.mpf(ln["nrm"]) * rho * c.mpf(f32(L["group_rho"]))
-    return bool(m > c.mpf(ln["tpp"]) * c.mpf(f32(L["group_tpp"])))
+    return L3.axial_group_reject(_magnitude, g, ln)
 
 
 # ---- the cases the CPU and the GPU tests share ----

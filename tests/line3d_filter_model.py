@@ -7,7 +7,10 @@ product.
   added operation is exact, so the oracle evaluates the line residual bit for bit without knowing the type.  Needs finite c.
 * prep / reject / group_reject: Filter32<kLine3D> (csrc/score_filters.hip.h) in the header's operation order and with the header's
   literals.  header_literals() reads the literals out of the header's text and OPERATION_LINES are the header's statements of the
-  operation order, so a test can hold model and header together: a coefficient or a statement changed on one side only fails it.  f32 arithmetic is mpmath at 24 bits of precision, fma an exact product and a sum rounded once (numpy has no fmaf, and an
+  operation order, so a test can hold model and header together: a coefficient or a statement changed on one side only fails it.
+  The part the header states once for the four axial types (AxialFilter32, axial_dist, axial_height) is restated once, here
+  (SHARED_*, axial_prep, axial_reject, axial_group_reject); cylinder_model.py, cone_model.py and torus_model.py add their shapes.
+  f32 arithmetic is mpmath at 24 bits of precision, fma an exact product and a sum rounded once (numpy has no fmaf, and an
   fma emulated through float64 rounds twice).  mpmath has no exponent limits: the model is for operands inside the f32 range, which
   is what prep's switch-off leaves.
 * point_row / group_row: the f32 rows of setpoints.hip (coordinates and P; the stored centre, the inflated radius about it, Pmax).
@@ -49,62 +52,99 @@ def sym_points(pts, m):
 # ---- the f32 filter ---------------------------------------------------------------------------------------------------------------
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "progressive-x_amd", "csrc", "score_filters.hip.h")
 
-# the literals of Filter32<kLine3D> as this model states them; header_literals() must give the same
-MODEL_LITERALS = dict(u=5.9604644775390625e-8, e1=2.0, e0=2.0, floor=1e-18, e2=8.0, dn_inflate=1.001, pn_inflate=1.001, pscale_max=1e17,
-                      pn_max=1e17, ts_min=1e-30, ts_max=1e30, margin_inv=64.0, group_l1_rho=1.74, group_rho=1.001, group_tpp=1.001)
+# The four axial filters (3-D line, cylinder, cone, torus) share AxialFilter32 in the header, and their restatements share this part:
+# the literals and statements of the shared block, prep's opening and end, the tails of reject and group_reject.  A type's module
+# (this one for the 3-D line) states its shape: its own literals and statements, its budget lines and the quantity that is compared.
+SHARED_LITERALS = dict(u=5.9604644775390625e-8, dn_inflate=1.001, pn_inflate=1.001, pscale_max=1e17, pn_max=1e17, ts_min=1e-30,
+                       ts_max=1e30, margin_inv=64.0, group_l1_rho=1.74, group_rho=1.001, group_tpp=1.001)
 
 _NUM = r"([0-9][0-9.e+-]*)"
-_LITERAL_PATTERNS = [
+_SHARED_PATTERNS = [
     (("u",), r"const double u = NUM;"),
-    (("e1",), r"ln\.e1 = f32_up\(NUM \* u \* dn\);"),
-    (("e0", "floor"), r"ln\.e0 = big \? __builtin_inff\(\) : f32_up\(NUM \* u \* dn \* pn \+ NUM\);"),
-    (("e2",), r"ln\.e2 = f32_up\(NUM \* u \* dn\);"),
     (("dn_inflate",), r"const double dn = sqrt\(\(d\[0\] \* d\[0\] \+ d\[1\] \* d\[1\]\) \+ d\[2\] \* d\[2\]\) \* NUM;"),
     (("pn_inflate",), r"const double pn = sqrt\(\(m\[0\] \* m\[0\] \+ m\[1\] \* m\[1\]\) \+ m\[2\] \* m\[2\]\) \* NUM;"),
     (("pscale_max", "pn_max", "ts_min", "ts_max"),
-     r"const bool big = !\(pscale <= NUM\) \|\| !\(pn <= NUM\) \|\| !\(Ts > NUM\) \|\| !\(Ts < NUM\) \|\| off;"),
+     r"const bool out = !\(pscale <= NUM\) \|\| !\(pn <= NUM\) \|\| !\(Ts > NUM\) \|\| !\(Ts < NUM\) \|\| off;"),
     (("margin_inv",), r"ln\.tpp = f32_up\(Ts \* \(1\.0 \+ 1\.0 / NUM\)\);"),
     (("group_l1_rho",), r"__builtin_fmaf\(NUMf, g\[3\], l1\)"),
     (("group_rho",), r"- ln\.nrm \* g\[3\] \* NUMf;"),
     (("group_tpp",), r"return m > ln\.tpp \* NUMf;"),
 ]
 
-# the header's statements of the f32 test's operation order, as _dist, reject and group_reject below restate them
-OPERATION_LINES = [
+# the shared block's statements of the f32 test's operation order, as prep_open, dist, height, reject_tail and group_tail restate them
+SHARED_OPERATION_LINES = [
     "const double Ts = sqrt(T2) * sc;",
-    "ln.nrm = f32_up(dn);",
     "const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];",
     "const float c0 = __builtin_fmaf(e1, d[2], -(e2 * d[1]));",
     "const float c1 = __builtin_fmaf(e2, d[0], -(e0 * d[2]));",
     "const float c2 = __builtin_fmaf(e0, d[1], -(e1 * d[0]));",
     "*l1 = (fabsf(e0) + fabsf(e1)) + fabsf(e2);",
     "return sqrtf(__builtin_fmaf(c0, c0, __builtin_fmaf(c1, c1, c2 * c2)));",
-    "const float m = s - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));",
+    "return __builtin_fmaf(e2, ln.d[2], __builtin_fmaf(e1, ln.d[1], e0 * ln.d[0]));",
+    "const float a = Shape::magnitude(p, ln, &l1);",
+    "const float m = a - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));",
     "return m > ln.tpp;",
     "if (ln.nanh != 0.0f) return true;",
-    "const float m = s - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;",
+    "const float a = Shape::magnitude(g, ln, &l1);",
+    "const float m = a - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;",
     "return m > ln.tpp * 1.001f;",
 ]
 
+# the 3-D line's shape: LineShape32
+MODEL_LITERALS = dict(SHARED_LITERALS, e1=2.0, e0=2.0, floor=1e-18, e2=8.0)
+_LITERAL_PATTERNS = [
+    (("e1",), r"ln\.e1 = f32_up\(NUM \* u \* dn\);"),
+    (("e0", "floor"), r"ln\.e0 = big \? __builtin_inff\(\) : f32_up\(NUM \* u \* dn \* pn \+ NUM\);"),
+    (("e2",), r"ln\.e2 = f32_up\(NUM \* u \* dn\);"),
+]
+OPERATION_LINES = SHARED_OPERATION_LINES + [
+    "ln.nrm = f32_up(dn);",
+    "static __device__ __forceinline__ float magnitude(const float* p, const Lane& ln, float* l1) { return axial_dist(p, ln, l1); }",
+]
 
-def header_block():
-    """the text of `template <> struct Filter32<kLine3D> { ... };` in score_filters.hip.h"""
+
+def shared_block():
+    """the header's text from the axial family's opening comment to the end of `template <class Shape> struct AxialFilter32 { ... };`"""
     text = open(HEADER).read()
-    start = text.index("template <> struct Filter32<kLine3D> {")
+    start = text.index("// ---- the axial family:")
+    return text[start:text.index("\n};\n", text.index("template <class Shape> struct AxialFilter32 : Shape {", start))]
+
+
+def shape_block(shape):
+    """the text of `struct <shape> { ... };` in score_filters.hip.h"""
+    text = open(HEADER).read()
+    start = text.index("struct %s {" % shape)
     return text[start:text.index("\n};\n", start)]
 
 
-def header_literals():
-    """MODEL_LITERALS' entries as the header's text has them"""
-    block = header_block()
+def read_literals(block, patterns):
+    """the patterns' literals as `block` has them, each pattern found exactly once"""
     out = {}
-    for names, pat in _LITERAL_PATTERNS:
+    for names, pat in patterns:
         found = re.findall(pat.replace("NUM", _NUM), block)
         assert len(found) == 1, (names, found)
         values = found[0] if isinstance(found[0], tuple) else (found[0],)
         for k, v in zip(names, values):
             out[k] = float(v)
     return out
+
+
+def axial_header_block(shape):
+    """the shared block followed by the shape's: where a type's statements stand"""
+    return shared_block() + "\n" + shape_block(shape)
+
+
+def axial_header_literals(shape, patterns):
+    """a type's MODEL_LITERALS as the header's text has them: the shared ones read from the shared block, its own from its shape's"""
+    return dict(read_literals(shared_block(), _SHARED_PATTERNS), **read_literals(shape_block(shape), patterns))
+
+
+def header_block():
+    return axial_header_block("LineShape32")
+
+
+def header_literals():
+    return axial_header_literals("LineShape32", _LITERAL_PATTERNS)
 
 
 _ctx = None
@@ -141,10 +181,10 @@ def pow2_normaliser(d):
     return float(np.ldexp(1.0, -int(e))), off
 
 
-def prep(m, pscale, T2, plant_zero_budget=False, lit=None):
-    """Filter32<kLine3D>::prep in float64, the lane's floats as Python floats holding f32 values.  plant_zero_budget: E = 0, for the
-    test that shows a missing budget is seen."""
-    L = MODEL_LITERALS if lit is None else lit
+def axial_prep(m, pscale, T2, L, budget, plant_zero_budget=False):
+    """AxialFilter32<Shape>::prep in float64, the lane's floats as Python floats holding f32 values: the shared opening, then
+    budget(ln, m, sc, dn, pn, u, out) - the shape's own fields, e1, e0, e2 and nrm - and tpp.  plant_zero_budget: E = 0, for the test
+    that shows a missing budget is seen."""
     m = [float(v) for v in m]
     sc, off = pow2_normaliser(m[3:6])
     with np.errstate(over="ignore", invalid="ignore"):
@@ -154,17 +194,25 @@ def prep(m, pscale, T2, plant_zero_budget=False, lit=None):
         Ts = np.sqrt(np.float64(T2)) * sc
         dn = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * L["dn_inflate"]
         pn = np.sqrt((np.float64(m[0]) * m[0] + np.float64(m[1]) * m[1]) + np.float64(m[2]) * m[2]) * L["pn_inflate"]
-        big = not (pscale <= L["pscale_max"]) or not (pn <= L["pn_max"]) or not (Ts > L["ts_min"]) or not (Ts < L["ts_max"]) or off
-        u = L["u"]
-        ln["e1"] = f32_up(L["e1"] * u * dn)
-        ln["e0"] = float("inf") if big else f32_up(L["e0"] * u * dn * pn + L["floor"])
-        ln["e2"] = f32_up(L["e2"] * u * dn)
+        out = not (pscale <= L["pscale_max"]) or not (pn <= L["pn_max"]) or not (Ts > L["ts_min"]) or not (Ts < L["ts_max"]) or off
+        budget(ln, m, sc, dn, pn, L["u"], out)
         ln["tpp"] = f32_up(Ts * (1.0 + 1.0 / L["margin_inv"]))
-        ln["nrm"] = f32_up(dn)
         ln["lit"] = L
     if plant_zero_budget:
         ln["e1"] = ln["e0"] = ln["e2"] = 0.0
     return ln
+
+
+def prep(m, pscale, T2, plant_zero_budget=False, lit=None):
+    """Filter32<kLine3D>::prep"""
+    L = MODEL_LITERALS if lit is None else lit
+
+    def budget(ln, m, sc, dn, pn, u, big):
+        ln["e1"] = f32_up(L["e1"] * u * dn)
+        ln["e0"] = float("inf") if big else f32_up(L["e0"] * u * dn * pn + L["floor"])
+        ln["e2"] = f32_up(L["e2"] * u * dn)
+        ln["nrm"] = f32_up(dn)
+    return axial_prep(m, pscale, T2, L, budget, plant_zero_budget)
 
 
 def _fma(c, a, b, d):
@@ -172,6 +220,7 @@ def _fma(c, a, b, d):
 
 
 def _dist(row, ln):
+    """axial_dist: (s~, l~)"""
     c = _mp24()
     x = [c.mpf(v) for v in row[:3]]
     p = [c.mpf(v) for v in ln["p"]]
@@ -184,24 +233,44 @@ def _dist(row, ln):
     return c.sqrt(_fma(c, c0, c0, _fma(c, c1, c1, c2 * c2))), l1
 
 
-def reject(row, ln):
-    """row = (x~, y~, z~, P): Filter32<kLine3D>::reject"""
+def _height(row, ln):
+    """axial_height: h~"""
     c = _mp24()
-    s, l1 = _dist(row, ln)
-    m = s - _fma(c, c.mpf(ln["e2"]), l1, _fma(c, c.mpf(ln["e1"]), c.mpf(row[3]), c.mpf(ln["e0"])))
+    x = [c.mpf(v) for v in row[:3]]
+    p = [c.mpf(v) for v in ln["p"]]
+    d = [c.mpf(v) for v in ln["d"]]
+    e0, e1, e2 = x[0] - p[0], x[1] - p[1], x[2] - p[2]
+    return _fma(c, e2, d[2], _fma(c, e1, d[1], e0 * d[0]))
+
+
+def axial_reject(magnitude, row, ln):
+    """row = (x~, y~, z~, P): AxialFilter32<Shape>::reject with the shape's magnitude(row, ln) = (the compared quantity, l~)"""
+    c = _mp24()
+    a, l1 = magnitude(row, ln)
+    m = a - _fma(c, c.mpf(ln["e2"]), l1, _fma(c, c.mpf(ln["e1"]), c.mpf(row[3]), c.mpf(ln["e0"])))
     return bool(m > c.mpf(ln["tpp"]))
 
 
-def group_reject(g, ln):
-    """g = (centre[3], rho, Pmax): Filter32<kLine3D>::group_reject"""
+def axial_group_reject(magnitude, g, ln):
+    """g = (centre[3], rho, Pmax): AxialFilter32<Shape>::group_reject"""
     if ln["nanh"] != 0.0:
         return True
     c = _mp24()
-    s, l1 = _dist(g, ln)
+    a, l1 = magnitude(g, ln)
     rho, L = c.mpf(g[3]), ln["lit"]
     E = _fma(c, c.mpf(ln["e2"]), _fma(c, c.mpf(f32(L["group_l1_rho"])), rho, l1), _fma(c, c.mpf(ln["e1"]), c.mpf(g[4]), c.mpf(ln["e0"])))
-    m = s - E - c.mpf(ln["nrm"]) * rho * c.mpf(f32(L["group_rho"]))
+    m = a - E - c.mpf(ln["nrm"]) * rho * c.mpf(f32(L["group_rho"]))
     return bool(m > c.mpf(ln["tpp"]) * c.mpf(f32(L["group_tpp"])))
+
+
+def reject(row, ln):
+    """Filter32<kLine3D>::reject: s~ itself is compared"""
+    return axial_reject(_dist, row, ln)
+
+
+def group_reject(g, ln):
+    """Filter32<kLine3D>::group_reject"""
+    return axial_group_reject(_dist, g, ln)
 
 
 def point_row(x):

@@ -19,7 +19,7 @@ from test_emu import emu  # noqa: F401  (the fixture that builds and loads libmf
 
 BOX, BOXALL, BALL, VANISHING = 0, 1, 2, 3          # score_plan.h GroupBound
 # name: (Filter<MT>::enabled, Filter32<MT>::enabled, Residual<MT>::bound, Filter32<MT> derives from Filter32<kHomography>)
-#   score_filters.hip.h:36,61,89 (Filter) and :147,215,296,375,435,454,508,572 (Filter32); residuals.hip.h:48,63,80,103,121,138,158,174 (bound)
+#   score_filters.hip.h:31,39,64,91 (Filter) and :128,172,250,331,410,469,518 + 566-567,614 + 663 (Filter32); residuals.hip.h:48,63,80,103,121,138,158,174 (bound)
 TYPES = {"line": (0, 1, BALL, 0), "homography": (1, 1, BOX, 1), "fundamental": (0, 1, BOXALL, 0), "pnp": (1, 1, BOX, 0),
          "vanishing_point": (0, 1, VANISHING, 0), "homography_sym": (1, 1, BOX, 1), "plane": (0, 1, BALL, 0), "sphere": (0, 1, BALL, 0)}
 K_SUPER = 8                 # pgx_internal.h:208

@@ -15,8 +15,6 @@
   literals (header_literals reads them out of the header's text), f32 arithmetic as in line3d_filter_model.py (mpmath at 24 bits, fma
   one rounding).
 """
-import re
-
 import numpy as np
 
 import line3d_filter_model as L3
@@ -523,127 +521,72 @@ def refit_ratios(model, ref, pts):
 
 
 # ---- the f32 filter -------------------------------------------------------------------------------------------------------------------
-MODEL_LITERALS = dict(u=5.9604644775390625e-8, e1=4.0, e0=2.0, e0_pn=2.0, e0_R=3.0, floor=2e-18, e2=18.0, dn_inflate=1.001, pn_inflate=1.001,
-                      pscale_max=1e17, pn_max=1e17, R_max=1e17, r_max=1e17, ts_min=1e-30, ts_max=1e30, margin_inv=64.0,
-                      group_l1_rho=1.74, group_rho=1.001, group_tpp=1.001)
+# the torus' shape, TorusShape32; the shared part (AxialFilter32) is line3d_filter_model's
+MODEL_LITERALS = dict(L3.SHARED_LITERALS, e1=4.0, e0=2.0, e0_pn=2.0, e0_R=3.0, floor=2e-18, e2=18.0, R_max=1e17, r_max=1e17)
 
 _LITERAL_PATTERNS = [
-    (("u",), r"const double u = NUM;"),
     (("e1",), r"ln\.e1 = f32_up\(NUM \* u \* dn\);"),
     (("e0", "e0_pn", "e0_R", "floor"),
      r"ln\.e0 = big \? __builtin_inff\(\) : f32_up\(NUM \* u \* \(\(NUM \* dn \* pn \+ NUM \* fabs\(R\)\) \+ fabs\(r\)\) \+ NUM\);"),
     (("e2",), r"ln\.e2 = f32_up\(NUM \* u \* dn\);"),
-    (("dn_inflate",), r"const double dn = sqrt\(\(d\[0\] \* d\[0\] \+ d\[1\] \* d\[1\]\) \+ d\[2\] \* d\[2\]\) \* NUM;"),
-    (("pn_inflate",), r"const double pn = sqrt\(\(m\[0\] \* m\[0\] \+ m\[1\] \* m\[1\]\) \+ m\[2\] \* m\[2\]\) \* NUM;"),
-    (("pscale_max", "pn_max", "R_max", "r_max", "ts_min", "ts_max"),
-     r"const bool big = !\(pscale <= NUM\) \|\| !\(pn <= NUM\) \|\| !\(fabs\(R\) <= NUM\) \|\| !\(fabs\(r\) <= NUM\) \|\| !\(Ts > NUM\) \|\| !\(Ts < NUM\) \|\| off;"),
-    (("margin_inv",), r"ln\.tpp = f32_up\(Ts \* \(1\.0 \+ 1\.0 / NUM\)\);"),
-    (("group_l1_rho",), r"__builtin_fmaf\(NUMf, g\[3\], l1\)"),
-    (("group_rho",), r"- ln\.nrm \* g\[3\] \* NUMf;"),
-    (("group_tpp",), r"return m > ln\.tpp \* NUMf;"),
+    (("R_max", "r_max"), r"const bool big = out \|\| !\(fabs\(R\) <= NUM\) \|\| !\(fabs\(r\) <= NUM\);"),
 ]
 
-# the header's statements of the f32 test's operation order, as prep, _signed, reject and group_reject below restate them (dist is the
-# 3-D line's: line3d_filter_model.OPERATION_LINES holds its statements)
-OPERATION_LINES = [
+# the header's statements of the f32 test's operation order, as prep and _magnitude below restate them, behind the shared block's
+OPERATION_LINES = L3.SHARED_OPERATION_LINES + [
     "const double R = m[6] * sc, r = m[7] * sc;",
     "ln.R = (float)R;",
     "ln.r = (float)r;",
-    "const double Ts = sqrt(T2) * sc;",
     "ln.nrm = f32_up(dn);",
-    "const float s = Line::dist(p, ln, l1);",
-    "const float e0 = p[0] - ln.p[0], e1 = p[1] - ln.p[1], e2 = p[2] - ln.p[2];",
-    "const float h = __builtin_fmaf(e2, ln.d[2], __builtin_fmaf(e1, ln.d[1], e0 * ln.d[0]));",
+    "const float s = axial_dist(p, ln, l1);",
+    "const float h = axial_height(p, ln);",
     "const float t = s - ln.R;",
     "const float w = sqrtf(__builtin_fmaf(t, t, h * h));",
-    "return w - ln.r;",
-    "const float m = fabsf(n) - __builtin_fmaf(ln.e2, l1, __builtin_fmaf(ln.e1, p[5], ln.e0));",
-    "return m > ln.tpp;",
-    "if (ln.nanh != 0.0f) return true;",
-    "const float m = fabsf(n) - __builtin_fmaf(ln.e2, __builtin_fmaf(1.74f, g[3], l1), __builtin_fmaf(ln.e1, g[4], ln.e0)) - ln.nrm * g[3] * 1.001f;",
-    "return m > ln.tpp * 1.001f;",
+    "return fabsf(w - ln.r);",
 ]
 
 
 def header_block():
-    """the text of `template <> struct Filter32<kTorus3D> { ... };` in score_filters.hip.h"""
-    text = open(L3.HEADER).read()
-    start = text.index("template <> struct Filter32<kTorus3D> {")
-    return text[start:text.index("\n};\n", start)]
+    return L3.axial_header_block("TorusShape32")
 
 
 def header_literals():
-    block = header_block()
-    out = {}
-    for names, pat in _LITERAL_PATTERNS:
-        found = re.findall(pat.replace("NUM", L3._NUM), block)
-        assert len(found) == 1, (names, found)
-        values = found[0] if isinstance(found[0], tuple) else (found[0],)
-        for k, v in zip(names, values):
-            out[k] = float(v)
-    return out
+    return L3.axial_header_literals("TorusShape32", _LITERAL_PATTERNS)
 
 
 def prep(m, pscale, T2, plant_zero_budget=False, lit=None):
     """Filter32<kTorus3D>::prep in float64, the lane's floats as Python floats holding f32 values"""
     L = MODEL_LITERALS if lit is None else lit
-    m = [float(v) for v in m]
-    sc, off = L3.pow2_normaliser(m[3:6])
-    with np.errstate(over="ignore", invalid="ignore"):
-        d = [np.float64(m[3 + k]) * sc for k in range(3)]
+
+    def budget(ln, m, sc, dn, pn, u, out):
         R, r = np.float64(m[6]) * sc, np.float64(m[7]) * sc
-        ln = dict(p=[f32(m[k]) for k in range(3)], d=[f32(d[k]) for k in range(3)], R=f32(R), r=f32(r))
-        ln["nanh"] = 1.0 if any(v != v for v in m) else 0.0
-        Ts = np.sqrt(np.float64(T2)) * sc
-        dn = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) * L["dn_inflate"]
-        pn = np.sqrt((np.float64(m[0]) * m[0] + np.float64(m[1]) * m[1]) + np.float64(m[2]) * m[2]) * L["pn_inflate"]
-        big = (not (pscale <= L["pscale_max"]) or not (pn <= L["pn_max"]) or not (abs(R) <= L["R_max"]) or not (abs(r) <= L["r_max"])
-               or not (Ts > L["ts_min"]) or not (Ts < L["ts_max"]) or off)
-        u = L["u"]
+        ln["R"], ln["r"] = f32(R), f32(r)
+        big = out or not (abs(R) <= L["R_max"]) or not (abs(r) <= L["r_max"])
         ln["e1"] = f32_up(L["e1"] * u * dn)
         ln["e0"] = float("inf") if big else f32_up(L["e0"] * u * ((L["e0_pn"] * dn * pn + L["e0_R"] * abs(R)) + abs(r)) + L["floor"])
         ln["e2"] = f32_up(L["e2"] * u * dn)
-        ln["tpp"] = f32_up(Ts * (1.0 + 1.0 / L["margin_inv"]))
         ln["nrm"] = f32_up(dn)
-        ln["lit"] = L
-    if plant_zero_budget:
-        ln["e1"] = ln["e0"] = ln["e2"] = 0.0
-    return ln
+    return L3.axial_prep(m, pscale, T2, L, budget, plant_zero_budget)
 
 
-def _signed(row, ln):
-    """Filter32<kTorus3D>::signed_dist: (n~, l~)"""
+def _magnitude(row, ln):
+    """TorusShape32::magnitude: (|n~|, l~)"""
     c = L3._mp24()
     s, l1 = L3._dist(row, ln)
-    x = [c.mpf(v) for v in row[:3]]
-    p = [c.mpf(v) for v in ln["p"]]
-    d = [c.mpf(v) for v in ln["d"]]
-    e0, e1, e2 = x[0] - p[0], x[1] - p[1], x[2] - p[2]
-    h = L3._fma(c, e2, d[2], L3._fma(c, e1, d[1], e0 * d[0]))
+    h = L3._height(row, ln)
     t = s - c.mpf(ln["R"])
     w = c.sqrt(L3._fma(c, t, t, h * h))
-    return w - c.mpf(ln["r"]), l1
+    return abs(w - c.mpf(ln["r"])), l1
 
 
 def reject(row, ln):
     """row = (x~, y~, z~, P): Filter32<kTorus3D>::reject"""
-    c = L3._mp24()
-    n, l1 = _signed(row, ln)
-    m = abs(n) - L3._fma(c, c.mpf(ln["e2"]), l1, L3._fma(c, c.mpf(ln["e1"]), c.mpf(row[3]), c.mpf(ln["e0"])))
-    return bool(m > c.mpf(ln["tpp"]))
+    return L3.axial_reject(_magnitude, row, ln)
 
 
 def group_reject(g, ln):
     """g = (centre[3], rho, Pmax): Filter32<kTorus3D>::group_reject"""
-    if ln["nanh"] != 0.0:
-        return True
-    c = L3._mp24()
-    n, l1 = _signed(g, ln)
-    rho, L = c.mpf(g[3]), ln["lit"]
-    E = L3._fma(c, c.mpf(ln["e2"]), L3._fma(c, c.mpf(f32(L["group_l1_rho"])), rho, l1),
-                L3._fma(c, c.mpf(ln["e1"]), c.mpf(g[4]), c.mpf(ln["e0"])))
-    m = abs(n) - E - c.mpf(ln["nrm"]) * rho * c.mpf(f32(L["group_rho"]))
-    return bool(m > c.mpf(ln["tpp"]) * c.mpf(f32(L["group_tpp"])))
+    return L3.axial_group_reject(_magnitude, g, ln)
 
 
 RATIOS = (1.05, 2.0, 5.0, 20.0, 50.0)
