@@ -475,6 +475,56 @@ int pgx_estimate_normals(pgx_ctx *ctx, const double *points, int64_t n, const do
 int pgx_label_components(pgx_ctx *ctx, const int32_t *labels, int64_t n, int32_t first_ignored, int32_t *comp_out,
                          int32_t *first_out, int64_t *sizes_out, int64_t *components);
 
+/* Extents of the instances of a labelled 3-D point cloud: per instance the bounds of its points in the surface's own parametrisation,
+ * the sectors its points occupy about the axis, an 8 x 8 occupancy of the bounded patch, and the count (no reference counterpart: the
+ * models are surfaces of infinite extent, and nothing says how far along them an instance reaches).  points: n x 3 doubles (host), the
+ * way pgx_estimate_normals takes them; labels: n int32 (host); frames: K rows of PGX_EXTENTS_FRAME doubles (host),
+ *   kind, o[3], g[3], u[3], v[3], R, r
+ * one per instance: the caller has turned each model into an origin o, an orthonormal triad (g, u, v) and two radii, and the call knows
+ * five KINDS and no model types (r is carried for the caller and not read).  The call neither reads nor alters anything resident -
+ * points, normals, weights, labels, graph, hypothesis batch, expansion memo - and needs no graph.  Outputs (host): count_out [K],
+ * lo_out [K][2], hi_out [K][2], sectors_out [K][2], occupancy_out [K], *skipped.  PGX_ERR_INVALID: n < 0 ("n = <n>"), K < 0
+ * ("K = <K>"), K > PGX_EXTENTS_MAX_INSTANCES ("<K> instances, at most <limit>"), skipped NULL, any other output or frames NULL while
+ * K > 0, points or labels NULL while n > 0 ("NULL argument"); a refused call writes nothing.  K == 0 is PGX_OK and writes *skipped = 0
+ * only; n == 0 is PGX_OK and writes the empty results below for all K instances.  The definition, all of it FP64 without contraction,
+ * IEEE division and square root, every dot product the left fold a.b = (a_0 b_0 + a_1 b_1) + a_2 b_2:
+ *   1. e = x - o per component.  The two coordinates (a, b) of a point by the kind of its instance's frame:
+ *        0 plane            a = e.u  linear                    b = e.v  linear
+ *        1 line             a = e.g  linear                    b unused
+ *        2 cylinder, cone   a = e.g  linear                    b = S(e.u, e.v)  angular
+ *        3 sphere           a = (e.g) / sqrt(e.e)  linear      b = S(e.u, e.v)  angular
+ *        4 torus            a = S(e.u, e.v)  angular           b = S(rho - R, e.g)  angular, rho = sqrt((e.u)(e.u) + (e.v)(e.v))
+ *      any other kind (-1 is the caller's "no frame"; NaN) has no coordinates;
+ *   2. a linear coordinate is canonicalised by c = c + 0.0, so -0 never reaches a comparison; it is defined always, except the
+ *      sphere's a where e.e == 0.  An angular coordinate S(x, y) is defined when x and y are finite and not both zero (a point on the
+ *      axis, or on the tube's centre circle, has none);
+ *   3. a point is LIVE when 0 <= labels[i] < K, the kind of frame labels[i] is 0..4, its three coordinates are finite, and every
+ *      coordinate its kind uses is defined and (linear) finite.  A point whose label is in range but which is not live adds 1 to
+ *      *skipped; a point whose label is out of range counts nowhere;
+ *   4. S(x, y), the sector 0..63 of the direction (x, y), without an arctangent (library arctangents differ in their last bits):
+ *      ax = |x|, ay = |y|, swap = ay > ax, t = swap ? ax / ay : ay / ax; s = the number of k in 1..7 with t >= T_k, T_k = tan(k pi / 32) as
+ *      the literals 0.09849140335716425, 0.198912367379658, 0.3033466836073424, 0.41421356237309503, 0.5345111359507916,
+ *      0.6681786379192989, 0.8206787908286602; q = swap ? 15 - s : s; S = q for x >= 0, y >= 0; 31 - q for x < 0, y >= 0; 32 + q for
+ *      x < 0, y < 0; 63 - q for x >= 0, y < 0 (-0 >= 0 holds).  A direction exactly on a sector boundary falls where this rule puts it;
+ *   5. count[j] = the number of live points of instance j.  For a linear coordinate w (0: a, 1: b) lo[j][w] = the minimum and hi[j][w] =
+ *      the maximum over the live points; +inf and -inf for an instance without live points and for an angular or unused coordinate.
+ *      sectors[j][w] = the OR of 1 << S over the live points for an angular coordinate, 0 for a linear or unused one;
+ *   6. occupancy[j] = the OR over the live points of 1 << (8 bin_a + bin_b), the bins taken once lo and hi are final: linear,
+ *      f = ((c - lo) / (hi - lo)) * 8.0 and bin = 7 for f >= 7, (int)f for 1 <= f < 7, 0 otherwise (f < 1; hi == lo, where f is not
+ *      formed; a NaN f, from a range that overflows) - that is min(7, (int)f); angular, bin = S >> 3; unused, bin = 0.
+ * Every result is an order-independent integer reduction (count: add; bounds: max of an order-preserving u64 key, the minimum as the
+ * maximum of the inverted key; masks: or) on a zero-initialised table, so the result is a pure function of the arguments in whatever
+ * order the lanes run.  One lane per point; a wave whose live lanes share a label merges first and sends one atomic per slot; for
+ * K <= PGX_EXTENTS_LDS_INSTANCES a workgroup accumulates in LDS and flushes the touched words, above it the lanes go to global
+ * memory: the same bits either way.  Three launches - bounds, finalise, occupancy - whose hand-overs are kernel boundaries. */
+#define PGX_EXTENTS_FRAME 15
+#define PGX_EXTENTS_LDS_INSTANCES 256
+#define PGX_EXTENTS_MAX_INSTANCES 1048576
+int pgx_instance_extents(pgx_ctx *ctx, const double *points, int64_t n,
+                         const int32_t *labels, const double *frames, int32_t K,
+                         int64_t *count_out, double *lo_out, double *hi_out,
+                         uint64_t *sectors_out, uint64_t *occupancy_out, int64_t *skipped);
+
 /* ---- the inlier/outlier graph cut of GC-RANSAC's local optimisation.
  * Replaces gcransac::GCRANSAC::labeling as reached from proposal_engine->run (progressive_x.h:294-299; settings
  * spatial_coherence_weight / threshold at :541-545).  The graph-cut-ransac sources are absent from the snapshot, so the

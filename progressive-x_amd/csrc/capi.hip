@@ -270,7 +270,7 @@ void pgx_destroy(pgx_ctx* ctx)
                       &ctx->red_partials, &ctx->red_out, &ctx->dq, &ctx->kmodels, &ctx->labels, &ctx->goff,
                       &ctx->gidx, &ctx->gmult, &ctx->grev, &ctx->scratch, &ctx->fit_scratch, &ctx->pts_s, &ctx->pts32_s,
                       &ctx->pmax_s, &ctx->comp_s, &ctx->pperm, &ctx->gbounds, &ctx->masks_s, &ctx->cull_lists, &ctx->cull_counts, &ctx->score_wl, &ctx->gc, &ctx->gc_sel,
-                      &ctx->weights, &ctx->normals, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops, &ctx->cc_buf};
+                      &ctx->weights, &ctx->normals, &ctx->stats_buf, &ctx->pts_g, &ctx->p32_g, &ctx->weights_scratch, &ctx->memo_snaps.buf, &ctx->prosac_tops, &ctx->cc_buf, &ctx->ext_buf};
     for (DevBuf* b : bufs) release(*b);
     for (DevBuf& b : ctx->slots) release(b);
     release(ctx->h_res);
@@ -1234,6 +1234,13 @@ int pgx_label_components(pgx_ctx* ctx, const int32_t* labels, int64_t n, int32_t
 {
     CTX_GUARD(ctx);
     return label_components_launch(ctx, labels, n, first_ignored, comp_out, first_out, sizes_out, components);
+}
+
+int pgx_instance_extents(pgx_ctx* ctx, const double* points, int64_t n, const int32_t* labels, const double* frames, int32_t K,
+                         int64_t* count_out, double* lo_out, double* hi_out, uint64_t* sectors_out, uint64_t* occupancy_out, int64_t* skipped)
+{
+    CTX_GUARD(ctx);
+    return instance_extents_launch(ctx, points, n, labels, frames, K, count_out, lo_out, hi_out, sectors_out, occupancy_out, skipped);
 }
 
 int pgx_gc_labeling(pgx_ctx* ctx, const double* model, double T2, double lambda, int32_t* flags, int64_t* count)

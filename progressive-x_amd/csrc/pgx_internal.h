@@ -162,6 +162,7 @@ struct pgx_ctx {
     double normal_cos2 = 0.0; // and pts_g (residuals.hip.h; place_oriented_normals).  kappa = cos^2(tolerance), pgx_set_normal_tolerance (context state)
     int64_t oriented_version = 0;   // bumped when an oriented type's normals or kappa change: part of a unary column's identity
     pgx::DevBuf cc_buf;       // pgx_label_components: its labels, parent[], counters, ranks and results (components.hip); nothing resident reads it
+    pgx::DevBuf ext_buf;      // pgx_instance_extents: its points, labels, frames, table and results (extents.hip); nothing resident reads it
 
     pgx::CommState* comm = nullptr;
 };
@@ -274,6 +275,9 @@ int estimate_normals_launch(pgx_ctx* ctx, const double* points, int64_t n, const
                             double* curvature_out, int64_t* undefined);   // normals.hip
 int label_components_launch(pgx_ctx* ctx, const int32_t* labels, int64_t n, int32_t first_ignored, int32_t* comp_out, int32_t* first_out,
                             int64_t* sizes_out, int64_t* components);   // components.hip
+int instance_extents_launch(pgx_ctx* ctx, const double* points, int64_t n, const int32_t* labels, const double* frames, int32_t K,
+                            int64_t* count_out, double* lo_out, double* hi_out, uint64_t* sectors_out, uint64_t* occupancy_out,
+                            int64_t* skipped);   // extents.hip
 int expand_alpha_tile(pgx_ctx* ctx, MoveRequest& rq);   // maxflow_tile.hip: the whole graph in one workgroup, one launch
 void tile_free(pgx_ctx* ctx);
 struct MfView;

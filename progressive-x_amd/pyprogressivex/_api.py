@@ -30,7 +30,7 @@ import sys
 
 import numpy as np
 
-from . import _components, _engine, _estimators, _lib, _proposal
+from . import _components, _engine, _estimators, _extents, _lib, _proposal
 
 _ctx = None
 
@@ -528,6 +528,63 @@ def splitComponents(points, labels, model_number, k=16, radius=None, minimum_poi
     ctx.graph_build(points, fetch=False, **graph)
     comp, first, sizes = ctx.label_components(device_labels, model_number)
     return _components.regroup(device_labels, model_number, comp, first, sizes, int(minimum_point_number), keep)
+
+
+def instanceExtents(points, labels, models, model_type, parent=None):
+    """Bounds the instances of a labelling on their surfaces, on the GPU: the find* calls return surfaces of infinite extent and
+    splitComponents a label per point; this call says how far along its surface each instance reaches - the length of a pipe, the
+    rectangle of a table top, whether a cylinder is a full pipe or a half shell, the covered area of a sphere cap (include/pgx.h
+    pgx_instance_extents states the definition).  points [n, 3]; labels [n] integers, 0 .. K'-1 the instances and anything else an
+    outlier; models [K, p] rows of model_type - planes 6, spheres 8, 3-D lines 12, cylinders 14, cones 16, tori 22, or the union types
+    18 and 20 whose first column is the class; parent [K'] integers as splitComponents returns them: instance j lies on
+    models[parent[j]].  parent=None: K' = K and instance j lies on model j.
+    Each instance gets a frame - an origin o, an axis g and two directions u, v, orthonormal - and two coordinates (a, b) of e = x - o:
+    plane (e.u, e.v); line (e.g, -); cylinder and cone (e.g, the angle about g from u towards v); sphere (the cosine of the angle to
+    g = e_z, the azimuth from e_x); torus (the angle about the axis, the angle about the tube's centre circle from the outward
+    direction towards g).  Angles are counted in 64 sectors of 2 pi / 64.
+    Returns a dict of arrays over the K' instances: kind (0 plane, 1 line, 2 cylinder or cone, 3 sphere, 4 torus, -1 no frame: a row
+    with a non-finite parameter, a zero direction or an unknown class), surface (the single model type, -1 without a frame), count,
+    origin, axis, u, v [K', 3], radii [K', 2] (cylinder (r, 0), cone (cos, sin) of the half-angle, sphere (r, 0), torus (R, r)), lo
+    and hi [K', 2] (the bounds of the linear coordinates; +inf and -inf where there are none), sectors [K', 2] uint64 (the occupied
+    sectors of the angular coordinates), occupancy [K'] uint64 (bit 8 bin_a + bin_b of the 8 x 8 grid between the bounds), arc
+    [K', 2, 2] (start and length in radians of the shortest run of sectors holding every occupied one; NaN for a linear coordinate),
+    area [K'] (the occupied cells in the surface's metric; NaN for a line) - and skipped, the number of points with an instance's label
+    that could not be placed (a non-finite coordinate, a point on the axis, an instance without a frame).
+    The function is a post-process of a finished labelling: it changes nothing about how the find* calls score, sample or label."""
+    points = _as_f64(points)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError("points should be an array with dims [n,3]")
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or labels.shape[0] != points.shape[0]:
+        raise ValueError("labels should be an array with dims [n], one entry per point")
+    if labels.dtype == np.bool_ or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError("labels should be integers")
+    if isinstance(model_type, bool) or not isinstance(model_type, (int, np.integer)) or int(model_type) not in _extents.MODEL_TYPES:
+        raise ValueError("model_type should be one of the 3-D surface types 6, 8, 12, 14, 16, 18, 20, 22")
+    model_type = int(model_type)
+    models = _as_f64(models)
+    if models.ndim != 2 or models.shape[1] != _extents.PARAM_DIM[model_type]:
+        raise ValueError(f"models should be an array with dims [K,{_extents.PARAM_DIM[model_type]}] for model_type {model_type}")
+    if parent is not None:
+        parent = np.asarray(parent)
+        if parent.ndim != 1:
+            raise ValueError("parent should be None or an array with dims [K']")
+        if parent.dtype == np.bool_ or not np.issubdtype(parent.dtype, np.integer):
+            raise ValueError("parent should be integers")
+        if len(parent) and (parent.min() < 0 or parent.max() >= models.shape[0]):
+            raise ValueError("parent should index the rows of models")
+    instances = models.shape[0] if parent is None else parent.shape[0]
+    if instances > _lib.EXTENTS_MAX_INSTANCES:
+        raise ValueError(f"at most {_lib.EXTENTS_MAX_INSTANCES} instances")
+    rows, surface = _extents.frames(models, model_type, parent)
+    live = (labels >= 0) & (labels < instances)                 # before the cast to int32: an int64 outlier label may not fit
+    device_labels = np.where(live, labels, -1).astype(np.int32)
+    out = _context().instance_extents(points, device_labels, rows)
+    arc, area = _extents.derive(surface, rows, out["lo"], out["hi"], out["sectors"], out["occupancy"])
+    return dict(kind=rows[:, 0].astype(np.int32), surface=surface, count=out["count"], skipped=out["skipped"],
+                origin=rows[:, 1:4].copy(), axis=rows[:, 4:7].copy(), u=rows[:, 7:10].copy(), v=rows[:, 10:13].copy(),
+                radii=rows[:, 13:15].copy(), lo=out["lo"], hi=out["hi"], sectors=out["sectors"], occupancy=out["occupancy"],
+                arc=arc, area=area)
 
 
 def findCylinders(points, normals, weights=None, threshold=0.05, conf=0.5, spatial_coherence_weight=0.0,

@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "pgx_score", "pgx_score_upload", "pgx_score_launch", "pgx_score_fetch", "pgx_score_algorithmic_bytes", "pgx_score_stats", "pgx_score_profile", "pgx_score_kernel_times", "pgx_score_debug_fetch", "pgx_score_debug_geometry",
     "pgx_preference", "pgx_get_preference", "pgx_compound_update",
     "pgx_pearl_unary", "pgx_set_unary_q", "pgx_set_graph", "pgx_graph_build", "pgx_graph_fetch", "pgx_set_weights", "pgx_gram", "pgx_solve_minimal", "pgx_set_radius_range", "pgx_set_major_radius_range", "pgx_set_primitive_classes", "pgx_set_normals", "pgx_set_normal_tolerance",
-    "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals", "pgx_label_components",
+    "pgx_set_labels", "pgx_get_labels", "pgx_energy", "pgx_expand_alpha", "pgx_expansion", "pgx_greedy_labeling", "pgx_expansion_stats", "pgx_expansion_paths", "pgx_expansion_schedule", "pgx_one_workgroup_launches", "pgx_host_rows_with_duplicates", "pgx_host_fisher_yates_rows", "pgx_graph_size", "pgx_eigh_smallest_batch", "pgx_estimate_normals", "pgx_label_components", "pgx_instance_extents",
     "pgx_bucket", "pgx_residual_sum", "pgx_gc_labeling", "pgx_gc_inliers", "pgx_epipolar_support", "pgx_gram_batch", "pgx_gram_labels", "pgx_residual_sums", "pgx_pnp_refine_batch",
     "pgx_comm_unique_id", "pgx_comm_init", "pgx_comm_destroy", "pgx_comm_barrier", "pgx_comm_allreduce_max_f64",
     "pgx_score_allgather", "pgx_score_fetch_all", "pgx_score_allgather_begin", "pgx_score_allgather_end", "pgx_compound_allreduce_max",
@@ -55,6 +55,9 @@ ABI_SYMBOLS = [
 
 GRAPH_KNN_IN_BALL, GRAPH_BALL, GRAPH_KNN = 0, 1, 2
 COMPONENTS_LONG_ROW = 64       # PGX_COMPONENTS_LONG_ROW (include/pgx.h): pgx_label_components hands a longer row to a whole wave
+EXTENTS_FRAME = 15             # PGX_EXTENTS_FRAME: doubles per frame row of pgx_instance_extents (kind, o, g, u, v, R, r)
+EXTENTS_LDS_INSTANCES = 256    # PGX_EXTENTS_LDS_INSTANCES: up to this many instances a workgroup accumulates in LDS
+EXTENTS_MAX_INSTANCES = 1 << 20   # PGX_EXTENTS_MAX_INSTANCES
 GRAM_AFFINE, GRAM_DLT_H, GRAM_EPI_F, GRAM_VP, GRAM_PNP_GN, GRAM_SPHERE, GRAM_CIRCLE, GRAM_CYL_GN, GRAM_CONE_GN, GRAM_TORUS_GN = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 GRAM_Q = {GRAM_DLT_H: 9, GRAM_EPI_F: 9, GRAM_VP: 3, GRAM_PNP_GN: 7, GRAM_SPHERE: 5, GRAM_CIRCLE: 4, GRAM_CYL_GN: 6, GRAM_CONE_GN: 7, GRAM_TORUS_GN: 8}   # GRAM_AFFINE: point dimension + 1
 
@@ -766,6 +769,28 @@ class Context:
                  "pgx_label_components")
         c = int(count.value)
         return comp[:lab.shape[0]], first[:c].copy(), sizes[:c].copy()
+
+    def instance_extents(self, points, labels, frames):
+        """pgx_instance_extents: dict(count int64 [K], lo / hi float64 [K, 2], sectors uint64 [K, 2], occupancy uint64 [K], skipped int) of
+        the points [n, 3] with labels [n] (0 .. K-1 the instances) in the frame rows [K, 15] (include/pgx.h states the definition).  Nothing
+        resident is read or changed, and no graph is needed."""
+        pts = _f64(points).reshape(-1, 3)
+        lab = _i32(labels).reshape(-1)
+        frm = _f64(frames).reshape(-1, EXTENTS_FRAME)
+        if lab.shape[0] != pts.shape[0]:
+            raise ValueError(f"{lab.shape[0]} labels for {pts.shape[0]} points")
+        k = frm.shape[0]
+        count = np.empty(k, dtype=np.int64)
+        lo = np.empty((k, 2), dtype=np.float64)
+        hi = np.empty((k, 2), dtype=np.float64)
+        sectors = np.empty((k, 2), dtype=np.uint64)
+        occupancy = np.empty(k, dtype=np.uint64)
+        skipped = C.c_int64()
+        self._ck(self._lib.pgx_instance_extents(self._h, _ptr(pts, C.c_double), C.c_int64(pts.shape[0]), _ptr(lab, C.c_int32),
+                                                _ptr(frm, C.c_double), C.c_int32(k), _ptr(count, C.c_int64), _ptr(lo, C.c_double),
+                                                _ptr(hi, C.c_double), _ptr(sectors, C.c_uint64), _ptr(occupancy, C.c_uint64),
+                                                C.byref(skipped)), "pgx_instance_extents")
+        return dict(count=count, lo=lo, hi=hi, sectors=sectors, occupancy=occupancy, skipped=int(skipped.value))
 
     def expansion_schedule(self):
         """How the level-synchronous min-cut spent its dependent steps (include/pgx.h pgx_expansion_schedule)."""
