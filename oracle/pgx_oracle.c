@@ -1178,7 +1178,7 @@ static void solve_h4(const double *pts, int64_t n, const int32_t *smp, double sc
 
 /* 3-point plane (include/pgx.h pgx_solve_minimal; PlaneEstimator.minimal's docstring): u = p1 - p0, v = p2 - p0, n = u x v in
  * cross3's component order, ln = sqrt((n0 n0 + n1 n1) + n2 n2), (a, b, c) = n / ln, d = -((a x0 + b y0) + c z0).  ln == 0
- * (collinear or coincident points) and NaN (ln > 0 is false) leave the NaN row. */
+ * (collinear or coincident points), NaN (ln > 0 is false) and a non-finite ln (an overflowing product) leave the NaN row. */
 static void solve_plane3(const double *pts, int64_t n, const int32_t *smp, double *out)
 {
     out[0] = out[1] = out[2] = out[3] = NAN;
@@ -1187,7 +1187,7 @@ static void solve_plane3(const double *pts, int64_t n, const int32_t *smp, doubl
     double nv[3];
     cross3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2], p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2], nv);
     const double ln = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
-    if (!(ln > 0.0)) return;
+    if (!(ln > 0.0 && isfinite(ln))) return;
     const double a = nv[0] / ln, b = nv[1] / ln, c = nv[2] / ln;
     out[0] = a; out[1] = b; out[2] = c;
     out[3] = -((a * p0[0] + b * p0[1]) + c * p0[2]);
@@ -1297,7 +1297,7 @@ int pgxo_solve_minimal_range(int model_type, const double *pts, int64_t n, const
             const double ax = pts[(size_t)i0 * 2], ay = pts[(size_t)i0 * 2 + 1];
             const double dx = pts[(size_t)i1 * 2] - ax, dy = pts[(size_t)i1 * 2 + 1] - ay;
             const double ln = sqrt(dx * dx + dy * dy);
-            if (ln > 0.0) {
+            if (ln > 0.0 && isfinite(ln)) {           /* a non-finite length (an overflowing square) leaves the NaN row */
                 m[0] = -dy / ln;
                 m[1] = dx / ln;
                 m[2] = -(m[0] * ax + m[1] * ay);
@@ -1309,7 +1309,7 @@ int pgxo_solve_minimal_range(int model_type, const double *pts, int64_t n, const
             cross3(b[0], b[1], 1.0, b[2], b[3], 1.0, l1);
             cross3(l0[0], l0[1], l0[2], l1[0], l1[1], l1[2], v);
             const double ln = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-            if (ln > 0.0) { m[0] = v[0] / ln; m[1] = v[1] / ln; m[2] = v[2] / ln; }
+            if (ln > 0.0 && isfinite(ln)) { m[0] = v[0] / ln; m[1] = v[1] / ln; m[2] = v[2] / ln; }
         }
     }
     return 0;

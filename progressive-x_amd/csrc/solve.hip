@@ -80,20 +80,22 @@ __device__ __forceinline__ void cross3(double a1, double b1, double c1, double a
 // Rmin, Rmax the context's pgx_set_major_radius_range and slot the solution asked for.
 template <int MT> using Type = std::integral_constant<int, MT>;
 
-// 2-point line [U-4]: unit normal (-dy, dx) / |d|, offset c = -(n . a); coincident points (ln == 0; also false on NaN) give NaN.
+// 2-point line [U-4]: unit normal (-dy, dx) / |d|, offset c = -(n . a); coincident points (ln == 0; also false on NaN) give NaN, and so
+// does a length that is not finite (an overflowing square): (-dy, dx) / inf would be a zero normal, and every point is an inlier of that.
 __device__ __forceinline__ void solve_minimal(Type<kLine2D>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double ax = p[0][0], ay = p[0][1];
     const double dx = p[1][0] - ax, dy = p[1][1] - ay;
     const double ln = sqrt(dx * dx + dy * dy);
-    if (ln > 0.0) {
+    if (ln > 0.0 && isfinite(ln)) {
         m[0] = -dy / ln;
         m[1] = dx / ln;
         m[2] = -(m[0] * ax + m[1] * ay);
     }
 }
 
-// vanishing point of two segments (solver_vanishing_point_two_lines.h:174-182); parallel or identical lines give NaN.
+// vanishing point of two segments (solver_vanishing_point_two_lines.h:174-182); parallel or identical lines give NaN, and so does a
+// norm that is not finite (the 2-point line's guard: v / inf would be the zero vector).
 __device__ __forceinline__ void solve_minimal(Type<kVanishingPoint>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double *a = p[0], *b = p[1];
@@ -102,20 +104,21 @@ __device__ __forceinline__ void solve_minimal(Type<kVanishingPoint>, const doubl
     cross3(b[0], b[1], 1.0, b[2], b[3], 1.0, l1);
     cross3(l0[0], l0[1], l0[2], l1[0], l1[1], l1[2], v);
     const double ln = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    if (ln > 0.0) { m[0] = v[0] / ln; m[1] = v[1] / ln; m[2] = v[2] / ln; }
+    if (ln > 0.0 && isfinite(ln)) { m[0] = v[0] / ln; m[1] = v[1] / ln; m[2] = v[2] / ln; }
 }
 
 // 3-point plane -> (a, b, c, d).  Operation order (the contract; PlaneEstimator.minimal restates it):
 //   u = p1 - p0, v = p2 - p0 (componentwise), n = cross3(u, v), ln = sqrt((n0 n0 + n1 n1) + n2 n2),
 //   a = n0 / ln, b = n1 / ln, c = n2 / ln, d = -((a x0 + b y0) + c z0).
-// ln == 0 (coincident or collinear points; also false on NaN) gives a NaN model.
+// ln == 0 (coincident or collinear points; also false on NaN) gives a NaN model, and so does a non-finite ln (an overflowing product):
+// n / inf would be a zero normal with a NaN offset, a row that is neither a model nor all NaN.
 __device__ __forceinline__ void solve_minimal(Type<kPlane3D>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double *p0 = p[0], *p1 = p[1], *p2 = p[2];
     double nv[3];
     cross3(p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2], p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2], nv);
     const double ln = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
-    if (ln > 0.0) {
+    if (ln > 0.0 && isfinite(ln)) {
         m[0] = nv[0] / ln;
         m[1] = nv[1] / ln;
         m[2] = nv[2] / ln;
@@ -177,8 +180,8 @@ __device__ __forceinline__ void solve_minimal(Type<kCircle2D>, const double* con
 // 2-point 3-D line -> (p, d), a point on the line and a unit direction.  Operation order (the contract; Line3DEstimator.minimal
 // restates it):
 //   v = b - a (componentwise), ln = sqrt((v0 v0 + v1 v1) + v2 v2), d = v / ln, p = a.
-// ln == 0 (coincident points; also false on NaN) gives a NaN model, and so does a non-finite ln, unlike the plane solver: v / inf
-// would be a zero direction, and every point is an inlier of that.
+// ln == 0 (coincident points; also false on NaN) gives a NaN model, and so does a non-finite ln, as in the 2-D line, vanishing point
+// and plane solvers: v / inf would be a zero direction, and every point is an inlier of that.
 __device__ __forceinline__ void solve_minimal(Type<kLine3D>, const double* const* p, const double* const*, double, double, double* m)
 {
     const double *a = p[0], *b = p[1];

@@ -137,11 +137,12 @@ class LineEstimator(Estimator):
 
     def minimal(self, pts, samples):
         a, b = pts[samples[:, 0]], pts[samples[:, 1]]
-        d = b - a
-        ln = np.linalg.norm(d, axis=1)
-        ok = ln > 0
-        nrm = np.column_stack([-d[:, 1], d[:, 0]]) / np.where(ok, ln, 1.0)[:, None]
-        c = -(nrm * a).sum(axis=1)
+        with np.errstate(all="ignore"):
+            d = b - a
+            ln = np.linalg.norm(d, axis=1)
+            ok = (ln > 0) & np.isfinite(ln)        # (a length that is not finite: (-dy, dx) / inf would be a zero normal)
+            nrm = np.column_stack([-d[:, 1], d[:, 0]]) / np.where(ok, ln, 1.0)[:, None]
+            c = -(nrm * a).sum(axis=1)
         models = np.column_stack([nrm, c])
         return models[ok], np.nonzero(ok)[0]
 
@@ -183,17 +184,18 @@ class PlaneEstimator(Estimator):
     def minimal(self, pts, samples):
         """samples [S, 3] -> unit-normal planes (a, b, c, d), bitwise csrc/solve.hip's solve_minimal for planes: n = u x v in cross3's
         component order, ln = sqrt((n0 n0 + n1 n1) + n2 n2), (a, b, c) = n / ln, d = -((a x0 + b y0) + c z0).  Collinear or
-        coincident samples (ln == 0) give no model."""
+        coincident samples (ln == 0) and a non-finite ln (NaN or Inf coordinates, an overflowing product) give no model."""
         p0, p1, p2 = pts[samples[:, 0]], pts[samples[:, 1]], pts[samples[:, 2]]
-        u, v = p1 - p0, p2 - p0
-        n0 = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
-        n1 = -(u[:, 0] * v[:, 2] - u[:, 2] * v[:, 0])
-        n2 = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
-        ln = np.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
-        ok = ln > 0
-        ln = np.where(ok, ln, 1.0)
-        a, b, c = n0 / ln, n1 / ln, n2 / ln
-        d = -((a * p0[:, 0] + b * p0[:, 1]) + c * p0[:, 2])
+        with np.errstate(all="ignore"):
+            u, v = p1 - p0, p2 - p0
+            n0 = u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1]
+            n1 = -(u[:, 0] * v[:, 2] - u[:, 2] * v[:, 0])
+            n2 = u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]
+            ln = np.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+            ok = (ln > 0) & np.isfinite(ln)
+            ln = np.where(ok, ln, 1.0)
+            a, b, c = n0 / ln, n1 / ln, n2 / ln
+            d = -((a * p0[:, 0] + b * p0[:, 1]) + c * p0[:, 2])
         models = np.column_stack([a, b, c, d])
         return models[ok], np.nonzero(ok)[0]
 
@@ -361,11 +363,11 @@ class SphereEstimator(RoundEstimator):
         det = (a1_0 n1_0 + a1_1 n1_1) + a1_2 n1_2, e_k = ((h1 n1_k + h2 n2_k) + h3 n3_k) / det, r = sqrt((e0 e0 + e1 e1) + e2 e2),
         c = p0 + e.  Coplanar or coincident samples (det == 0), non-finite values and radii outside radius_range give no model."""
         p0 = pts[samples[:, 0]]
-        a = [pts[samples[:, i]] - p0 for i in (1, 2, 3)]
-        h = [0.5 * ((ai[:, 0] * ai[:, 0] + ai[:, 1] * ai[:, 1]) + ai[:, 2] * ai[:, 2]) for ai in a]
-        n1, n2, n3 = _cross3(a[1], a[2]), _cross3(a[2], a[0]), _cross3(a[0], a[1])
-        det = (a[0][:, 0] * n1[0] + a[0][:, 1] * n1[1]) + a[0][:, 2] * n1[2]
         with np.errstate(all="ignore"):
+            a = [pts[samples[:, i]] - p0 for i in (1, 2, 3)]
+            h = [0.5 * ((ai[:, 0] * ai[:, 0] + ai[:, 1] * ai[:, 1]) + ai[:, 2] * ai[:, 2]) for ai in a]
+            n1, n2, n3 = _cross3(a[1], a[2]), _cross3(a[2], a[0]), _cross3(a[0], a[1])
+            det = (a[0][:, 0] * n1[0] + a[0][:, 1] * n1[1]) + a[0][:, 2] * n1[2]
             e = [((h[0] * n1[k] + h[1] * n2[k]) + h[2] * n3[k]) / det for k in range(3)]
             r = np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
             models = np.column_stack([p0[:, 0] + e[0], p0[:, 1] + e[1], p0[:, 2] + e[2], r])
@@ -994,11 +996,11 @@ class CircleEstimator(RoundEstimator):
         e_1 = (a_10 h_2 - a_20 h_1) / det, r = sqrt(e_0 e_0 + e_1 e_1), c = p0 + e.  Collinear or coincident samples (det == 0),
         non-finite values and radii outside radius_range give no model."""
         p0 = pts[samples[:, 0]]
-        a1, a2 = pts[samples[:, 1]] - p0, pts[samples[:, 2]] - p0
-        h1 = 0.5 * (a1[:, 0] * a1[:, 0] + a1[:, 1] * a1[:, 1])
-        h2 = 0.5 * (a2[:, 0] * a2[:, 0] + a2[:, 1] * a2[:, 1])
-        det = a1[:, 0] * a2[:, 1] - a1[:, 1] * a2[:, 0]
         with np.errstate(all="ignore"):
+            a1, a2 = pts[samples[:, 1]] - p0, pts[samples[:, 2]] - p0
+            h1 = 0.5 * (a1[:, 0] * a1[:, 0] + a1[:, 1] * a1[:, 1])
+            h2 = 0.5 * (a2[:, 0] * a2[:, 0] + a2[:, 1] * a2[:, 1])
+            det = a1[:, 0] * a2[:, 1] - a1[:, 1] * a2[:, 0]
             e0 = (h1 * a2[:, 1] - h2 * a1[:, 1]) / det
             e1 = (a1[:, 0] * h2 - a2[:, 0] * h1) / det
             r = np.sqrt(e0 * e0 + e1 * e1)
@@ -1023,12 +1025,13 @@ class VanishingPointEstimator(Estimator):
     def minimal(self, pts, samples):
         s0, s1 = pts[samples[:, 0]], pts[samples[:, 1]]
         one = np.ones(len(samples))
-        l0 = self._cross(s0[:, 0], s0[:, 1], one, s0[:, 2], s0[:, 3], one)      # :174-176
-        l1 = self._cross(s1[:, 0], s1[:, 1], one, s1[:, 2], s1[:, 3], one)      # :177-179
-        v = np.column_stack(self._cross(l0[0], l0[1], l0[2], l1[0], l1[1], l1[2]))  # :180-182
-        ln = np.sqrt((v * v).sum(axis=1))                                        # :123-131 vec_norm
-        ok = ln > 0
-        v = v / np.where(ok, ln, 1.0)[:, None]
+        with np.errstate(all="ignore"):
+            l0 = self._cross(s0[:, 0], s0[:, 1], one, s0[:, 2], s0[:, 3], one)      # :174-176
+            l1 = self._cross(s1[:, 0], s1[:, 1], one, s1[:, 2], s1[:, 3], one)      # :177-179
+            v = np.column_stack(self._cross(l0[0], l0[1], l0[2], l1[0], l1[1], l1[2]))  # :180-182
+            ln = np.sqrt((v * v).sum(axis=1))                                    # :123-131 vec_norm
+            ok = (ln > 0) & np.isfinite(ln)        # (a norm that is not finite: v / inf would be the zero vector)
+            v = v / np.where(ok, ln, 1.0)[:, None]
         return v[ok], np.nonzero(ok)[0]
 
     def _fit_many(self, gram, B, inits):

@@ -35,6 +35,7 @@ SAMPLE = dict(homography=4, fundamental=7, pnp=3)
 DIM = dict(homography=4, fundamental=4, pnp=5)
 BATCHES = (1, 63, 64, 65, 129)
 ACCURACY, COVERAGE, NO_MODEL = 0, 1, 2
+RANGE = 3                # (tests/minimal_closed_cases.py) inputs whose squares overflow or underflow: a slot is empty or within tolerance of a solution
 COVERAGE_MATCH = 1e-6
 IDENTIFIED = 1e-4        # a tenth of the separation a COVERAGE fixture guarantees: a slot this near a solution is that solution and no other
 MAX_ROWS = 768
@@ -60,6 +61,10 @@ CLASSES = dict(
 SHARED_V = [c[0] for c in CLASSES["pnp"]].index("two poses share v")
 FIELDS = ("samples", "set_of", "cls", "kind", "draw", "nref", "ref", "cond", "kappa", "tol")
 EXTRA = dict(homography=("sym",), fundamental=("detk",), pnp=("sep", "den"))
+# What a sibling table (tests/minimal_closed_cases.py) adds per type besides its rows in CLASSES, SLOTS, PARAMS and COMPARED:
+FLIP = dict(fundamental=[-1.0] * 9)      # the entries whose common sign is free in the comparison
+AS_RETURNED = {"pnp"}                    # compared as returned, without a change of coordinates
+CHECKS = {}                              # name -> check(case, f, model, reference solution, tolerance): the type's invariants and exact contracts
 
 
 class Case:
@@ -69,19 +74,25 @@ class Case:
     parent [F, 4, 12] (the oracle's output at the commit before the P3P change, recorded)"""
 
 
+def read_case(z, name, k, set_names, fields, scale=lambda pts: 1.0):
+    """one type's Case from the arrays k_* of the file z"""
+    c = Case()
+    c.name = name
+    c.sets = []
+    for s, sname in enumerate(set_names):
+        pts = np.ascontiguousarray(z[k + "_pts"][z[k + "_ptset"] == s])
+        c.sets.append((sname, pts, scale(pts)))
+    for field in fields:
+        setattr(c, field, z[k + "_" + field])
+    return c
+
+
 def load():
     z = np.load(FILE)
     out = {}
     for name in TYPES:
-        k = KEY[name]
-        c = Case()
-        c.name = name
-        c.sets = []
-        for s, (sname, anchor) in enumerate(SETS[name]):
-            pts = np.ascontiguousarray(z[k + "_pts"][z[k + "_ptset"] == s])
-            c.sets.append((sname, pts, 1.0 if name == "pnp" else max(1.0, float(np.abs(pts).max()))))
-        for field in FIELDS + EXTRA[name]:
-            setattr(c, field, z[k + "_" + field])
+        c = read_case(z, name, KEY[name], [sname for sname, _ in SETS[name]], FIELDS + EXTRA[name],
+                      (lambda pts: 1.0) if name == "pnp" else (lambda pts: max(1.0, float(np.abs(pts).max()))))
         if name == "pnp":
             c.parent = z["p3p_parent_models"]
         if name == "fundamental":       # the parent's answers on the pure-translation class (recorded), by fixture number
@@ -100,7 +111,7 @@ def compared(name, model, scale):
     """homography: S H S^-1 (S = diag(1/scale, 1/scale, 1)) at unit norm with the last entry positive; fundamental matrix:
     S^-1 F S^-1 at unit norm; both in rational arithmetic up to the final normalisation; pose: as returned"""
     model = np.asarray(model, dtype=np.float64)
-    if name == "pnp":
+    if name in AS_RETURNED:
         return model
     m = [Fraction(float(x)) for x in model[:9]]
     s = Fraction(float(scale))
@@ -141,6 +152,7 @@ def match(name, case, f, models, scale, where=(), strict=True, coverage_tol=None
     filled = [m for m in models if np.isfinite(m).all()]
     partly = [m for m in models if np.isfinite(m).any() and not np.isfinite(m).all()]
     nref = int(case.nref[f])
+    ranged = case.kind[f] == RANGE
 
     def refuse(what):
         if strict:
@@ -148,16 +160,21 @@ def match(name, case, f, models, scale, where=(), strict=True, coverage_tol=None
         return np.inf
     if partly:
         return refuse("a slot is partly NaN")
-    if len(filled) != nref:
+    if len(filled) != nref and not (ranged and len(filled) < nref):
         return refuse(f"{len(filled)} models, the reference has {nref}")
-    if nref == 0:
+    if nref == 0 or not filled:
         return 0.0
     got = np.array([compared(name, m, scale) for m in filled])
     ref = case.ref[f][:nref, :COMPARED[name]]
     tol = np.full(nref, coverage_tol or COVERAGE_MATCH) if case.kind[f] == COVERAGE else case.tol[f][:nref]
     dist = np.abs(got[None, :, :] - ref[:, None, :]).max(axis=2)            # [reference solution, slot]
-    if name == "fundamental":
-        dist = np.minimum(dist, np.abs(got[None, :, :] + ref[:, None, :]).max(axis=2))
+    if name in FLIP:
+        dist = np.minimum(dist, np.abs(got[None, :, :] * np.asarray(FLIP[name]) - ref[:, None, :]).max(axis=2))
+    if ranged:                                  # every filled slot is a reference solution of its own; an empty slot is accepted
+        back = dist.argmin(axis=0)
+        if len(set(back.tolist())) != len(filled):
+            return refuse(f"two slots are nearest to one reference solution (distances {dist.tolist()})")
+        ref, tol, dist, nref = ref[back], tol[back], dist[back], len(filled)
     pick = dist.argmin(axis=1)
     if len(set(pick.tolist())) != nref:
         return refuse(f"two reference solutions are nearest to one slot (distances {dist.tolist()})")
@@ -167,6 +184,9 @@ def match(name, case, f, models, scale, where=(), strict=True, coverage_tol=None
     try:
         for i, m in enumerate(filled):
             check_invariants(name, m, where)
+        if name in CHECKS:
+            for r in range(nref):
+                CHECKS[name](case, f, filled[pick[r]], ref[r], tol[r])
         if name == "fundamental":           # rank 2, in the compared coordinates: |det| within what the stages from the cubic on can leave
             for r in range(nref):
                 assert abs(_det_exact(got[pick[r]])) <= 32 * EPS * case.detk[f][r] + 16 * EPS * np.abs(got[pick[r]]).max() ** 3, \
@@ -190,11 +210,15 @@ def device_ratios(name, case, ctx, strict=True, batches=BATCHES, coverage_tol=No
     out = {}
     for s, (sname, pts, scale) in enumerate(case.sets):
         ctx.set_points(est.model_type, pts)
+        if hasattr(case, "prepare"):            # what the set has resident besides its points (normals, radius ranges)
+            case.prepare(ctx, s)
         for S in batches:
             take, idx = batch_of(case, s, S)
             models = np.asarray(ctx.solve_minimal(idx)).reshape(S, slots, P)
             for j, f in enumerate(take):
                 out[(sname, S, int(f))] = match(name, case, f, models[j], scale, (sname, S), strict, coverage_tol)
+    if hasattr(case, "prepare"):
+        case.prepare(ctx, None)                 # the context's ranges as at creation
     return out
 
 
